@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the AMWG hot path on N MI355X, measured the way BASELINE.json asks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (config.workload): BASELINE.json configs[1] -- Normal(mu, sigma) model, 1e4 synthetic
@@ -13,10 +13,16 @@ kernel launches of --steps-per-launch steps) that also records every `--thin`-th
 followed for N > 1 by the RCCL gather of the recorded draws to rank 0 (the "gather at sample collection" of north_star).  Inputs are resident in
 HBM before the timed region; the D2H copy of draws is outside it (see DESIGN.md for the PCIe-inclusive rate).
 
-value = (chains on all GPUs) * K * P / seconds of the MEDIAN timed region  [param-updates/s].  The K-step region (barrier +
-    synchronize on both sides, max over ranks) is repeated until >= 1 s has been timed (at least 3, at most 400 regions) and the
-    median region is reported, so that the driver's short `--steps 20` run reports the steady state instead of one launch
-    on a chip that has not clocked up yet; `timing` carries every region's figure incl. the first.
+value = (chains on all GPUs) * K * P / seconds of the timed K-step region (barrier + synchronize on both sides, max over ranks)
+    [param-updates/s]; ms_per_step = those seconds * 1e3 / K.  A plain run times that region ONCE, so K is exactly the number of
+    timed steps; the last min(W, K) warm-up steps go through the timed path's own calls, so that their once-per-process costs are
+    not inside it.  Nothing else runs: no parity schedule, no side kernels, no CPU baseline.
+--full: everything else the bench measures and checks.  The K-step region is repeated until >= --min-seconds (default 1 s) has been
+    timed (at least 3, at most 400 regions) and the median region is reported; `timing` carries every region's figure incl. the
+    first.  The golden schedule runs on the timed sampler first (parity), and the roofline, posterior moments, other configs,
+    JavaScript end-to-end run and CPU baselines below are added to the record.
+--dump-outputs DIR: after the timed steps, the last recorded draw of every chain ([P + derived][chains], the last step's with
+    --thin 1) as DIR/last_draws.npy in float64.  Data and seeds are fixed, so the same arguments give the same inputs in every run.
 roofline: the binding roof of this path is fp64 VALU issue (78.6 TFLOP/s = 3.93e13 lane-operations/s), NOT HBM: the data vector
     is staged once per launch into LDS and re-read from there.  roofline.frac = algorithmic fp64 lane-operations (8 per
     observation: sub, mul, the 4-operation correctly rounded quotient, sub, add) / second / peak.  The SURVEY.md section 8(d)
@@ -692,10 +698,18 @@ def main_inproc(args):
         shards.append(A.Sampler(spec, chains=cnt, seed=SEED, chain_offset=off, device=r, lanes_per_chain=args.lanes, block_threads=args.block,
                                 steps_per_launch=args.steps_per_launch, group_local=int(args.group_local)))
         off += cnt
+    warm = min(W, K) if not args.full else 0      # (one timed region: the last min(W, K) warm-up steps go through the region's own calls)
     for s in shards:
-        s.burn_async(W)
+        s.burn_async(W - warm)
     for s in shards:
         s.sync()
+    if warm:
+        for s in shards:
+            s.sample_async(warm, thin)
+        for s in shards:
+            s.sync()
+        A.group_gather_draws(shards, root=0, to_host=False)
+        A.group_moments(shards)
 
     def region():
         t0 = time.perf_counter()
@@ -707,7 +721,7 @@ def main_inproc(args):
         mean, sd = A.group_moments(shards)     # per-device sums, RCCL all-reduce (inside the library)
         return time.perf_counter() - t0, mean, sd
     regs = [region()]
-    n_regions = 1 if args.single_region else int(min(400, max(3, np.ceil(args.min_seconds / max(regs[0][0], 1e-6)))))
+    n_regions = 1 if (args.single_region or not args.full) else int(min(400, max(3, np.ceil(args.min_seconds / max(regs[0][0], 1e-6)))))
     while len(regs) < n_regions:
         regs.append(region())
     order = sorted(range(len(regs)), key=lambda i: regs[i][0])
@@ -715,17 +729,20 @@ def main_inproc(args):
     value = total * K * P / dt
     kernel_ms = max(s.launch_info()["kernel_ms"] for s in shards)
     li = shards[0].launch_info()
-    # how the draws reach the HOST: what the Node front-end does (every device copies its own block: N PCIe links in parallel) against
-    # gather-to-one-device-then-one-copy (north_star's wording); both once, outside the timed regions
-    collection = {}
-    t0 = time.perf_counter()
-    for s in shards:
-        s.fetch_draws()
-    collection["per_device_copy_ms"] = (time.perf_counter() - t0) * 1e3
-    t0 = time.perf_counter()
-    A.group_gather_draws(shards, root=0, to_host=True)
-    collection["gather_then_one_copy_ms"] = (time.perf_counter() - t0) * 1e3
-    collection["bytes"] = sum(s._pending * s.PR * s.C * 8 for s in shards)
+    outputs = {"last_draws": np.concatenate([s.fetch_draws()[-1] for s in shards], axis=1)} if args.dump_outputs else None
+    collection = None
+    if args.full:
+        # how the draws reach the HOST: what the Node front-end does (every device copies its own block: N PCIe links in parallel) against
+        # gather-to-one-device-then-one-copy (north_star's wording); both once, outside the timed regions
+        collection = {}
+        t0 = time.perf_counter()
+        for s in shards:
+            s.fetch_draws()
+        collection["per_device_copy_ms"] = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        A.group_gather_draws(shards, root=0, to_host=True)
+        collection["gather_then_one_copy_ms"] = (time.perf_counter() - t0) * 1e3
+        collection["bytes"] = sum(s._pending * s.PR * s.C * 8 for s in shards)
     comm = A.group_comm_info(shards)
     sweep = str(li.get("kernel", "")).startswith("amwg_sweep_kernel")
     lane_ops = sweep_lane_ops(value, P, n_obs) if sweep else value * n_obs * ops_per_obs * ((2.0 / P) if args.group_local else 1.0)
@@ -735,13 +752,15 @@ def main_inproc(args):
                        "block_threads": li["block_threads"], "steps_per_launch": args.steps_per_launch,
                        "path": "one process, one sampler per device (amwg_sample_async x N + amwg_sync), the recorded draws gathered to device 0 by amwg_group_gather_draws, summaries by amwg_group_moments (RCCL inside the library)",
                        "rccl_ranks_seen": comm["rccl_ranks_seen"], "devices": comm["devices"], "collection_to_host": collection},
-               timing={"regions": len(regs), "reported": "median region (wall clock around sample_async x N + sync x N + group_gather_draws + group_moments)",
+               timing={"regions": len(regs), "reported": ("median region" if len(regs) > 1 else "the one region") + " (wall clock around sample_async x N + sync x N + group_gather_draws + group_moments)",
                        "region_ms": [r[0] * 1e3 for r in regs][:64], "slowest_device_kernel_ms_last_region": kernel_ms},
                roofline={"bound": "fp64_valu", "achieved": lane_ops, "peak": FP64_VALU_PEAK * N, "frac": lane_ops / (FP64_VALU_PEAK * N),
                          "unit": "fp64 lane-operations/s", "lane_ops_per_obs": HIER_SWEEP_OPS if sweep else ops_per_obs,
                          "lane_ops_note": HIER_SWEEP_OPS_NOTE if sweep else OPS_NOTE[spec["model"]], "kernel": li.get("kernel"),
                          "note": ("the sweep kernel: one certified 2-operation pass over the data per step of %d updates" % P) if sweep else None},
                posterior={"mean": mean.tolist()[:8], "sd": sd.tolist()[:8], "note": "amwg_group_moments over the recorded draws of all shards (last region)"})
+    if outputs is not None:
+        out["outputs"] = write_outputs(args.dump_outputs, outputs)
     emit(out)
     for s in shards:
         s.close()
@@ -882,6 +901,196 @@ def emit(obj, detail_path=None):
         os.write(_REAL_STDOUT, line)
 
 
+DUMP_LIMIT_BYTES = 60_000_000      # --dump-outputs: all files together stay under 64 MB
+DUMP_SAMPLE_SEED = 20260925
+
+
+def last_step_outputs(draws, gathered_lib, gathered, rows, shard_sizes):
+    """What the timed path hands its caller, for its LAST step: the last recorded draw of every chain of the job, [P + derived][chains] (with --thin 1
+    the draw of the last timed step).  For N > 1 the blocks gathered to rank 0, in chain order.  -> {name: array on the host}"""
+    import torch
+    PR = draws.shape[1]
+    if len(shard_sizes) == 1:
+        last = draws[-1]
+    elif gathered_lib is not None:      # (blocks back to back in rank order, [rows][P + derived][chains of that rank] each)
+        parts, off = [], 0
+        for n in shard_sizes:
+            parts.append(gathered_lib[off: off + rows * PR * n].view(rows, PR, n)[-1])
+            off += rows * PR * n
+        last = torch.cat(parts, dim=1)
+    elif gathered is not None:
+        last = torch.cat([g[-1].cpu() for g in gathered], dim=1)
+    else:
+        last = draws[-1]
+    return {"last_draws": last.cpu().numpy()}
+
+
+def write_outputs(directory, outputs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as DIR/<name>.npy, float32 kept, everything else as float64.  When the arrays hold more than `limit` bytes together, each
+    keeps a fixed, seeded sample of its last axis (the chains: the same columns in every run of the same arguments), and the column numbers go beside it
+    as DIR/<name>_columns.npy (float64, exact).  -> {name: {"file", "shape", "dtype"[, "columns"]}} for the record"""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in outputs.items()}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        entry = {}
+        if total > limit and a.ndim >= 1 and a.shape[-1] > 1:
+            n_cols = a.shape[-1]
+            keep = max(1, min(n_cols, int(limit * a.nbytes / total) // (a.nbytes // n_cols + 8)))
+            cols = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_cols, size=keep, replace=False))
+            a = a[..., cols]
+            np.save(os.path.join(directory, name + "_columns.npy"), cols.astype(np.float64))
+            entry["columns"] = "%d of %d, a seeded sample (%s_columns.npy)" % (keep, n_cols, name)
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+        entry.update(file=name + ".npy", shape=list(a.shape), dtype=str(a.dtype))
+        written[name] = entry
+    return written
+
+
+def full_record(out, args, A, s, spec, pooled, lib_moments, gathered_lib, draws, parity, dist, rows, chains, offset, dev_index, li, n_obs, ops_per_obs, b_alg,
+                launch_s, updates_per_launch, regions):
+    """--full, rank 0: everything the run measures and checks beyond the headline, added to `out` -- posterior moments (checked against the library's
+    own), the roofline with its side kernels and the measured fp64 peak, the library's build identity, the golden parity, the other configs, the
+    JavaScript end-to-end run and the CPU baselines.  `regions`: how many K-step regions were timed."""
+    import torch
+    P, K, W = spec["P"], args.steps, args.warmup
+    value, world = out["value"], out["n_gpus"]
+    eff_gbps = updates_per_launch * b_alg / launch_s / 1e9
+    mean, sd = (s.moments() if dist is None else (pooled[0].cpu().numpy(), pooled[1].cpu().numpy()))
+    pm = pooled[0].cpu().numpy()
+    assert dist is not None or np.allclose(pm, mean, rtol=1e-10, atol=0), "library moments differ from the pooled restatement"
+    if lib_moments is not None:
+        assert np.allclose(lib_moments[0], pm, rtol=1e-9, atol=1e-300), "amwg_comm_moments differs from the pooled restatement"
+        if gathered_lib is not None:      # rank 0's own block is where its rank says (blocks back to back in rank order)
+            own = gathered_lib[: rows * P * chains].view(rows, P, chains)
+            assert torch.equal(own, draws), "amwg_comm_gather_draws: rank 0's block is not where it belongs"
+    measured_peak = A.fp64_peak(dev_index)      # register-only fma kernel: what the chip sustains under fp64 load
+    x = spec["data"]["x"]
+    version = A.lib().amwg_version().decode()
+    kname = {"normal": "NormalModel", "beta_bern": "BetaBernModel", "hier_normal": "HierNormalModel", "pois_glm": "PoisGlmModel"}[spec["model"]]
+    bt_class = 256 if li["block_threads"] <= 256 else (512 if li["block_threads"] <= 512 else 1024)
+    kernel = li.get("kernel") or "amwg_step_kernel<%s,%d,%d>" % (kname, li["lanes_per_chain"], bt_class)      # (amwg_kernel_name: what a profiler lists)
+    roof_launch_s, roof_updates, roof_note, full_eval = launch_s, updates_per_launch, None, None
+    term_by_term = None
+    if args.workload == "cfg3" and not args.single_region:      # (profiling runs keep to ONE kind of launch)
+        # beside the default (the exact fast-forward of the two-valued sum: pass-free, priced against vector issue below): the TERM-BY-TERM pass
+        # (exact_division = 1: one fp64 add per observation)
+        t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=1, steps_per_launch=20, exact_division=1)
+        t.burn(40)
+        t.burn(20)
+        tv = chains * 20 * P / (t.launch_info()["kernel_ms"] * 1e-3)
+        term_by_term = {"value": tv, "frac": tv * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": t.launch_info()["kernel"],
+                        "note": "options.exact_division = 1: the scalar jump-table pass, one fp64 add per observation (bit-identical to the fast-forward)"}
+        t.close()
+    if args.workload == "cfg4" and not args.group_local and not args.full_evaluation and not args.single_region:      # (profiling runs -- --single-region -- keep to ONE kernel)
+        t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=args.lanes, block_threads=args.block, steps_per_launch=args.steps_per_launch, full_evaluation=1)
+        t.burn(2 * args.steps_per_launch)
+        t.burn(3 * args.steps_per_launch)
+        full_launch_s, full_updates = t.launch_info()["kernel_ms"] * 1e-3, chains * 3 * args.steps_per_launch * P
+        full_eval = {"value": full_updates / full_launch_s, "frac": full_updates / full_launch_s * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": t.launch_info()["kernel"]}
+        if not str(li.get("kernel", "")).startswith("amwg_sweep_kernel"):
+            roof_launch_s, roof_updates, kernel = full_launch_s, full_updates, "%s with options.full_evaluation = 1" % full_eval["kernel"]
+            roof_note = "roofline = every evaluation passes over all the data (full_evaluation = 1), %.3g param-updates/s" % full_eval["value"]
+        t.close()
+    ckind = certified_kind(spec["model"], li["lanes_per_chain"], args.full_evaluation)
+    certified = ckind is not None
+    ops_note = OPS_NOTE[spec["model"]]
+    if certified:
+        # `value` and `frac` describe the same kernel: the certified pass and ITS operations per observation; the expression kernel is measured beside it
+        if not args.single_region:
+            few = 2 * args.steps_per_launch if ckind == "normal" else max(4, min(args.steps_per_launch, 10))
+            t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=li["lanes_per_chain"], block_threads=args.block, steps_per_launch=args.steps_per_launch, full_evaluation=1)
+            t.burn(few)
+            t.burn(few)
+            fl = t.launch_info()
+            fv = chains * few * P / (fl["kernel_ms"] * 1e-3)
+            full_eval = {"value": fv, "frac": fv * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": fl["kernel"], "lane_ops_per_obs": ops_per_obs,
+                         "note": "options.full_evaluation = 1: the reference's expression, term by term, in every update (rounds 1-4's kernel)"}
+            t.close()
+        ops_per_obs, ops_note = (CERTIFIED_OPS_PER_OBS, CERTIFIED_NOTE) if ckind == "normal" else (CERTIFIED_GLM_OPS_PER_OBS, CERTIFIED_GLM_NOTE)
+    traffic, traffic_src, traffic_alg, traffic_why_not = measured_traffic(chains, args.steps_per_launch, args.workload, li["lanes_per_chain"], args.group_local, kernel_id_of(version), kernel)
+    lane_ops = roof_updates * n_obs * ops_per_obs / roof_launch_s
+    if str(kernel).startswith("amwg_sweep_kernel"):
+        # `value` and `frac` describe the same kernel: the sweep kernel against the arithmetic of its three passes per step
+        lane_ops = sweep_lane_ops(roof_updates / roof_launch_s, P, n_obs)
+        fe = full_eval or {"value": float("nan"), "frac": float("nan")}
+        roof_note = SWEEP_NOTE % (kernel, P, n_obs, fe["value"], fe["frac"])
+        ops_per_obs, ops_note = HIER_SWEEP_OPS, HIER_SWEEP_OPS_NOTE
+    if args.group_local:
+        lane_ops *= 2.0 / P          # two passes per step of P updates (see measure_other_config)
+    out.update({
+        "roofline": {"bound": "fp64_valu", "achieved": lane_ops, "peak": FP64_VALU_PEAK, "unit": "fp64 lane-operations/s", "frac": lane_ops / FP64_VALU_PEAK,
+                     "peak_note": "78.6 TFLOP/s fp64 vector (MI355X datasheet) = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz = 3.93e13 lane-FMA/s",
+                     "measured_peak": measured_peak, "frac_of_measured_peak": lane_ops / measured_peak,
+                     "measured_peak_note": "amwg_fp64_peak: independent v_fma_f64 chains, no memory traffic, same process",
+                     "lane_ops_per_obs": ops_per_obs, "lane_ops_note": ops_note,
+                     "kernel": kernel + (" (certified decisions)" if certified else ""), "launch_ms": roof_launch_s * 1e3, "updates_per_launch": roof_updates,
+                     "traffic": traffic, "traffic_source": traffic_src, "traffic_refused": traffic_why_not if traffic is None else None,
+                     "traffic_unit": "HBM bytes per launch, (2*FETCH_SIZE + WRITE_SIZE) KB from separate rocprofv3 --pmc passes",
+                     "algorithmic_bytes_per_launch": updates_per_launch * b_alg, "algorithmic_bytes_per_update": b_alg,
+                     "traffic_ratio": (traffic / traffic_alg) if (traffic and traffic_alg) else None,
+                     "traffic_note": "traffic and traffic_ratio are per launch of the PROFILED command (%d steps per launch, profiles/): measured HBM bytes / algorithmic bytes of that launch" % args.steps_per_launch,
+                     "effective_hbm": {"achieved": eff_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": eff_gbps / HBM_PEAK_GBPS, "lds_resident": True,
+                                       "note": "SURVEY.md section 8(d) contract figure: algorithmic bytes (one pass over the data per update) / launch time.  "
+                                               "The data vector is staged once per launch into LDS (L2/MALL for cfg5) and re-read from there, so this is an "
+                                               "EFFECTIVE rate that exceeds the HBM peak by design; it is not the roof this kernel runs against"},
+                     "note": roof_note},
+        "full_evaluation": full_eval,
+        "posterior": {"mean": mean.tolist()[:8], "sd": sd.tolist()[:8], "data_mean": float(np.mean(x)), "data_sd": float(np.std(x, ddof=1)),
+                      "note": "moments over the recorded draws of the last region on ALL ranks (all-reduce of per-rank sums for N > 1; after %d warm-up + %d timed steps)" % (W, K * (regions - 1))},
+    })
+    if args.workload == "cfg3":
+        # `value` and `frac` describe the SAME kernel (round-5 review, item 5): a pass-free update is bound by vector ISSUE -- the stepper's instructions per update
+        # (committed rocprofv3 PMC pass of these kernel sources) x the measured update rate, against 1024 SIMDs x 2.4 GHz / 4 wave64 instructions per second
+        vpu, vfile, why = profiled_valu_per_update("cfg3", kernel, kernel_id_of(version))
+        rate = updates_per_launch / launch_s
+        out["roofline"].update({"bound": "valu_issue", "achieved": (rate / 64.0) * vpu if vpu else None, "peak": VALU_ISSUE_PEAK, "unit": "wave64 vector instructions/s",
+                                "frac": ((rate / 64.0) * vpu / VALU_ISSUE_PEAK) if vpu else None, "frac_of_measured_peak": None, "valu_per_64_updates": vpu,
+                                "valu_profile": vfile, "valu_profile_refused": why, "lane_ops_per_obs": None,
+                                "lane_ops_note": "pass-free update: the exact fast-forward of the two-valued sum (csrc/amwg_twoval.h, ~log2 N binade steps) -- Philox, Leva's rnorm, two "
+                                                 "logarithms and the bisection are all there is; the roof is vector issue, priced with the PMC pass of the same kernel sources"})
+        out["term_by_term"] = term_by_term
+    out["roofline"].update(sweep_roofline_units(lane_ops) if str(kernel).startswith("amwg_sweep_kernel") else
+                           roofline_units(spec["model"], lane_ops, ops_per_obs) if not certified else
+                           {"frac_issue": lane_ops / FP64_VALU_PEAK, "frac_survey_flops": (roof_updates / roof_launch_s) * n_obs * (3 if ckind == "normal" else 50) / FP64_FLOPS_PEAK,
+                            "survey_flops_note": "the certified pass in flops (an FMA = 2) against 78.6 TFLOP/s: a sub and an fma per observation = 3 (Normal); 8 + 21 fmas = 50 (Poisson)"})
+    import build_id
+    out["library"] = {"version": version, "built_from_this_tree": ("build " + build_id.build_id()) in version and ("kernels " + build_id.kernel_id()) in version,
+                      "note": "amwg_version(): a hash over every source of libamwg.so and one over the device sources + compiler flags (tools/build_id.py); "
+                              "built_from_this_tree compares them with the sources beside this bench.py"}
+    if parity is not None:
+        out["parity"] = parity
+        fr = flip_rate_record(kernel_id_of(version))
+        if fr is not None:
+            out["parity"]["flip_rate"] = fr
+    if world == 1 and args.workload == "cfg2" and not args.no_other_configs:
+        out["other_configs"] = {}
+        for name in ("cfg3", "cfg4", "cfg5", "cfg4_group_local"):
+            try:
+                out["other_configs"][name] = measure_other_config(A, name.split("_")[0], dev_index, group_local=int(name.endswith("group_local")))
+            except Exception as e:      # a failure here must not cost the headline line
+                out["other_configs"][name] = {"error": repr(e)}
+        try:      # the opt-in third tier of the Normal family (amwg_options::sufficient_statistics), beside the headline's pass kernel and full_evaluation
+            out["sufficient_statistics"] = measure_sufficient_statistics(A, spec, chains, dev_index)
+        except Exception as e:
+            out["sufficient_statistics"] = {"error": repr(e)}
+        if not args.no_js:
+            out["end_to_end_js"] = end_to_end_js(chains, n_obs)
+        o = out["other_configs"]
+        if "value" in o.get("cfg4", {}) and "value" in o.get("cfg4_group_local", {}):
+            o["cfg4_group_local"]["speedup_over_cfg4"] = o["cfg4_group_local"]["value"] / o["cfg4"]["value"]
+    if world == 1 and not args.no_cpu_baseline:
+        ref = cpu_baseline_reference(args.workload)
+        out["cpu_baseline"] = ref if ref is not None else cpu_baseline_port(spec)
+        if ref is not None:
+            out["cpu_baseline_port"] = cpu_baseline_port(spec, budget_s=3.0)
+        port_rate = (out.get("cpu_baseline_port") or out["cpu_baseline"])["value"]
+        out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(spec, port_rate)
+        out["chains_equiv"] = value / out["cpu_baseline"]["value"]
+
+
 def main():
     claim_stdout()
     ap = argparse.ArgumentParser()
@@ -905,8 +1114,14 @@ def main():
     ap.add_argument("--no-parity", action="store_true", help="profiling runs only: skip the golden schedule on the timed sampler (its launches record every draw)")
     ap.add_argument("--no-js", action="store_true", help="skip the end-to-end run through the JavaScript host (bench/js_e2e.js)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the short measurements of cfg3 / cfg4 / cfg5 appended to the default line")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the timed K-step region until this much time is on the clock (median reported)")
-    ap.add_argument("--single-region", action="store_true", help="time the K-step region once (profiling runs)")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="--full only: repeat the timed K-step region until this much time is on the clock (median reported)")
+    ap.add_argument("--single-region", action="store_true", help="--full only: time the K-step region once (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the golden parity schedule on the timed sampler, the K-step region repeated for --min-seconds (median "
+                         "reported), the roofline (measured fp64 peak, full-evaluation side kernels, committed profiles), posterior moments, the other configs, "
+                         "the JavaScript end-to-end run and the CPU baselines.  Without it a run sets up, warms up, times EXACTLY --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the draws row a caller of sample() receives) as DIR/<name>.npy")
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg3", "cfg4", "cfg5", "readme"],
                     help="cfg2 (default) is the bench line; the others measure the remaining BASELINE.json configs")
     args = ap.parse_args()
@@ -974,7 +1189,7 @@ def main():
     mk = lambda off: A.Sampler(spec, chains=chains, seed=SEED, chain_offset=off, device=dev_index, group_local=int(args.group_local), full_evaluation=int(args.full_evaluation),
                                lanes_per_chain=args.lanes, block_threads=args.block, steps_per_launch=args.steps_per_launch)
     parity = None
-    if world == 1 and args.workload in GOLDEN_OF and not args.no_parity:
+    if args.full and world == 1 and args.workload in GOLDEN_OF and not args.no_parity:
         # the proof that this build reproduces the reference, taken from the sampler that is timed below (its first steps ARE the golden schedule)
         probe = mk(0)
         timed_lanes = probe.launch_info()["lanes_per_chain"]
@@ -984,7 +1199,7 @@ def main():
         s = mk(offset)
     P, K, W, thin = spec["P"], args.steps, args.warmup, max(1, args.thin)
     rows = -(-K // thin)
-    draws = torch.empty((rows, P, chains), dtype=torch.float64, device="cuda")
+    draws = torch.zeros((rows, P, chains), dtype=torch.float64, device="cuda")      # (zeros: every page of the buffers is touched before any timing)
     # The gather at sample collection is the LIBRARY's (amwg_comm_*: a communicator over the ranks from a shared id, grouped ncclSend / ncclRecv of
     # every rank's block to rank 0) -- what a one-process-per-device host of the product calls; torch.distributed only carries the 128-byte id,
     # the barriers and the max-over-ranks of the timing.  --torch-gather (or a failure to build the communicator, recorded in the line) times
@@ -1024,9 +1239,9 @@ def main():
                 comm.close()
                 comm, comm_error = None, "another rank could not build the communicator"
     gather_elems = rows * P * total_chains_job
-    gathered_lib = torch.empty(gather_elems, dtype=torch.float64, device="cuda") if (comm is not None and rank == 0) else None
+    gathered_lib = torch.zeros(gather_elems, dtype=torch.float64, device="cuda") if (comm is not None and rank == 0) else None
     shard_sizes = [chain_shard(r, world, total_chains_job)[1] for r in range(world)] if args.strong else [chains] * world
-    gathered = [torch.empty((rows, P, shard_sizes[r]), dtype=draws.dtype, device=coll_dev) for r in range(world)] if (comm is None and world > 1 and rank == 0) else None
+    gathered = [torch.zeros((rows, P, shard_sizes[r]), dtype=draws.dtype, device=coll_dev) for r in range(world)] if (comm is None and world > 1 and rank == 0) else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -1034,8 +1249,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    if W > 0:
+    if W > 0 and args.full:
         s.burn(W)
+    elif W > 0:
+        # W untimed steps; the last min(W, K) of them go through the timed path itself (sample_device into the same buffer + the gather) so that what
+        # that path meets once per process -- the recording launches, the communicator's first send / receive -- is met here and not inside the ONE
+        # timed region (--full reports the median of several instead).  burn and sample step the chains alike: they are where W steps of burn() would leave them.
+        m = min(W, K)
+        if W > m:
+            s.burn(W - m)
+        s.sample_device(m, thin, draws.data_ptr(), draws.numel() * 8)
+        s.sync()
+        if comm is not None:
+            comm.gather_draws(s, 0, gathered_lib.data_ptr() if rank == 0 else 0, gather_elems * 8)
+        elif dist is not None:
+            gather_draws(dist, draws if coll_dev == "cuda" else draws.cpu(), gathered, rank, equal_sizes=len(set(shard_sizes)) == 1)
 
     def timed_region():
         """EXACTLY K steps between barrier + synchronize pairs; -> (wall seconds, HIP-event kernel ms), max over ranks"""
@@ -1056,23 +1284,27 @@ def main():
             dt, kms = float(t[0]), float(t[1])
         return dt, kms
 
-    # the K-step region, repeated until >= 1 s is on the clock (3..400 regions; every rank derives the same count from the
-    # max-over-ranks time of the first region), median region reported
+    # ONE region of exactly K steps.  --full: the K-step region repeated until >= --min-seconds is on the clock (3..400 regions; every rank derives the
+    # same count from the max-over-ranks time of the first region), median region reported
     regions = [timed_region()]
-    n_regions = int(min(400, max(3, np.ceil(args.min_seconds / max(regions[0][0], 1e-6)))))
-    if args.single_region:
-        n_regions = 1
+    n_regions = 1
+    if args.full and not args.single_region:
+        n_regions = int(min(400, max(3, np.ceil(args.min_seconds / max(regions[0][0], 1e-6)))))
     while len(regions) < n_regions:
         regions.append(timed_region())
     order = sorted(range(len(regions)), key=lambda r: regions[r][0])
     dt, kernel_ms = regions[order[len(order) // 2]]
     li = s.launch_info()
-    # posterior moments over the recorded draws of ALL ranks: per-rank sums + all-reduce (RCCL for N > 1; bayes.js_amd/shard.py,
-    # the one-process-per-GPU twin of the library's amwg_group_moments) -- outside the timed regions
-    from shard import pooled_moments
-    pooled = pooled_moments(dist, draws if (dist is None or coll_dev == "cuda") else draws.cpu())
-
-    lib_moments = comm.moments(s) if comm is not None else None      # collective: the library's all-reduce twin of pooled_moments
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        outputs = last_step_outputs(draws, gathered_lib, gathered, rows, shard_sizes)
+    pooled, lib_moments = None, None
+    if args.full:
+        # posterior moments over the recorded draws of ALL ranks: per-rank sums + all-reduce (RCCL for N > 1; bayes.js_amd/shard.py,
+        # the one-process-per-GPU twin of the library's amwg_group_moments) -- outside the timed regions
+        from shard import pooled_moments
+        pooled = pooled_moments(dist, draws if (dist is None or coll_dev == "cuda") else draws.cpu())
+        lib_moments = comm.moments(s) if comm is not None else None      # collective: the library's all-reduce twin of pooled_moments
     rank_devices = [dev_index]
     if dist is not None:
         box = [None] * world
@@ -1084,69 +1316,7 @@ def main():
         launches = max(1, li["n_launches"])
         launch_s = kernel_ms * 1e-3 / launches
         updates_per_launch = chains * (K / launches) * P
-        eff_gbps = updates_per_launch * b_alg / launch_s / 1e9
-        mean, sd = (s.moments() if dist is None else (pooled[0].cpu().numpy(), pooled[1].cpu().numpy()))
-        pm = pooled[0].cpu().numpy()
-        assert dist is not None or np.allclose(pm, mean, rtol=1e-10, atol=0), "library moments differ from the pooled restatement"
-        if lib_moments is not None:
-            assert np.allclose(lib_moments[0], pm, rtol=1e-9, atol=1e-300), "amwg_comm_moments differs from the pooled restatement"
-            if gathered_lib is not None:      # rank 0's own block is where its rank says (blocks back to back in rank order)
-                own = gathered_lib[: rows * P * chains].view(rows, P, chains)
-                assert torch.equal(own, draws), "amwg_comm_gather_draws: rank 0's block is not where it belongs"
-        measured_peak = A.fp64_peak(dev_index)      # register-only fma kernel: what the chip sustains under fp64 load
-        x = spec["data"]["x"]
-        version = A.lib().amwg_version().decode()
-        kname = {"normal": "NormalModel", "beta_bern": "BetaBernModel", "hier_normal": "HierNormalModel", "pois_glm": "PoisGlmModel"}[spec["model"]]
-        bt_class = 256 if li["block_threads"] <= 256 else (512 if li["block_threads"] <= 512 else 1024)
-        kernel = li.get("kernel") or "amwg_step_kernel<%s,%d,%d>" % (kname, li["lanes_per_chain"], bt_class)      # (amwg_kernel_name: what a profiler lists)
-        roof_launch_s, roof_updates, roof_note, full_eval = launch_s, updates_per_launch, None, None
-        term_by_term = None
-        if args.workload == "cfg3" and not args.single_region:      # (profiling runs keep to ONE kind of launch)
-            # beside the default (the exact fast-forward of the two-valued sum: pass-free, priced against vector issue below): the TERM-BY-TERM pass
-            # (exact_division = 1: one fp64 add per observation)
-            t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=1, steps_per_launch=20, exact_division=1)
-            t.burn(40)
-            t.burn(20)
-            tv = chains * 20 * P / (t.launch_info()["kernel_ms"] * 1e-3)
-            term_by_term = {"value": tv, "frac": tv * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": t.launch_info()["kernel"],
-                            "note": "options.exact_division = 1: the scalar jump-table pass, one fp64 add per observation (bit-identical to the fast-forward)"}
-            t.close()
-        if args.workload == "cfg4" and not args.group_local and not args.full_evaluation and not args.single_region:      # (profiling runs -- --single-region -- keep to ONE kernel)
-            t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=args.lanes, block_threads=args.block, steps_per_launch=args.steps_per_launch, full_evaluation=1)
-            t.burn(2 * args.steps_per_launch)
-            t.burn(3 * args.steps_per_launch)
-            full_launch_s, full_updates = t.launch_info()["kernel_ms"] * 1e-3, chains * 3 * args.steps_per_launch * P
-            full_eval = {"value": full_updates / full_launch_s, "frac": full_updates / full_launch_s * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": t.launch_info()["kernel"]}
-            if not str(li.get("kernel", "")).startswith("amwg_sweep_kernel"):
-                roof_launch_s, roof_updates, kernel = full_launch_s, full_updates, "%s with options.full_evaluation = 1" % full_eval["kernel"]
-                roof_note = "roofline = every evaluation passes over all the data (full_evaluation = 1), %.3g param-updates/s" % full_eval["value"]
-            t.close()
-        ckind = certified_kind(spec["model"], li["lanes_per_chain"], args.full_evaluation)
-        certified = ckind is not None
-        ops_note = OPS_NOTE[spec["model"]]
-        if certified:
-            # `value` and `frac` describe the same kernel: the certified pass and ITS operations per observation; the expression kernel is measured beside it
-            if not args.single_region:
-                few = 2 * args.steps_per_launch if ckind == "normal" else max(4, min(args.steps_per_launch, 10))
-                t = A.Sampler(spec, chains=chains, seed=SEED, chain_offset=offset, device=dev_index, lanes_per_chain=li["lanes_per_chain"], block_threads=args.block, steps_per_launch=args.steps_per_launch, full_evaluation=1)
-                t.burn(few)
-                t.burn(few)
-                fl = t.launch_info()
-                fv = chains * few * P / (fl["kernel_ms"] * 1e-3)
-                full_eval = {"value": fv, "frac": fv * n_obs * ops_per_obs / FP64_VALU_PEAK, "kernel": fl["kernel"], "lane_ops_per_obs": ops_per_obs,
-                             "note": "options.full_evaluation = 1: the reference's expression, term by term, in every update (rounds 1-4's kernel)"}
-                t.close()
-            ops_per_obs, ops_note = (CERTIFIED_OPS_PER_OBS, CERTIFIED_NOTE) if ckind == "normal" else (CERTIFIED_GLM_OPS_PER_OBS, CERTIFIED_GLM_NOTE)
-        traffic, traffic_src, traffic_alg, traffic_why_not = measured_traffic(chains, args.steps_per_launch, args.workload, li["lanes_per_chain"], args.group_local, kernel_id_of(version), kernel)
-        lane_ops = roof_updates * n_obs * ops_per_obs / roof_launch_s
-        if str(kernel).startswith("amwg_sweep_kernel"):
-            # `value` and `frac` describe the same kernel: the sweep kernel against the arithmetic of its three passes per step
-            lane_ops = sweep_lane_ops(roof_updates / roof_launch_s, P, n_obs)
-            fe = full_eval or {"value": float("nan"), "frac": float("nan")}
-            roof_note = SWEEP_NOTE % (kernel, P, n_obs, fe["value"], fe["frac"])
-            ops_per_obs, ops_note = HIER_SWEEP_OPS, HIER_SWEEP_OPS_NOTE
         if args.group_local:
-            lane_ops *= 2.0 / P          # two passes per step of P updates (see measure_other_config)
             label += " -- GROUP-LOCAL evaluation (opt-in; not the reference's operation schedule)"
         out = {
             "metric": "posterior draws/sec (= param-updates/sec)", "value": value, "unit": "param-updates/s",
@@ -1161,77 +1331,16 @@ def main():
                                  else (("torch.distributed %s gather of recorded draws to rank 0" % ("rccl" if backend == "nccl" else backend)) if world > 1 else "none (1 GPU, --torch-gather or no communicator)"),
                        "rccl_ranks_seen": (comm_info or {}).get("rccl_ranks_seen"), "rccl_note": "ncclCommCount of the library's communicator (amwg_comm_info)",
                        "communicator_error": comm_error, "ranks": rank_devices},
-            "timing": {"regions": len(regions), "reported": "median region", "region_ms": [r[0] * 1e3 for r in regions][:64],
+            "timing": {"regions": len(regions), "reported": "median region" if len(regions) > 1 else "the one region", "region_ms": [r[0] * 1e3 for r in regions][:64],
                        "first_region_ms": regions[0][0] * 1e3, "min_region_ms": regions[order[0]][0] * 1e3, "max_region_ms": regions[order[-1]][0] * 1e3,
                        "steps_per_region": K, "note": "every region is exactly K steps between barrier + synchronize pairs; chains keep adapting across regions"},
-            "roofline": {"bound": "fp64_valu", "achieved": lane_ops, "peak": FP64_VALU_PEAK, "unit": "fp64 lane-operations/s", "frac": lane_ops / FP64_VALU_PEAK,
-                         "peak_note": "78.6 TFLOP/s fp64 vector (MI355X_MICROARCH.md) = 256 CU x 4 SIMD x 16 lanes/clk x 2.4 GHz = 3.93e13 lane-FMA/s",
-                         "measured_peak": measured_peak, "frac_of_measured_peak": lane_ops / measured_peak,
-                         "measured_peak_note": "amwg_fp64_peak: independent v_fma_f64 chains, no memory traffic, same process",
-                         "lane_ops_per_obs": ops_per_obs, "lane_ops_note": ops_note,
-                         "kernel": kernel + (" (certified decisions)" if certified else ""), "launch_ms": roof_launch_s * 1e3, "updates_per_launch": roof_updates,
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_refused": traffic_why_not if traffic is None else None,
-                         "traffic_unit": "HBM bytes per launch, (2*FETCH_SIZE + WRITE_SIZE) KB from separate rocprofv3 --pmc passes",
-                         "algorithmic_bytes_per_launch": updates_per_launch * b_alg, "algorithmic_bytes_per_update": b_alg,
-                         "traffic_ratio": (traffic / traffic_alg) if (traffic and traffic_alg) else None,
-                         "traffic_note": "traffic and traffic_ratio are per launch of the PROFILED command (%d steps per launch, profiles/): measured HBM bytes / algorithmic bytes of that launch" % args.steps_per_launch,
-                         "effective_hbm": {"achieved": eff_gbps, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": eff_gbps / HBM_PEAK_GBPS, "lds_resident": True,
-                                           "note": "SURVEY.md section 8(d) contract figure: algorithmic bytes (one pass over the data per update) / launch time.  "
-                                                   "The data vector is staged once per launch into LDS (L2/MALL for cfg5) and re-read from there, so this is an "
-                                                   "EFFECTIVE rate that exceeds the HBM peak by design; it is not the roof this kernel runs against"},
-                         "note": roof_note},
-            "kernel_only_value": chains * K * P / (kernel_ms * 1e-3), "full_evaluation": full_eval,
-            "posterior": {"mean": mean.tolist()[:8], "sd": sd.tolist()[:8], "data_mean": float(np.mean(x)), "data_sd": float(np.std(x, ddof=1)),
-                          "note": "moments over the recorded draws of the last region on ALL ranks (all-reduce of per-rank sums for N > 1; after %d warm-up + %d timed steps)" % (W, K * (len(regions) - 1))},
+            "kernel_only_value": chains * K * P / (kernel_ms * 1e-3),
         }
-        if args.workload == "cfg3":
-            # `value` and `frac` describe the SAME kernel (round-5 review, item 5): a pass-free update is bound by vector ISSUE -- the stepper's instructions per update
-            # (committed rocprofv3 PMC pass of these kernel sources) x the measured update rate, against 1024 SIMDs x 2.4 GHz / 4 wave64 instructions per second
-            vpu, vfile, why = profiled_valu_per_update("cfg3", kernel, kernel_id_of(version))
-            rate = updates_per_launch / launch_s
-            out["roofline"].update({"bound": "valu_issue", "achieved": (rate / 64.0) * vpu if vpu else None, "peak": VALU_ISSUE_PEAK, "unit": "wave64 vector instructions/s",
-                                    "frac": ((rate / 64.0) * vpu / VALU_ISSUE_PEAK) if vpu else None, "frac_of_measured_peak": None, "valu_per_64_updates": vpu,
-                                    "valu_profile": vfile, "valu_profile_refused": why, "lane_ops_per_obs": None,
-                                    "lane_ops_note": "pass-free update: the exact fast-forward of the two-valued sum (csrc/amwg_twoval.h, ~log2 N binade steps) -- Philox, Leva's rnorm, two "
-                                                     "logarithms and the bisection are all there is; the roof is vector issue, priced with the PMC pass of the same kernel sources"})
-            out["term_by_term"] = term_by_term
-        out["roofline"].update(sweep_roofline_units(lane_ops) if str(kernel).startswith("amwg_sweep_kernel") else
-                               roofline_units(spec["model"], lane_ops, ops_per_obs) if not certified else
-                               {"frac_issue": lane_ops / FP64_VALU_PEAK, "frac_survey_flops": (roof_updates / roof_launch_s) * n_obs * (3 if ckind == "normal" else 50) / FP64_FLOPS_PEAK,
-                                "survey_flops_note": "the certified pass in flops (an FMA = 2) against 78.6 TFLOP/s: a sub and an fma per observation = 3 (Normal); 8 + 21 fmas = 50 (Poisson)"})
-        import build_id
-        out["library"] = {"version": version, "built_from_this_tree": ("build " + build_id.build_id()) in version and ("kernels " + build_id.kernel_id()) in version,
-                          "note": "amwg_version(): a hash over every source of libamwg.so and one over the device sources + compiler flags (tools/build_id.py); "
-                                  "built_from_this_tree compares them with the sources beside this bench.py"}
-        if parity is not None:
-            out["parity"] = parity
-            fr = flip_rate_record(kernel_id_of(version))
-            if fr is not None:
-                out["parity"]["flip_rate"] = fr
-        if world == 1 and args.workload == "cfg2" and not args.no_other_configs:
-            out["other_configs"] = {}
-            for name in ("cfg3", "cfg4", "cfg5", "cfg4_group_local"):
-                try:
-                    out["other_configs"][name] = measure_other_config(A, name.split("_")[0], dev_index, group_local=int(name.endswith("group_local")))
-                except Exception as e:      # a failure here must not cost the headline line
-                    out["other_configs"][name] = {"error": repr(e)}
-            try:      # the opt-in third tier of the Normal family (amwg_options::sufficient_statistics), beside the headline's pass kernel and full_evaluation
-                out["sufficient_statistics"] = measure_sufficient_statistics(A, spec, chains, dev_index)
-            except Exception as e:
-                out["sufficient_statistics"] = {"error": repr(e)}
-            if not args.no_js:
-                out["end_to_end_js"] = end_to_end_js(chains, n_obs)
-            o = out["other_configs"]
-            if "value" in o.get("cfg4", {}) and "value" in o.get("cfg4_group_local", {}):
-                o["cfg4_group_local"]["speedup_over_cfg4"] = o["cfg4_group_local"]["value"] / o["cfg4"]["value"]
-        if world == 1 and not args.no_cpu_baseline:
-            ref = cpu_baseline_reference(args.workload)
-            out["cpu_baseline"] = ref if ref is not None else cpu_baseline_port(spec)
-            if ref is not None:
-                out["cpu_baseline_port"] = cpu_baseline_port(spec, budget_s=3.0)
-            port_rate = (out.get("cpu_baseline_port") or out["cpu_baseline"])["value"]
-            out["cpu_baseline_all_cores"] = cpu_baseline_all_cores(spec, port_rate)
-            out["chains_equiv"] = value / out["cpu_baseline"]["value"]
+        if args.full:
+            full_record(out, args, A, s, spec, pooled, lib_moments, gathered_lib, draws, parity, dist=dist, rows=rows, chains=chains, offset=offset, dev_index=dev_index,
+                        li=li, n_obs=n_obs, ops_per_obs=ops_per_obs, b_alg=b_alg, launch_s=launch_s, updates_per_launch=updates_per_launch, regions=len(regions))
+        if outputs is not None:
+            out["outputs"] = write_outputs(args.dump_outputs, outputs)
         emit(out)
     s.close()
     if comm is not None:

@@ -160,3 +160,32 @@ def test_sweep_kernel_roofline_counts_one_certified_pass_per_step():
     # 3.4e9 updates/s of the 34-component model over 1e4 observations: 1e8 steps/s x 1 pass (the sweep's sums of squares; mu and sigma read no data) x 1e4 x 2 operations
     ops = bench.sweep_lane_ops(3.4e9, 34, 10_000)
     assert abs(ops - 3.4e9 / 34 * 1 * 10_000 * 2) < 1 and 0.04 < ops / bench.FP64_VALU_PEAK < 0.08
+
+
+def test_dump_outputs_are_float_npy_files_and_a_seeded_sample_keeps_them_under_the_limit(tmp_path):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 / float64; over the limit each keeps the same seeded sample of its chains in every run,
+    with the column numbers beside it, and everything written stays under the limit."""
+    import numpy as np
+    import bench
+    draws = np.arange(2 * 1000, dtype=np.float64).reshape(2, 1000)
+    small = bench.write_outputs(str(tmp_path / "a"), {"last_draws": draws, "flags": np.ones(3, dtype=np.int32)})
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["flags.npy", "last_draws.npy"]
+    assert np.load(str(tmp_path / "a" / "last_draws.npy")).tobytes() == draws.tobytes() and small["last_draws"]["shape"] == [2, 1000]
+    assert np.load(str(tmp_path / "a" / "flags.npy")).dtype == np.float64
+    limit = 4000
+    for run in ("b", "c"):
+        bench.write_outputs(str(tmp_path / run), {"last_draws": draws}, limit=limit)
+        assert sum(p.stat().st_size - 128 for p in (tmp_path / run).iterdir()) <= limit      # (128: the .npy header)
+    cols = np.load(str(tmp_path / "b" / "last_draws_columns.npy"))
+    got = np.load(str(tmp_path / "b" / "last_draws.npy"))
+    assert cols.dtype == np.float64 and got.dtype == np.float64 and got.shape == (2, cols.size) and 0 < cols.size < 1000
+    assert got.tobytes() == draws[:, cols.astype(np.int64)].tobytes()
+    for name in ("last_draws.npy", "last_draws_columns.npy"):
+        assert (tmp_path / "b" / name).read_bytes() == (tmp_path / "c" / name).read_bytes()
+
+
+def test_full_and_dump_outputs_are_options_of_the_bench():
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    text = p.stdout + p.stderr      # (stdout is kept for the one JSON line: the usage goes to stderr)
+    assert p.returncode == 0 and "--full" in text and "--dump-outputs" in text, text

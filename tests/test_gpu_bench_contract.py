@@ -28,7 +28,7 @@ def _bench(*extra, detail=False):
 
 
 def test_default_line_has_the_contract_fields_and_an_honest_roofline():
-    d, full = _bench("--chains-per-gpu", "4096", "--lanes", "1", detail=True)     # (one lane per chain, as the full-size default picks: reference order)
+    d, full = _bench("--full", "--chains-per-gpu", "4096", "--lanes", "1", detail=True)     # (one lane per chain, as the full-size default picks: reference order)
     for key, want in (("unit", "param-updates/s"), ("n_gpus", 1), ("steps", 5), ("warmup", 2), ("higher_is_better", True), ("scaling", "weak"),
                       ("vs_baseline", None), ("dtype", "f64"), ("data", "synthetic")):
         assert d[key] == want and full[key] == want, key
@@ -98,6 +98,31 @@ def test_default_line_has_the_contract_fields_and_an_honest_roofline():
     assert c["kind"] == "reference" or c.get("reference_unavailable") is True
 
 
+def test_plain_line_times_exactly_k_steps_once_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full: one region of exactly --steps steps, the contract's fields and nothing measured beside them (no parity schedule, roofline, other
+    configs or CPU baseline); --dump-outputs writes the last recorded draw of every chain, and two runs of the same arguments write the same bytes."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out_dir = tmp_path / ("run%d" % i)
+        d, full = _bench("--chains-per-gpu", "4096", "--dump-outputs", str(out_dir), detail=True)
+        for key, want in (("unit", "param-updates/s"), ("n_gpus", 1), ("steps", 5), ("warmup", 2), ("higher_is_better", True), ("dtype", "f64")):
+            assert d[key] == want, key
+        assert "param-updates" in d["metric"] and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 4096 * 5 * 2 / (d["ms_per_step"] * 5e-3)) < 1e-5 * d["value"]
+        assert full["timing"]["regions"] == 1 and full["timing"]["steps_per_region"] == 5 and len(full["timing"]["region_ms"]) == 1
+        assert abs(full["timing"]["region_ms"][0] - d["ms_per_step"] * 5) < 1e-5 * full["timing"]["region_ms"][0]
+        for k in ("roofline", "parity", "other_configs", "cpu_baseline", "end_to_end_js", "sufficient_statistics", "posterior"):
+            assert k not in full, k
+        files = sorted(p.name for p in out_dir.iterdir())
+        assert files == ["last_draws.npy"], files
+        a = np.load(str(out_dir / "last_draws.npy"))
+        assert a.dtype == np.float64 and a.shape == (2, 4096) and np.all(np.isfinite(a)) and np.all(a[1] > 0)      # (mu, sigma) of every chain; sigma > 0
+        assert full["outputs"]["last_draws"]["shape"] == [2, 4096]
+        runs.append(a)
+    assert runs[0].tobytes() == runs[1].tobytes()
+
+
 def test_gpus_n_without_a_launcher_never_leaves_without_a_line():
     """`python bench.py --gpus 2` with WORLD_SIZE unset (round-4 review: that was a SystemExit): the one-process multi-device path when two devices
     are visible, otherwise the "not measured" line -- rc 0 and one parseable line either way."""
@@ -117,7 +142,7 @@ def test_gpus_n_without_a_launcher_never_leaves_without_a_line():
 
 @pytest.mark.parametrize("workload", ["cfg3", "cfg4"])
 def test_other_workloads_report_a_roofline(workload):
-    d = _bench("--workload", workload, "--no-cpu-baseline", "--chains-per-gpu", "2048")
+    d = _bench("--full", "--workload", workload, "--no-cpu-baseline", "--chains-per-gpu", "2048")
     assert "cpu_baseline" not in d
     if workload == "cfg3":
         # value and roofline describe the same kernel: the pass-free default against vector issue (frac from the committed PMC profile of these kernel sources, or

@@ -75,8 +75,12 @@ def test_constructor_errors_are_the_references():
     assert p.returncode == 0 and "stepper host ok" in p.stdout, p.stdout + p.stderr
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/mcmc.js"), reason="the reference is only present in the build container")
 def test_committed_stepper_golden_is_what_the_reference_produces():
+    # (the generator loads the unmodified reference where oracle/ref_dir.js finds it: $AMWG_REF_DIR, or the pinned copy build() leaves in oracle/_ref)
+    q = subprocess.run([NODE, "-e", "process.stdout.write(require('./oracle/ref_dir.js').refDir() || '')"], cwd=ROOT, capture_output=True, text=True, timeout=60)
+    assert q.returncode == 0, q.stderr
+    if not q.stdout:
+        pytest.skip("the unmodified reference is not at hand: no $AMWG_REF_DIR and no oracle/_ref copy")
     p = subprocess.run([NODE, os.path.join(ROOT, "oracle", "gen_stepper_golden.js")], cwd=ROOT, capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stderr
     assert p.stdout == open(os.path.join(ROOT, "tests", "golden", "steppers.json")).read()

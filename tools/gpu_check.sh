@@ -10,7 +10,7 @@ cd $R
 python -m pytest tests -m gpu -q "$@" 2>&1 | tail -40 > $OUT/${TAG}_pytest_gpu.log
 tail -3 $OUT/${TAG}_pytest_gpu.log
 for W in cfg4 cfg2 cfg5 cfg3; do
-  python bench.py --workload $W --no-cpu-baseline --min-seconds 0.6 > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
+  python bench.py --full --workload $W --no-cpu-baseline --min-seconds 0.6 > $OUT/${TAG}_bench_$W.json 2> $OUT/${TAG}_bench_$W.err
   python - <<PY
 import json
 try:
@@ -20,8 +20,8 @@ except Exception as e:
     print("$W failed", e, open("$OUT/${TAG}_bench_$W.err").read()[-800:])
 PY
 done
-python bench.py --workload cfg4 --chains-per-gpu 16384 --no-cpu-baseline --min-seconds 0.6 > $OUT/${TAG}_bench_cfg4_16384.json 2>/dev/null
-python bench.py --workload readme --steps 20000 --warmup 2000 --thin 1 --no-cpu-baseline --min-seconds 0.5 > $OUT/${TAG}_bench_readme.json 2>/dev/null
+python bench.py --full --workload cfg4 --chains-per-gpu 16384 --no-cpu-baseline --min-seconds 0.6 > $OUT/${TAG}_bench_cfg4_16384.json 2>/dev/null
+python bench.py --full --workload readme --steps 20000 --warmup 2000 --thin 1 --no-cpu-baseline --min-seconds 0.5 > $OUT/${TAG}_bench_readme.json 2>/dev/null
 python - <<PY
 import json
 for n in ("cfg4_16384", "readme"):

@@ -11,7 +11,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 ARGS="${@:---steps 500 --warmup 1000}"   # (cfg4 / cfg5: add --weak to profile the per-GPU shard of the 8-GPU job, 2 048 / 8 192 chains)
-CMD="python $R/bench.py --no-cpu-baseline --single-region --no-other-configs --no-parity $ARGS"
+CMD="python $R/bench.py --full --no-cpu-baseline --single-region --no-other-configs --no-parity $ARGS"
 echo "$CMD" > $OUT/command.txt
 # (bench.py's stdout is the <= 4 KB line; the whole record -- what tools/summarize_profile.py reads -- is the detail file)
 AMWG_BENCH_DETAIL=$OUT/bench_under_trace.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $CMD > $OUT/bench_line.json 2> $OUT/trace_err.log
