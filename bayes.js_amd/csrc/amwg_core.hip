@@ -299,6 +299,34 @@ bool hier_rows_fit(const amwg_sampler *s, int bt, size_t max_lds) {
   return lds_layout(data, s->P, bt / 64, s->pl.max_top, s->n_params).total <= max_lds;
 }
 
+// DataRef::wave_scratch for the geometry in s->grid / s->block: one line of 64 doubles per wavefront of the launch (amwg_pass.h wave_scratch_of indexes it by
+// blockIdx.x * (blockDim.x / 64) + wavefront).  Only one-lane-per-chain kernels read it (the certified pass of the Normal family, a closure's certified tail); with the
+// replica fallback (cpb < 64 chains in a one-wavefront workgroup) that is C / cpb lines, not C / 64.  Grows, never shrinks: an autotune candidate's launch and the
+// adopted geometry find it large enough.  AMWG_WAVE_SCRATCH=0 (read while the sampler is constructed): none, the pass broadcasts with v_readlane.
+// Its size is the allocation's own (hipMemGetAddressRange); launch_steps checks the invariant.
+static size_t wave_scratch_lines(const amwg_sampler *s) {
+  if (!s->d.wave_scratch) return 0;
+  hipDeviceptr_t base = nullptr;
+  size_t bytes = 0;
+  if (hipMemGetAddressRange(&base, &bytes, s->d.wave_scratch) != hipSuccess || base != s->d.wave_scratch) return 0;
+  return bytes / (64 * sizeof(double));
+}
+static int size_wave_scratch(amwg_sampler *s) {
+  const char *env = getenv("AMWG_WAVE_SCRATCH");
+  if ((env && env[0] == '0') || s->lanes != 1) return AMWG_OK;
+  const size_t lines = (size_t)s->grid * (size_t)(s->block / 64);
+  if (s->d.wave_scratch && lines <= wave_scratch_lines(s)) return AMWG_OK;
+  double *p = nullptr;
+  const int rc = dev_alloc(s, &p, lines * 64);
+  if (rc != AMWG_OK) return rc;
+  if (s->d.wave_scratch) {
+    for (auto it = s->dev_allocs.begin(); it != s->dev_allocs.end(); ++it)
+      if (*it == s->d.wave_scratch) { (void)hipFree(*it); s->dev_allocs.erase(it); break; }
+  }
+  s->d.wave_scratch = p;
+  return AMWG_OK;
+}
+
 int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
   const amwg_options &o = s->opt;
   // cpb: chains per workgroup; 0 = blockDim / G.  A smaller value (one-wavefront workgroups only) is the fallback for models
@@ -393,7 +421,7 @@ int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
     s->d.pad = rows ? HierNormalModel::row_pitch(s->user_rows_n) : 0;
     s->user_sweep = rows && user_sweep_wanted(s, s->lanes, s->block, max_lds);
     s->certified = s->user_sweep ? user_rows_cert_wanted(s) : user_cert_wanted(s, s->lanes);      // (amwg_user_sweep_cert / amwg_user_step_cert)
-    return AMWG_OK;
+    return size_wave_scratch(s);
   }
   const bool rows = !s->mc.group_local && hier_rows_wanted(s, s->lanes) && hier_rows_fit(s, s->block, max_lds);
   if (s->model == AMWG_MODEL_NORMAL) s->d.pad = (s->lanes == 1 && normal_tile_wanted(s, s->block)) ? 1 : 0;
@@ -401,7 +429,7 @@ int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
   s->certified = s->kernel != nullptr;
   if (!s->kernel) s->kernel = s->mc.group_local ? amwg_kernel_hier_gl(s->block) : (rows ? amwg_kernel_hier_sweep(s->block) : pick_kernel(s->model, s->lanes, s->block));
   if (!s->kernel) return fail(AMWG_EINVAL, "no kernel for model %d with %d lanes per chain in workgroups of %d", s->model, s->lanes, s->block);
-  return AMWG_OK;
+  return size_wave_scratch(s);
 }
 
 // Optional tracing: roctx ranges around every burn/sample call, visible to `rocprofv3 --marker-trace`.
@@ -445,6 +473,8 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
   }
   // the invariants the kernel relies on, enforced where the launch is made (the kernel's own guards -- device_error -- are the backstop)
   if (s->cpb > 0 && s->block != 64) return fail(AMWG_EINVAL, "internal: %d chains per workgroup of %d threads (replicated chains need one-wavefront workgroups)", s->cpb, s->block);
+  if (s->lanes == 1 && s->d.wave_scratch && wave_scratch_lines(s) < (size_t)s->grid * (size_t)(s->block / 64))
+    return fail(AMWG_EINVAL, "internal: a wave scratch of %zu lines for %d workgroups of %d threads (one line per wavefront)", wave_scratch_lines(s), s->grid, s->block);
   if (chunk > 65535) return fail(AMWG_EINVAL, "internal: launches of %lld steps (at most 65535)", (long long)chunk);
   StepArgs a{};
   a.C = s->C;
@@ -465,6 +495,7 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
 #endif
   a.mc = s->mc;
   a.d = s->d;
+  if (s->lanes != 1) a.d.wave_scratch = nullptr;      // (sized for one-lane geometries only; no other kernel reads it)
   a.ch = s->ch;
   // (a 0-step finalize launch on chains that have stepped -- amwg_chain_diag asking for the expression's value after a certified kernel ran -- is not "the latest call":
   // the sample call's launch count, its per-launch marks and its event pair stay, so that a diag() between sample_async and fetch_draws neither loses the copy overlap
@@ -816,12 +847,8 @@ static int alloc_chain_state(amwg_sampler *s, const amwg_param_desc *params, int
   TRYB(dev_alloc(s, &ch.lp_curr, C));
   TRYB(dev_alloc(s, &ch.lp_eps, C));
   // (64 doubles per wavefront of a one-lane-per-chain launch: where the certified pass of the Normal family / a closure's certified tail leaves the wavefront's means for the
-  // scalar memory path, amwg_pass.h norm_sq_pass_wave.  C / 64 wavefronts + the last workgroup's spare ones; AMWG_WAVE_SCRATCH=0: none, the pass broadcasts with v_readlane)
+  // scalar memory path, amwg_pass.h norm_sq_pass_wave.  Allocated once the geometry is known: size_wave_scratch)
   s->d.wave_scratch = nullptr;
-  {
-    const char *env = getenv("AMWG_WAVE_SCRATCH");
-    if (!(env && env[0] == '0')) TRYB(dev_alloc(s, &s->d.wave_scratch, ((size_t)C / 64 + 64) * 64));
-  }
   TRYB(dev_alloc(s, &ch.error, (size_t)1));
   ch.audit = nullptr;
   ch.audit_hist = nullptr;
@@ -1110,6 +1137,7 @@ static int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, Prepare
   s->lanes = c.lanes; s->block = c.block; s->grid = c.grid; s->lds = c.lds; s->cpb = c.cpb; s->kernel = c.kernel; s->user_module = c.module; s->user_fn = c.fn;
   s->certified = s->user ? (c.sweep ? user_rows_cert_wanted(s) : user_cert_wanted(s, c.lanes)) : (c.kernel != nullptr && c.kernel == pick_certified_kernel(s->model, c.lanes, c.block));
   s->d.pad = c.pad; s->user_sweep = c.sweep;      // (the row layout and the sweep kernel go with the geometry)
+  if (int rc = size_wave_scratch(s); rc != AMWG_OK) return rc;
   s->tuned.clear();
   for (auto &q : cand) s->tuned.push_back({q.lanes, q.ms});
   s->n_launches = 0;
@@ -1222,7 +1250,9 @@ int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t
     // amwg_options::sufficient_statistics: the two sufficient statistics of the Normal likelihood, in quad precision -- xbar as a double-double (its error must stay
     // far below an ulp of xbar - mu when mu sits next to the data: 2^-106 |xbar|), SS = sum (x_i - xbar)^2 rounded once
     if (m->model != AMWG_MODEL_NORMAL) return bail(fail(AMWG_EINVAL, "sufficient_statistics: only the Normal family has a pass-free certified value"));
-    if (options->lanes_per_chain > 1) return bail(fail(AMWG_EINVAL, "sufficient_statistics decides from the one-lane certified kernel: lanes_per_chain must be 0 or 1"));
+    // (AMWG_LANES_AUTOTUNE would time -- and could keep -- a multi-lane kernel, which never reads mc.sufficient; AMWG_LANES_FASTEST is taken as 1 below)
+    if (options->lanes_per_chain > 1 || options->lanes_per_chain == AMWG_LANES_AUTOTUNE)
+      return bail(fail(AMWG_EINVAL, "sufficient_statistics decides from the one-lane certified kernel: lanes_per_chain must be 0, 1 or AMWG_LANES_FASTEST, got %d", options->lanes_per_chain));
     __float128 sum = 0;
     for (int i = 0; i < N; ++i) sum += (__float128)m->x[i];
     const __float128 xbar = N > 0 ? sum / (__float128)N : (__float128)0;

@@ -346,6 +346,16 @@ const BENCH = {
       for (var i = 0; i < data.x.length; i++) lp += ld.norm(data.x[i], state.a + 0.5 * state.b, 1 / Math.sqrt(state.tau));
       return lp;
     } },
+  // (the certified tail with per-chain state too large for 64 chains' LDS: dim [300] at one lane per chain takes the replica fallback -- 64-thread workgroups that
+  // hold fewer than 64 chains each, so more wavefronts than C / 64; tests/test_gpu_geometry.py)
+  bench_replica_tail: { params: () => ({ theta: { dim: [300], init: 0 }, mu: { type: 'real' }, sigma: { type: 'real', lower: 0 } }),
+    data: () => ({ x: synth.normal(1000, 20260930).x }),
+    log_post: function(state, data) {
+      var lp = ld.norm(state.mu, 0, 100) + ld.unif(state.sigma, 0, 100);
+      for (var g = 0; g < 300; g++) lp += ld.norm(state.theta[g], state.mu, 1);
+      for (var i = 0; i < data.x.length; i++) lp += ld.norm(data.x[i], state.mu, state.sigma);
+      return lp;
+    } },
   bench_hier: { params: CASES.hier_normal_closure.params, data: () => synth.hier(10000, 32, 20260925), log_post: CASES.hier_normal_closure.log_post },
   bench_glm: { params: CASES.pois_glm_closure.params, data: () => synth.glm(50000, 20260925), log_post: CASES.pois_glm_closure.log_post },
   // (round 6, the certified Poisson tail of translate.js poisTailPlan on its FALLBACK paths -- csrc/amwg_ptail.h: a predictor that is not linear (a product of two

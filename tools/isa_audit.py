@@ -159,6 +159,102 @@ def loop_stats(lines):
     return {"in_loops": cnt, "whole_kernel": tot, "loops": len(depth_marks)}
 
 
+# INLINE SCALAR LOADS.  norm_sq_pass_wave (csrc/amwg_pass.h) fetches the wavefront's means with s_load_dwordx16 from inline asm and waits for them with an
+# `s_waitcnt lgkmcnt(0)` of its own: the compiler's wait-count pass does not track loads it did not emit.  Rule: every s_load_dwordx16 inside an inline-asm region
+# (;;#ASMSTART .. ;;#ASMEND) reaches an s_waitcnt with lgkmcnt(0) before any instruction that reads or writes one of its destination SGPRs, and before any label or
+# branch; a checked kernel must contain at least one such load.
+INLINE_SMEM_KERNELS = ["NormalModel,1,256,cert", "NormalModel,1,512,cert"]
+_SREG = re.compile(r"\bs\[(\d+):(\d+)\]|\bs(\d+)\b")
+
+
+def _sgprs(operands):
+    out = set()
+    for m in _SREG.finditer(operands):
+        if m.group(3) is not None:
+            out.add(int(m.group(3)))
+        else:
+            out.update(range(int(m.group(1)), int(m.group(2)) + 1))
+    return out
+
+
+def inline_smem_waits(lines):
+    """-> (number of s_load_dwordx16 inside inline-asm regions, [violations]) for one kernel body"""
+    items, in_asm = [], False
+    for ln in lines:
+        raw = ln.strip()
+        if raw.startswith(";;#ASMSTART"):
+            in_asm = True
+            continue
+        if raw.startswith(";;#ASMEND"):
+            in_asm = False
+            continue
+        s = raw.split(";")[0].strip()
+        if not s:
+            continue
+        if re.match(r"^[.\w]+:", s):
+            items.append(("label", s, in_asm))
+        elif not s.startswith("."):
+            items.append(("ins", s, in_asm))
+    loads, bad = 0, []
+    for i, (kind, s, in_asm) in enumerate(items):
+        if kind != "ins" or not in_asm or s.split()[0] != "s_load_dwordx16":
+            continue
+        loads += 1
+        dst = _sgprs(s.split(None, 1)[1].split(",")[0])
+        for kind2, s2, _ in items[i + 1:]:
+            op = s2.split()[0]
+            if kind2 == "label":
+                bad.append("%s: a label (%s) before s_waitcnt lgkmcnt(0)" % (s, s2))
+                break
+            if op == "s_waitcnt" and re.search(r"\blgkmcnt\(0\)", s2):
+                break
+            if op.startswith("s_branch") or op.startswith("s_cbranch") or op in ("s_setpc_b64", "s_swappc_b64", "s_endpgm"):
+                bad.append("%s: a branch (%s) before s_waitcnt lgkmcnt(0)" % (s, s2))
+                break
+            used = _sgprs(s2.split(None, 1)[1]) if len(s2.split(None, 1)) > 1 else set()
+            if used & dst:
+                bad.append("%s: `%s` touches its registers before s_waitcnt lgkmcnt(0)" % (s, s2))
+                break
+        else:
+            bad.append("%s: no s_waitcnt lgkmcnt(0) after it" % s)
+    return loads, bad
+
+
+def user_cert_asm(name="bench_normal", lanes=1, block=256):
+    """device assembly of amwg_user_step_cert of a translated closure (tests/js/user_models.js), compiled with hipcc -S from the program amwg_core.hip
+    hands to hiprtc for that geometry (user_program: the closure's text + the kernel wrapper); None when node is not installed"""
+    import shutil
+    if shutil.which("node") is None:
+        return None
+    sys.path[:0] = [os.path.join(ROOT, "tests")]
+    import user_host
+    src, _, meta = user_host.translated(name)
+    assert meta["cert_tail_n"] > 0, "%s has no certified tail" % name
+    prog = ('#include "amwg_kernel.h"\n#include "amwg_user.h"\n' + src +
+            '\nextern "C" __global__ void __launch_bounds__(%d) amwg_user_step_cert(const amwg::StepArgs a) {\n'
+            '  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n'
+            '  if constexpr (amwg::CertifiedAt<amwg::UserModel, %d>::value && !amwg::CertNeedsRows<amwg::UserModel>::value) amwg::step_body<amwg::UserModel, %d, %d, false, false, true>(a, smem);\n}\n'
+            % (block, lanes, lanes, 256 if block <= 256 else 1024))
+    d = tempfile.mkdtemp(prefix="amwg_user_isa_")
+    f, out = os.path.join(d, "u.hip"), os.path.join(d, "u.s")
+    open(f, "w").write(prog)
+    subprocess.check_call([HIPCC] + FLAGS + ["-I", CSRC, "-o", out, f], stderr=subprocess.DEVNULL)
+    return out
+
+
+def user_kernel_body(txt, symbol):
+    body, cur = [], None
+    for line in txt.splitlines():
+        if cur is None and line.startswith(symbol + ":"):
+            cur = body
+            continue
+        if cur is not None:
+            if line.startswith(".Lfunc_end"):
+                break
+            cur.append(line)
+    return body
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--asm", nargs="*", help="existing device assembly files (else amwg_kernels.hip is compiled for --families)")
@@ -174,7 +270,7 @@ def main():
         import concurrent.futures
         with concurrent.futures.ThreadPoolExecutor(4) as ex:
             asms = list(ex.map(compile_asm, args.families))
-    rows, bad = [], []
+    rows, bad, smem_checked = [], [], {}
     for asm in asms:
         txt = open(asm).read()
         meta, bodies = kernel_metadata(txt), kernel_bodies(txt)
@@ -188,6 +284,8 @@ def main():
             st = loop_stats(bodies.get(n, []))
             row = {"kernel": short, **meta[n], **{"loop_" + k: v for k, v in st["in_loops"].items()}, "total_instructions": st["whole_kernel"]["instructions"]}
             rows.append(row)
+            if short in INLINE_SMEM_KERNELS:
+                smem_checked[short] = inline_smem_waits(bodies.get(n, []))
             gated = short in args.gate
             row["gated"] = gated
             if gated:
@@ -204,6 +302,17 @@ def main():
                     why.append("%d v_readlane/v_writelane inside loops (> %d)" % (row["loop_lane_moves"], args.max_lane_moves))
                 if why:
                     bad.append((short, why))
+    if not args.asm and 0 in args.families:
+        for k in INLINE_SMEM_KERNELS:
+            smem_checked.setdefault(k, (0, []))
+        user = user_cert_asm()
+        if user is not None:
+            smem_checked["amwg_user_step_cert(bench_normal,1,256)"] = inline_smem_waits(user_kernel_body(open(user).read(), "amwg_user_step_cert"))
+    for k, (n_loads, why) in sorted(smem_checked.items()):
+        if n_loads == 0:
+            why = why + ["no s_load_dwordx16 inside an inline-asm region: the rule checked nothing"]
+        if why:
+            bad.append((k, why[:5]))
     rows.sort(key=lambda r: r["kernel"])
     hdr = "%-34s %5s %5s %6s %6s %7s %6s | %7s %7s %7s %7s %7s" % ("kernel<Model,G,BT>", "vgpr", "sgpr", "vspill", "sspill", "scratch", "maxwg", "l.instr", "l.valu", "l.scr", "l.lane", "l.wait")
     print(hdr)
@@ -219,6 +328,9 @@ def main():
         sys.exit(1)
     print("isa audit ok: %d gated instantiations: no scratch traffic inside a pass; no VGPR spill and no scratch traffic in the loops of the <= 512-thread classes "
           "except the documented allowances (%s); SGPR-spill moves within %d" % (sum(r["gated"] for r in rows), ", ".join(sorted(SPILL_ALLOW)), args.max_lane_moves))
+    if smem_checked:
+        print("isa audit ok: inline s_load_dwordx16 waited for (lgkmcnt(0)) before any use of their registers, label or branch: %s"
+              % ", ".join("%s %d" % (k, n) for k, (n, _) in sorted(smem_checked.items())))
 
 
 if __name__ == "__main__":
