@@ -41,7 +41,8 @@ using namespace amwg;
 // together with the very same step kernel source the built-in models are compiled from.
 extern "C" {
 extern const char amwg_hdr_stdint[], amwg_hdr_types[], amwg_hdr_math[], amwg_hdr_div[], amwg_hdr_ld[], amwg_hdr_philox[],
-    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[];
+    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[],
+    amwg_hdr_user_kernels[];
 }
 
 // the step kernels of the built-in families, one translation unit each (amwg_kernels.hip): kernel for (lanes per chain, workgroup size)
@@ -209,6 +210,79 @@ int gl_layout(const double *y, const int32_t *g, int N, int Gn, GlLayoutHost *ou
   return AMWG_OK;
 }
 
+// ---- The launch plan: variant_for decides the kernel of a geometry, choose_geometry picks the geometry, adopt_plan sets what goes with it.
+// Per variant: the kernel's name (a translated closure's: its hiprtc symbol, amwg_user_kernels.h) and whether it decides accept tests from certified values
+// (amwg_kernel.h kCert).  The certified kernels evaluate the expression in the reference's order: their summation order is 1.
+struct VariantInfo { const char *name; bool certified; };
+const VariantInfo kVariants[] = {
+    {"amwg_step_kernel", false}, {"amwg_step_kernel_cert", true}, {"amwg_sweep_kernel", false}, {"amwg_sweep_kernel_cert", true}, {"amwg_gl_kernel", false},
+    {"amwg_user_step", false}, {"amwg_user_step_cert", true}, {"amwg_user_sweep", false}, {"amwg_user_sweep_cert", true}};
+const VariantInfo &info(Variant v) { return kVariants[(int)v]; }
+
+// The kernel G lanes per chain in workgroups of bt threads with max_lds bytes of LDS run, and its DataRef::pad: the plan's lanes, block, variant and pad.
+//   * certified decisions unless full_evaluation or exact_division ask for the expression: the Normal family at one lane per chain, the Poisson family at
+//     16, the hierarchical family's sweep kernel; a closure without binary parameters with a certified tail (amwg_user.h norm_tail_approx: one lane;
+//     amwg_ptail.h pois_tail_approx: 16 lanes, four chains sharing every row they read) or a row plan marked kRowCert (amwg_rows.h);
+//   * the row layout (lane-local re-evaluation) of the hierarchical family and of a closure's row plan (amwg_rows.h): a chain on one wavefront, not
+//     switched off, the tile, the label bytes and the per-wavefront term rows beside the stepper state.  Its sweep kernels are compiled for at most 512
+//     threads: a caller who ASKS for 1024 gets the kernel that evaluates everything, not a "no launch geometry fits" that names the wrong cause.  A
+//     closure sweeps when a lane's sum depends on one entry of the swept vector (rows_sweep), no parameter is binary (BinaryStepper draws differently)
+//     and every parameter vector fits the lanes of a wavefront;
+//   * the Normal family at one lane per chain stages its observations in LDS for the certified pass (NormalModel::lds_bytes_of: pad = 1) in workgroups
+//     of at most 512 threads, unless sufficient statistics replace the pass.
+LaunchPlan variant_for(const amwg_sampler *s, int G, int bt, size_t max_lds) {
+  const amwg_options &o = s->opt;
+  LaunchPlan p;
+  p.lanes = G, p.block = bt;
+  const bool decide_certified = o.full_evaluation == 0 && !o.exact_division;
+  const bool rows_wanted = G == 64 && o.full_evaluation != 1 && !(o.block_threads > 512);
+  auto rows_fit = [&](int pitch, int groups) {
+    return lds_layout(HierNormalModel::rows_lds_bytes(pitch, bt / 64, groups), s->P, bt / 64, s->pl.max_top, s->n_params).total <= max_lds;
+  };
+  if (s->user) {
+    const bool rows = rows_wanted && s->user_rows_n >= 64 && s->user_rows_groups >= 1 && s->user_rows_groups <= 64 && bt <= 512 &&
+                      rows_fit(HierNormalModel::row_pitch(s->user_rows_n), s->user_rows_groups);
+    const bool cert = decide_certified && !s->user_has_binary;
+    p.pad = rows ? HierNormalModel::row_pitch(s->user_rows_n) : 0;
+    if (rows && s->user_rows_sweep && !s->user_has_binary && s->pl.max_top <= 64)
+      p.variant = cert && s->user_rows_cert ? Variant::UserSweepCert : Variant::UserSweep;
+    else
+      p.variant = cert && ((s->user_cert_tail_n > 0 && G == 1) || (s->user_pois_tail_n > 0 && G == 16)) ? Variant::UserStepCert : Variant::UserStep;
+    return p;
+  }
+  if (s->mc.group_local) { p.variant = Variant::GroupLocal, p.pad = s->gl_rounds; return p; }
+  const bool rows = s->model == AMWG_MODEL_HIER_NORMAL && rows_wanted && ((s->hier_periodic_mask >> 6) & 1u) && s->d.G <= 64 && s->d.n_obs >= 64 &&
+                    rows_fit(HierNormalModel::row_pitch(s->d.n_obs), s->d.G);
+  const bool cert = decide_certified && ((s->model == AMWG_MODEL_NORMAL && G == 1) || (s->model == AMWG_MODEL_POIS_GLM && G == 16) || rows) &&
+                    pick_certified_kernel(s->model, G, bt) != nullptr;
+  p.variant = rows ? (cert ? Variant::HierSweepCert : Variant::HierSweep) : (cert ? Variant::StepCert : Variant::Step);
+  p.pad = rows ? HierNormalModel::row_pitch(s->d.n_obs) : ((cert && s->model == AMWG_MODEL_NORMAL && bt <= 512 && !o.sufficient_statistics) ? 1 : 0);
+  return p;
+}
+
+// does the plan use the row layout (the hierarchical family's sweep kernels; a closure's row plan)?
+bool row_layout(const amwg_sampler *s, const LaunchPlan &p) {
+  return p.variant == Variant::HierSweep || p.variant == Variant::HierSweepCert || (s->user && p.pad > 0);
+}
+
+// LDS bytes of a workgroup of the plan: the data its variant stages, then the stepper state of `cpb` chains (0: block / lanes).  cpb < block / lanes
+// (one-wavefront workgroups only) is the fallback for models whose per-chain state is so large that 64 / G copies do not fit: the spare lane groups
+// replicate the last chain.
+uint32_t lds_of(const amwg_sampler *s, const LaunchPlan &p, int cpb = 0) {
+  const int G = p.lanes, bt = p.block;
+  size_t data = 0;
+  switch (p.variant) {
+    case Variant::GroupLocal: data = HierGlModel::gl_lds_bytes(p.pad, bt / 64); break;
+    case Variant::HierSweep: case Variant::HierSweepCert: data = HierNormalModel::rows_lds_bytes(p.pad, bt / 64, s->d.G); break;
+    case Variant::Step: case Variant::StepCert:
+      data = (s->model == AMWG_MODEL_NORMAL && G == 1) ? (p.pad ? NormalModel::one_lane_tile_bytes(s->d.n_obs) : 0) : model_lds_bytes(s->model, s->d.n_obs, s->d.G, G);
+      break;
+    default:      // a translated closure: its row plan, else the translator's figure
+      data = p.pad ? HierNormalModel::rows_lds_bytes(p.pad, bt / 64, s->user_rows_groups) : (size_t)(G == 1 ? s->user_lds_one_lane : s->user_lds);
+  }
+  return G > 64 ? lds_layout(data, s->P, G / 64, s->pl.max_top, s->n_params, true).total : lds_layout(data, s->P, cpb ? cpb : bt / G, s->pl.max_top, s->n_params).total;
+}
+
 // Geometry.  For every lanes-per-chain G take the largest workgroup that still gives every CU a workgroup (more waves
 // share one LDS copy of the data) and price it with a two-term model of one parameter update:
 //     cost(G) = rounds * [ S(G) * max(w_res, 1.8) + (W / G) * max(w_res, 1.15) * (1 + 0.3 / w_res) ]
@@ -217,32 +291,13 @@ int gl_layout(const double *y, const int32_t *g, int N, int Gn, GlLayoutHost *ou
 // such batches; the floors are the occupancies below which each part is latency- rather than issue-bound.  The cheapest
 // G wins, ties go to the smaller G.  The choice depends only on the model, the data size and the chain count, so a
 // given sampler configuration always gets the same G (the lane count fixes the summation order, hence the draws).
-bool hier_rows_wanted(const amwg_sampler *s, int G);
-// would this geometry run a kernel that decides from certified values (amwg_kernel.h kCert)?  The Normal family at one lane per chain, the Poisson family at 16,
-// the hierarchical family's sweep kernel (64 lanes, the row layout in use); options.full_evaluation = 0, no exact_division, no group_local, not a closure
-static bool certified_wanted(const amwg_sampler *s, int lanes, bool rows) {
-  if (s->user || s->opt.full_evaluation != 0 || s->opt.exact_division || s->mc.group_local) return false;
-  return (s->model == AMWG_MODEL_NORMAL && lanes == 1) || (s->model == AMWG_MODEL_POIS_GLM && lanes == 16) || (s->model == AMWG_MODEL_HIER_NORMAL && lanes == 64 && rows);
-}
-bool hier_rows_fit(const amwg_sampler *s, int bt, size_t max_lds);
-// the Normal family at one lane per chain stages its observations in LDS only for the wavefront's certified pass (NormalModel::lds_bytes_of: DataRef::pad = 1)
-static bool normal_tile_wanted(const amwg_sampler *s, int bt) { return !s->user && s->model == AMWG_MODEL_NORMAL && certified_wanted(s, 1, false) && bt <= 512 && !s->opt.sufficient_statistics; }
-// ... a translated closure with a certified tail (amwg_user.h norm_tail_approx; read off the generated source by amwg_create_user): one lane per chain
-// ... or a certified Poisson tail (amwg_ptail.h pois_tail_approx; kPoisTail of the generated source): 16 lanes per chain, four chains sharing every row they read
-static bool user_cert_wanted(const amwg_sampler *s, int lanes) {
-  if (!s->user || s->opt.full_evaluation != 0 || s->opt.exact_division || s->user_has_binary) return false;
-  return (s->user_cert_tail_n > 0 && lanes == 1) || (s->user_pois_tail_n > 0 && lanes == 16);
-}
-// ... and a closure whose row plan the translator marked kRowCert: the sweep kernel decides from certified values, against the expression in the reference's order
-static bool user_rows_cert_wanted(const amwg_sampler *s) { return s->user && s->user_rows_cert && s->opt.full_evaluation == 0 && !s->opt.exact_division && !s->user_has_binary; }
-bool user_rows_wanted(const amwg_sampler *s, int G);
-bool user_rows_fit(const amwg_sampler *s, int bt, size_t max_lds);
-
+// W is priced for the kernel G lanes would run in 256-thread workgroups with 160 KB of LDS, whatever the device.
 double model_work(const amwg_sampler *s, int G) {
+  const LaunchPlan q = variant_for(s, G, 256, (size_t)160 * 1024);
   const double N = (double)s->d.n_obs;
   switch (s->model) {
     // (one lane per chain: accept tests are decided from the certified pass -- two operations per observation -- unless the caller asked for the expression in every update)
-    case AMWG_MODEL_NORMAL: return (G == 1 && s->opt.full_evaluation == 0 && !s->opt.exact_division) ? (s->opt.sufficient_statistics ? 40.0 : 2.6 * N) : 9.0 * N;
+    case AMWG_MODEL_NORMAL: return q.variant == Variant::StepCert ? (s->opt.sufficient_statistics ? 40.0 : 2.6 * N) : 9.0 * N;
     case AMWG_MODEL_BETA_BERN:   // one lane: exact fast-forward over ~log2(N) binades (or the scalar jump-table pass, one add per observation)
       return G == 1 ? (s->mc.exact_division ? 1.8 * N : 400.0 * (1.0 + std::log2(N + 2.0))) : 6.0 * N;
     case AMWG_MODEL_HIER_NORMAL: {
@@ -254,52 +309,27 @@ double model_work(const amwg_sampler *s, int G) {
       double w = (periodic ? 8.6 : 12.0) * N + 12.0 * s->d.G;
       // lane-local re-evaluation (row layout): of the G + 2 updates of a step only two make the full pass, the others re-form the sums of
       // the lanes of one group (~0.3 of a pass in time: a dependent chain on one lane)
-      if (hier_rows_wanted(s, G) && hier_rows_fit(s, 256, (size_t)160 * 1024)) w *= (2.0 + 0.35 * s->d.G) / (2.0 + s->d.G);
+      if (row_layout(s, q)) w *= (2.0 + 0.35 * s->d.G) / (2.0 + s->d.G);
       return w;
     }
-    case AMWG_MODEL_POIS_GLM: return (G == 16 && s->opt.full_evaluation == 0 && !s->opt.exact_division) ? 36.0 * N : 90.0 * N;      // (16 lanes per chain: the certified pass, four chains sharing every row they read)
+    case AMWG_MODEL_POIS_GLM: return q.variant == Variant::StepCert ? 36.0 * N : 90.0 * N;      // (16 lanes per chain: the certified pass, four chains sharing every row they read)
   }
-  if (user_cert_wanted(s, G) && s->user_pois_tail_n > 0) {      // exp + log per observation (~70 of the term's operations) become exp_bounded's 19, and a row is read once for four chains
+  if (q.variant == Variant::UserStepCert && s->user_pois_tail_n > 0) {      // exp + log per observation (~70 of the term's operations) become exp_bounded's 19, and a row is read once for four chains
     const double n = (double)s->user_pois_tail_n, w = s->user_work > 0 ? s->user_work : 1e6;
     return (w - 70.0 * n > 0.4 * w) ? w - 70.0 * n : 0.4 * w;
   }
-  if (user_cert_wanted(s, G)) {      // the tail loop's ~16 instructions per observation become the certified pass's 2.6
+  if (q.variant == Variant::UserStepCert) {      // the tail loop's ~16 instructions per observation become the certified pass's 2.6
     const double w1 = s->user_work_one_lane > 0 ? s->user_work_one_lane : s->user_work, n = (double)s->user_cert_tail_n;
     return (w1 - 16.0 * n > 0 ? w1 - 16.0 * n : 0.0) + 2.6 * n;
   }
   if (G == 1 && s->user_work_one_lane > 0) return s->user_work_one_lane;   // translated closure with a two-valued sum: fast-forwarded
   double w = s->user_work > 0 ? s->user_work : 1e6;   // translated closure: the translator's estimate
   // row plan (lane-local re-evaluation, like the hierarchical family's): of the groups + 2 updates of a step only a few make the full pass
-  if (user_rows_wanted(s, G) && user_rows_fit(s, 256, (size_t)160 * 1024)) w *= (2.0 + 0.35 * s->user_rows_groups) / (2.0 + s->user_rows_groups);
+  if (row_layout(s, q)) w *= (2.0 + 0.35 * s->user_rows_groups) / (2.0 + s->user_rows_groups);
   return w;
 }
 
-// the hierarchical family's row layout (amwg_models.h: lane-local re-evaluation): a chain on one wavefront, labels that repeat with the lane
-// stride, not switched off -- and the tile, the label bytes and the per-wavefront term rows must fit beside the stepper state.  The sweep kernel that
-// goes with it is compiled for workgroups of at most 512 threads: a caller who ASKS for more (options.block_threads = 1024) gets the kernel that
-// evaluates everything, as before round 4, instead of a "no launch geometry fits" that names the wrong cause
-bool hier_rows_wanted(const amwg_sampler *s, int G) {
-  return !(s->opt.block_threads > 512) && !s->user && s->model == AMWG_MODEL_HIER_NORMAL && !s->mc.group_local && s->opt.full_evaluation != 1 && G == 64 && ((s->hier_periodic_mask >> 6) & 1u) && s->d.G <= 64 && s->d.n_obs >= 64;
-}
-// a translated closure with a row plan (amwg_rows.h; translate.js): the same layout, LDS bytes by the same formula (UserRows<M> has HierNormalModel's)
-bool user_rows_wanted(const amwg_sampler *s, int G) {
-  return s->user && s->user_rows_n >= 64 && s->user_rows_groups >= 1 && s->user_rows_groups <= 64 && s->opt.full_evaluation != 1 && !(s->opt.block_threads > 512) && G == 64;
-}
-size_t user_rows_bytes(const amwg_sampler *s, int bt) { return HierNormalModel::rows_lds_bytes(HierNormalModel::row_pitch(s->user_rows_n), bt / 64, s->user_rows_groups); }
-bool user_rows_fit(const amwg_sampler *s, int bt, size_t max_lds) {
-  return bt <= 512 && lds_layout(user_rows_bytes(s, bt), s->P, bt / 64, s->pl.max_top, s->n_params).total <= max_lds;
-}
-// ... and the sweep prefetch with it, when the translator proved that a lane's sum depends on one entry of the swept vector (rows_sweep), the
-// model has no binary parameter (BinaryStepper draws differently) and the order of every parameter vector fits the lanes of a wavefront
-bool user_sweep_wanted(const amwg_sampler *s, int G, int bt, size_t max_lds) {
-  return user_rows_wanted(s, G) && user_rows_fit(s, bt, max_lds) && s->user_rows_sweep && !s->user_has_binary && s->pl.max_top <= 64;
-}
-bool hier_rows_fit(const amwg_sampler *s, int bt, size_t max_lds) {
-  const size_t data = HierNormalModel::rows_lds_bytes(HierNormalModel::row_pitch(s->d.n_obs), bt / 64, s->d.G);
-  return lds_layout(data, s->P, bt / 64, s->pl.max_top, s->n_params).total <= max_lds;
-}
-
-// DataRef::wave_scratch for the geometry in s->grid / s->block: one line of 64 doubles per wavefront of the launch (amwg_pass.h wave_scratch_of indexes it by
+// DataRef::wave_scratch for the geometry in s->plan: one line of 64 doubles per wavefront of the launch (amwg_pass.h wave_scratch_of indexes it by
 // blockIdx.x * (blockDim.x / 64) + wavefront).  Only one-lane-per-chain kernels read it (the certified pass of the Normal family, a closure's certified tail); with the
 // replica fallback (cpb < 64 chains in a one-wavefront workgroup) that is C / cpb lines, not C / 64.  Grows, never shrinks: an autotune candidate's launch and the
 // adopted geometry find it large enough.  AMWG_WAVE_SCRATCH=0 (read while the sampler is constructed): none, the pass broadcasts with v_readlane.
@@ -313,8 +343,8 @@ static size_t wave_scratch_lines(const amwg_sampler *s) {
 }
 static int size_wave_scratch(amwg_sampler *s) {
   const char *env = getenv("AMWG_WAVE_SCRATCH");
-  if ((env && env[0] == '0') || s->lanes != 1) return AMWG_OK;
-  const size_t lines = (size_t)s->grid * (size_t)(s->block / 64);
+  if ((env && env[0] == '0') || s->plan.lanes != 1) return AMWG_OK;
+  const size_t lines = (size_t)s->plan.grid * (size_t)(s->plan.block / 64);
   if (s->d.wave_scratch && lines <= wave_scratch_lines(s)) return AMWG_OK;
   double *p = nullptr;
   const int rc = dev_alloc(s, &p, lines * 64);
@@ -327,44 +357,38 @@ static int size_wave_scratch(amwg_sampler *s) {
   return AMWG_OK;
 }
 
-int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
+// The plan for lanes_per_chain `lanes` (0 = auto, AMWG_LANES_FASTEST, or one lane count: autotune_geometry asks for each in turn).  No HIP calls, no writes
+// to the sampler: adopt_plan does the rest.
+int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds, LaunchPlan *out) {
   const amwg_options &o = s->opt;
-  // cpb: chains per workgroup; 0 = blockDim / G.  A smaller value (one-wavefront workgroups only) is the fallback for models
-  // whose per-chain state is so large that 64 / G copies do not fit LDS: the spare lane groups replicate the last chain.
-  auto layout = [&](int bt, int G, int cpb = 0) {
-    const size_t data_bytes = s->user ? ((user_rows_wanted(s, G) && user_rows_fit(s, bt, max_lds)) ? user_rows_bytes(s, bt) : (size_t)(G == 1 ? s->user_lds_one_lane : s->user_lds))
-                              : (s->mc.group_local ? HierGlModel::gl_lds_bytes(s->d.pad, bt / 64)
-                                 : ((hier_rows_wanted(s, G) && hier_rows_fit(s, bt, max_lds)) ? HierNormalModel::rows_lds_bytes(HierNormalModel::row_pitch(s->d.n_obs), bt / 64, s->d.G)
-                                    : ((!s->user && s->model == AMWG_MODEL_NORMAL && G == 1) ? (normal_tile_wanted(s, bt) ? NormalModel::one_lane_tile_bytes(s->d.n_obs) : 0)
-                                       : model_lds_bytes(s->model, s->d.n_obs, s->d.G, G))));
-    return G > 64 ? lds_layout(data_bytes, s->P, G / 64, s->pl.max_top, s->n_params, true) : lds_layout(data_bytes, s->P, cpb ? cpb : bt / G, s->pl.max_top, s->n_params);
-  };
   const int max_bt = s->user ? s->user_max_threads : model_max_threads(s->model);
-  // (the hierarchical family's sweep kernel -- row layout, 64 lanes per chain -- keeps the window stream and the sweep's per-lane values in registers:
-  // compiled for at most 512 threads, where a lane has 256 of them; with the 128 of a 1024-thread workgroup it ran from scratch memory, five times slower)
-  // (one lane per chain with certified decisions -- the Normal family, a closure with a certified tail --: the wavefront's pass keeps 64 partial sums per lane: the 512
-  // registers of a 256-thread workgroup with blocks of 16 observations, the 256 of a 512-thread one with blocks of 8 (round 6, last day: 9 spilled registers; 1.58e9 against
-  // the 256-thread class's 1.55e9 at >= 131 072 chains, where 512-thread workgroups still fill every CU).  The 1024-thread class keeps the scalar-path pass (7.2e8) and is not
-  // picked unless asked for; a closure's certified tail is compiled for the 256-thread class only)
-  const bool cert_one_lane = (!s->user && s->model == AMWG_MODEL_NORMAL && certified_wanted(s, 1, false)) || user_cert_wanted(s, 1);
-  auto fits = [&](int bt, int G) { return bt <= max_bt && bt % G == 0 && layout(bt, G).total <= max_lds && !(bt > 512 && hier_rows_wanted(s, G) && hier_rows_fit(s, 512, max_lds)) &&
-                                          !(bt > 512 && user_rows_wanted(s, G) && user_rows_fit(s, 512, max_lds)) && !(bt > (user_cert_wanted(s, 1) ? 256 : 512) && G == 1 && cert_one_lane && !o.block_threads); };
+  auto fits = [&](int bt, int G) {
+    if (bt > max_bt || bt % G != 0) return false;
+    const LaunchPlan p = variant_for(s, G, bt, max_lds);
+    // (the sweep kernels -- row layout, 64 lanes per chain -- keep the window stream and the sweep's per-lane values in registers: compiled for at most 512 threads,
+    // where a lane has 256 of them; with the 128 of a 1024-thread workgroup the hierarchical family's ran from scratch memory, five times slower)
+    if (lds_of(s, p) > max_lds || (bt > 512 && row_layout(s, variant_for(s, G, 512, max_lds)))) return false;
+    // (one lane per chain with certified decisions -- the Normal family, a closure with a certified tail --: the wavefront's pass keeps 64 partial sums per lane: the 512
+    // registers of a 256-thread workgroup with blocks of 16 observations, the 256 of a 512-thread one with blocks of 8 (round 6, last day: 9 spilled registers; 1.58e9 against
+    // the 256-thread class's 1.55e9 at >= 131 072 chains, where 512-thread workgroups still fill every CU).  The 1024-thread class keeps the scalar-path pass (7.2e8) and is not
+    // picked unless asked for; a closure's certified tail is compiled for the 256-thread class only)
+    return !(G == 1 && info(p.variant).certified && !o.block_threads && bt > (p.variant == Variant::UserStepCert ? 256 : 512));
+  };
   // (a closure's certified row plan -- amwg_user_sweep_cert -- ran in 256-thread workgroups for a day of round 6: in 512-thread ones it spilled 520 registers.  With the
   // S2 pass out of line -- amwg_rows.h rows_sq -- it spills 40 and the 512-thread class, two wavefronts per SIMD, is the faster one again: 2.82e9 against 1.90e9)
-  if (s->user && !s->user_parallel && o.lanes_per_chain > 1)
-    return fail(AMWG_EINVAL, "this closure has no loop that can be split over lanes: lanes_per_chain must be 1 (or 0 = auto), got %d", o.lanes_per_chain);
+  if (s->user && !s->user_parallel && lanes > 1)
+    return fail(AMWG_EINVAL, "this closure has no loop that can be split over lanes: lanes_per_chain must be 1 (or 0 = auto), got %d", lanes);
   const int bts[5] = {1024, 512, 256, 128, 64};
-  int bestG = 0, bestB = 0, bestCpb = 0;
-  double bestOcc = -1.0, cost1 = -1.0;
-  int block1 = 0, cpb1 = 0;
-  const bool fixed_lanes = o.lanes_per_chain > 0;      // (autotune_geometry calls this once per lane count, each time as a fixed one)
+  LaunchPlan best, one;      // the cheapest plan, and the one with one lane per chain
+  double best_cost = -1.0, cost1 = -1.0;
+  const bool fixed_lanes = lanes > 0;
   for (int G = 1; G <= 1024; G <<= 1) {
-    if (fixed_lanes && G != o.lanes_per_chain) continue;
+    if (fixed_lanes && G != lanes) continue;
     if (s->user && !s->user_parallel && G > 1) break;   // nothing to split: one lane per chain
     // translated closures: with one lane per chain every data index is wave-uniform and the compiler moves the
     // per-observation integer logic to the scalar unit, which issues 4x slower than the vector lanes (measured 2.5x on
     // the beta-Bernoulli closure); two lanes per chain keep it on the vector path at no measurable cost elsewhere
-    if (s->user && s->user_parallel && !fixed_lanes && G == 1 && !(s->user_work_one_lane > 0) && !user_cert_wanted(s, 1)) continue;
+    if (s->user && s->user_parallel && !fixed_lanes && G == 1 && !(s->user_work_one_lane > 0) && variant_for(s, 1, 256, max_lds).variant != Variant::UserStepCert) continue;
     int pick = 0;
     for (int bi = 0; bi < 5; ++bi) {   // largest workgroup with >= one workgroup per CU, else the smallest that fits
       const int bt = bts[bi];
@@ -377,12 +401,14 @@ int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
     int cpb = 0;
     if (!pick && G < 64 && max_bt >= 64 && (!o.block_threads || o.block_threads == 64)) {
       for (int c = 32 / G; c >= 1; c >>= 1)      // fewer chains than lane groups in a one-wavefront workgroup
-        if (layout(64, G, c).total <= max_lds) { pick = 64; cpb = c; break; }
+        if (lds_of(s, variant_for(s, G, 64, max_lds), c) <= max_lds) { pick = 64; cpb = c; break; }
     }
     if (!pick) continue;
+    LaunchPlan p = variant_for(s, G, pick, max_lds);
+    p.cpb = cpb;
     const int CPB = cpb ? cpb : pick / G;
     const int64_t blocks = (s->C + CPB - 1) / CPB;
-    const uint32_t lds = layout(pick, G, cpb).total;
+    const uint32_t lds = lds_of(s, p, cpb);
     int64_t per_cu = 2048 / pick;                                  // 32 waves per CU
     if (lds > 0 && (int64_t)(max_lds / lds) < per_cu) per_cu = (int64_t)(max_lds / lds);
     if (per_cu < 1) per_cu = 1;
@@ -401,34 +427,39 @@ int choose_geometry(amwg_sampler *s, int n_cus, size_t max_lds) {
     // of its own non-arithmetic instructions, 10 % at cfg2 with one lane per chain vs four waves -- measured 3.64e8 vs 4.03e8)
     const double w1 = w_res > 1.0 ? w_res : 1.0;
     const double cost = (w_total / w_res) * (S * (w_res > 1.8 ? w_res : 1.8) + Wl * w1 * (1.0 + 0.14 / w1));
-    if (G == 1) { cost1 = cost; block1 = pick; cpb1 = cpb; }
-    if (bestOcc < 0 || cost < bestOcc * (1.0 - 1e-9)) { bestOcc = cost; bestG = G; bestB = pick; bestCpb = cpb; }   // bestOcc holds the best cost
+    if (G == 1) { cost1 = cost; one = p; }
+    if (best_cost < 0 || cost < best_cost * (1.0 - 1e-9)) { best_cost = cost; best = p; }
   }
   // Reference order first: with ONE lane per chain a chain's log_post is summed exactly as the reference sums it (`lp += term`,
   // mcmc.js:958-960), so every draw of a seeded run is the reference's bit for bit; with more lanes only the decisions are
   // (tested), the doubles are those of the G-lane order.  Unless the caller asked for a lane count (or for AMWG_LANES_FASTEST),
   // take one lane per chain whenever the model prices it within 12 % of the cheapest geometry.
-  if (o.lanes_per_chain == 0 && bestG > 1 && cost1 > 0 && cost1 <= 1.12 * bestOcc) { bestG = 1; bestB = block1; bestCpb = cpb1; }
-  if (!bestG) return fail(AMWG_EINVAL, "no launch geometry fits: the model needs more than %zu bytes of LDS", max_lds);
-  s->lanes = bestG;
-  s->block = bestB;
-  s->cpb = bestCpb;
-  const int CPB = bestG > 64 ? 1 : (bestCpb ? bestCpb : bestB / bestG);
-  s->grid = (int)((s->C + CPB - 1) / CPB);
-  s->lds = (int)layout(bestB, bestG, bestCpb).total;
-  if (s->user) {    // the kernel is compiled for this geometry afterwards
-    const bool rows = user_rows_wanted(s, s->lanes) && user_rows_fit(s, s->block, max_lds);
-    s->d.pad = rows ? HierNormalModel::row_pitch(s->user_rows_n) : 0;
-    s->user_sweep = rows && user_sweep_wanted(s, s->lanes, s->block, max_lds);
-    s->certified = s->user_sweep ? user_rows_cert_wanted(s) : user_cert_wanted(s, s->lanes);      // (amwg_user_sweep_cert / amwg_user_step_cert)
-    return size_wave_scratch(s);
+  if (lanes == 0 && best.lanes > 1 && cost1 > 0 && cost1 <= 1.12 * best_cost) best = one;
+  if (!best.lanes) return fail(AMWG_EINVAL, "no launch geometry fits: the model needs more than %zu bytes of LDS", max_lds);
+  const int CPB = best.lanes > 64 ? 1 : (best.cpb ? best.cpb : best.block / best.lanes);
+  best.grid = (int)((s->C + CPB - 1) / CPB);
+  best.lds = (int)lds_of(s, best, best.cpb);
+  *out = best;
+  return AMWG_OK;
+}
+
+// Everything that goes with a plan: the sampler's geometry, DataRef::pad, the constant-mean pass of the hierarchical family (HierNormalModel::pass_fast:
+// the labels repeat with the lane stride), the built-in kernel and the wave scratch.  A translated closure's kernel is compiled and loaded afterwards
+// (amwg_create_user, prepare).
+int adopt_plan(amwg_sampler *s, const LaunchPlan &p) {
+  s->plan = p;
+  s->d.pad = p.pad;
+  if (s->user) return size_wave_scratch(s);
+  int lg = 0;
+  for (int g = p.lanes; g > 1; g >>= 1) ++lg;
+  if (s->model == AMWG_MODEL_HIER_NORMAL) s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> lg) & 1u);
+  switch (p.variant) {
+    case Variant::StepCert: case Variant::HierSweepCert: s->kernel = pick_certified_kernel(s->model, p.lanes, p.block); break;
+    case Variant::HierSweep: s->kernel = amwg_kernel_hier_sweep(p.block); break;
+    case Variant::GroupLocal: s->kernel = amwg_kernel_hier_gl(p.block); break;
+    default: s->kernel = pick_kernel(s->model, p.lanes, p.block);
   }
-  const bool rows = !s->mc.group_local && hier_rows_wanted(s, s->lanes) && hier_rows_fit(s, s->block, max_lds);
-  if (s->model == AMWG_MODEL_NORMAL) s->d.pad = (s->lanes == 1 && normal_tile_wanted(s, s->block)) ? 1 : 0;
-  s->kernel = certified_wanted(s, s->lanes, rows) ? pick_certified_kernel(s->model, s->lanes, s->block) : nullptr;
-  s->certified = s->kernel != nullptr;
-  if (!s->kernel) s->kernel = s->mc.group_local ? amwg_kernel_hier_gl(s->block) : (rows ? amwg_kernel_hier_sweep(s->block) : pick_kernel(s->model, s->lanes, s->block));
-  if (!s->kernel) return fail(AMWG_EINVAL, "no kernel for model %d with %d lanes per chain in workgroups of %d", s->model, s->lanes, s->block);
+  if (!s->kernel) return fail(AMWG_EINVAL, "no kernel for model %d with %d lanes per chain in workgroups of %d", s->model, p.lanes, p.block);
   return size_wave_scratch(s);
 }
 
@@ -451,13 +482,6 @@ struct Roctx {
 };
 Roctx &roctx() { static Roctx r; return r; }
 
-// which of the three kernels of a translated closure's code object this sampler launches (user_program)
-static const char *user_kernel_symbol(const amwg_sampler *s) {
-  return s->user_sweep ? (s->certified ? "amwg_user_sweep_cert" : "amwg_user_sweep") : (s->certified ? "amwg_user_step_cert" : "amwg_user_step");
-}
-// does this sampler's kernel decide from a model's cheaper value of log_post (amwg_kernel.h kCert: NormalModel at one lane per chain, PoisGlmModel at 16)?
-static bool certified_kernel(const amwg_sampler *s) { return s->certified; }
-
 int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool finalize = false) {
   Roctx &rx = roctx();
   if (rx.push) rx.push(d_draws ? "amwg_sample" : "amwg_burn");
@@ -472,9 +496,10 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     if (steps < (double)chunk) chunk = steps < 16.0 ? 16 : (int64_t)steps;
   }
   // the invariants the kernel relies on, enforced where the launch is made (the kernel's own guards -- device_error -- are the backstop)
-  if (s->cpb > 0 && s->block != 64) return fail(AMWG_EINVAL, "internal: %d chains per workgroup of %d threads (replicated chains need one-wavefront workgroups)", s->cpb, s->block);
-  if (s->lanes == 1 && s->d.wave_scratch && wave_scratch_lines(s) < (size_t)s->grid * (size_t)(s->block / 64))
-    return fail(AMWG_EINVAL, "internal: a wave scratch of %zu lines for %d workgroups of %d threads (one line per wavefront)", wave_scratch_lines(s), s->grid, s->block);
+  const LaunchPlan &p = s->plan;
+  if (p.cpb > 0 && p.block != 64) return fail(AMWG_EINVAL, "internal: %d chains per workgroup of %d threads (replicated chains need one-wavefront workgroups)", p.cpb, p.block);
+  if (p.lanes == 1 && s->d.wave_scratch && wave_scratch_lines(s) < (size_t)p.grid * (size_t)(p.block / 64))
+    return fail(AMWG_EINVAL, "internal: a wave scratch of %zu lines for %d workgroups of %d threads (one line per wavefront)", wave_scratch_lines(s), p.grid, p.block);
   if (chunk > 65535) return fail(AMWG_EINVAL, "internal: launches of %lld steps (at most 65535)", (long long)chunk);
   StepArgs a{};
   a.C = s->C;
@@ -485,9 +510,9 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
   a.cc = s->d_cc;
   a.is_adapting = s->d_adapt;
   a.pl = s->pl;
-  a.cpb = s->cpb;
+  a.cpb = p.cpb;
   a.sweep_update_by_update = s->opt.full_evaluation == 2 ? 1 : 0;
-  a.certified = s->certified ? 1 : 0;      // (informational: certified decisions are the kernel's, not a switch inside it)
+  a.certified = info(p.variant).certified ? 1 : 0;      // (informational: certified decisions are the kernel's, not a switch inside it)
   a.bound_scale = std::ldexp(1.0, s->opt.test_bound_shift);
   a.audit_adversarial = 0;
 #if defined(AMWG_AUDIT)
@@ -495,7 +520,7 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
 #endif
   a.mc = s->mc;
   a.d = s->d;
-  if (s->lanes != 1) a.d.wave_scratch = nullptr;      // (sized for one-lane geometries only; no other kernel reads it)
+  if (p.lanes != 1) a.d.wave_scratch = nullptr;      // (sized for one-lane geometries only; no other kernel reads it)
   a.ch = s->ch;
   // (a 0-step finalize launch on chains that have stepped -- amwg_chain_diag asking for the expression's value after a certified kernel ran -- is not "the latest call":
   // the sample call's launch count, its per-launch marks and its event pair stay, so that a diag() between sample_async and fetch_draws neither loses the copy overlap
@@ -518,14 +543,14 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     if (s->user) {
       size_t arg_bytes = sizeof a;
       void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_bytes, HIP_LAUNCH_PARAM_END};
-      HIP_TRY(hipModuleLaunchKernel(s->user_fn, (unsigned)s->grid, 1, 1, (unsigned)s->block, 1, 1, (unsigned)s->lds, s->stream, nullptr, extra));
+      HIP_TRY(hipModuleLaunchKernel(s->user_fn, (unsigned)p.grid, 1, 1, (unsigned)p.block, 1, 1, (unsigned)p.lds, s->stream, nullptr, extra));
     } else {
-      hipLaunchKernelGGL(s->kernel, dim3(s->grid), dim3(s->block), (size_t)s->lds, s->stream, a);
+      hipLaunchKernelGGL(s->kernel, dim3(p.grid), dim3(p.block), (size_t)p.lds, s->stream, a);
       HIP_TRY(hipGetLastError());
     }
     s->lp_ready = true;
     if (finalize || a.init_lp) s->lp_is_expression = true;                        // (the launch began / ends with the expression)
-    if (m > 0 && !finalize && certified_kernel(s)) s->lp_is_expression = false;      // (it may have left the stepper's cheaper value and its bound behind)
+    if (m > 0 && !finalize && info(p.variant).certified) s->lp_is_expression = false;      // (it may have left the stepper's cheaper value and its bound behind)
     if (!quiet) s->n_launches++;
     if (d_draws) row += (m > a.step0) ? (m - a.step0 + thin - 1) / thin : 0;
     // a mark for amwg_fetch_draws*: only for the library's own buffer, and only once >= 8 MB of new rows (or the end of the call) stand
@@ -560,10 +585,11 @@ int finish_timing(amwg_sampler *s) {
     HIP_TRY(hipMemcpy(&bits, s->ch.error, sizeof bits, hipMemcpyDeviceToHost));
     if (bits) {
       HIP_TRY(hipMemset(s->ch.error, 0, sizeof bits));
-      return fail(AMWG_EHIP, "the step kernel reported an internal error (bits %d:%s%s%s%s): the chains' state is not to be trusted", bits,
+      return fail(AMWG_EHIP, "the step kernel reported an internal error (bits %d:%s%s%s%s%s): the chains' state is not to be trusted", bits,
                   (bits & 1) ? " replicated chains in a workgroup of more than one wavefront" : "", (bits & 2) ? " more than 65535 steps in one launch" : "",
                   (bits & 4) ? " the register mirror of the state is out of sync with the state" : "",
-                  (bits & 8) ? " the sweep kernel was launched for a parameter vector of more than 64 entries" : "");
+                  (bits & 8) ? " the sweep kernel was launched for a parameter vector of more than 64 entries" : "",
+                  (bits & 16) ? " the launched kernel has no body for this closure at this geometry" : "");
     }
   }
   return AMWG_OK;
@@ -886,39 +912,10 @@ static int alloc_chain_state(amwg_sampler *s, const amwg_param_desc *params, int
   return AMWG_OK;
 }
 
-// ---- hiprtc: a translated closure + the step kernel -> code object for one (lanes, workgroup) geometry
+// ---- hiprtc: a translated closure + its step kernels (amwg_user_kernels.h) -> code object for one (lanes, workgroup) geometry
 static std::string user_program(const char *source, int lanes, int block) {
-  std::string p = "#include \"amwg_kernel.h\"\n#include \"amwg_user.h\"\n";
-  p += source;
-  char tail[1200];
-  // amwg_user_step: the step kernel for this geometry.  amwg_user_sweep: for a closure with a row plan (amwg_rows.h: UserModel::kLaneReuse) on a whole
-  // wavefront per chain, the same stepper with the sweep prefetch (amwg_sweep_kernel's twin); an empty kernel otherwise -- the host never launches it then.
-  snprintf(tail, sizeof tail,
-           "\nextern \"C\" __global__ void __launch_bounds__(%d) amwg_user_step(const amwg::StepArgs a) {\n"
-           "  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
-           "  amwg::step_body<amwg::UserModel, %d>(a, smem);\n}\n"
-           "extern \"C\" __global__ void __launch_bounds__(%d) amwg_user_sweep(const amwg::StepArgs a) {\n"
-           "  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
-           "  if constexpr (amwg::LaneReuseOf<amwg::UserModel>::value && %d == 64 && %d <= 512) amwg::step_body<amwg::UserModel, 64, 512, false, true>(a, smem);\n}\n",
-           block, lanes, block, lanes, block);
-  p += tail;
-  // amwg_user_step_cert: for a closure with a certified tail (amwg_user.h norm_tail_approx: UserModel::kCertified) at the lane count it has one for, the stepper
-  // that decides accept tests from it (amwg_step_kernel_cert's twin; BT: the wavefront's pass needs the 512 registers of a workgroup of at most 256 threads)
-  // amwg_user_sweep_cert: a row plan the translator marked kRowCert (amwg_rows.h: certified values + the expression in the reference's order): amwg_sweep_kernel_cert's twin
-  snprintf(tail, sizeof tail,
-           "extern \"C\" __global__ void __launch_bounds__(%d) amwg_user_sweep_cert(const amwg::StepArgs a) {\n"
-           "  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
-           "  if constexpr (amwg::LaneReuseOf<amwg::UserModel>::value && amwg::CertifiedAt<amwg::UserModel, 64>::value && amwg::CertNeedsRows<amwg::UserModel>::value && %d == 64 && %d <= 512)\n"
-           "    amwg::step_body<amwg::UserModel, 64, 512, false, true, true>(a, smem);\n}\n",
-           block, lanes, block);
-  p += tail;
-  snprintf(tail, sizeof tail,
-           "extern \"C\" __global__ void __launch_bounds__(%d) amwg_user_step_cert(const amwg::StepArgs a) {\n"
-           "  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n"
-           "  if constexpr (amwg::CertifiedAt<amwg::UserModel, %d>::value && !amwg::CertNeedsRows<amwg::UserModel>::value) amwg::step_body<amwg::UserModel, %d, %d, false, false, true>(a, smem);\n}\n",
-           block, lanes, lanes, block <= 256 ? 256 : 1024);
-  p += tail;
-  return p;
+  return "#include \"amwg_kernel.h\"\n#include \"amwg_user.h\"\n#define AMWG_USER_LANES " + std::to_string(lanes) + "\n#define AMWG_USER_BLOCK " + std::to_string(block) + "\n" +
+         source + "\n#include \"amwg_user_kernels.h\"\n";
 }
 
 // ---- on-disk cache of compiled code objects.  hiprtc takes ~0.6 s per closure and geometry; the reference's own use -- one chain, a
@@ -1007,10 +1004,10 @@ static void dump_code_object(const std::vector<char> &code) {      // developmen
 
 // use_cache = false: compile even if the on-disk cache has the object (the caller found the cached one unloadable)
 static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool use_cache = true) {
-  static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h",
-                                "amwg_kernel.h", "amwg_user.h", "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h"};
-  const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox,
-                         amwg_hdr_kernel, amwg_hdr_user, amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail};
+  static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h", "amwg_kernel.h", "amwg_user.h",
+                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_user_kernels.h"};
+  const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox, amwg_hdr_kernel, amwg_hdr_user,
+                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_user_kernels};
   constexpr int kHeaders = (int)(sizeof(texts) / sizeof(texts[0]));
   const std::string prog_src = user_program(source, lanes, block);
 #if defined(AMWG_AUDIT)      // (libamwg_audit.so: the certified kernels of translated closures record |A - E| / eps as the built-in families' do)
@@ -1064,11 +1061,24 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
   return AMWG_OK;
 }
 
-// ---- AMWG_LANES_AUTOTUNE: measure instead of model.  Every lane count whose geometry fits is prepared (`prepare`: kernel lookup or
-// hiprtc compile + load, plus whatever depends on the lane count), run for a few steps on the real chain state -- which is saved
+// What the generated source of a translated closure (translate.js) states about itself, read off its markers: the row plan (kRowN, kRowGroups, kRowSweep,
+// kRowCert; -1 = no such marker), the certified tail (kCertifiedTail, kTailN) and the certified Poisson tail (kPoisTail, kTailN); 0 = none.
+struct SourceTraits { long row_n, row_groups; bool row_sweep, row_cert; int cert_tail_n, pois_tail_n; };
+static SourceTraits source_traits(const char *src) {
+  auto int_after = [&](const char *key) -> long {
+    const char *q = strstr(src, key);
+    return q ? strtol(q + strlen(key), nullptr, 10) : -1;
+  };
+  auto tail_n = [&](const char *marker) { const long n = strstr(src, marker) ? int_after("kTailN = ") : 0; return n > 0 && n < (1l << 28) ? (int)n : 0; };
+  return SourceTraits{int_after("kRowN = "), int_after("kRowGroups = "), strstr(src, "kRowSweep = true") != nullptr, strstr(src, "kRowCert = true") != nullptr,
+                      tail_n("kCertifiedTail = true"), tail_n("kPoisTail = true")};
+}
+
+// ---- AMWG_LANES_AUTOTUNE: measure instead of model.  Every lane count whose geometry fits is adopted (adopt_plan) and prepared (`prepare`: kernel
+// attribute, or hiprtc compile + load), run for a few steps on the real chain state -- which is saved
 // before and restored after, so tuning leaves no trace in the chains -- and timed with HIP events.  The fastest wins, except that one
 // lane per chain (the reference's summation order) is kept whenever it MEASURES within 12 % of the fastest.
-struct TuneCandidate { int lanes, block, grid, lds, cpb; step_kernel_t kernel; hipModule_t module; hipFunction_t fn; float ms; int pad; bool sweep; };
+struct TuneCandidate { LaunchPlan plan; hipModule_t module; hipFunction_t fn; float ms; };
 
 template <class Prepare>
 static int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, Prepare prepare) {
@@ -1093,13 +1103,12 @@ static int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, Prepare
     return hipStreamSynchronize(s->stream);
   };
   HIP_TRY(copy_all(false));
-  const int32_t wanted = s->opt.lanes_per_chain;
   std::vector<TuneCandidate> cand;
   std::string first_error;
   for (int G = 1; G <= 1024; G <<= 1) {
-    s->opt.lanes_per_chain = G;
-    if (choose_geometry(s, n_cus, max_lds) != AMWG_OK || prepare() != AMWG_OK) { if (first_error.empty()) first_error = g_err; continue; }
-    TuneCandidate c{s->lanes, s->block, s->grid, s->lds, s->cpb, s->kernel, s->user_module, s->user_fn, 0.f, s->d.pad, s->user_sweep};
+    LaunchPlan plan;
+    if (choose_geometry(s, G, n_cus, max_lds, &plan) != AMWG_OK || adopt_plan(s, plan) != AMWG_OK || prepare() != AMWG_OK) { if (first_error.empty()) first_error = g_err; continue; }
+    TuneCandidate c{plan, s->user_module, s->user_fn, 0.f};
     // One untimed launch first (it evaluates log_post(init), stages the data for the first time and warms the instruction cache); then the
     // run length is scaled until a launch takes >= 1 ms -- short data loops would otherwise be ranked by launch overhead and noise -- and the
     // candidate's figure is the FASTEST of three such launches, per step.  The runs continue the chains from one another (a valid lp_curr,
@@ -1127,19 +1136,17 @@ static int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, Prepare
     s->user_module = nullptr;
     s->user_fn = nullptr;
   }
-  s->opt.lanes_per_chain = wanted;
   if (cand.empty()) return fail(AMWG_EINVAL, "autotune: no lane count could be run (%s)", first_error.c_str());
   size_t best = 0;
   for (size_t i = 1; i < cand.size(); ++i) if (cand[i].ms < cand[best].ms) best = i;
-  if (cand[0].lanes == 1 && cand[0].ms <= 1.12f * cand[best].ms) best = 0;      // reference order first
+  if (cand[0].plan.lanes == 1 && cand[0].ms <= 1.12f * cand[best].ms) best = 0;      // reference order first
   for (size_t i = 0; i < cand.size(); ++i) if (i != best && cand[i].module) (void)hipModuleUnload(cand[i].module);
   const TuneCandidate &c = cand[best];
-  s->lanes = c.lanes; s->block = c.block; s->grid = c.grid; s->lds = c.lds; s->cpb = c.cpb; s->kernel = c.kernel; s->user_module = c.module; s->user_fn = c.fn;
-  s->certified = s->user ? (c.sweep ? user_rows_cert_wanted(s) : user_cert_wanted(s, c.lanes)) : (c.kernel != nullptr && c.kernel == pick_certified_kernel(s->model, c.lanes, c.block));
-  s->d.pad = c.pad; s->user_sweep = c.sweep;      // (the row layout and the sweep kernel go with the geometry)
-  if (int rc = size_wave_scratch(s); rc != AMWG_OK) return rc;
+  s->user_module = c.module;
+  s->user_fn = c.fn;
+  if (int rc = adopt_plan(s, c.plan); rc != AMWG_OK) return rc;
   s->tuned.clear();
-  for (auto &q : cand) s->tuned.push_back({q.lanes, q.ms});
+  for (auto &q : cand) s->tuned.push_back({q.plan.lanes, q.ms});
   s->n_launches = 0;
   s->kernel_ms = 0;
   return AMWG_OK;
@@ -1306,7 +1313,7 @@ int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t
         HIPB(hipMemcpy(dl, gl.lane, sizeof gl.lane, hipMemcpyHostToDevice));
         d.x = dt;
         d.arr[0] = dl;
-        d.pad = gl.rounds;
+        s->gl_rounds = gl.rounds;
         d.K = gl.n_min;
       }
     }
@@ -1371,19 +1378,12 @@ int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t
       if (periodic) s->hier_periodic_mask |= 1u << j;
     }
   }
-  auto prepare = [&]() -> int {      // whatever depends on the lane count, once the geometry is fixed
-    if (m->model == AMWG_MODEL_HIER_NORMAL) {   // HierNormalModel::pass_fast: constant-mean pass when the labels repeat with the lane stride
-      int lg = 0;
-      for (int g = s->lanes; g > 1; g >>= 1) ++lg;
-      s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> lg) & 1u);
-      if (!s->mc.group_local)      // (the group-local kernel has its own use of DataRef::pad)
-        s->d.pad = (hier_rows_wanted(s, s->lanes) && hier_rows_fit(s, s->block, max_lds)) ? HierNormalModel::row_pitch(s->d.n_obs) : 0;
-    }
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(s->kernel), hipFuncAttributeMaxDynamicSharedMemorySize, s->lds);
+  auto prepare = [&]() -> int {      // once the plan is adopted
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(s->kernel), hipFuncAttributeMaxDynamicSharedMemorySize, s->plan.lds);
     return e == hipSuccess ? AMWG_OK : fail(AMWG_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
   };
   if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE) TRYB(autotune_geometry(s, n_cus, max_lds, prepare));
-  else { TRYB(choose_geometry(s, n_cus, max_lds)); }
+  else { LaunchPlan plan; TRYB(choose_geometry(s, s->opt.lanes_per_chain, n_cus, max_lds, &plan)); TRYB(adopt_plan(s, plan)); }
   clk.mark("geometry");
   TRYB(prepare());
   clk.mark("kernel attribute (module load)");
@@ -1420,25 +1420,18 @@ int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, in
   s->user_work_one_lane = m->work_one_lane;
   if (m->rows_n_obs < 0 || m->rows_groups < 0) { delete s; return fail(AMWG_EINVAL, "amwg_create_user: negative row plan"); }
   {
-    // The row plan is honoured only as far as the GENERATED SOURCE states it (kRowN / kRowGroups / kRowSweep of translate.js): the source is what gets compiled, and
-    // a caller built against an older amwg_user_model -- a shorter struct: the rows_* fields are then whatever follows it in memory -- must not switch a layout on
-    // that the model has no code for (round-5 advisor finding).  The certified tail is read from the source alone (kCertifiedTail / kTailN): no struct field carries it.
-    auto int_after = [&](const char *key) -> long {
-      const char *q = strstr(m->source, key);
-      return q ? strtol(q + strlen(key), nullptr, 10) : -1;
-    };
-    const long src_n = int_after("kRowN = "), src_g = int_after("kRowGroups = ");
-    const bool src_sweep = strstr(m->source, "kRowSweep = true") != nullptr;
-    const bool rows_ok = m->rows_n_obs > 0 && src_n == (long)m->rows_n_obs && src_g == (long)m->rows_groups;
-    if (m->rows_n_obs > 0 && !rows_ok && src_n >= 0) { delete s; return fail(AMWG_EINVAL, "amwg_create_user: row plan (%d observations, %d groups) does not match the generated source (kRowN = %ld, kRowGroups = %ld)", m->rows_n_obs, m->rows_groups, src_n, src_g); }
+    // The row plan is honoured only as far as the GENERATED SOURCE states it: the source is what gets compiled, and a caller built against an older
+    // amwg_user_model -- a shorter struct: the rows_* fields are then whatever follows it in memory -- must not switch a layout on that the model has
+    // no code for (round-5 advisor finding).  The certified tails are read from the source alone: no struct field carries them.
+    const SourceTraits t = source_traits(m->source);
+    const bool rows_ok = m->rows_n_obs > 0 && t.row_n == (long)m->rows_n_obs && t.row_groups == (long)m->rows_groups;
+    if (m->rows_n_obs > 0 && !rows_ok && t.row_n >= 0) { delete s; return fail(AMWG_EINVAL, "amwg_create_user: row plan (%d observations, %d groups) does not match the generated source (kRowN = %ld, kRowGroups = %ld)", m->rows_n_obs, m->rows_groups, t.row_n, t.row_groups); }
     s->user_rows_n = rows_ok ? m->rows_n_obs : 0;
     s->user_rows_groups = rows_ok ? m->rows_groups : 0;
-    s->user_rows_sweep = (rows_ok && m->rows_sweep && src_sweep) ? 1 : 0;
-    s->user_rows_cert = s->user_rows_sweep && strstr(m->source, "kRowCert = true") != nullptr;
-    const long tail_n = strstr(m->source, "kCertifiedTail = true") ? int_after("kTailN = ") : 0;
-    s->user_cert_tail_n = tail_n > 0 && tail_n < (1l << 28) ? (int)tail_n : 0;
-    const long ptail_n = strstr(m->source, "kPoisTail = true") ? int_after("kTailN = ") : 0;
-    s->user_pois_tail_n = ptail_n > 0 && ptail_n < (1l << 28) ? (int)ptail_n : 0;
+    s->user_rows_sweep = (rows_ok && m->rows_sweep && t.row_sweep) ? 1 : 0;
+    s->user_rows_cert = s->user_rows_sweep && t.row_cert;
+    s->user_cert_tail_n = t.cert_tail_n;
+    s->user_pois_tail_n = t.pois_tail_n;
   }
   s->C = options->chains;
   s->device = options->device;
@@ -1502,38 +1495,39 @@ int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, in
   auto prepare = [&]() -> int {
     static std::mutex mu;
     static std::map<std::string, std::vector<char>> cache;
-    const std::string key = std::string(prop.gcnArchName) + "|" + std::to_string(s->lanes) + "|" + std::to_string(s->block) + "|" + m->source;
+    const LaunchPlan &p = s->plan;
+    const std::string key = std::string(prop.gcnArchName) + "|" + std::to_string(p.lanes) + "|" + std::to_string(p.block) + "|" + m->source;
     std::lock_guard<std::mutex> lock(mu);
     auto it = cache.find(key);
     if (it == cache.end()) {
       std::vector<char> code;
-      int rc = compile_user(m->source, s->lanes, s->block, prop.gcnArchName, &code);
+      int rc = compile_user(m->source, p.lanes, p.block, prop.gcnArchName, &code);
       if (rc != AMWG_OK) return rc;
       it = cache.emplace(key, std::move(code)).first;
     }
     if (s->user_module) return AMWG_OK;      // (autotune hands back the module it kept)
     hipError_t e = hipModuleLoadData(&s->user_module, it->second.data());
-    if (e == hipSuccess) e = hipModuleGetFunction(&s->user_fn, s->user_module, user_kernel_symbol(s));
+    if (e == hipSuccess) e = hipModuleGetFunction(&s->user_fn, s->user_module, info(p.variant).name);
     if (e != hipSuccess) {
       // the cache is never a requirement: an object the loader refuses (a planted or half-written file that still passed the checks, another
       // driver) is dropped and the closure compiled afresh, once
       (void)hipGetLastError();
       if (s->user_module) { (void)hipModuleUnload(s->user_module); s->user_module = nullptr; }
       std::vector<char> fresh;
-      int rc = compile_user(m->source, s->lanes, s->block, prop.gcnArchName, &fresh, false);
+      int rc = compile_user(m->source, p.lanes, p.block, prop.gcnArchName, &fresh, false);
       if (rc != AMWG_OK) return rc;
       it->second = std::move(fresh);
       e = hipModuleLoadData(&s->user_module, it->second.data());
-      if (e == hipSuccess) e = hipModuleGetFunction(&s->user_fn, s->user_module, user_kernel_symbol(s));
+      if (e == hipSuccess) e = hipModuleGetFunction(&s->user_fn, s->user_module, info(p.variant).name);
       if (e != hipSuccess) return fail(AMWG_EHIP, "loading the compiled log_post failed: %s", hipGetErrorString(e));
     }
     // workgroups of this kernel use up to the whole 160 KB LDS of a CU; not every runtime needs (or accepts) the opt-in for module functions
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(s->user_fn), hipFuncAttributeMaxDynamicSharedMemorySize, s->lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(s->user_fn), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds);
     (void)hipGetLastError();
     return AMWG_OK;
   };
   if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE) TRYB(autotune_geometry(s, n_cus, max_lds, prepare));
-  else { TRYB(choose_geometry(s, n_cus, max_lds)); }
+  else { LaunchPlan plan; TRYB(choose_geometry(s, s->opt.lanes_per_chain, n_cus, max_lds, &plan)); TRYB(adopt_plan(s, plan)); }
   TRYB(prepare());
   HIPB(hipStreamSynchronize(s->stream));
   *out = s;
@@ -1899,10 +1893,10 @@ int64_t amwg_num_chains(const amwg_sampler *s) { return s ? s->C : 0; }
 
 int amwg_launch_info(const amwg_sampler *s, int32_t *lanes, int32_t *block, int32_t *grid, int32_t *lds, int32_t *n_launches, double *kernel_ms) {
   if (!s) return fail(AMWG_EINVAL, "amwg_launch_info: null sampler");
-  if (lanes) *lanes = s->lanes;
-  if (block) *block = s->block;
-  if (grid) *grid = s->grid;
-  if (lds) *lds = s->lds;
+  if (lanes) *lanes = s->plan.lanes;
+  if (block) *block = s->plan.block;
+  if (grid) *grid = s->plan.grid;
+  if (lds) *lds = s->plan.lds;
   if (n_launches) *n_launches = s->n_launches;
   if (kernel_ms) *kernel_ms = s->kernel_ms;
   return AMWG_OK;
@@ -1910,25 +1904,24 @@ int amwg_launch_info(const amwg_sampler *s, int32_t *lanes, int32_t *block, int3
 
 int amwg_summation_order(const amwg_sampler *s) {
   if (!s) return fail(AMWG_EINVAL, "amwg_summation_order: null sampler");
-  // (the certified kernels of the Poisson and the hierarchical family evaluate the expression in the reference's order: amwg_kernel.h kRefOrder)
-  if (s->lanes > 1 && certified_kernel(s) && (s->user || s->model == AMWG_MODEL_POIS_GLM || s->model == AMWG_MODEL_HIER_NORMAL)) return 1;      // (a closure: amwg_user_sweep_cert)
-  return s->lanes;
+  // (the certified kernels evaluate the expression in the reference's order: amwg_kernel.h kRefOrder)
+  return info(s->plan.variant).certified ? 1 : s->plan.lanes;
 }
 
 const char *amwg_kernel_name(const amwg_sampler *s) {
   if (!s) { (void)fail(AMWG_EINVAL, "amwg_kernel_name: null sampler"); return ""; }
   amwg_sampler *m = const_cast<amwg_sampler *>(s);
   if (m->kernel_name.empty()) {
-    const int cls = s->block <= 256 ? 256 : (s->block <= 512 ? 512 : 1024);
+    const LaunchPlan &p = s->plan;
+    const int cls = p.block <= 256 ? 256 : (p.block <= 512 ? 512 : 1024);
+    const char *name = info(p.variant).name;
+    static const char *const fam[] = {"NormalModel", "BetaBernModel", "HierNormalModel", "PoisGlmModel"};      // (AMWG_MODEL_* - 1)
     char buf[96];
-    if (s->user) snprintf(buf, sizeof buf, "%s", user_kernel_symbol(s));
-    else if (s->mc.group_local) snprintf(buf, sizeof buf, "amwg_gl_kernel<HierGlModel,%d>", cls);
-    else if (s->model == AMWG_MODEL_HIER_NORMAL && s->d.pad > 0) snprintf(buf, sizeof buf, "amwg_sweep_kernel%s<HierNormalModel,%d>", s->certified ? "_cert" : "", cls);
-    else {
-      static const char *const fam[] = {"NormalModel", "BetaBernModel", "HierNormalModel", "PoisGlmModel"};
-      const int f = s->model == AMWG_MODEL_NORMAL ? 0 : (s->model == AMWG_MODEL_BETA_BERN ? 1 : (s->model == AMWG_MODEL_HIER_NORMAL ? 2 : 3));
-      snprintf(buf, sizeof buf, "amwg_step_kernel%s<%s,%d,%d>", s->certified ? "_cert" : "", fam[f], s->lanes, s->lanes > 64 ? (s->lanes <= 256 ? 256 : (s->lanes <= 512 ? 512 : 1024)) : cls);
-    }
+    if (p.variant == Variant::Step || p.variant == Variant::StepCert)
+      snprintf(buf, sizeof buf, "%s<%s,%d,%d>", name, fam[s->model - 1], p.lanes, p.lanes > 64 ? (p.lanes <= 256 ? 256 : (p.lanes <= 512 ? 512 : 1024)) : cls);
+    else if (p.variant == Variant::GroupLocal || p.variant == Variant::HierSweep || p.variant == Variant::HierSweepCert)
+      snprintf(buf, sizeof buf, "%s<%s,%d>", name, p.variant == Variant::GroupLocal ? "HierGlModel" : "HierNormalModel", cls);
+    else snprintf(buf, sizeof buf, "%s", name);      // a translated closure: its hiprtc symbol
     m->kernel_name = buf;
   }
   return m->kernel_name.c_str();

@@ -574,7 +574,8 @@ __device__ __forceinline__ double lane_value(double v, int src) {
 // Device-side invariants.  The host keeps them (choose_geometry pairs cpb with one-wavefront workgroups, launch_steps cuts calls into launches
 // of at most 65 535 steps); a launch that breaks one -- a future geometry or launch change -- must not look like a successful no-op: the
 // kernel leaves a bit in ChainArrays::error, which the host reads after every call (finish_timing) and reports as AMWG_EHIP.
-constexpr int kErrReplicasNeedOneWave = 1, kErrLaunchTooLong = 2, kErrMirrorOutOfSync = 4, kErrSweepNeedsOrderInRegisters = 8;
+// kErrNoKernelBody: a kernel of a translated closure's code object (amwg_user_kernels.h) launched at a geometry the closure has no body for.
+constexpr int kErrReplicasNeedOneWave = 1, kErrLaunchTooLong = 2, kErrMirrorOutOfSync = 4, kErrSweepNeedsOrderInRegisters = 8, kErrNoKernelBody = 16;
 __device__ __forceinline__ void device_error(const StepArgs &a, int code) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (threadIdx.x == 0) (void)atomicOr(a.ch.error, code);
@@ -773,7 +774,7 @@ __device__ __forceinline__ void step_body(const StepArgs &a, unsigned char *smem
   const int lane64 = tid & 63;
   int ord = lane64;
   (void)ord;      // (the group-local kernel keeps its own order)
-  // (the sweep kernel is only launched for a parameter vector of at most 64 entries -- hier_rows_wanted, amwg_core.hip --: the order is always in
+  // (the sweep kernel is only launched for a parameter vector of at most 64 entries -- variant_for, amwg_core.hip --: the order is always in
   // registers there, and the LDS-table walk is not compiled in; a launch that breaks this is refused like the other device-side invariants)
   if (SW && a.pl.max_top > 64) { device_error(a, kErrSweepNeedsOrderInRegisters); return; }
   const bool ord_in_regs = SW ? true : (G >= 64 && a.pl.max_top <= 64);

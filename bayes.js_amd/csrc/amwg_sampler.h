@@ -13,6 +13,20 @@
 
 typedef void (*step_kernel_t)(const amwg::StepArgs);
 
+// The step kernel a sampler launches.  The variant fixes the LDS data layout, DataRef::pad, the kernel's name and whether it decides from certified
+// values (amwg_core.hip: variant_for decides it, kVariants describes it).
+enum class Variant : uint8_t {
+  Step, StepCert, HierSweep, HierSweepCert, GroupLocal,              // built-in families (amwg_kernels.hip)
+  UserStep, UserStepCert, UserSweep, UserSweepCert                   // translated closures (amwg_user_kernels.h)
+};
+// One launch geometry and the kernel that runs it.  cpb: chains per workgroup if fewer than block / lanes (StepArgs::cpb); pad: DataRef::pad for this
+// variant (the group-local row count, the Normal family's one-lane tile flag, or the row pitch of the row layout; 0 = none)
+struct LaunchPlan {
+  int lanes = 0, block = 0, grid = 0, lds = 0, cpb = 0;
+  Variant variant = Variant::Step;
+  int pad = 0;
+};
+
 struct amwg_sampler {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -29,10 +43,9 @@ struct amwg_sampler {
   uint8_t *d_adapt = nullptr;
   std::vector<uint8_t> h_adapt;
   std::vector<int32_t> h_layout;   // [4][n_params] base | len | top | multidim (ParamLayout::tab on the device)
-  // geometry
-  int lanes = 0, block = 0, grid = 0, lds = 0, cpb = 0;   // cpb: chains per workgroup if fewer than block / lanes (StepArgs::cpb)
-  step_kernel_t kernel = nullptr;
-  bool certified = false;      // `kernel` is one of the kernels that decide from certified values (amwg_kernel.h kCert: amwg_step_kernel_cert / amwg_sweep_kernel_cert)
+  LaunchPlan plan;                  // geometry and kernel (adopt_plan)
+  step_kernel_t kernel = nullptr;   // the built-in kernel of plan.variant
+  int gl_rounds = 0;                // group_local: rows of the lane-major tile (GlLayoutHost::rounds; the group-local kernel's DataRef::pad)
   std::string kernel_name;          // amwg_kernel_name(): filled on first request
   uint32_t hier_periodic_mask = 0;   // HIER: bit j set = the group labels repeat with a lane stride of 2^j (g[i] == g[i mod 2^j])
   bool lp_ready = false;
@@ -46,7 +59,7 @@ struct amwg_sampler {
   bool user_rows_cert = false;     // the row plan has certified values (kRowCert of the generated source: amwg_rows.h log_post_approx / sweep_approx / reference_order)
   int user_cert_tail_n = 0;        // certified tail of a translated closure (amwg_user.h norm_tail_approx): observations of its final constant-mean normal loop (kTailN of the generated source); 0 = none
   int user_pois_tail_n = 0;        // certified Poisson tail of a translated closure (amwg_ptail.h pois_tail_approx): observations of its final log-link Poisson loop (kPoisTail / kTailN of the generated source); 0 = none
-  bool user_sweep = false, user_has_binary = false;                  // the chosen geometry runs amwg_user_sweep; the model has binary parameters
+  bool user_has_binary = false;    // the model has binary parameters
   double user_work = 0;            // translator's estimate of the instructions of one log_post evaluation
   double user_work_one_lane = 0;   // the same with one lane per chain when that enables a fast-forwarded sum (0 = n/a)
   hipFunction_t user_fn = nullptr;

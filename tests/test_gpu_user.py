@@ -284,6 +284,21 @@ def test_certified_tail_beyond_the_readme_shape(name, params, init, n):
     assert np.isfinite(np.frombuffer(outs[0][2], dtype=np.float64)).all()
 
 
+def test_a_closure_kernel_without_a_body_at_its_geometry_fails_the_call():
+    """The host picks the kernel from the markers of the generated source (amwg_core.hip source_traits, variant_for); the kernels of the code object
+    (csrc/amwg_user_kernels.h) have a body where the closure's own traits give one.  A certified-tail marker in a comment of a closure that has no
+    certified tail makes the two disagree: the launched amwg_user_step_cert has no body, and sample() must fail with AMWG_EHIP naming the cause
+    instead of returning chains that never moved."""
+    spec, m, gold = spec_for("readme_normal")
+    assert m.meta["cert_tail_n"] == 0 and "kCertifiedTail" not in m.source and "kTailN" not in m.source
+    spec["user"] = dict(spec["user"], source=m.source + "\n// kCertifiedTail = true; kTailN = 20\n")
+    s = A.Sampler(spec, chains=64, seed=gold["case"]["seed"], lanes_per_chain=1)
+    assert s.launch_info()["kernel"] == "amwg_user_step_cert"
+    with pytest.raises(A.AmwgError, match=r"^amwg error -2: .*the launched kernel has no body for this closure at this geometry"):
+        s.sample(10)
+    s.close()
+
+
 def test_certified_poisson_tail_of_a_translated_closure_reproduces_the_reference_and_the_full_evaluation():
     """translate.js poisTailPlan + csrc/amwg_ptail.h: a closure that ends in `lp += ld.pois(y[i], Math.exp(eta))` runs amwg_user_step_cert at 16 lanes per chain (four
     chains of a wavefront share every row).  Its decisions are the expression's in the REFERENCE's order: chain by chain the reference's golden trajectory, and every bit

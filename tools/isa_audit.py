@@ -220,9 +220,19 @@ def inline_smem_waits(lines):
     return loads, bad
 
 
+def user_asm(src, lanes, block):
+    """device assembly (hipcc -S) of the program amwg_core.hip (user_program) hands to hiprtc for a translated closure at one geometry: the closure's text,
+    then csrc/amwg_user_kernels.h; -> path of the .s file"""
+    d = tempfile.mkdtemp(prefix="amwg_user_isa_")
+    f, out = os.path.join(d, "u.hip"), os.path.join(d, "u.s")
+    open(f, "w").write('#include "amwg_kernel.h"\n#include "amwg_user.h"\n#define AMWG_USER_LANES %d\n#define AMWG_USER_BLOCK %d\n%s\n#include "amwg_user_kernels.h"\n' % (lanes, block, src))
+    subprocess.check_call([HIPCC] + FLAGS + ["-I", CSRC, "-o", out, f], stderr=subprocess.DEVNULL)
+    return out
+
+
 def user_cert_asm(name="bench_normal", lanes=1, block=256):
-    """device assembly of amwg_user_step_cert of a translated closure (tests/js/user_models.js), compiled with hipcc -S from the program amwg_core.hip
-    hands to hiprtc for that geometry (user_program: the closure's text + the kernel wrapper); None when node is not installed"""
+    """device assembly of the kernels of a translated closure (tests/js/user_models.js) for that geometry, amwg_user_step_cert among them; None when node is
+    not installed"""
     import shutil
     if shutil.which("node") is None:
         return None
@@ -230,16 +240,7 @@ def user_cert_asm(name="bench_normal", lanes=1, block=256):
     import user_host
     src, _, meta = user_host.translated(name)
     assert meta["cert_tail_n"] > 0, "%s has no certified tail" % name
-    prog = ('#include "amwg_kernel.h"\n#include "amwg_user.h"\n' + src +
-            '\nextern "C" __global__ void __launch_bounds__(%d) amwg_user_step_cert(const amwg::StepArgs a) {\n'
-            '  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n'
-            '  if constexpr (amwg::CertifiedAt<amwg::UserModel, %d>::value && !amwg::CertNeedsRows<amwg::UserModel>::value) amwg::step_body<amwg::UserModel, %d, %d, false, false, true>(a, smem);\n}\n'
-            % (block, lanes, lanes, 256 if block <= 256 else 1024))
-    d = tempfile.mkdtemp(prefix="amwg_user_isa_")
-    f, out = os.path.join(d, "u.hip"), os.path.join(d, "u.s")
-    open(f, "w").write(prog)
-    subprocess.check_call([HIPCC] + FLAGS + ["-I", CSRC, "-o", out, f], stderr=subprocess.DEVNULL)
-    return out
+    return user_asm(src, lanes, block)
 
 
 def user_kernel_body(txt, symbol):

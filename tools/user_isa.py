@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """tools/user_isa.py NAME [LANES ...] -- what the gfx950 compiler makes of a TRANSLATED closure's step kernel (no GPU needed).
-Translates tests/js/user_models.js:NAME, writes the program csrc/amwg_core.hip would hand to hiprtc, compiles it with hipcc -S and lists
-the innermost loops by VALU count (the likelihood loop's unrolled body is the largest)."""
-import os, re, subprocess, sys, tempfile
+Translates tests/js/user_models.js:NAME, compiles the program csrc/amwg_core.hip would hand to hiprtc (isa_audit.user_asm) with hipcc -S and lists
+the innermost loops of amwg_user_step by VALU count (the likelihood loop's unrolled body is the largest)."""
+import os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "bayes.js_amd")]
 import isa_audit
@@ -13,14 +13,7 @@ lanes = [int(a) for a in sys.argv[2:]] or [64]
 src, arrays, meta = user_host.translated(name)
 for G in lanes:
     block = min(256, meta["max_threads"])
-    prog = '#include "amwg_kernel.h"\n#include "amwg_user.h"\n' + src + (
-        '\nextern "C" __global__ void __launch_bounds__(%d) amwg_user_step(const amwg::StepArgs a) {\n'
-        '  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];\n  amwg::step_body<amwg::UserModel, %d>(a, smem);\n}\n' % (block, G))
-    d = tempfile.mkdtemp()
-    f = os.path.join(d, "u.hip")
-    open(f, "w").write(prog)
-    out = os.path.join(d, "u.s")
-    subprocess.check_call([isa_audit.HIPCC] + isa_audit.FLAGS + ["-I", isa_audit.CSRC, "-o", out, f])
+    out = isa_audit.user_asm(src, G, block)
     txt = open(out).read()
     meta_k = isa_audit.kernel_metadata(txt)
     print(name, "G=%d" % G, meta_k.get("amwg_user_step"), out)
