@@ -1,0 +1,264 @@
+// amwg_diag.hip -- what a caller can ask about a sampler and its draws (moments, R-hat / ESS, stepper state, launch geometry, kernel name), about the
+// library (version, last error) and about the device (fp64 peak); the host build of the kernel arithmetic; the three small kernels these need.
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+
+#include "amwg_build_id.h"
+#include "amwg_host.h"
+#include "amwg_math.h"
+#include "amwg_philox.h"
+
+using namespace amwg;
+
+namespace {
+__global__ void moments_kernel(const double *draws, int64_t rows, int P, int64_t C, double *mean, double *sd) {
+  __shared__ double red[1024];
+  const int p = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+  const int64_t n = rows * C;
+  double sum = 0;
+  for (int64_t i = tid; i < n; i += nt) sum += draws[((i / C) * P + p) * C + (i % C)];
+  red[tid] = sum;
+  __syncthreads();
+  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+  const double m = red[0] / (double)n;
+  __syncthreads();
+  double ss = 0;
+  for (int64_t i = tid; i < n; i += nt) { const double dlt = draws[((i / C) * P + p) * C + (i % C)] - m; ss += dlt * dlt; }
+  red[tid] = ss;
+  __syncthreads();
+  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+  if (tid == 0) { mean[p] = m; sd[p] = n > 1 ? sqrt(red[0] / (double)(n - 1)) : 0.0; }
+}
+
+// per chain and recorded value: mean and (n-1) variance of each half of the chain's kept draws
+// out[((h*2 + stat) * PR + p) * C + c], stat 0 = mean, 1 = variance; draws [row][PR][C] (coalesced over chains)
+__global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, int64_t C, double *out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = blockIdx.y;
+  if (c >= C) return;
+  const int64_t half = rows / 2;
+  for (int h = 0; h < 2; ++h) {
+    const int64_t r0 = h * half, r1 = r0 + half;
+    double m = 0, m2 = 0;   // Welford
+    for (int64_t r = r0; r < r1; ++r) {
+      const double x = draws[(r * PR + p) * C + c];
+      const double dlt = x - m;
+      m += dlt / (double)(r - r0 + 1);
+      m2 += dlt * (x - m);
+    }
+    out[((size_t)(h * 2 + 0) * PR + p) * C + c] = m;
+    out[((size_t)(h * 2 + 1) * PR + p) * C + c] = half > 1 ? m2 / (double)(half - 1) : 0.0;
+  }
+}
+
+// 8 independent fma chains per lane, no memory traffic: the fp64 issue rate the chip sustains
+__global__ void __launch_bounds__(1024) fp64_peak_kernel(double *out, int iters, double a, double b) {
+  double x0 = threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
+  for (int i = 0; i < iters; ++i) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      x0 = __builtin_fma(x0, a, b); x1 = __builtin_fma(x1, a, b); x2 = __builtin_fma(x2, a, b); x3 = __builtin_fma(x3, a, b);
+      x4 = __builtin_fma(x4, a, b); x5 = __builtin_fma(x5, a, b); x6 = __builtin_fma(x6, a, b); x7 = __builtin_fma(x7, a, b);
+    }
+  }
+  out[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = ((x0 + x1) + (x2 + x3)) + ((x4 + x5) + (x6 + x7));
+}
+
+}  // namespace
+
+thread_local std::string g_err;
+
+int amwg_fail(int code, const char *fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return code;
+}
+
+extern "C" {
+
+const char *amwg_last_error(void) { return g_err.c_str(); }
+// which sources this binary was built from (tools/build_id.py: a hash over every source of the library, and one over the device sources + compiler flags)
+const char *amwg_version(void) { return "amwg-mi355x 0.4 (gfx950) build " AMWG_BUILD_ID " kernels " AMWG_KERNEL_ID; }
+
+double amwg_exp(double x) { return exp_v8(x); }
+double amwg_log(double x) { return log_v8(x); }
+double amwg_uniform(uint64_t seed, uint64_t chain, uint64_t index) {
+  ChainStream s;
+  s.init(seed, chain, index);
+  return s.next();
+}
+
+int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
+  if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: null argument");
+  if (!s->last_draws || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
+  HIP_TRY(hipSetDevice(s->device));
+  const int PR = s->P + s->D;
+  const size_t C = (size_t)s->C, n_out = 4 * (size_t)PR * C;
+  DevBuf dout;
+  HIP_TRY(dout.alloc(n_out * 8));
+  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, dout.as<double>());
+  std::vector<double> h(n_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h.data(), dout.p, n_out * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  const double n = (double)(s->last_rows / 2), m = 2.0 * (double)C;   // 2C half-chains of n draws
+  for (int p = 0; p < PR; ++p) {
+    // W = mean within-sequence variance; B/n = variance of the sequence means (over the 2C halves)
+    long double sw = 0, sm = 0;
+    for (int hf = 0; hf < 2; ++hf)
+      for (size_t c = 0; c < C; ++c) { sm += h[((size_t)(hf * 2 + 0) * PR + p) * C + c]; sw += h[((size_t)(hf * 2 + 1) * PR + p) * C + c]; }
+    const double W = (double)(sw / m), gm = (double)(sm / m);
+    long double sb = 0, sbc = 0;
+    for (int hf = 0; hf < 2; ++hf)
+      for (size_t c = 0; c < C; ++c) { const double dlt = h[((size_t)(hf * 2 + 0) * PR + p) * C + c] - gm; sb += (long double)dlt * dlt; }
+    const double B_over_n = (double)(sb / (m - 1));
+    const double var_plus = (n - 1) / n * W + B_over_n;
+    rhat[p] = W > 0 ? std::sqrt(var_plus / W) : (double)NAN;
+    // whole-chain means: average of the two half means (equal lengths)
+    long double smc = 0;
+    for (size_t c = 0; c < C; ++c) smc += 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]);
+    const double gmc = (double)(smc / (double)C);
+    for (size_t c = 0; c < C; ++c) { const double dlt = 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]) - gmc; sbc += (long double)dlt * dlt; }
+    const double var_chain_mean = (double)(sbc / ((double)C - 1));
+    ess[p] = var_chain_mean > 0 ? (double)C * var_plus / var_chain_mean : (double)NAN;
+  }
+  return AMWG_OK;
+}
+
+int amwg_info(amwg_sampler *s, double *pls, int32_t *ac, int32_t *it, int32_t *bc, int64_t *acc, int64_t *inb) {
+  if (!s) return amwg_fail(AMWG_EINVAL, "amwg_info: null sampler");
+  const size_t PC = (size_t)s->P * (size_t)s->C;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (pls) HIP_TRY(hipMemcpy(pls, s->ch.prop_log_scale, PC * 8, hipMemcpyDeviceToHost));
+  if (ac) HIP_TRY(hipMemcpy(ac, s->ch.acceptance_count, PC * 4, hipMemcpyDeviceToHost));
+  if (it) HIP_TRY(hipMemcpy(it, s->ch.iterations_since_adaption, PC * 4, hipMemcpyDeviceToHost));
+  if (bc) HIP_TRY(hipMemcpy(bc, s->ch.batch_count, PC * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> tmp(PC);
+  for (auto [out, dev] : {std::make_pair(acc, s->ch.accepts), std::make_pair(inb, s->ch.inbounds)}) {      // run totals: 32 bits on the device
+    if (!out) continue;
+    HIP_TRY(hipMemcpy(tmp.data(), dev, PC * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < PC; ++i) out[i] = tmp[i];
+  }
+  return AMWG_OK;
+}
+
+int amwg_chain_diag(amwg_sampler *s, uint64_t *uniforms, double *log_post_out, int32_t *named_order) {
+  if (!s) return amwg_fail(AMWG_EINVAL, "amwg_chain_diag: null sampler");
+  const size_t C = (size_t)s->C;
+  HIP_TRY(hipSetDevice(s->device));
+  // (log_post of the current state as the expression gives it: a 0-step launch computes it where it was never formed or where the stepper's cheaper value stands in)
+  if (!s->lp_ready || !s->lp_is_expression) { int rc = launch_steps(s, 0, 1, nullptr, true); if (rc != AMWG_OK) return rc; }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (uniforms) HIP_TRY(hipMemcpy(uniforms, s->ch.rng_n, C * 8, hipMemcpyDeviceToHost));
+  if (log_post_out) HIP_TRY(hipMemcpy(log_post_out, s->ch.lp_curr, C * 8, hipMemcpyDeviceToHost));
+  if (named_order && s->ch.perm16) {
+    std::vector<uint16_t> p16((size_t)s->n_params * C);
+    HIP_TRY(hipMemcpy(p16.data(), s->ch.perm16, p16.size() * 2, hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < C; ++c)
+      for (int k = 0; k < s->n_params; ++k) named_order[c * s->n_params + k] = (int32_t)p16[(size_t)k * C + c];
+  } else if (named_order) {
+    std::vector<uint64_t> pv(C);
+    HIP_TRY(hipMemcpy(pv.data(), s->ch.perm, C * 8, hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < C; ++c)
+      for (int k = 0; k < s->n_params; ++k) named_order[c * s->n_params + k] = (int32_t)((pv[c] >> (4 * k)) & 0xF);
+  }
+  return AMWG_OK;
+}
+
+int amwg_last_sample_moments(amwg_sampler *s, double *mean, double *sd) {
+  if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: null argument");
+  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: no sample() call yet");
+  HIP_TRY(hipSetDevice(s->device));
+  DevBuf buf;
+  const int PR = s->P + s->D;
+  HIP_TRY(buf.alloc((size_t)PR * 16));
+  double *dm = buf.as<double>();
+  hipLaunchKernelGGL(moments_kernel, dim3(PR), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, dm, dm + PR);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(mean, dm, (size_t)PR * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(sd, dm + PR, (size_t)PR * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMWG_OK;
+}
+
+int amwg_tuning(const amwg_sampler *s, int32_t *lanes, double *ms, int32_t cap) {
+  if (!s) return 0;
+  for (int32_t i = 0; i < cap && i < (int32_t)s->tuned.size(); ++i) {
+    if (lanes) lanes[i] = s->tuned[i].first;
+    if (ms) ms[i] = s->tuned[i].second;
+  }
+  return (int)s->tuned.size();
+}
+
+int amwg_num_components(const amwg_sampler *s) { return s ? s->P : 0; }
+int amwg_num_recorded(const amwg_sampler *s) { return s ? s->P + s->D : 0; }
+int64_t amwg_num_chains(const amwg_sampler *s) { return s ? s->C : 0; }
+
+int amwg_launch_info(const amwg_sampler *s, int32_t *lanes, int32_t *block, int32_t *grid, int32_t *lds, int32_t *n_launches, double *kernel_ms) {
+  if (!s) return amwg_fail(AMWG_EINVAL, "amwg_launch_info: null sampler");
+  if (lanes) *lanes = s->plan.lanes;
+  if (block) *block = s->plan.block;
+  if (grid) *grid = s->plan.grid;
+  if (lds) *lds = s->plan.lds;
+  if (n_launches) *n_launches = s->n_launches;
+  if (kernel_ms) *kernel_ms = s->kernel_ms;
+  return AMWG_OK;
+}
+
+int amwg_summation_order(const amwg_sampler *s) {
+  if (!s) return amwg_fail(AMWG_EINVAL, "amwg_summation_order: null sampler");
+  // (the certified kernels evaluate the expression in the reference's order: amwg_kernel.h kRefOrder)
+  return info(s->plan.variant).certified ? 1 : s->plan.lanes;
+}
+
+const char *amwg_kernel_name(const amwg_sampler *s) {
+  if (!s) { (void)amwg_fail(AMWG_EINVAL, "amwg_kernel_name: null sampler"); return ""; }
+  amwg_sampler *m = const_cast<amwg_sampler *>(s);
+  if (m->kernel_name.empty()) {
+    const LaunchPlan &p = s->plan;
+    const int cls = p.block <= 256 ? 256 : (p.block <= 512 ? 512 : 1024);
+    const char *name = info(p.variant).name;
+    static const char *const fam[] = {"NormalModel", "BetaBernModel", "HierNormalModel", "PoisGlmModel"};      // (AMWG_MODEL_* - 1)
+    char buf[96];
+    if (p.variant == Variant::Step || p.variant == Variant::StepCert)
+      snprintf(buf, sizeof buf, "%s<%s,%d,%d>", name, fam[s->model - 1], p.lanes, p.lanes > 64 ? (p.lanes <= 256 ? 256 : (p.lanes <= 512 ? 512 : 1024)) : cls);
+    else if (p.variant == Variant::GroupLocal || p.variant == Variant::HierSweep || p.variant == Variant::HierSweepCert)
+      snprintf(buf, sizeof buf, "%s<%s,%d>", name, p.variant == Variant::GroupLocal ? "HierGlModel" : "HierNormalModel", cls);
+    else snprintf(buf, sizeof buf, "%s", name);      // a translated closure: its hiprtc symbol
+    m->kernel_name = buf;
+  }
+  return m->kernel_name.c_str();
+}
+
+int amwg_fp64_peak(int32_t device, double *lane_ops_per_s) {
+  if (!lane_ops_per_s) return amwg_fail(AMWG_EINVAL, "amwg_fp64_peak: null argument");
+  TRYB(use_device(device));
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  const int blocks = (prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 2, threads = 1024, iters = 20000;
+  DevBuf dout;
+  HIP_TRY(dout.alloc((size_t)blocks * threads * 8));
+  EventPair ev;
+  HIP_TRY(hipEventCreate(&ev.e0));
+  HIP_TRY(hipEventCreate(&ev.e1));
+  float best = 1e30f;
+  for (int rep = 0; rep < 3; ++rep) {    // first repetition warms the clocks up
+    HIP_TRY(hipEventRecord(ev.e0, 0));
+    hipLaunchKernelGGL(fp64_peak_kernel, dim3(blocks), dim3(threads), 0, 0, dout.as<double>(), iters, 0.999999, 1e-7);
+    HIP_TRY(hipEventRecord(ev.e1, 0));
+    HIP_TRY(hipEventSynchronize(ev.e1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    if (rep > 0 && ms < best) best = ms;
+  }
+  *lane_ops_per_s = (double)blocks * threads * (double)iters * 64.0 / (best * 1e-3);
+  return AMWG_OK;
+}
+
+}  // extern "C"

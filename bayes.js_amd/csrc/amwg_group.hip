@@ -11,7 +11,7 @@
 //     shard by a kernel -- RCCL refuses duplicate devices in a communicator -- then the leaders all-reduce, then the result
 //     is copied back to the followers.  A one-device group still runs the (one-rank) RCCL all-reduce.
 //
-// Statistics (same definitions as the single-sampler entry points in amwg_core.hip):
+// Statistics (same definitions as the single-sampler entry points in amwg_diag.hip):
 //   moments      two passes: all-reduce of (count, sum) -> mean; all-reduce of sum (x - mean)^2 -> sd (n - 1)
 //   diagnostics  split-R-hat / ESS from per-chain half means and variances (chain_halves): all-reduce of
 //                (sum var_h, sum mean_h, sum chain_mean) -> W, grand means; all-reduce of (sum (mean_h - gm)^2, sum (cm - gmc)^2)
@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(1024) draw_sums_kernel(const double *draws, in
 }
 
 // per chain and recorded value: mean and (n-1) variance of each half of the chain's kept draws (the same kernel as in
-// amwg_core.hip): out[((h*2 + stat) * PR + p) * C + c]
+// amwg_diag.hip): out[((h*2 + stat) * PR + p) * C + c]
 __global__ void group_chain_halves_kernel(const double *draws, int64_t rows, int PR, int64_t C, double *out) {
   const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int p = blockIdx.y;

@@ -3,31 +3,24 @@
 //
 // BT is the register budget the instantiation is compiled for (__launch_bounds__): workgroups of up to 256 threads may use 512
 // VGPRs per lane, 512 threads 256, 1024 threads 128.  A chain on G > 64 lanes is exactly one workgroup of G threads, so those have
-// one class each.  The host (amwg_core.hip, choose_geometry) asks for the kernel of (G, workgroup size) through the lookup below.
+// one class each.  The host (amwg_plan.hip) reads the family's row of facts (amwg_host.h FamilyRow), exported at the end of this file: the lookups
+// of the kernel for (G, workgroup size), the LDS bytes of the family's data and its largest workgroup.
 #include <hip/hip_runtime.h>
 
+#include "amwg_host.h"
 #include "amwg_kernel.h"
 #include "amwg_models.h"
-#include "amwg_sampler.h"
 
 using namespace amwg;
 
 #if AMWG_FAMILY == 0
 using Family = NormalModel;
-#define AMWG_FAMILY_LOOKUP amwg_kernels_normal
-#define AMWG_FAMILY_CERT_LOOKUP amwg_kernels_cert_normal
 #elif AMWG_FAMILY == 1
 using Family = BetaBernModel;
-#define AMWG_FAMILY_LOOKUP amwg_kernels_beta_bern
-#define AMWG_FAMILY_CERT_LOOKUP amwg_kernels_cert_beta_bern
 #elif AMWG_FAMILY == 2
 using Family = HierNormalModel;
-#define AMWG_FAMILY_LOOKUP amwg_kernels_hier_normal
-#define AMWG_FAMILY_CERT_LOOKUP amwg_kernels_cert_hier_normal
 #elif AMWG_FAMILY == 3
 using Family = PoisGlmModel;
-#define AMWG_FAMILY_LOOKUP amwg_kernels_pois_glm
-#define AMWG_FAMILY_CERT_LOOKUP amwg_kernels_cert_pois_glm
 #else
 #error "AMWG_FAMILY must be 0..3"
 #endif
@@ -105,10 +98,9 @@ step_kernel_t certified_lookup(int lanes, int block) {
   (void)lanes; (void)block;
   return nullptr;
 }
-}  // namespace
-step_kernel_t AMWG_FAMILY_CERT_LOOKUP(int lanes, int block) { return certified_lookup<Family>(lanes, block); }
+step_kernel_t certified(int lanes, int block) { return certified_lookup<Family>(lanes, block); }
 
-step_kernel_t AMWG_FAMILY_LOOKUP(int lanes, int block) {
+step_kernel_t lookup(int lanes, int block) {
   switch (lanes) {
     case 1: return single_wave<1>(block);
     case 2: return single_wave<2>(block);
@@ -123,4 +115,9 @@ step_kernel_t AMWG_FAMILY_LOOKUP(int lanes, int block) {
     case 1024: return multi_wave<1024>(block);
   }
   return nullptr;
+}
+}  // namespace
+
+template <> FamilyRow amwg_family_row<AMWG_FAMILY>() {
+  return {lookup, certified, [](int n_obs, int groups, int lanes) -> size_t { return Family::lds_bytes(n_obs, groups, lanes); }, Family::kMaxThreads};
 }

@@ -1,5 +1,5 @@
 /* amwg_rtc_headers.c -- the kernel headers as NUL-terminated text inside libamwg.so, so that
- * amwg_create_user can hand them to hiprtc (csrc/amwg_core.hip, compile_user).  Paths are
+ * amwg_create_user can hand them to hiprtc (csrc/amwg_rtc.hip, compile_user).  Paths are
  * relative to this directory (the Makefile builds from here). */
 #define AMWG_TEXT(sym, file)                                                        \
   __asm__(".section .rodata\n.global " #sym "\n.type " #sym ", @object\n" #sym ":\n" \

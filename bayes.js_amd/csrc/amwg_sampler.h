@@ -1,5 +1,5 @@
-// amwg_sampler.h -- the sampler handle behind the C ABI (internal to libamwg.so; shared by amwg_core.hip and
-// amwg_summaries.hip).
+// amwg_sampler.h -- the sampler handle behind the C ABI (internal to libamwg.so; shared by the host units -- amwg_host.h --,
+// amwg_summaries.hip and amwg_group.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,7 +14,7 @@
 typedef void (*step_kernel_t)(const amwg::StepArgs);
 
 // The step kernel a sampler launches.  The variant fixes the LDS data layout, DataRef::pad, the kernel's name and whether it decides from certified
-// values (amwg_core.hip: variant_for decides it, kVariants describes it).
+// values (amwg_plan.hip: variant_for decides it, kVariants describes it).
 enum class Variant : uint8_t {
   Step, StepCert, HierSweep, HierSweepCert, GroupLocal,              // built-in families (amwg_kernels.hip)
   UserStep, UserStepCert, UserSweep, UserSweepCert                   // translated closures (amwg_user_kernels.h)
@@ -78,5 +78,5 @@ struct amwg_sampler {
   hipStream_t copy_stream = nullptr;
 };
 
-// shared helper: records an error message for amwg_last_error() and returns `code`
+// shared helper (amwg_diag.hip): records an error message for amwg_last_error() and returns `code`
 int amwg_fail(int code, const char *fmt, ...);

@@ -1,0 +1,105 @@
+// amwg_selftest.hip -- the test-only entry points of include/amwg_selftest.h: the building blocks one by one, for the test suite.  Linked into
+// libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
+#include "../../include/amwg_selftest.h"
+#include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
+#include "amwg_host.h"
+#include "amwg_kernel.h"
+#include "amwg_models.h"
+
+using namespace amwg;
+// tests only: thread j sums the same bit sequence from acc0[j] with addends l1[j], l0[j], once with two_valued_sum and
+// once term by term
+__global__ void two_valued_check_kernel(const uint32_t *tab, int N, int64_t m, const double *acc0, const double *l1, const double *l0,
+                                        double *out_ff, double *out_seq) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const size_t W = BetaBernModel::words(N);
+  BitData B{tab, tab + W, tab + 2 * W, tab + 3 * W, tab + 4 * W, tab + 5 * W, N};
+  out_ff[j] = two_valued_sum(acc0[j], l1[j], l0[j], B);
+  double acc = acc0[j];
+  for (int i = 0; i < N; ++i) acc = acc + (((tab[i >> 5] >> (i & 31)) & 1u) ? l1[j] : l0[j]);
+  out_seq[j] = acc;
+}
+
+extern "C" {
+double amwg_pow(double x, double y) { return pow_v8(x, y); }
+double amwg_log1p(double x) { return log1p_v8(x); }
+double amwg_expm1(double x) { return expm1_v8(x); }
+double amwg_math1(int32_t fn, double x) { return math1_by_id(fn, x); }
+double amwg_math2(int32_t fn, double x, double y) {
+  switch (fn) {
+    case 0: return atan2_v8(x, y);
+    case 1: return hypot2_v8(x, y);
+    case 2: return js_mod(x, y);                 // JavaScript's `%`
+    case 3: return (double)js_toint32(x);        // `x | 0`
+  }
+  return __builtin_nan("");
+}
+double amwg_hypot3(double x, double y, double z) { return hypot3_v8(x, y, z); }
+double amwg_ld_host(int32_t id, double x, double a, double b, double c) { return ld_by_id(id, x, a, b, c); }
+
+// include/amwg_selftest.h: the host-side machinery that makes sample()'s destination resident ahead of the device-to-host copies (amwg_run.hip Prefaulter), run on a
+// caller's buffer cut into `n_chunks` chunks with `threads` helpers: no byte may change, whatever the alignment and the sizes.  No GPU involved.
+int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads) {
+  if (!buf || n_chunks < 1 || threads < 0 || threads > 16) return amwg_fail(AMWG_EINVAL, "amwg_prefault_selftest: bad argument");
+  Prefaulter pf((size_t)n_chunks);
+  const size_t per = bytes / (size_t)n_chunks;
+  for (int32_t j = 0; j < n_chunks; ++j) pf.add(buf + (size_t)j * per, j == n_chunks - 1 ? bytes - (size_t)j * per : per, (size_t)j);
+  pf.start(threads);
+  for (int32_t j = 0; j < n_chunks; ++j) pf.wait_chunk((size_t)j);
+  return AMWG_OK;
+}
+
+int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_t m, const double *acc0, const double *l1, const double *l0,
+                              double *out_fast_forward, double *out_term_by_term) {
+  if (!x || !acc0 || !l1 || !l0 || !out_fast_forward || !out_term_by_term || n < 0 || m < 0) return amwg_fail(AMWG_EINVAL, "amwg_two_valued_sum_check: bad argument");
+  TRYB(use_device(device));
+  std::vector<uint8_t> xb((size_t)n);
+  for (int i = 0; i < n; ++i) xb[i] = x[i] == 1 ? 1 : 0;
+  const std::vector<uint32_t> tab = two_valued_tables(xb.data(), n);
+  DevBuf dtab, d[5];
+  HIP_TRY(dtab.alloc(tab.size() * 4));
+  HIP_TRY(hipMemcpy(dtab.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  const double *src[3] = {acc0, l1, l0};
+  for (int k = 0; k < 5; ++k) {
+    HIP_TRY(d[k].alloc((size_t)m * 8));
+    if (k < 3 && m) HIP_TRY(hipMemcpy(d[k].p, src[k], (size_t)m * 8, hipMemcpyHostToDevice));
+  }
+  if (m) hipLaunchKernelGGL(two_valued_check_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, 0, dtab.as<uint32_t>(), n, m,
+                            d[0].as<double>(), d[1].as<double>(), d[2].as<double>(), d[3].as<double>(), d[4].as<double>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out_fast_forward, d[3].p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_term_by_term, d[4].p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+int amwg_ld_device(int32_t device, int64_t n, const double *records, double *out) {
+  if (!records || !out || n < 0) return amwg_fail(AMWG_EINVAL, "amwg_ld_device: bad argument");
+  TRYB(use_device(device));
+  DevBuf dr, dout;
+  HIP_TRY(dr.alloc((size_t)n * 40));
+  HIP_TRY(dout.alloc((size_t)n * 8));
+  HIP_TRY(hipMemcpy(dr.p, records, (size_t)n * 40, hipMemcpyHostToDevice));
+  if (n) hipLaunchKernelGGL(amwg_ld_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, n, dr.as<double>(), dout.as<double>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+int amwg_device_eval(int32_t device, int32_t op, int64_t n, const double *a, const double *b, const double *c, double *out) {
+  if (!a || !out || n < 0) return amwg_fail(AMWG_EINVAL, "amwg_device_eval: bad argument");
+  TRYB(use_device(device));
+  DevBuf da, db, dc, dout;
+  const size_t bytes = (size_t)n * 8;
+  HIP_TRY(da.alloc(bytes));
+  HIP_TRY(dout.alloc(bytes));
+  HIP_TRY(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
+  if (b) { HIP_TRY(db.alloc(bytes)); HIP_TRY(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice)); }
+  if (c) { HIP_TRY(dc.alloc(bytes)); HIP_TRY(hipMemcpy(dc.p, c, bytes, hipMemcpyHostToDevice)); }
+  if (n) hipLaunchKernelGGL(amwg_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, n, da.as<double>(), db.as<double>(), dc.as<double>(), dout.as<double>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+}  // extern "C"

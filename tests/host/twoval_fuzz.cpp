@@ -12,7 +12,7 @@
 
 using namespace amwg;
 
-static std::vector<uint32_t> tables(const std::vector<uint8_t> &x) {   // same recipe as amwg_core.hip two_valued_tables
+static std::vector<uint32_t> tables(const std::vector<uint8_t> &x) {   // same recipe as amwg_create.hip two_valued_tables
   const int N = (int)x.size();
   const size_t W = two_valued_words(N);
   std::vector<uint32_t> tab(6 * W, 0u);

@@ -179,7 +179,7 @@ def test_certified_bounds_host_replay_in_quad_precision(tmp_path):
 
 
 def test_copy_out_prefaulter_touches_without_changing_a_byte():
-    """csrc/amwg_core.hip Prefaulter (round 6: what makes sample()'s 1 GB copy-out run at the link's rate instead of the page-fault rate): on fresh, on
+    """csrc/amwg_run.hip Prefaulter (round 6: what makes sample()'s 1 GB copy-out run at the link's rate instead of the page-fault rate): on fresh, on
     already-resident and on oddly aligned buffers, with 0 / 1 / 4 helper threads and more chunks than pieces, every byte stays what it was."""
     import ctypes as C
     import numpy as np

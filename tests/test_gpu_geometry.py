@@ -154,7 +154,7 @@ def test_certified_normal_kernel_equals_the_expression_in_every_geometry(block, 
 
 def test_auto_geometry_at_131109_chains_is_the_512_class_and_equals_the_expression():
     """From 131 072 chains on the host picks 512-thread workgroups by itself (at least one per CU): the certified kernel with blocks of 8
-    (csrc/amwg_core.hip choose_geometry).  131 072 + 37 chains: the last workgroup holds one partial wavefront."""
+    (csrc/amwg_plan.hip choose_geometry).  131 072 + 37 chains: the last workgroup holds one partial wavefront."""
     C, n, steps = 131072 + 37, 1000, 48
     spec = _normal_spec(n)
     s = A.Sampler(spec, chains=C, seed=SEED, chain_offset=OFFSET, steps_per_launch=SPL)

@@ -431,7 +431,7 @@ def _shuffled_hier(n_obs, G, seed, sizes=None):
                                            (2000, 32, None), (130, 64, [3] * 2 + [2] * 62)])
 def test_group_local_any_labels_any_group_count_equals_its_oracle(n_obs, G, sizes):
     """Round 4: the group-local kernel takes any labels and any G <= 64 -- the host deals the wavefront's lanes to the groups in aligned
-    power-of-two blocks and lays the data out lane-major (amwg_core.hip gl_layout; restated in the oracle).  Ragged designs: groups of
+    power-of-two blocks and lays the data out lane-major (amwg_plan.hip gl_layout; restated in the oracle).  Ragged designs: groups of
     very different sizes, empty groups, two groups, 64 groups, fewer observations than lanes; chains 0 and 2 of 3, every double."""
     data = _shuffled_hier(n_obs, G, 100 + n_obs + G, sizes)
     spec = model_spec.build_spec("hier_normal", data)

@@ -285,7 +285,7 @@ def test_certified_tail_beyond_the_readme_shape(name, params, init, n):
 
 
 def test_a_closure_kernel_without_a_body_at_its_geometry_fails_the_call():
-    """The host picks the kernel from the markers of the generated source (amwg_core.hip source_traits, variant_for); the kernels of the code object
+    """The host picks the kernel from the markers of the generated source (amwg_rtc.hip source_traits, amwg_plan.hip variant_for); the kernels of the code object
     (csrc/amwg_user_kernels.h) have a body where the closure's own traits give one.  A certified-tail marker in a comment of a closure that has no
     certified tail makes the two disagree: the launched amwg_user_step_cert has no body, and sample() must fail with AMWG_EHIP naming the cause
     instead of returning chains that never moved."""

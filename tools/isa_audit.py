@@ -221,7 +221,7 @@ def inline_smem_waits(lines):
 
 
 def user_asm(src, lanes, block):
-    """device assembly (hipcc -S) of the program amwg_core.hip (user_program) hands to hiprtc for a translated closure at one geometry: the closure's text,
+    """device assembly (hipcc -S) of the program amwg_rtc.hip (user_program) hands to hiprtc for a translated closure at one geometry: the closure's text,
     then csrc/amwg_user_kernels.h; -> path of the .s file"""
     d = tempfile.mkdtemp(prefix="amwg_user_isa_")
     f, out = os.path.join(d, "u.hip"), os.path.join(d, "u.s")

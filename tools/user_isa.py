@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/user_isa.py NAME [LANES ...] -- what the gfx950 compiler makes of a TRANSLATED closure's step kernel (no GPU needed).
-Translates tests/js/user_models.js:NAME, compiles the program csrc/amwg_core.hip would hand to hiprtc (isa_audit.user_asm) with hipcc -S and lists
+Translates tests/js/user_models.js:NAME, compiles the program csrc/amwg_rtc.hip would hand to hiprtc (isa_audit.user_asm) with hipcc -S and lists
 the innermost loops of amwg_user_step by VALU count (the likelihood loop's unrolled body is the largest)."""
 import os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
