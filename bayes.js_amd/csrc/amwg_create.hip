@@ -437,6 +437,7 @@ static int adopt_user_model(amwg_sampler *s, const amwg_user_model *m, int max_t
   s->user_rows_cert = s->user_rows_sweep && t.row_cert;
   s->user_cert_tail_n = t.cert_tail_n;
   s->user_pois_tail_n = t.pois_tail_n;
+  s->user_logit_tail_n = t.logit_tail_n;
   return AMWG_OK;
 }
 

@@ -460,6 +460,55 @@ AMWG_HD double exp_bounded(double x, const C &c) {
 }
 constexpr double kExpBoundedRel = 0x1p-46;
 
+// softplus(x) = log(1 + e^x) = max(x, 0) + log1p(e^-|x|), |x| <= 690, to an ABSOLUTE error below kSoftplusBoundedAbs -- NOT the reference's
+// log1p_v8(exp_v8(x)) (log1p_exp_v8 below is), for the certified pass of a logistic likelihood, which uses the value with its bound only (amwg_ltail.h).  One
+// straight line: no branch on the data, no IEEE division.  a = min(|x|, 64) (what the cut drops is below e^-64 < 2^-92); t = exp_bounded(-a) in [2^-93, 1];
+// s = t / (2 + t) in (0, 1/3] by quot_plain (reciprocal, two Newton steps, quotient, residual: 2 + t in (2, 3] and t need no exponent juggling -- the correctly
+// rounded quotient, so the host build, which divides, gives the same bits); log1p(t) = 2 atanh(s) = 2 s + s z Q(z), z = s s <= 1/9, Q the polynomial of degree 9
+// that interpolates 2 (1/3 + z/5 + z^2/7 + ...) at the ten Chebyshev nodes of [0, 1/9] (tools/softplus_poly.py: 50-digit arithmetic; with its coefficients
+// rounded to doubles 2 s + s z Q(z) is 4.9e-18 from log1p(t) in exact arithmetic).  The error, u = 2^-53, term by term:
+//   the cut at 64: 2^-92;  exp_bounded: 2^-46 t relative to t, and d log1p / dt = 1 / (1 + t): <= 2^-46 t / (1 + t) <= 2^-47;  2 + t and the quotient round:
+//   s is within 2 u s of t / (2 + t), d (2 atanh) / ds = 2 / (1 - s^2) <= 2.25 and s <= 1/3: 1.5 u;  z (3 u relative), w = s z (4.5 u), Q's nine fused steps
+//   (Q <= 0.7) and the product, all scaled by w Q <= 0.026: < 0.5 u;  the closing fused step on a value <= ln 2: 0.35 u;  the polynomial: 0.05 u;  and the
+//   closing max(x, 0) + log1p: for x < 64 half an ulp of a value below 64, 2^-48; beyond the cut the second summand is below 2^-92, the sum IS x, and what is
+//   lost is log1p(e^-x) < 2^-92, counted above.
+//   In all 2^-48 + 2^-47 + 2.4 u + 2^-92 = 1.09e-14 < kSoftplusBoundedAbs = 2^-46 = 1.42e-14 (the classical bound; measured 3.6e-15 = 2^-48, met at x in [32, 37)
+//   where the last rounding is all of it, and 2.4e-16 for |x| <= 1: tests/host/softplus_bounded_fuzz.cpp).
+// 17 + 22 operations.  C: the coefficients as a type (literals, or per-lane registers: SoftplusRegs).
+struct SoftplusLiterals : ExpTaylorLiterals {
+  static constexpr double q0 = 0x1.5555555555555p-1, q1 = 0x1.999999999a3ddp-2, q2 = 0x1.24924923d44bfp-2, q3 = 0x1.c71c72714385ap-3, q4 = 0x1.745cf0b0cfb22p-3,
+                          q5 = 0x1.3b18b2968f08ep-3, q6 = 0x1.10ac75bea1337p-3, q7 = 0x1.eb9060bb72aeap-4, q8 = 0x1.687a6330dbf14p-4, q9 = 0x1.4b0a32c0a7a68p-3;
+};
+struct SoftplusRegs : ExpTaylorRegs { double q0, q1, q2, q3, q4, q5, q6, q7, q8, q9; };
+AMWG_HD SoftplusRegs softplus_regs() {
+  typedef SoftplusLiterals L;
+  SoftplusRegs k;
+  static_cast<ExpTaylorRegs &>(k) = exp_taylor_regs();
+  k.q0 = L::q0; k.q1 = L::q1; k.q2 = L::q2; k.q3 = L::q3; k.q4 = L::q4; k.q5 = L::q5; k.q6 = L::q6; k.q7 = L::q7; k.q8 = L::q8; k.q9 = L::q9;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(k.q0), "+v"(k.q1), "+v"(k.q2), "+v"(k.q3), "+v"(k.q4), "+v"(k.q5), "+v"(k.q6), "+v"(k.q7), "+v"(k.q8), "+v"(k.q9));
+#endif
+  return k;
+}
+template <class C>
+AMWG_HD double softplus_bounded(double x, const C &c) {
+  const double t = exp_bounded(-__builtin_fmin(__builtin_fabs(x), 64.0), c);
+  const double s = quot_plain(t, 2.0 + t);
+  const double z = s * s;
+  double q = __builtin_fma(c.q9, z, c.q8);
+  q = __builtin_fma(q, z, c.q7);
+  q = __builtin_fma(q, z, c.q6);
+  q = __builtin_fma(q, z, c.q5);
+  q = __builtin_fma(q, z, c.q4);
+  q = __builtin_fma(q, z, c.q3);
+  q = __builtin_fma(q, z, c.q2);
+  q = __builtin_fma(q, z, c.q1);
+  q = __builtin_fma(q, z, c.q0);
+  return __builtin_fmax(x, 0.0) + __builtin_fma(s * z, q, s + s);
+}
+AMWG_HD double softplus_bounded(double x) { return softplus_bounded(x, SoftplusLiterals{}); }
+constexpr double kSoftplusBoundedAbs = 0x1p-46;
+
 AMWG_HD double lo_zeroed(double x) { return bits_f64(f64_bits(x) & 0xffffffff00000000ull); }
 AMWG_HD double scalbn_v8(double x, int n) {
   const double two54 = 1.80143985094819840000e+16, twom54 = 5.55111512312578270212e-17, huge = 1.0e+300, tiny = 1.0e-300;

@@ -85,7 +85,8 @@ const VariantInfo &info(Variant v) { return kVariants[(int)v]; }
 // The kernel G lanes per chain in workgroups of bt threads with max_lds bytes of LDS run, and its DataRef::pad: the plan's lanes, block, variant and pad.
 //   * certified decisions unless full_evaluation or exact_division ask for the expression: the Normal family at one lane per chain, the Poisson family at
 //     16, the hierarchical family's sweep kernel; a closure without binary parameters with a certified tail (amwg_user.h norm_tail_approx: one lane;
-//     amwg_ptail.h pois_tail_approx: 16 lanes, four chains sharing every row they read) or a row plan marked kRowCert (amwg_rows.h);
+//     amwg_ptail.h pois_tail_approx / amwg_ltail.h logit_tail_approx: 16 lanes, four chains sharing every row they read) or a row plan marked kRowCert
+//     (amwg_rows.h);
 //   * the row layout (lane-local re-evaluation) of the hierarchical family and of a closure's row plan (amwg_rows.h): a chain on one wavefront, not
 //     switched off, the tile, the label bytes and the per-wavefront term rows beside the stepper state.  Its sweep kernels are compiled for at most 512
 //     threads: a caller who ASKS for 1024 gets the kernel that evaluates everything, not a "no launch geometry fits" that names the wrong cause.  A
@@ -110,7 +111,7 @@ static LaunchPlan variant_for(const amwg_sampler *s, int G, int bt, size_t max_l
     if (rows && s->user_rows_sweep && !s->user_has_binary && s->pl.max_top <= 64)
       p.variant = cert && s->user_rows_cert ? Variant::UserSweepCert : Variant::UserSweep;
     else
-      p.variant = cert && ((s->user_cert_tail_n > 0 && G == 1) || (s->user_pois_tail_n > 0 && G == 16)) ? Variant::UserStepCert : Variant::UserStep;
+      p.variant = cert && ((s->user_cert_tail_n > 0 && G == 1) || ((s->user_pois_tail_n > 0 || s->user_logit_tail_n > 0) && G == 16)) ? Variant::UserStepCert : Variant::UserStep;
     return p;
   }
   if (s->mc.group_local) { p.variant = Variant::GroupLocal, p.pad = s->gl_rounds; return p; }
@@ -179,6 +180,12 @@ static double model_work(const amwg_sampler *s, int G) {
   if (q.variant == Variant::UserStepCert && s->user_pois_tail_n > 0) {      // exp + log per observation (~70 of the term's operations) become exp_bounded's 19, and a row is read once for four chains
     const double n = (double)s->user_pois_tail_n, w = s->user_work > 0 ? s->user_work : 1e6;
     return (w - 70.0 * n > 0.4 * w) ? w - 70.0 * n : 0.4 * w;
+  }
+  if (q.variant == Variant::UserStepCert && s->user_logit_tail_n > 0) {
+    // exp, log1p and two quotients per observation (130 vector instructions per observation and chain in the lane-split loop) become softplus_bounded's 52, and a row is
+    // read once for four chains.  0.36 of the translator's estimate: the ratio of the rates MEASURED on logit_n10k at 8 192 chains, 16 lanes, 512 threads -- 2.13e7
+    // updates/s for the lane-order kernel, 5.95e7 for this one
+    return 0.36 * (s->user_work > 0 ? s->user_work : 1e6);
   }
   if (q.variant == Variant::UserStepCert) {      // the tail loop's ~16 instructions per observation become the certified pass's 2.6
     const double w1 = s->user_work_one_lane > 0 ? s->user_work_one_lane : s->user_work, n = (double)s->user_cert_tail_n;

@@ -17,7 +17,7 @@
 // together with the very same step kernel source the built-in models are compiled from.
 extern "C" {
 extern const char amwg_hdr_stdint[], amwg_hdr_types[], amwg_hdr_math[], amwg_hdr_div[], amwg_hdr_ld[], amwg_hdr_philox[],
-    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[],
+    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[], amwg_hdr_ltail[],
     amwg_hdr_user_kernels[];
 }
 
@@ -114,9 +114,9 @@ static void dump_code_object(const std::vector<char> &code) {      // developmen
 // use_cache = false: compile even if the on-disk cache has the object (the caller found the cached one unloadable)
 static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool use_cache = true) {
   static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h", "amwg_kernel.h", "amwg_user.h",
-                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_user_kernels.h"};
+                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_ltail.h", "amwg_user_kernels.h"};
   const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox, amwg_hdr_kernel, amwg_hdr_user,
-                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_user_kernels};
+                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_ltail, amwg_hdr_user_kernels};
   constexpr int kHeaders = (int)(sizeof(texts) / sizeof(texts[0]));
   const std::string prog_src = user_program(source, lanes, block);
 #if defined(AMWG_AUDIT)      // (libamwg_audit.so: the certified kernels of translated closures record |A - E| / eps as the built-in families' do)
@@ -171,7 +171,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
 }
 
 // What the generated source of a translated closure (translate.js) states about itself, read off its markers: the row plan (kRowN, kRowGroups, kRowSweep,
-// kRowCert; -1 = no such marker), the certified tail (kCertifiedTail, kTailN) and the certified Poisson tail (kPoisTail, kTailN); 0 = none.
+// kRowCert; -1 = no such marker), the certified tail (kCertifiedTail, kTailN), the certified Poisson tail (kPoisTail, kTailN) and the certified logistic tail (kLogitTail, kTailN); 0 = none.
 SourceTraits source_traits(const char *src) {
   auto int_after = [&](const char *key) -> long {
     const char *q = strstr(src, key);
@@ -179,7 +179,7 @@ SourceTraits source_traits(const char *src) {
   };
   auto tail_n = [&](const char *marker) { const long n = strstr(src, marker) ? int_after("kTailN = ") : 0; return n > 0 && n < (1l << 28) ? (int)n : 0; };
   return SourceTraits{int_after("kRowN = "), int_after("kRowGroups = "), strstr(src, "kRowSweep = true") != nullptr, strstr(src, "kRowCert = true") != nullptr,
-                      tail_n("kCertifiedTail = true"), tail_n("kPoisTail = true")};
+                      tail_n("kCertifiedTail = true"), tail_n("kPoisTail = true"), tail_n("kLogitTail = true")};
 }
 
 // ---- compile for the adopted plan (cached per process by source text + geometry + arch) and load on the sampler's device

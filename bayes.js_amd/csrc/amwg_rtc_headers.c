@@ -19,4 +19,5 @@ AMWG_TEXT(amwg_hdr_pass, "amwg_pass.h");
 AMWG_TEXT(amwg_hdr_rows, "amwg_rows.h");
 AMWG_TEXT(amwg_hdr_window, "amwg_window.h");
 AMWG_TEXT(amwg_hdr_ptail, "amwg_ptail.h");
+AMWG_TEXT(amwg_hdr_ltail, "amwg_ltail.h");
 AMWG_TEXT(amwg_hdr_user_kernels, "amwg_user_kernels.h");

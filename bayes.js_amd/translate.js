@@ -1303,6 +1303,22 @@ Translator.prototype.deriveStore = function () {
   return 'if constexpr (DERIVE) { ' + this.derivedFinal.map((nm, q) => 'dv[' + q + '] = dq_' + nm + ';').join(' ') + ' }';
 };
 
+// The emitted term of a logistic likelihood, `((<cast>A<y>[v_<i>] * <eta>) - log1p_exp_v8(<eta>))` with the factors in either order and the SAME text for eta in
+// both places -> [term, cast, y, i, eta] (the shape of the Poisson candidate's match) or null
+function logitTerm(code) {
+  const cut = ' - log1p_exp_v8(';
+  const at = code.lastIndexOf(cut);
+  if (at < 0 || code.slice(0, 2) !== '((' || code.slice(-2) !== '))' || code[at - 1] !== ')') return null;
+  const eta = code.slice(at + cut.length, -2), prod = code.slice(2, at - 1);
+  const balanced = (t) => { let dep = 0; for (const ch of t) { if (ch === '(' || ch === '[') dep++; else if ((ch === ')' || ch === ']') && --dep < 0) return false; } return dep === 0; };
+  if (!eta || !balanced(eta) || !balanced(prod)) return null;
+  const yre = /^((?:\(double\))?)A(\d+)\[v_(\w+)\]$/;
+  let my = null;
+  if (prod.slice(-(eta.length + 3)) === ' * ' + eta) my = yre.exec(prod.slice(0, -(eta.length + 3)));
+  if (!my && prod.slice(0, eta.length + 3) === eta + ' * ') my = yre.exec(prod.slice(eta.length + 3));
+  return my ? [code, my[1], my[2], my[3], eta] : null;
+}
+
 Translator.prototype.forLoop = function (s, out, indent, ctx) {
   const canon = this.canonicalLoop(s);
   const split = !ctx.inLoop && this.splittable(s, canon);
@@ -1482,12 +1498,17 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
       }
       // `for (i = 0; i < y.length; i++) { <eta from the state and row i>; lp += ld.pois(y[i], Math.exp(eta)); }` over whole arrays of counts: CERTIFIED POISSON TAIL
       // candidate (csrc/amwg_ptail.h).  run() decides (it must be the LAST statement: poisTailPlan); the loop itself is emitted as any other lane-split loop.
-      const mp = /^ld_pois_pre_exp\(((?:\(double\))?)A(\d+)\[v_(\w+)\], (.+), A(\d+)\[v_\3\]\)$/.exec(term.code);
+      // ... and `{ <eta>; lp += y[i] * eta - Math.log1p(Math.exp(eta)); }` over whole arrays, every y[i] finite: CERTIFIED LOGISTIC TAIL candidate (csrc/amwg_ltail.h;
+      // logitTailPlan), under the same conditions and with the same analyses of the statements -- except the linear predictor's: eta stays the reference's bits.
+      const ml = logitTerm(term.code);
+      const mp = ml || /^ld_pois_pre_exp\(((?:\(double\))?)A(\d+)\[v_(\w+)\], (.+), A(\d+)\[v_\3\]\)$/.exec(term.code);
       let ptailCand = false;
       if (mp && mp[3] === canon.name && startV.cst === 0 && !canon.le && L.preamble.length === 0 && !this.isHelper && !this.opts.no_cert_tail && !this.linear && this.acc &&
           loopAcc === this.acc && indent === '    ' && !this.condDepth) {
-        const ya = this.arrays[Number(mp[2])], la = this.arrays[Number(mp[5])], text = bodyText + ' ' + mp[4];
-        let ok = ya.type !== 0 && boundV.cst === ya.flat.length && boundV.cst === la.flat.length && boundV.cst >= 64 && !/\b(sub|G|dq_\w+|dv|return|goto|tb_\w*|it_\w*|u_|rr_)\b/.test(text);
+        const ya = this.arrays[Number(mp[2])], la = ml ? ya : this.arrays[Number(mp[5])], text = bodyText + ' ' + mp[4];
+        let ok = (ml || ya.type !== 0) && boundV.cst === ya.flat.length && boundV.cst === la.flat.length && boundV.cst >= 64 && !/\b(sub|G|dq_\w+|dv|return|goto|tb_\w*|it_\w*|u_|rr_)\b/.test(text);
+        if (ml) for (let i = 0; ok && i < ya.flat.length; i++) ok = Number.isFinite(ya.flat[i]);
+        else
         for (let i = 0; ok && i < ya.flat.length; i++) ok = ya.flat[i] >= 0 && Number.isFinite(la.flat[i]);      // (a negative count: the reference's term is -inf)
         // are the state's entries the statements read the same for every observation?  Every S(index): a constant, or constant + the counter of an inner loop with
         // constant bounds (and nothing else writes that counter).  Then the pass keeps the four chains' entries in scalar registers (UniformState).
@@ -1546,7 +1567,7 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
         // if (...) eta += b[7]`?  Then the pass forms it by fused steps (one rounding per product instead of two) and bounds |eta| AND the distance between the two
         // etas by H = sum |b_k| max_i |x_ik| + ..., once per pass, instead of taking max |eta_i| over the rows (csrc/amwg_ptail.h, kTailLinear).
         let linInfo = null;
-        if (rowInfo && /^v_\w+$/.test(rowInfo.eta) && !this.opts.no_tail_linear) {
+        if (!ml && rowInfo && /^v_\w+$/.test(rowInfo.eta) && !this.opts.no_tail_linear) {
           const E = rowInfo.eta, Ee = E.replace(/[$]/g, '\\$'), T = rowInfo.body;
           const loops = [];      // {name, lo, hi, from, to}: the constant-bound loops of the statements and the extent of their bodies in T
           const reFor = /for \((v_\w+) = (\d+); \1 < (\d+); \1 \+= 1\) \{/g;
@@ -1616,7 +1637,11 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
           }
           if (good) linInfo = { body: fused, hlin: terms.join(' + '), roundings: refRound + fusedRound };
         }
-        if (ok) {
+        if (ok && ml) {
+          ptailCand = true;
+          this.ltailInfo = { y: Number(mp[2]), cast: mp[1], n: boundV.cst, acc: loopAcc, i: canon.name, uniform, eta: mp[4], body: bodyText, rows: rowInfo };
+          out.push(indent + '//@LTAIL');
+        } else if (ok) {
           ptailCand = true;
           this.ptailInfo = { y: Number(mp[2]), lf: Number(mp[5]), cast: mp[1], n: boundV.cst, acc: loopAcc, i: canon.name, uniform, eta: mp[4], body: bodyText, rows: rowInfo, linear: linInfo };
           out.push(indent + '//@PTAIL');
@@ -1624,7 +1649,7 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
       }
       this.otherSplitLoops = (this.otherSplitLoops || 0) + 1;
       this.emitSplit(out, indent, L.preamble, head, loop, [loopAcc]);
-      if (ptailCand) out.push(indent + '//@PTAIL_END');
+      if (ptailCand) out.push(indent + (ml ? '//@LTAIL_END' : '//@PTAIL_END'));
       return;
     }
     this.loopLabels.push({ native: true });
@@ -1947,7 +1972,10 @@ Translator.prototype.run = function () {
   const maxThreads = this.opts.max_threads || (this.heavyLoop ? (off > 73728 ? 512 : 256) : 1024);
   const rows = this.rowPlan(body);
   const tail = rows ? null : this.tailPlan(body);
-  const ptail = (rows || tail) ? null : this.poisTailPlan(body);
+  const ptail0 = (rows || tail) ? null : this.poisTailPlan(body);
+  const ltail = (rows || tail || ptail0) ? null : this.logitTailPlan(body);
+  // (the logistic candidate's markers are the plan's alone: the text of the closure's evaluation stays what it was)
+  body = body.filter((ln) => !/^\/\/@LTAIL(_END)?$/.test(ln.trim()));
   const src = [];
   src.push('// generated by bayes.js_amd/translate.js from the user\'s log_post closure');
   src.push('namespace amwg {');
@@ -2041,38 +2069,50 @@ Translator.prototype.run = function () {
     src.push('    return norm_tail_approx<UserModel, G, BT>(S, d, smem, sub);');
     src.push('  }');
   }
-  if (ptail) {
+  if (ptail0 || ltail) {
     // CERTIFIED POISSON TAIL (csrc/amwg_ptail.h; amwg_kernel.h "certified decisions"): with 16 lanes per chain the stepper decides accept tests from
     // head + sum eta y - sum e^eta - sum lfactorial(y) and its bound, and evaluates the closure in the reference's order where that does not decide
+    // CERTIFIED LOGISTIC TAIL (csrc/amwg_ltail.h): the same for head + sum eta y - sum softplus(eta); its members are ltail_*, and eta is never fused
+    const ptail = ptail0 || ltail, pf = ltail ? 'ltail' : 'ptail';
     const arrDecl = (j) => { const a = this.arrays[j], pl = plan[j];
       return '    const ' + a.ctype + ' *A' + j + ' = ' + (pl.lds ? 'reinterpret_cast<const ' + a.ctype + ' *>(smem + ' + pl.off + ')' : 'static_cast<const ' + a.ctype + ' *>(user_arr<' + j + '>(d))') + ';'; };
+    if (ltail) {
+      src.push('  // ---- certified logistic tail: `' + ptail.acc + '` ends in  for (i < ' + ptail.n + ') { ...; ' + ptail.acc + ' += A' + ptail.y + '[i] * eta - Math.log1p(Math.exp(eta)) }');
+      src.push('  static constexpr bool kLogitTail = true, kCertified = true, kReferenceOrder = true;');
+    } else {
     src.push('  // ---- certified Poisson tail: `' + ptail.acc + '` ends in  for (i < ' + ptail.n + ') { ...; ' + ptail.acc + ' += ld.pois(A' + ptail.y + '[i], Math.exp(eta)) }');
     src.push('  static constexpr bool kPoisTail = true, kCertified = true, kReferenceOrder = true;');
+    }
     src.push('  static constexpr int kCertifiedLanes = 16, kTailN = ' + ptail.n + ', kStateN = ' + this.P + ';');
     src.push('  static constexpr bool kTailUniformState = ' + (ptail.uniform && this.P <= 12 ? 'true' : 'false') + ';      // the entries of the state the loop reads do not depend on the observation (and are few): scalar registers');
     src.push('  typedef TailApprox Approx;');
+    if (ltail) src.push('  __device__ __forceinline__ static double ltail_sum_abs_y() { return ' + hexFloat(ptail.sumAbsY) + '; }      // >= sum |y[i]| = ' + ptail.sumAbsY);
+    else {
     src.push('  __device__ __forceinline__ static double ptail_sum_y() { return ' + hexFloat(ptail.sumY) + '; }      // sum y[i] = ' + ptail.sumY);
     src.push('  __device__ __forceinline__ static double ptail_sum_lf() { return ' + hexFloat(ptail.sumLF) + '; }      // sum lfactorial(y[i]) = ' + ptail.sumLF);
-    src.push('  __device__ __forceinline__ static double ptail_y(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
+    }
+    src.push('  __device__ __forceinline__ static double ' + pf + '_y(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
     src.push(arrDecl(ptail.y));
     src.push('    return (double)A' + ptail.y + '[i]; }');
+    if (!ltail) {
     src.push('  __device__ __forceinline__ static double ptail_lf(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
     src.push(arrDecl(ptail.lf));
     src.push('    return A' + ptail.lf + '[i]; }');
+    }
     src.push('  // the loop\'s statements up to the term: eta of observation v_' + ptail.i + ' for the chain whose state is S');
     src.push('  template <class SV>');
-    src.push('  __device__ __forceinline__ static double ptail_eta(const SV &S, const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ') {');
+    src.push('  __device__ __forceinline__ static double ' + pf + '_eta(const SV &S, const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ') {');
     this.arrays.forEach((a, j) => src.push(arrDecl(j)));
     src.push('    (void)smem; (void)d; (void)S;');
     for (const dl of ptail.decls) src.push('    ' + dl);
     src.push('    ' + ptail.body);
     src.push('    return ' + ptail.eta + ';');
     src.push('  }');
-    src.push('  static constexpr bool kTailRows = ' + (ptail.rows ? 'true' : 'false') + ';      // every data read of the statements addresses the observation\'s own row: loaded a round ahead (ptail_load)');
+    src.push('  static constexpr bool kTailRows = ' + (ptail.rows ? 'true' : 'false') + ';      // every data read of the statements addresses the observation\'s own row: loaded a round ahead (' + pf + '_load)');
     if (ptail.rows) {
       const per = ptail.rows.per, js = Object.keys(per).map(Number).sort((a, b) => a - b);
       src.push('  struct TailRow { ' + js.map((j) => this.arrays[j].ctype + ' a' + j + '[' + (per[j].hi - per[j].lo) + '];').join(' ') + ' };');
-      src.push('  __device__ __forceinline__ static void ptail_load(const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ', TailRow &R) {');
+      src.push('  __device__ __forceinline__ static void ' + pf + '_load(const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ', TailRow &R) {');
       for (const j of js) src.push(arrDecl(j));
       src.push('    (void)smem; (void)d;');
       for (const j of js) {
@@ -2080,9 +2120,9 @@ Translator.prototype.run = function () {
         src.push('    for (int q_ = 0; q_ < ' + (per[j].hi - per[j].lo) + '; ++q_) R.a' + j + '[q_] = A' + j + '[v_' + ptail.i + ' * ' + per[j].stride + ' + ' + per[j].lo + ' + q_];');
       }
       src.push('  }');
-      src.push('  __device__ __forceinline__ static double ptail_y_row(const TailRow &R) { return (double)R.a' + ptail.y + '[0]; }');
+      src.push('  __device__ __forceinline__ static double ' + pf + '_y_row(const TailRow &R) { return (double)R.a' + ptail.y + '[0]; }');
       src.push('  template <class SV>');
-      src.push('  __device__ __forceinline__ static double ptail_eta_row(const SV &S, const TailRow &R, const int v_' + ptail.i + ') {');
+      src.push('  __device__ __forceinline__ static double ' + pf + '_eta_row(const SV &S, const TailRow &R, const int v_' + ptail.i + ') {');
       src.push('    (void)S; (void)R;');
       for (const dl of ptail.decls) src.push('    ' + dl);
       src.push('    ' + ptail.rows.body);
@@ -2110,10 +2150,10 @@ Translator.prototype.run = function () {
     for (const ln of ptail.head) src.push(ln);
     src.push('    return v_' + ptail.acc + ';');
     src.push('  }');
-    src.push('  __device__ static double ptail_head_sequence(const StateView &S, const DataRef &d, const unsigned char *smem) { return tail_head<1>(S, d, smem, 0); }      // (one lane\'s walk: the reference\'s order)');
+    src.push('  __device__ static double ' + pf + '_head_sequence(const StateView &S, const DataRef &d, const unsigned char *smem) { return tail_head<1>(S, d, smem, 0); }      // (one lane\'s walk: the reference\'s order)');
     src.push('  // ... with the magnitudes of what it adds up and the number of additions');
     src.push('  template <int G>');
-    src.push('  __device__ __forceinline__ static HeadPair ptail_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
+    src.push('  __device__ __forceinline__ static HeadPair ' + pf + '_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
     this.arrays.forEach((a, j) => src.push(arrDecl(j)));
     src.push('    (void)smem; (void)sub; (void)d;');
     src.push('    double mag_ = 0.0, cnt_ = 0.0;');
@@ -2122,11 +2162,11 @@ Translator.prototype.run = function () {
     src.push('  }');
     src.push('  template <int G, int BT, class C>');
     src.push('  __device__ __forceinline__ static Approx log_post_approx(C &, const StateView &S, const ModelConsts &, const DataRef &d, const unsigned char *smem, int sub) {');
-    src.push('    return pois_tail_approx<UserModel, G, BT>(S, d, smem, sub);');
+    src.push('    return ' + (ltail ? 'logit' : 'pois') + '_tail_approx<UserModel, G, BT>(S, d, smem, sub);');
     src.push('  }');
     src.push('  template <int G, class C>');
     src.push('  __device__ __forceinline__ static double reference_order(C &, const StateView &S, const ModelConsts &, const DataRef &d, const unsigned char *smem, int sub) {');
-    src.push('    return pois_tail_reference<UserModel, G>(S.base, &d, smem, sub);');
+    src.push('    return ' + (ltail ? 'logit' : 'pois') + '_tail_reference<UserModel, G>(S.base, &d, smem, sub);');
     src.push('  }');
   }
   src.push('#endif');
@@ -2171,7 +2211,9 @@ Translator.prototype.run = function () {
     cert_tail_n: tail ? tail.n : 0,
     rows_cert: rows && rows.cert ? 1 : 0,
     // certified Poisson tail (csrc/amwg_ptail.h): observations of the closure's final log-link Poisson loop; 0 = none (the host library reads kPoisTail / kTailN off the source)
-    pois_tail_n: ptail ? ptail.n : 0,
+    pois_tail_n: ptail0 ? ptail0.n : 0,
+    // certified logistic tail (csrc/amwg_ltail.h): observations of the closure's final logistic-regression loop; 0 = none (kLogitTail / kTailN of the source)
+    logit_tail_n: ltail ? ltail.n : 0,
   };
 };
 
@@ -2220,6 +2262,32 @@ Translator.prototype.poisTailPlan = function (body) {
     sF = t;
   }
   return Object.assign({}, info, { decls, head, headMag: hm.mag, sumY, sumLF: sF + cF });
+};
+
+// The CERTIFIED LOGISTIC TAIL of a closure (csrc/amwg_ltail.h): its LAST statement before `return acc` is the logistic-regression loop forLoop() marked with //@LTAIL;
+// the head under the Poisson tail's conditions.  Switched off by no_cert_tail and no_logit_tail.
+// -> {y (array index), n, acc, i, uniform, eta, body, rows, decls, head, headMag, sumAbsY} or null
+Translator.prototype.logitTailPlan = function (body) {
+  if (!this.ltailInfo || this.derived.length || this.isHelper || this.opts.no_cert_tail || this.opts.no_logit_tail || this.hasBinary) return null;
+  let iB = -1, iE = -1, nB = 0;
+  body.forEach((ln, i) => { const t = ln.trim(); if (t === '//@LTAIL') { iB = i; nB++; } else if (t === '//@LTAIL_END') iE = i; });
+  if (nB !== 1 || iE < iB) return null;      // (ltailInfo describes the last candidate: it must be the only one)
+  const info = this.ltailInfo;
+  const tailLines = body.slice(iE + 1).map((ln) => ln.trim()).filter((t) => t && t.indexOf('//') !== 0);
+  if (!(tailLines.length === 2 && /^if constexpr \(DERIVE\) \{ \(void\)dv; \}$/.test(tailLines[0]) && tailLines[1] === 'return v_' + info.acc + ';')) return null;
+  const head = body.slice(0, iB);
+  if (head.some((ln) => /\breturn\b|\bdv\[|\bdq_/.test(ln))) return null;
+  const hm = this.headMagnitude(head, info.acc);
+  if (hm.why) return null;
+  const decls = [];
+  for (const ln of head) { const m = /^(double|int) (v_\w+) = 0;$/.exec(ln.trim()); if (m && m[2] !== 'v_' + info.i) decls.push(ln.trim()); }
+  // sum |y| (the bound's Y), pushed up by more than a plain sum's rounding so that it is not below the real sum
+  let sumAbsY = 0;
+  const yf = this.arrays[info.y].flat;
+  for (let i = 0; i < info.n; i++) sumAbsY += Math.abs(yf[i]);
+  if (!Number.isInteger(sumAbsY) || sumAbsY > 9007199254740992) sumAbsY *= 1 + info.n * Math.pow(2, -52);
+  if (!Number.isFinite(sumAbsY)) return null;
+  return Object.assign({}, info, { decls, head, headMag: hm.mag, sumAbsY });
 };
 
 // The head of a plan (everything before the closure's final loop) as value + MAGNITUDES: the certified values bound the two orders the head's terms are summed in

@@ -185,7 +185,8 @@ typedef struct {
    * The struct carries no size or version field: amwg_create_user therefore honours these three only as far as the GENERATED SOURCE states the same
    * (kRowN, kRowGroups, kRowSweep) and refuses a mismatch -- a caller built against an older, shorter struct cannot switch a layout on that the source has
    * no code for.  Everything the translator added since is read from the source alone: kRowCert (certified decisions in the row layout: amwg_user_sweep_cert),
-   * kCertifiedTail / kTailN (certified decisions for a closure ending in a constant-mean normal loop: amwg_user_step_cert). */
+   * kCertifiedTail / kTailN (certified decisions for a closure ending in a constant-mean normal loop: amwg_user_step_cert at one lane per chain), kPoisTail / kTailN
+   * and kLogitTail / kTailN (the same for a closure ending in a log-link Poisson loop or in a logistic-regression loop: amwg_user_step_cert at 16 lanes per chain). */
   int32_t rows_n_obs, rows_groups, rows_sweep;
 } amwg_user_model;
 

@@ -19,6 +19,7 @@ verdict goes wrong or a chain differs from the expression-in-every-update run.
 
     python tools/bound_audit.py --out profiles/r06_bound_audit.json            # everything (a few minutes of GPU)
     python tools/bound_audit.py --quick                                        # the small cases only (what tests/test_gpu_bound_audit.py asserts)
+    python tools/bound_audit.py --only logit                                   # the certified logistic tail's cases alone (tests/test_gpu_logit_tail.py)
 """
 import argparse
 import ctypes as C
@@ -184,6 +185,31 @@ def cases(quick):
     return out
 
 
+def logit_cases():
+    """The certified LOGISTIC TAIL of a translated closure (translate.js logitTailPlan, csrc/amwg_ltail.h logit_tail_approx: amwg_user_step_cert at 16 lanes per chain):
+    the closures of tests/js/logit_models.js -- the small one at n in {64, 65, 517}, its fallback paths, real weights for y --, predictors at +-36 (where the
+    reference's softplus leaves its straight line) and on either side of the 690 cut-off (x1 holds 2 and -2: a start state b1 puts max |eta| at 2 b1), all-zero and
+    all-one y.  Names begin with logit_: part of the full run and of --only logit, not of --quick."""
+    out = []
+    if not shutil.which("node"):
+        return out
+    import logit_host
+    def case(name, label, state=None, steps=150, chains=64):
+        spec, _, _ = logit_host.spec(label)
+        out.append(dict(name=name, spec=spec, chains=chains, steps=steps, lanes=16, state=state, seed=19))
+    for n in (64, 65, 517):
+        case("logit_n%d" % n, "logit_tail_small@%d" % n)
+    for nm in ("logit_tail_gather", "logit_tail_next_row", "logit_tail_weights"):
+        case(nm, nm)
+    case("logit_eta_36", "logit_tail_small", state=[0.0, 18.0, 0.0, 0.0], steps=100)
+    case("logit_eta_minus_36", "logit_tail_small", state=[-30.0, 3.0, 0.0, 0.0], steps=100)
+    case("logit_H_689", "logit_tail_small", state=[0.0, 344.6, 0.0, 0.0], steps=100)      # H within 1 of the 690 cut-off: the bound is finite ...
+    case("logit_H_691", "logit_tail_small", state=[0.0, 345.4, 0.0, 0.0], steps=100)      # ... and beyond it the expression decides (nothing audited while H > 690)
+    case("logit_all_zero_y", "logit_tail_small@517@zeros")
+    case("logit_all_one_y", "logit_tail_small@65@ones")
+    return out
+
+
 def run_case(c, shift=0, full_evaluation=0):
     s = A.Sampler(c["spec"], chains=c["chains"], seed=c["seed"], lanes_per_chain=c["lanes"], test_bound_shift=shift, full_evaluation=full_evaluation,
                   sufficient_statistics=(c.get("suff", 0) if full_evaluation == 0 else 0))
@@ -215,7 +241,7 @@ def main():
     rec = {"library": A.lib().amwg_version().decode(), "cases": [], "shrink": []}
     worst_v = worst_d = 0.0
     wrong = 0
-    for c in cases(a.quick):
+    for c in (logit_cases() if a.only.startswith("logit") else cases(a.quick) + ([] if a.quick else logit_cases())):
         if a.only and a.only not in c["name"]:
             continue
         r = run_case(c)
