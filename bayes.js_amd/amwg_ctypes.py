@@ -46,7 +46,7 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+EXPORTS = ["amwg_create_datasets", "amwg_num_datasets", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
 SELFTEST_EXPORTS = ["amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
@@ -63,6 +63,11 @@ def lib():
         pd, pi32, pi64, pu64 = C.POINTER(dbl), C.POINTER(i32), C.POINTER(i64), C.POINTER(u64)
         L.amwg_create.argtypes = [C.POINTER(ModelDesc), C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt),
                                   C.POINTER(Options), C.POINTER(vp)]
+        L.amwg_create_datasets.argtypes = [C.POINTER(ModelDesc), i32, C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt),
+                                           C.POINTER(Options), C.POINTER(vp)]
+        L.amwg_num_datasets.argtypes = [vp]
+        L.amwg_last_sample_dataset_moments.argtypes = [vp, pd, pd]
+        L.amwg_last_sample_dataset_diagnostics.argtypes = [vp, pd, pd]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -175,12 +180,18 @@ class Sampler:
                  steps_per_launch=0, exact_division=0, group_local=0, full_evaluation=0, test_bound_shift=0, sufficient_statistics=0):
         L = lib()
         keep = []
+        specs = None
+        if isinstance(spec, (list, tuple)):      # one spec per dataset: amwg_create_datasets (the parameters, init and stepper options are those of the first)
+            specs = list(spec)
+            if not specs or any(q.get("user") is not None for q in specs):
+                raise AmwgError("a list of specs is one built-in family on several datasets: it must not be empty or hold translated closures")
+            spec = specs[0]
         user = spec.get("user")
-        if user is None:
-            d = spec["data"]
-            md = ModelDesc()
-            md.model = MODEL_ID[spec["model"]]
-            md.n_obs = spec["n_obs"]
+
+        def model_desc(md, q):
+            d = q["data"]
+            md.model = MODEL_ID[q["model"]]
+            md.n_obs = q["n_obs"]
             x = np.ascontiguousarray(d["x"], dtype=np.float64)
             keep.append(x)
             md.x = _dp(x)
@@ -192,10 +203,18 @@ class Sampler:
                 g = np.ascontiguousarray(d["g"], dtype=np.int32)
                 keep.append(g)
                 md.g = g.ctypes.data_as(C.POINTER(C.c_int32))
-            md.G = int(spec.get("G", 0))
-            md.K = int(spec.get("K", 0))
-            for i, v in enumerate(spec.get("hyper") or DEFAULT_HYPER[spec["model"]]):
+            md.G = int(q.get("G", 0))
+            md.K = int(q.get("K", 0))
+            for i, v in enumerate(q.get("hyper") or DEFAULT_HYPER[q["model"]]):
                 md.hyper[i] = float(v)
+
+        if specs is not None:
+            mds = (ModelDesc * len(specs))()
+            for k, q in enumerate(specs):
+                model_desc(mds[k], q)
+        elif user is None:
+            md = ModelDesc()
+            model_desc(md, spec)
         else:
             um = UserModel()
             src = user["source"].encode() if isinstance(user["source"], str) else user["source"]
@@ -241,7 +260,9 @@ class Sampler:
         op.test_bound_shift = test_bound_shift
         op.sufficient_statistics = sufficient_statistics
         h = C.c_void_p()
-        if user is None:
+        if specs is not None:
+            _check(L.amwg_create_datasets(mds, len(specs), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
+        elif user is None:
             _check(L.amwg_create(C.byref(md), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
         else:
             _check(L.amwg_create_user(C.byref(um), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
@@ -250,6 +271,7 @@ class Sampler:
         self.PR = L.amwg_num_recorded(h)   # values per draw row: P + derived quantities
         self.C = chains
         self.n_params = n
+        self.D = L.amwg_num_datasets(h)      # datasets (1 unless made from a list of specs)
 
     def close(self):
         if getattr(self, "h", None):
@@ -329,6 +351,18 @@ class Sampler:
         _check(lib().amwg_last_sample_moments(self.h, _dp(m), _dp(s)))
         return m, s
 
+    def dataset_moments(self):
+        """-> mean, sd, arrays [datasets][P + derived]: moments() per dataset (amwg_last_sample_dataset_moments)"""
+        m, s = np.empty((self.D, self.PR)), np.empty((self.D, self.PR))
+        _check(lib().amwg_last_sample_dataset_moments(self.h, _dp(m), _dp(s)))
+        return m, s
+
+    def dataset_convergence(self):
+        """-> rhat, ess, arrays [datasets][P + derived]: convergence() per dataset (amwg_last_sample_dataset_diagnostics)"""
+        r, e = np.empty((self.D, self.PR)), np.empty((self.D, self.PR))
+        _check(lib().amwg_last_sample_dataset_diagnostics(self.h, _dp(r), _dp(e)))
+        return r, e
+
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)
         assert st.shape == (self.P, self.C)
@@ -360,7 +394,7 @@ class Sampler:
         _check(lib().amwg_launch_info(self.h, *[C.byref(x) for x in v], C.byref(ms)))
         return {"lanes_per_chain": v[0].value, "block_threads": v[1].value, "grid_blocks": v[2].value,
                 "lds_bytes": v[3].value, "n_launches": v[4].value, "kernel_ms": ms.value, "kernel": (lib().amwg_kernel_name(self.h) or b"").decode(),
-                "summation_order": lib().amwg_summation_order(self.h)}
+                "summation_order": lib().amwg_summation_order(self.h), "datasets": lib().amwg_num_datasets(self.h)}
 
 
 def _group(samplers):

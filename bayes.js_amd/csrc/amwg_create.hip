@@ -4,9 +4,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 
 #include "amwg_host.h"
+#include "amwg_dataset.h"
 #include "amwg_kernel.h"
 #include "amwg_models.h"
 
@@ -311,16 +313,33 @@ static int group_local_setup(amwg_sampler *s, const amwg_model_desc *m, const am
   return AMWG_OK;
 }
 
+// A dataset sampler (amwg_create_datasets) keeps the arrays of its D datasets back to back at a fixed stride, one allocation per array: the stride of an
+// array of n elements (rounded up so that every dataset's copy starts on a 256-byte boundary, like an allocation of its own; D == 1: n, the ordinary sampler's
+// allocation).  `packed` receives the D copies; -> what to upload and how many elements.
+static size_t dataset_stride(size_t n, int D, size_t align) { return D > 1 ? (n + align - 1) / align * align : n; }
+template <class T, class Get>
+static int upload_datasets(amwg_sampler *s, int D, size_t n, size_t stride, Get get, T **dev) {      // get(d): dataset d's n elements on the host
+  if (D == 1) return upload(s, get(0), n, dev);
+  std::vector<T> packed(stride * (size_t)D, T(0));
+  for (int d = 0; d < D; ++d) { const T *src = get(d); for (size_t i = 0; i < n; ++i) packed[(size_t)d * stride + i] = src[i]; }
+  return upload(s, packed.data(), packed.size(), dev);
+}
+
 // Normal and hierarchical families: the observations; the hierarchical family's group labels as bytes; with group_local the lane-major tile and the
-// lane table instead of the observations (amwg_gl.h)
-static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *m, const GlLayoutHost &gl) {
+// lane table instead of the observations (amwg_gl.h).  (D > 1 datasets: the Normal family only; data_mid_range is a per-dataset constant)
+static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *models, int D, const GlLayoutHost &gl, std::vector<DatasetConsts> &consts) {
+  const amwg_model_desc *m = &models[0];
   const int N = m->n_obs;
   DataRef &d = s->d;
-  bool mid = true;
-  for (int i = 0; i < N; ++i) mid = mid && (m->x[i] == 0.0 || mid_range(std::fabs(m->x[i])));
-  s->mc.data_mid_range = mid ? 1 : 0;
+  for (int k = 0; k < D; ++k) {
+    bool mid = true;
+    for (int i = 0; i < N; ++i) mid = mid && (models[k].x[i] == 0.0 || mid_range(std::fabs(models[k].x[i])));
+    consts[k].data_mid_range = mid ? 1 : 0;
+  }
+  s->mc.data_mid_range = consts[0].data_mid_range;
   double *dx = nullptr;
-  TRYB(upload(s, m->x, (size_t)N, &dx));
+  s->ds_stride[0] = (int64_t)dataset_stride((size_t)N, D, 32);
+  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[0], [&](int k) { return models[k].x; }, &dx));
   d.x = dx;
   if (m->model != AMWG_MODEL_HIER_NORMAL) return AMWG_OK;
   std::vector<uint8_t> gb((size_t)N);
@@ -342,47 +361,61 @@ static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *m, const G
   d.K = gl.n_min;
   return AMWG_OK;
 }
-// Bernoulli family: the observations as bytes and as bits, and the tables of two_valued_sum
-static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *m) {
-  const int N = m->n_obs;
-  std::vector<uint8_t> xb((size_t)N);
-  std::vector<uint32_t> xw(BetaBernModel::words(N), 0u);
-  bool invalid = false;
-  for (int i = 0; i < N; ++i) {
-    const bool one = m->x[i] == 1;
-    invalid = invalid || !(one || m->x[i] == 0);
-    xb[i] = one ? 1 : 0;
-    if (one) xw[(size_t)i >> 5] |= 1u << (i & 31);
+// Bernoulli family: the observations as bytes and as bits, and the tables of two_valued_sum -- per dataset, as is has_invalid
+static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *models, int D, std::vector<DatasetConsts> &consts) {
+  const int N = models[0].n_obs;
+  const size_t W = BetaBernModel::words(N), T = 6 * two_valued_words(N);
+  std::vector<std::vector<uint8_t>> xb((size_t)D, std::vector<uint8_t>((size_t)N));
+  std::vector<std::vector<uint32_t>> xw((size_t)D, std::vector<uint32_t>(W, 0u)), tab((size_t)D);
+  for (int k = 0; k < D; ++k) {
+    bool invalid = false;
+    for (int i = 0; i < N; ++i) {
+      const bool one = models[k].x[i] == 1;
+      invalid = invalid || !(one || models[k].x[i] == 0);
+      xb[k][i] = one ? 1 : 0;
+      if (one) xw[k][(size_t)i >> 5] |= 1u << (i & 31);
+    }
+    consts[k].has_invalid = invalid ? 1 : 0;
+    tab[k] = two_valued_tables(xb[k].data(), N);
+    if (tab[k].size() != T) return amwg_fail(AMWG_EINVAL, "internal: two_valued_tables of %zu words, expected %zu", tab[k].size(), T);
   }
-  s->mc.has_invalid = invalid ? 1 : 0;
-  const std::vector<uint32_t> tab = two_valued_tables(xb.data(), N);
+  s->mc.has_invalid = consts[0].has_invalid;
+  s->ds_stride[3] = (int64_t)dataset_stride((size_t)N, D, 256);
+  s->ds_stride[4] = (int64_t)dataset_stride(W, D, 64);
+  s->ds_stride[5] = (int64_t)dataset_stride(T, D, 64);
   uint8_t *dxb = nullptr;
   uint32_t *dxw = nullptr, *dtab = nullptr;
-  TRYB(upload(s, tab.data(), tab.size(), &dtab));
+  TRYB(upload_datasets(s, D, T, (size_t)s->ds_stride[5], [&](int k) { return tab[k].data(); }, &dtab));
   s->d.arr[0] = dtab;
-  TRYB(dev_alloc(s, &dxb, (size_t)N));
-  TRYB(upload(s, xw.data(), xw.size(), &dxw));
-  if (N) HIP_TRY(hipMemcpy(dxb, xb.data(), (size_t)N, hipMemcpyHostToDevice));
+  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[3], [&](int k) { return xb[k].data(); }, &dxb));
+  TRYB(upload_datasets(s, D, W, (size_t)s->ds_stride[4], [&](int k) { return xw[k].data(); }, &dxw));
   s->d.xb = dxb;
   s->d.xw = dxw;
   return AMWG_OK;
 }
-// Poisson family: the design matrix column-major, the counts, log(y_i!), and what the bounds of the certified pass are made of (PoisGlmModel::log_post_approx)
-static int upload_poisson_data(amwg_sampler *s, const amwg_model_desc *m) {
-  const int N = m->n_obs;
-  ModelConsts &mc = s->mc;
-  std::vector<double> lf((size_t)N);
-  for (int i = 0; i < N; ++i) lf[i] = m->y[i] < 0 ? (double)INFINITY : lfactorial_js(m->y[i]);
+// Poisson family: the design matrix column-major, the counts, log(y_i!), and what the bounds of the certified pass are made of (PoisGlmModel::log_post_approx) --
+// per dataset
+static int upload_poisson_data(amwg_sampler *s, const amwg_model_desc *models, int D, std::vector<DatasetConsts> &consts) {
+  const int N = models[0].n_obs;
+  std::vector<std::vector<double>> lf((size_t)D, std::vector<double>((size_t)N)), Xt((size_t)D, std::vector<double>((size_t)N * 7));
+  for (int d = 0; d < D; ++d) {
+    const amwg_model_desc *m = &models[d];
+    DatasetConsts &mc = consts[d];
+    for (int i = 0; i < N; ++i) lf[d][i] = m->y[i] < 0 ? (double)INFINITY : lfactorial_js(m->y[i]);
+    for (int i = 0; i < N; ++i) for (int k = 0; k < 7; ++k) Xt[d][(size_t)k * N + i] = m->x[(size_t)i * 7 + k];   // row-major [N][7] -> column-major [7][N]
+    for (int k = 0; k < 7; ++k) { double mx = 0; for (int i = 0; i < N; ++i) { const double v = std::fabs(m->x[(size_t)i * 7 + k]); mx = (v > mx || v != v) ? v : mx; } mc.glm_xmax[k] = mx; }
+    mc.glm_sum_y = 0; mc.glm_sum_lf = 0;
+    for (int i = 0; i < N; ++i) { mc.glm_sum_y += std::fabs(m->y[i]); mc.glm_sum_lf += std::fabs(lf[d][i]); }
+  }
+  for (int k = 0; k < 7; ++k) s->mc.glm_xmax[k] = consts[0].glm_xmax[k];
+  s->mc.glm_sum_y = consts[0].glm_sum_y; s->mc.glm_sum_lf = consts[0].glm_sum_lf;
+  s->ds_stride[0] = (int64_t)dataset_stride((size_t)N * 7, D, 32);
+  s->ds_stride[1] = s->ds_stride[2] = (int64_t)dataset_stride((size_t)N, D, 32);
   double *dX = nullptr, *dy = nullptr, *dlf = nullptr;
-  std::vector<double> Xt((size_t)N * 7);   // row-major [N][7] -> column-major [7][N]
-  for (int i = 0; i < N; ++i) for (int k = 0; k < 7; ++k) Xt[(size_t)k * N + i] = m->x[(size_t)i * 7 + k];
-  TRYB(upload(s, Xt.data(), Xt.size(), &dX));
-  TRYB(upload(s, m->y, (size_t)N, &dy));
-  TRYB(upload(s, lf.data(), lf.size(), &dlf));
+  TRYB(upload_datasets(s, D, (size_t)N * 7, (size_t)s->ds_stride[0], [&](int d) { return Xt[d].data(); }, &dX));
+  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[1], [&](int d) { return models[d].y; }, &dy));
+  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[2], [&](int d) { return lf[d].data(); }, &dlf));
   s->d.x = dX; s->d.y = dy; s->d.lfact = dlf;
-  for (int k = 0; k < 7; ++k) { double mx = 0; for (int i = 0; i < N; ++i) { const double v = std::fabs(m->x[(size_t)i * 7 + k]); mx = (v > mx || v != v) ? v : mx; } mc.glm_xmax[k] = mx; }
-  mc.glm_sum_y = 0; mc.glm_sum_lf = 0;
-  for (int i = 0; i < N; ++i) { mc.glm_sum_y += std::fabs(m->y[i]); mc.glm_sum_lf += std::fabs(lf[i]); }
   return AMWG_OK;
 }
 
@@ -482,11 +515,11 @@ static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *m) {
   return AMWG_OK;
 }
 
-extern "C" {
-
-int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t n_params, const double *init,
-                const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
-  if (!m || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "amwg_create: null argument");
+// ---- amwg_create and amwg_create_datasets from here on: D datasets of one built-in family (D == 1: the ordinary sampler).  What depends on the data is computed
+// per dataset (DatasetConsts) and, for D > 1, travels to the kernels in a device table beside the arrays laid back to back (amwg_dataset.h).
+static int create_builtin(const amwg_model_desc *models, int D, const amwg_param_desc *params, int32_t n_params, const double *init,
+                          const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  const amwg_model_desc *m = &models[0];
   if (n_params < 1 || n_params > kMaxIndex) return amwg_fail(AMWG_EINVAL, "amwg_create: %d named parameters (supported: 1..%d)", n_params, kMaxIndex);
   if (m->n_obs < 0) return amwg_fail(AMWG_EINVAL, "amwg_create: n_obs < 0");
   const FamilyRow *family = family_of(m->model);      // (an unknown model is reported by check_family_args, after the options and the layout)
@@ -495,29 +528,71 @@ int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t
   amwg_sampler *s = guard.s;
   PhaseClock clk;
   TRYB(build_layout(s, params, n_params, false));
-  TRYB(check_family_args(m, params, n_params, s->P));
+  for (int d = 0; d < D; ++d) TRYB(check_family_args(&models[d], params, n_params, s->P));
   hipDeviceProp_t prop;
   clk.mark("layout + checks");
   TRYB(open_device(s, &prop));
   clk.mark("open device (HIP runtime)");
   model_constants(m, options, s->mc);
-  if (options->sufficient_statistics) TRYB(sufficient_statistics(s, m, options));
+  std::vector<DatasetConsts> consts((size_t)D, DatasetConsts{});
+  for (DatasetConsts &k : consts) { k.data_mid_range = s->mc.data_mid_range; k.has_invalid = s->mc.has_invalid; }
+  if (options->sufficient_statistics)
+    for (int d = D - 1; d >= 0; --d) {      // (dataset 0 last: its numbers are the ones s->mc keeps)
+      TRYB(sufficient_statistics(s, &models[d], options));
+      consts[d].suff_xbar_hi = s->mc.suff_xbar_hi; consts[d].suff_xbar_lo = s->mc.suff_xbar_lo; consts[d].suff_ss = s->mc.suff_ss;
+    }
   GlLayoutHost gl;
   if (options->group_local) TRYB(group_local_setup(s, m, params, n_params, options, &gl));
   s->d.n_obs = m->n_obs; s->d.G = m->G; s->d.K = m->K;
-  if (m->model == AMWG_MODEL_NORMAL || m->model == AMWG_MODEL_HIER_NORMAL) TRYB(upload_normal_data(s, m, gl));
-  else if (m->model == AMWG_MODEL_BETA_BERN) TRYB(upload_bernoulli_data(s, m));
-  else TRYB(upload_poisson_data(s, m));
+  if (m->model == AMWG_MODEL_NORMAL || m->model == AMWG_MODEL_HIER_NORMAL) TRYB(upload_normal_data(s, models, D, gl, consts));
+  else if (m->model == AMWG_MODEL_BETA_BERN) TRYB(upload_bernoulli_data(s, models, D, consts));
+  else TRYB(upload_poisson_data(s, models, D, consts));
+  if (D > 1) {
+    TRYB(upload(s, consts.data(), consts.size(), &s->d_ds_consts));
+    s->n_datasets = D;
+  }
   clk.mark("device + data upload");
   TRYB(alloc_chain_state(s, params, n_params, init, comp_opts));
   clk.mark("chain state");
   if (m->model == AMWG_MODEL_HIER_NORMAL && !options->exact_division) s->hier_periodic_mask = periodic_label_mask(m);
   TRYB(plan_and_prepare(s, prop, clk, [s]() -> int {      // once the plan is adopted
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(s->kernel), hipFuncAttributeMaxDynamicSharedMemorySize, s->plan.lds);
+    const void *kernel = s->n_datasets > 1 ? reinterpret_cast<const void *>(s->ds_kernel) : reinterpret_cast<const void *>(s->kernel);
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, s->plan.lds);
     return e == hipSuccess ? AMWG_OK : amwg_fail(AMWG_EHIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(e));
   }));
   *out = guard.release();
   return AMWG_OK;
+}
+
+extern "C" {
+
+int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t n_params, const double *init,
+                const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  if (!m || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "amwg_create: null argument");
+  return create_builtin(m, 1, params, n_params, init, comp_opts, options, out);
+}
+
+int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                         const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  if (!models || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: null argument");
+  if (n_datasets < 1) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: n_datasets must be >= 1, got %d", n_datasets);
+  if (n_datasets == 1) return amwg_create(models, params, n_params, init, comp_opts, options, out);
+  if (options->chains % n_datasets != 0)
+    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: chains (%lld, the total) must be a multiple of n_datasets (%d)", (long long)options->chains, n_datasets);
+  for (int d = 1; d < n_datasets; ++d) {
+    if (models[d].model != models[0].model) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d is of model %d, dataset 0 of model %d (one family per sampler)", d, models[d].model, models[0].model);
+    if (models[d].n_obs != models[0].n_obs) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has n_obs = %d, dataset 0 has %d (ragged datasets are not supported)", d, models[d].n_obs, models[0].n_obs);
+    if (models[d].K != models[0].K || models[d].G != models[0].G) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has K = %d, G = %d, dataset 0 has K = %d, G = %d", d, models[d].K, models[d].G, models[0].K, models[0].G);
+    for (int k = 0; k < 8; ++k)
+      if (memcmp(&models[d].hyper[k], &models[0].hyper[k], sizeof(double)) != 0)
+        return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has hyper[%d] = %g, dataset 0 has %g (the hyper-parameters are shared)", d, k, models[d].hyper[k], models[0].hyper[k]);
+  }
+  if (models[0].model == AMWG_MODEL_HIER_NORMAL)
+    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: the hierarchical family is not supported (its launch plan depends on properties of the group labels, which differ between datasets)");
+  if (options->group_local) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: group_local is an evaluation of the hierarchical family, which dataset samplers do not support");
+  if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE)
+    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: AMWG_LANES_AUTOTUNE is not supported (the timing runs would have to search the geometries that serve whole datasets); give lanes_per_chain or leave it 0");
+  return create_builtin(models, n_datasets, params, n_params, init, comp_opts, options, out);
 }
 
 int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, int32_t n_params, const double *init,

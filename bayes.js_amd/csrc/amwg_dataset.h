@@ -1,0 +1,74 @@
+// amwg_dataset.h -- many datasets in one sampler (amwg_create_datasets): the kernels' second argument and the entry points that use it.
+//
+// Chains keep their one global numbering; dataset d owns the local chains [d * cpd, (d + 1) * cpd), cpd = chains / D.  A workgroup serves exactly ONE
+// dataset -- the host only plans geometries whose chains per workgroup divide cpd (amwg_plan.hip) -- so everything that tells datasets apart is
+// wave-uniform: d = blockIdx.x / blocks_per_dataset, the shifted data pointers and the data-dependent constants all sit in scalar registers, worked out
+// once in the entry block.  The entry points below are twins of amwg_step_kernel / amwg_step_kernel_cert: they build the workgroup's DataRef and
+// ModelConsts and hand them to the same step_body.  Nothing else changes: the per-chain arrays, the draws [row][P][C], the wavefront ids behind
+// wave_scratch_of and the Philox key (seed, chain_offset + c) are those of an ordinary sampler, which is why dataset d's chains equal the chains of an
+// ordinary sampler on dataset d with chain_offset = d * cpd, bit for bit (tests/test_gpu_datasets.py).
+//
+// StepArgs stays the kernels' FIRST parameter and keeps its size: cold_args() (amwg_kernel.h) reads it through the kernel-argument pointer, and what is
+// read that way -- the per-chain arrays, the draws, the hyper-parameters of the Normal prior -- is the same for every dataset.
+#pragma once
+#include "amwg_kernel.h"
+
+namespace amwg {
+
+// what the host computes per dataset instead of once (amwg_create.hip); the rest of ModelConsts follows from the hyper-parameters, which all datasets share
+struct DatasetConsts {
+  int32_t data_mid_range, has_invalid;
+  double glm_xmax[7], glm_sum_y, glm_sum_lf;
+  double suff_xbar_hi, suff_xbar_lo, suff_ss;
+};
+
+// The datasets' arrays lie back to back at a fixed stride, one allocation per array: dataset d's begin at base + d * stride (strides in ELEMENTS of the
+// array's type; 0 for an array the family does not have).
+struct DatasetArgs {
+  int32_t blocks_per_dataset, n_datasets;
+  int64_t stride_x, stride_y, stride_lfact, stride_xb, stride_xw, stride_arr0;      // (arr[0]: the beta-Bernoulli family's tables of two_valued_sum, 32-bit words)
+  const DatasetConsts *consts;                                                      // [n_datasets], device memory
+};
+
+// the argument block as the workgroup of dataset blockIdx.x / blocks_per_dataset sees it
+__device__ __forceinline__ void dataset_view(StepArgs &v, const DatasetArgs &ds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  // (made a scalar explicitly: the quotient of two scalars is formed with the vector unit's reciprocal)
+  const int64_t d = (int64_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x / (uint32_t)ds.blocks_per_dataset));
+#else
+  const int64_t d = 0;
+#endif
+  v.d.x += d * ds.stride_x;
+  v.d.y += d * ds.stride_y;
+  v.d.lfact += d * ds.stride_lfact;
+  v.d.xb += d * ds.stride_xb;
+  v.d.xw += d * ds.stride_xw;
+  v.d.arr[0] = static_cast<const uint32_t *>(v.d.arr[0]) + d * ds.stride_arr0;
+  const DatasetConsts &k = ds.consts[d];      // (a uniform address: scalar loads)
+  v.mc.data_mid_range = k.data_mid_range;
+  v.mc.has_invalid = k.has_invalid;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) v.mc.glm_xmax[j] = k.glm_xmax[j];
+  v.mc.glm_sum_y = k.glm_sum_y;
+  v.mc.glm_sum_lf = k.glm_sum_lf;
+  v.mc.suff_xbar_hi = k.suff_xbar_hi;
+  v.mc.suff_xbar_lo = k.suff_xbar_lo;
+  v.mc.suff_ss = k.suff_ss;
+}
+
+template <class Model, int G, int BT>
+__global__ void __launch_bounds__(BT, MinWavesOf<Model>::value) amwg_step_kernel_ds(const StepArgs a, const DatasetArgs ds) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  StepArgs v = a;
+  dataset_view(v, ds);
+  step_body<Model, G, BT>(v, smem);
+}
+template <class Model, int G, int BT>
+__global__ void __launch_bounds__(BT, MinWavesOf<Model>::value) amwg_step_kernel_cert_ds(const StepArgs a, const DatasetArgs ds) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  StepArgs v = a;
+  dataset_view(v, ds);
+  step_body<Model, G, BT, false, false, true>(v, smem);
+}
+
+}  // namespace amwg

@@ -52,6 +52,54 @@ __global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, i
   }
 }
 
+// ---- a dataset sampler (amwg_create_datasets): the same summaries per dataset, one workgroup per (recorded value, dataset); dataset d owns the chains
+// [d * cpd, (d + 1) * cpd)
+__device__ inline double block_sum(double v, double *red) {      // sum over the workgroup (a power-of-two size), in every thread
+  const int tid = threadIdx.x, nt = blockDim.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+  return red[0];
+}
+// mean and sd (n - 1 denominator) over the dataset's chains x kept draws: the order of moments_kernel over the dataset's own columns; out [D][PR] each
+__global__ void __launch_bounds__(1024) dataset_moments_kernel(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, double *mean, double *sd) {
+  __shared__ double red[1024];
+  const int p = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  const int64_t n = rows * cpd, c0 = (int64_t)d * cpd;
+  double sum = 0;
+  for (int64_t i = tid; i < n; i += nt) sum += draws[((i / cpd) * PR + p) * C + c0 + (i % cpd)];
+  const double m = block_sum(sum, red) / (double)n;
+  double ss = 0;
+  for (int64_t i = tid; i < n; i += nt) { const double dlt = draws[((i / cpd) * PR + p) * C + c0 + (i % cpd)] - m; ss += dlt * dlt; }
+  const double tot = block_sum(ss, red);
+  if (tid == 0) { mean[(size_t)d * PR + p] = m; sd[(size_t)d * PR + p] = n > 1 ? sqrt(tot / (double)(n - 1)) : 0.0; }
+}
+// split-R-hat and ESS of one dataset from the per-chain halves (chain_halves_kernel's layout): the definition of amwg_last_sample_diagnostics over the
+// dataset's cpd chains; out [D][PR] each
+__global__ void __launch_bounds__(256) dataset_diagnostics_kernel(const double *hv, int64_t rows, int PR, int64_t C, int64_t cpd, double *rhat, double *ess) {
+  __shared__ double red[256];
+  const int p = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  const int64_t c0 = (int64_t)d * cpd;
+  const double *m0 = hv + ((size_t)0 * PR + p) * C + c0, *v0 = hv + ((size_t)1 * PR + p) * C + c0, *m1 = hv + ((size_t)2 * PR + p) * C + c0, *v1 = hv + ((size_t)3 * PR + p) * C + c0;
+  const double n = (double)(rows / 2), m = 2.0 * (double)cpd;      // 2 cpd half-chains of n draws
+  double sm = 0, sw = 0, smc = 0;
+  for (int64_t c = tid; c < cpd; c += nt) { sm += m0[c] + m1[c]; sw += v0[c] + v1[c]; smc += 0.5 * (m0[c] + m1[c]); }
+  const double W = block_sum(sw, red) / m, gm = block_sum(sm, red) / m, gmc = block_sum(smc, red) / (double)cpd;
+  double sb = 0, sbc = 0;
+  for (int64_t c = tid; c < cpd; c += nt) {
+    const double a = m0[c] - gm, b = m1[c] - gm, w = 0.5 * (m0[c] + m1[c]) - gmc;
+    sb += a * a + b * b;
+    sbc += w * w;
+  }
+  const double B_over_n = block_sum(sb, red) / (m - 1), var_chain_mean = block_sum(sbc, red) / ((double)cpd - 1);
+  const double var_plus = (n - 1) / n * W + B_over_n;
+  if (tid == 0) {
+    rhat[(size_t)d * PR + p] = W > 0 ? sqrt(var_plus / W) : __builtin_nan("");
+    ess[(size_t)d * PR + p] = var_chain_mean > 0 ? (double)cpd * var_plus / var_chain_mean : __builtin_nan("");
+  }
+}
+
 // 8 independent fma chains per lane, no memory traffic: the fp64 issue rate the chip sustains
 __global__ void __launch_bounds__(1024) fp64_peak_kernel(double *out, int iters, double a, double b) {
   double x0 = threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
@@ -79,6 +127,13 @@ int amwg_fail(int code, const char *fmt, ...) {
   return code;
 }
 
+// a pooled summary over the chains of a dataset sampler would mix posteriors that have nothing to do with each other
+int amwg_refuse_pooled(const amwg_sampler *s, const char *call) {
+  if (s && s->n_datasets > 1)
+    return amwg_fail(AMWG_EINVAL, "%s: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_moments / amwg_last_sample_dataset_diagnostics", call, s->n_datasets);
+  return AMWG_OK;
+}
+
 extern "C" {
 
 const char *amwg_last_error(void) { return g_err.c_str(); }
@@ -93,8 +148,49 @@ double amwg_uniform(uint64_t seed, uint64_t chain, uint64_t index) {
   return s.next();
 }
 
+int amwg_num_datasets(const amwg_sampler *s) { return s ? s->n_datasets : 0; }
+
+int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd) {
+  if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: null argument");
+  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: no sample() call yet");
+  HIP_TRY(hipSetDevice(s->device));
+  const int PR = s->P + s->D, D = s->n_datasets;
+  const size_t n = (size_t)D * PR;
+  DevBuf buf;
+  HIP_TRY(buf.alloc(n * 16));
+  double *dm = buf.as<double>();
+  hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMWG_OK;
+}
+
+int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
+  if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: null argument");
+  const int D = s->n_datasets;
+  if (!s->last_draws || s->last_rows < 4 || s->C / D < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains per dataset");
+  HIP_TRY(hipSetDevice(s->device));
+  const int PR = s->P + s->D;
+  const size_t C = (size_t)s->C, n_halves = 4 * (size_t)PR * C, n = (size_t)D * PR;
+  DevBuf halves, out;
+  HIP_TRY(halves.alloc(n_halves * 8));
+  HIP_TRY(out.alloc(n * 16));
+  double *dr = out.as<double>();
+  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves.as<double>());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dataset_diagnostics_kernel, dim3(PR, D), dim3(256), 0, s->stream, halves.as<double>(), s->last_rows, PR, s->C, s->C / D, dr, dr + n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rhat, dr, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(ess, dr + n, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMWG_OK;
+}
+
 int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: null argument");
+  TRYB(amwg_refuse_pooled(s, "amwg_last_sample_diagnostics"));
   if (!s->last_draws || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
   HIP_TRY(hipSetDevice(s->device));
   const int PR = s->P + s->D;
@@ -173,6 +269,7 @@ int amwg_chain_diag(amwg_sampler *s, uint64_t *uniforms, double *log_post_out, i
 
 int amwg_last_sample_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: null argument");
+  TRYB(amwg_refuse_pooled(s, "amwg_last_sample_moments"));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: no sample() call yet");
   HIP_TRY(hipSetDevice(s->device));
   DevBuf buf;
@@ -223,7 +320,9 @@ const char *amwg_kernel_name(const amwg_sampler *s) {
   if (m->kernel_name.empty()) {
     const LaunchPlan &p = s->plan;
     const int cls = p.block <= 256 ? 256 : (p.block <= 512 ? 512 : 1024);
-    const char *name = info(p.variant).name;
+    // (a dataset sampler launches the kernel's twin, amwg_dataset.h: the same name with the marker _ds)
+    const std::string variant_name = std::string(info(p.variant).name) + (s->n_datasets > 1 ? "_ds" : "");
+    const char *name = variant_name.c_str();
     static const char *const fam[] = {"NormalModel", "BetaBernModel", "HierNormalModel", "PoisGlmModel"};      // (AMWG_MODEL_* - 1)
     char buf[96];
     if (p.variant == Variant::Step || p.variant == Variant::StepCert)

@@ -295,10 +295,17 @@ __global__ void pick_quantiles_kernel2(const double *sorted, int64_t n, const do
 
 }  // namespace
 
+// the pooled summaries are refused when a shard is a dataset sampler (amwg_create_datasets): see amwg_refuse_pooled
+static int refuse_pooled_shards(amwg_sampler *const *shards, int n, const char *call) {
+  for (int i = 0; shards && i < n; ++i) { const int rc = amwg_refuse_pooled(shards[i], call); if (rc != AMWG_OK) return rc; }
+  return AMWG_OK;
+}
+
 extern "C" {
 
 int amwg_group_moments(amwg_sampler *const *shards, int32_t n, double *mean, double *sd) {
   if (!mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_group_moments: null argument");
+  { const int rp = refuse_pooled_shards(shards, n, "amwg_group_moments"); if (rp != AMWG_OK) return rp; }
   Group g;
   const int PR0 = (shards && n > 0 && shards[0]) ? shards[0]->P + shards[0]->D : 0;
   int rc = open_group(shards, n, (size_t)PR0 + 1, true, &g);
@@ -337,6 +344,7 @@ int amwg_group_moments(amwg_sampler *const *shards, int32_t n, double *mean, dou
 }
 
 int amwg_group_diagnostics(amwg_sampler *const *shards, int32_t n, double *rhat, double *ess) {
+  { const int rp = refuse_pooled_shards(shards, n, "amwg_group_diagnostics"); if (rp != AMWG_OK) return rp; }
   if (!rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_group_diagnostics: null argument");
   Group g;
   const int PR0 = (shards && n > 0 && shards[0]) ? shards[0]->P + shards[0]->D : 0;
@@ -385,6 +393,7 @@ int amwg_group_diagnostics(amwg_sampler *const *shards, int32_t n, double *rhat,
 }
 
 int amwg_group_quantiles(amwg_sampler *const *shards, int32_t n, const double *probs, int32_t n_probs, double *out) {
+  { const int rp = refuse_pooled_shards(shards, n, "amwg_group_quantiles"); if (rp != AMWG_OK) return rp; }
   if (!probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_group_quantiles: bad argument");
   Group g;
   int rc = open_group(shards, n, 1, true, &g);
@@ -660,6 +669,7 @@ int amwg_comm_moments(amwg_sampler *s, amwg_comm *c, double *mean, double *sd) {
   // -inf, so that every rank sees a total that is not a count and returns an error, instead of the others waiting in the collective for good)
   char why[200] = "";
   if (!mean || !sd) snprintf(why, sizeof why, "null output");
+  else if (s->n_datasets > 1) snprintf(why, sizeof why, "this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_moments", s->n_datasets);
   else if (!s->last_draws || s->last_rows < 1) snprintf(why, sizeof why, "no sample() call yet");
   else if (s->device != c->device) snprintf(why, sizeof why, "the sampler is on device %d, the communicator on %d", s->device, c->device);
   else if (amwg_sync(s) != AMWG_OK) snprintf(why, sizeof why, "%.190s", amwg_last_error());

@@ -49,6 +49,7 @@ struct FamilyRow {
   step_kernel_t (*kernel)(int lanes, int block), (*certified)(int lanes, int block);      // the step kernel of a geometry, and the one that decides from certified values (kCert); nullptr: none
   size_t (*lds_bytes)(int n_obs, int groups, int lanes);      // LDS bytes of the data the family stages
   int max_threads;                                            // the family's largest workgroup
+  dataset_kernel_t (*dataset_kernel)(int lanes, int block), (*dataset_certified)(int lanes, int block);      // their dataset twins (amwg_dataset.h); nullptr: none
 };
 template <int Family> FamilyRow amwg_family_row();
 

@@ -10,6 +10,9 @@
 #include "amwg_host.h"
 #include "amwg_kernel.h"
 #include "amwg_models.h"
+#if AMWG_FAMILY != 2
+#include "amwg_dataset.h"      // (the dataset twins: every family but the hierarchical one, whose plan depends on properties of the labels)
+#endif
 
 using namespace amwg;
 
@@ -118,6 +121,62 @@ step_kernel_t lookup(int lanes, int block) {
 }
 }  // namespace
 
+// ---- the dataset twins (amwg_dataset.h; amwg_create_datasets): the same lookups, instantiated for the Normal, beta-Bernoulli and Poisson families
+#if AMWG_FAMILY != 2
+namespace {
+template <int G>
+dataset_kernel_t ds_single_wave(int block) {
+  switch (class_of(block)) {
+    case 256: return amwg_step_kernel_ds<Family, G, 256>;
+    case 512: if constexpr (Family::kMaxThreads >= 512) return amwg_step_kernel_ds<Family, G, 512>; else return nullptr;
+    default: if constexpr (Family::kMaxThreads >= 1024) return amwg_step_kernel_ds<Family, G, 1024>; else return nullptr;
+  }
+}
+template <int G>
+dataset_kernel_t ds_multi_wave(int block) {
+  if (block != G) return nullptr;
+  if constexpr (G <= Family::kMaxThreads) return amwg_step_kernel_ds<Family, G, class_of(G)>;
+  else return nullptr;
+}
+template <class Family>
+dataset_kernel_t ds_certified_lookup(int lanes, int block) {
+  if constexpr (CertifiedOf<Family>::value && !CertNeedsRows<Family>::value) {
+    constexpr int GC = CertifiedOf<Family>::lanes;
+    if (lanes != GC) return nullptr;
+    switch (class_of(block)) {
+      case 256: return amwg_step_kernel_cert_ds<Family, GC, 256>;
+      case 512: if constexpr (Family::kMaxThreads >= 512) return amwg_step_kernel_cert_ds<Family, GC, 512>; else return nullptr;
+      default: if constexpr (Family::kMaxThreads >= 1024) return amwg_step_kernel_cert_ds<Family, GC, 1024>; else return nullptr;
+    }
+  }
+  (void)lanes; (void)block;
+  return nullptr;
+}
+dataset_kernel_t ds_certified(int lanes, int block) { return ds_certified_lookup<Family>(lanes, block); }
+dataset_kernel_t ds_lookup(int lanes, int block) {
+  switch (lanes) {
+    case 1: return ds_single_wave<1>(block);
+    case 2: return ds_single_wave<2>(block);
+    case 4: return ds_single_wave<4>(block);
+    case 8: return ds_single_wave<8>(block);
+    case 16: return ds_single_wave<16>(block);
+    case 32: return ds_single_wave<32>(block);
+    case 64: return ds_single_wave<64>(block);
+    case 128: return ds_multi_wave<128>(block);
+    case 256: return ds_multi_wave<256>(block);
+    case 512: return ds_multi_wave<512>(block);
+    case 1024: return ds_multi_wave<1024>(block);
+  }
+  return nullptr;
+}
+}  // namespace
+#else
+namespace {
+dataset_kernel_t ds_certified(int, int) { return nullptr; }
+dataset_kernel_t ds_lookup(int, int) { return nullptr; }
+}  // namespace
+#endif
+
 template <> FamilyRow amwg_family_row<AMWG_FAMILY>() {
-  return {lookup, certified, [](int n_obs, int groups, int lanes) -> size_t { return Family::lds_bytes(n_obs, groups, lanes); }, Family::kMaxThreads};
+  return {lookup, certified, [](int n_obs, int groups, int lanes) -> size_t { return Family::lds_bytes(n_obs, groups, lanes); }, Family::kMaxThreads, ds_lookup, ds_certified};
 }

@@ -195,25 +195,30 @@ static napi_value wrap_sampler(napi_env env, amwg_sampler *s) {
   return ext;
 }
 
+/* {model, n_obs, G, K, x, y, g, hyper} -> amwg_model_desc (the typed arrays stay the caller's) */
+static void read_model_desc(napi_env env, napi_value o, amwg_model_desc *md) {
+  memset(md, 0, sizeof *md);
+  md->model = (int32_t)prop_i64(env, o, "model", 0);
+  md->n_obs = (int32_t)prop_i64(env, o, "n_obs", 0);
+  md->G = (int32_t)prop_i64(env, o, "G", 0);
+  md->K = (int32_t)prop_i64(env, o, "K", 0);
+  napi_value v;
+  size_t n = 0;
+  if (prop(env, o, "x", &v)) md->x = (const double *)typed_data(env, v, napi_float64_array, &n);
+  if (prop(env, o, "y", &v)) md->y = (const double *)typed_data(env, v, napi_float64_array, &n);
+  if (prop(env, o, "g", &v)) md->g = (const int32_t *)typed_data(env, v, napi_int32_array, &n);
+  if (prop(env, o, "hyper", &v)) {
+    const double *h = (const double *)typed_data(env, v, napi_float64_array, &n);
+    for (size_t i = 0; h && i < n && i < 8; i++) md->hyper[i] = h[i];
+  }
+}
+
 /* create(model, params[], init Float64Array, compOpts[], options) -> external handle */
 static napi_value Create(napi_env env, napi_callback_info info) {
   napi_value a[5];
   if (!get_args(env, info, 5, a)) return NULL;
   amwg_model_desc md;
-  memset(&md, 0, sizeof md);
-  md.model = (int32_t)prop_i64(env, a[0], "model", 0);
-  md.n_obs = (int32_t)prop_i64(env, a[0], "n_obs", 0);
-  md.G = (int32_t)prop_i64(env, a[0], "G", 0);
-  md.K = (int32_t)prop_i64(env, a[0], "K", 0);
-  napi_value v;
-  size_t n = 0;
-  if (prop(env, a[0], "x", &v)) md.x = (const double *)typed_data(env, v, napi_float64_array, &n);
-  if (prop(env, a[0], "y", &v)) md.y = (const double *)typed_data(env, v, napi_float64_array, &n);
-  if (prop(env, a[0], "g", &v)) md.g = (const int32_t *)typed_data(env, v, napi_int32_array, &n);
-  if (prop(env, a[0], "hyper", &v)) {
-    const double *h = (const double *)typed_data(env, v, napi_float64_array, &n);
-    for (size_t i = 0; h && i < n && i < 8; i++) md.hyper[i] = h[i];
-  }
+  read_model_desc(env, a[0], &md);
   amwg_param_desc *pd; amwg_comp_opt *co; uint32_t n_params; const double *init; amwg_options op;
   if (!parse_common(env, a, &pd, &co, &n_params, &init, &op)) return NULL;
   amwg_sampler *s = NULL;
@@ -223,6 +228,56 @@ static napi_value Create(napi_env env, napi_callback_info info) {
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   return wrap_sampler(env, s);
 }
+
+/* createDatasets(models[], params[], init Float64Array, compOpts[], options) -> external handle: one built-in family on several datasets
+ * (amwg_create_datasets; options.chains is the total) */
+static napi_value CreateDatasets(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  uint32_t n_models = 0;
+  if (napi_get_array_length(env, a[0], &n_models) != napi_ok || n_models < 1) {
+    napi_throw_type_error(env, NULL, "amwg_napi.createDatasets: models must be a non-empty array");
+    return NULL;
+  }
+  amwg_model_desc *md = (amwg_model_desc *)calloc(n_models, sizeof *md);
+  for (uint32_t i = 0; i < n_models; i++) {
+    napi_value e;
+    napi_get_element(env, a[0], i, &e);
+    read_model_desc(env, e, &md[i]);
+  }
+  amwg_param_desc *pd; amwg_comp_opt *co; uint32_t n_params; const double *init; amwg_options op;
+  if (!parse_common(env, a, &pd, &co, &n_params, &init, &op)) { free(md); return NULL; }
+  amwg_sampler *s = NULL;
+  int rc = amwg_create_datasets(md, (int32_t)n_models, pd, (int32_t)n_params, init, co, &op, &s);
+  free(md);
+  free(pd);
+  free(co);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  return wrap_sampler(env, s);
+}
+
+/* datasetMoments(handle) -> {mean, sd}, datasetConvergence(handle) -> {rhat, ess}: Float64Arrays [datasets][recorded] over the last sample() */
+static napi_value dataset_summary(napi_env env, napi_callback_info info, int (*fn)(amwg_sampler *, double *, double *), const char *k0, const char *k1) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  const size_t n = (size_t)amwg_num_recorded(s) * (size_t)amwg_num_datasets(s);
+  double *p0, *p1;
+  napi_value v0 = new_f64(env, n, &p0), v1 = new_f64(env, n, &p1);
+  if (!v0 || !v1) return NULL;
+  int rc = fn(s, p0, p1);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, k0, v0);
+  napi_set_named_property(env, o, k1, v1);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  return o;
+}
+static napi_value DatasetMoments(napi_env env, napi_callback_info info) { return dataset_summary(env, info, amwg_last_sample_dataset_moments, "mean", "sd"); }
+static napi_value DatasetConvergence(napi_env env, napi_callback_info info) { return dataset_summary(env, info, amwg_last_sample_dataset_diagnostics, "rhat", "ess"); }
 
 /* createUser({source, arrays: [Float64Array...], n_derived, lds_bytes, parallel, max_threads}, params[], init, compOpts[], options)
  * -- a closure translated by bayes.js_amd/translate.js (amwg_create_user) */
@@ -713,6 +768,8 @@ static napi_value LaunchInfo(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, o, "kernel", t);
   napi_create_int32(env, amwg_summation_order(s), &t);      /* 1: decisions and log_post in the reference's own order */
   napi_set_named_property(env, o, "summation_order", t);
+  napi_create_int32(env, amwg_num_datasets(s), &t);         /* > 1: a dataset sampler (createDatasets) */
+  napi_set_named_property(env, o, "datasets", t);
   /* lanes_per_chain: -2 (AMWG_LANES_AUTOTUNE): what was timed at construction, [{lanes_per_chain, ms}, ...] */
   int32_t tl[16];
   double tm[16];
@@ -770,7 +827,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

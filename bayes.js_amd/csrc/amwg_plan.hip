@@ -82,6 +82,10 @@ static const VariantInfo kVariants[] = {
     {"amwg_user_step", false}, {"amwg_user_step_cert", true}, {"amwg_user_sweep", false}, {"amwg_user_sweep_cert", true}};
 const VariantInfo &info(Variant v) { return kVariants[(int)v]; }
 
+// A dataset sampler (amwg_create_datasets; amwg_dataset.h): chains per dataset, 0 for every other sampler; and the chains a workgroup of a geometry serves
+static int64_t chains_per_dataset(const amwg_sampler *s) { return s->n_datasets > 1 ? s->C / s->n_datasets : 0; }
+static int chains_per_workgroup(int lanes, int block) { return lanes > 64 ? 1 : block / lanes; }
+
 // The kernel G lanes per chain in workgroups of bt threads with max_lds bytes of LDS run, and its DataRef::pad: the plan's lanes, block, variant and pad.
 //   * certified decisions unless full_evaluation or exact_division ask for the expression: the Normal family at one lane per chain, the Poisson family at
 //     16, the hierarchical family's sweep kernel; a closure without binary parameters with a certified tail (amwg_user.h norm_tail_approx: one lane;
@@ -230,8 +234,11 @@ static int size_wave_scratch(amwg_sampler *s) {
 int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds, LaunchPlan *out) {
   const amwg_options &o = s->opt;
   const int max_bt = s->user ? s->user_max_threads : family_of(s->model)->max_threads;
+  // a dataset sampler: a workgroup serves ONE dataset, so the chains per workgroup divide the chains per dataset -- only such geometries are searched
+  const int64_t cpd = chains_per_dataset(s);
   auto fits = [&](int bt, int G) {
     if (bt > max_bt || bt % G != 0) return false;
+    if (cpd && cpd % chains_per_workgroup(G, bt) != 0) return false;
     const LaunchPlan p = variant_for(s, G, bt, max_lds);
     // (the sweep kernels -- row layout, 64 lanes per chain -- keep the window stream and the sweep's per-lane values in registers: compiled for at most 512 threads,
     // where a lane has 256 of them; with the 128 of a 1024-thread workgroup the hierarchical family's ran from scratch memory, five times slower)
@@ -267,7 +274,8 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
       if ((s->C + bt / G - 1) / (bt / G) >= n_cus) break;
     }
     int cpb = 0;
-    if (!pick && G < 64 && max_bt >= 64 && (!o.block_threads || o.block_threads == 64)) {
+    // (the replica fallback is refused for dataset samplers rather than reasoned about: none of their three families can reach it)
+    if (!pick && !cpd && G < 64 && max_bt >= 64 && (!o.block_threads || o.block_threads == 64)) {
       for (int c = 32 / G; c >= 1; c >>= 1)      // fewer chains than lane groups in a one-wavefront workgroup
         if (lds_of(s, variant_for(s, G, 64, max_lds), c) <= max_lds) { pick = 64; cpb = c; break; }
     }
@@ -301,6 +309,9 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
   // (tested), the doubles are those of the G-lane order.  Unless the caller asked for a lane count (or for AMWG_LANES_FASTEST),
   // take one lane per chain whenever the model prices it within 12 % of the cheapest geometry.
   if (lanes == 0 && best.lanes > 1 && cost1 > 0 && cost1 <= 1.12 * best_cost) best = one;
+  if (!best.lanes && cpd)
+    return amwg_fail(AMWG_EINVAL, "no launch geometry serves whole datasets: the chains of a workgroup (block_threads / lanes_per_chain, or 1 for a chain on several wavefronts) must divide "
+                     "cpd = %lld chains per dataset; asked for lanes %d (0 = any), block %d (0 = any), %zu bytes of LDS", (long long)cpd, lanes, o.block_threads, max_lds);
   if (!best.lanes) return amwg_fail(AMWG_EINVAL, "no launch geometry fits: the model needs more than %zu bytes of LDS", max_lds);
   const int CPB = best.lanes > 64 ? 1 : (best.cpb ? best.cpb : best.block / best.lanes);
   best.grid = (int)((s->C + CPB - 1) / CPB);
@@ -316,6 +327,16 @@ int adopt_plan(amwg_sampler *s, const LaunchPlan &p) {
   s->plan = p;
   s->d.pad = p.pad;
   if (s->user) return size_wave_scratch(s);
+  if (s->n_datasets > 1) {      // the dataset twin (amwg_dataset.h), and how many workgroups serve one dataset
+    const int cpw = chains_per_workgroup(p.lanes, p.block);
+    const int64_t cpd = chains_per_dataset(s);
+    if (p.cpb || (p.variant != Variant::Step && p.variant != Variant::StepCert) || cpd % cpw != 0)
+      return amwg_fail(AMWG_EINVAL, "internal: a plan of %d lanes in workgroups of %d (cpb %d) for datasets of %lld chains", p.lanes, p.block, p.cpb, (long long)cpd);
+    s->ds_blocks_per_dataset = (int)(cpd / cpw);
+    s->ds_kernel = p.variant == Variant::StepCert ? family_of(s->model)->dataset_certified(p.lanes, p.block) : family_of(s->model)->dataset_kernel(p.lanes, p.block);
+    if (!s->ds_kernel) return amwg_fail(AMWG_EINVAL, "no dataset kernel for model %d with %d lanes per chain in workgroups of %d", s->model, p.lanes, p.block);
+    return size_wave_scratch(s);
+  }
   if (s->model == AMWG_MODEL_HIER_NORMAL) s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> log2_of(p.lanes)) & 1u);
   switch (p.variant) {
     case Variant::StepCert: case Variant::HierSweepCert: s->kernel = family_of(s->model)->certified(p.lanes, p.block); break;

@@ -9,6 +9,7 @@
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
 #include "amwg_host.h"
 #include "amwg_kernel.h"      // (StepArgs, and the kErr* bits the step kernels report)
+#include "amwg_dataset.h"     // (DatasetArgs: the second argument of a dataset sampler's kernel)
 
 using namespace amwg;
 
@@ -81,6 +82,16 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
   a.d = s->d;
   if (p.lanes != 1) a.d.wave_scratch = nullptr;      // (sized for one-lane geometries only; no other kernel reads it)
   a.ch = s->ch;
+  DatasetArgs ds{};      // (a dataset sampler: which workgroups serve which dataset, and where its data and constants lie)
+  if (s->n_datasets > 1) {
+    if (!s->ds_kernel || s->ds_blocks_per_dataset < 1 || (int64_t)s->ds_blocks_per_dataset * s->n_datasets != p.grid)
+      return amwg_fail(AMWG_EINVAL, "internal: %d workgroups for %d datasets of %d workgroups each", p.grid, s->n_datasets, s->ds_blocks_per_dataset);
+    ds.blocks_per_dataset = s->ds_blocks_per_dataset;
+    ds.n_datasets = s->n_datasets;
+    ds.stride_x = s->ds_stride[0]; ds.stride_y = s->ds_stride[1]; ds.stride_lfact = s->ds_stride[2];
+    ds.stride_xb = s->ds_stride[3]; ds.stride_xw = s->ds_stride[4]; ds.stride_arr0 = s->ds_stride[5];
+    ds.consts = s->d_ds_consts;
+  }
   // (a 0-step finalize launch on chains that have stepped -- amwg_chain_diag asking for the expression's value after a certified kernel ran -- is not "the latest call":
   // the sample call's launch count, its per-launch marks and its event pair stay, so that a diag() between sample_async and fetch_draws neither loses the copy overlap
   // nor replaces the call's kernel time with its own; round-5 advisor finding)
@@ -103,6 +114,9 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
       size_t arg_bytes = sizeof a;
       void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_bytes, HIP_LAUNCH_PARAM_END};
       HIP_TRY(hipModuleLaunchKernel(s->user_fn, (unsigned)p.grid, 1, 1, (unsigned)p.block, 1, 1, (unsigned)p.lds, s->stream, nullptr, extra));
+    } else if (s->n_datasets > 1) {
+      hipLaunchKernelGGL(s->ds_kernel, dim3(p.grid), dim3(p.block), (size_t)p.lds, s->stream, a, ds);
+      HIP_TRY(hipGetLastError());
     } else {
       hipLaunchKernelGGL(s->kernel, dim3(p.grid), dim3(p.block), (size_t)p.lds, s->stream, a);
       HIP_TRY(hipGetLastError());

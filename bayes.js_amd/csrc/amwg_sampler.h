@@ -12,6 +12,8 @@
 #include "amwg_types.h"
 
 typedef void (*step_kernel_t)(const amwg::StepArgs);
+namespace amwg { struct DatasetArgs; struct DatasetConsts; }
+typedef void (*dataset_kernel_t)(const amwg::StepArgs, const amwg::DatasetArgs);      // a dataset twin (amwg_dataset.h)
 
 // The step kernel a sampler launches.  The variant fixes the LDS data layout, DataRef::pad, the kernel's name and whether it decides from certified
 // values (amwg_plan.hip: variant_for decides it, kVariants describes it).
@@ -45,6 +47,13 @@ struct amwg_sampler {
   std::vector<int32_t> h_layout;   // [4][n_params] base | len | top | multidim (ParamLayout::tab on the device)
   LaunchPlan plan;                  // geometry and kernel (adopt_plan)
   step_kernel_t kernel = nullptr;   // the built-in kernel of plan.variant
+  // many datasets in one sampler (amwg_create_datasets; amwg_dataset.h): D > 1 datasets of cpd = C / D chains each, the kernel's second argument as far as it
+  // is fixed at construction (blocks_per_dataset follows the plan: adopt_plan), and the twin that takes it
+  int n_datasets = 1;
+  int64_t ds_stride[6] = {0, 0, 0, 0, 0, 0};      // elements: x, y, lfact, xb, xw, arr[0]
+  amwg::DatasetConsts *d_ds_consts = nullptr;
+  int ds_blocks_per_dataset = 0;
+  dataset_kernel_t ds_kernel = nullptr;
   int gl_rounds = 0;                // group_local: rows of the lane-major tile (GlLayoutHost::rounds; the group-local kernel's DataRef::pad)
   std::string kernel_name;          // amwg_kernel_name(): filled on first request
   uint32_t hier_periodic_mask = 0;   // HIER: bit j set = the group labels repeat with a lane stride of 2^j (g[i] == g[i mod 2^j])
@@ -81,3 +90,5 @@ struct amwg_sampler {
 
 // shared helper (amwg_diag.hip): records an error message for amwg_last_error() and returns `code`
 int amwg_fail(int code, const char *fmt, ...);
+// shared helper (amwg_diag.hip): AMWG_EINVAL with a message that points to the per-dataset calls when `s` is a dataset sampler (amwg_create_datasets), else AMWG_OK
+int amwg_refuse_pooled(const amwg_sampler *s, const char *call);

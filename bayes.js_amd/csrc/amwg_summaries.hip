@@ -39,6 +39,7 @@ __global__ void pick_quantiles_kernel(const double *sorted, int64_t n, const dou
 
 extern "C" int amwg_last_sample_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: bad argument");
+  { const int rp = amwg_refuse_pooled(s, "amwg_last_sample_quantiles"); if (rp != AMWG_OK) return rp; }
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: no sample() call yet");
   const int PR = s->P + s->D;
   const int64_t n = s->last_rows * s->C;

@@ -184,6 +184,16 @@ function AmwgSampler(params, log_post, data, options) {
   this.thin(opt('thin', 1));
   this.monitor(opt('monitor', null));
   this.options = options;
+  // options.datasets: the same model on many datasets, a posterior per dataset, in ONE sampler (amwg_create_datasets).  An array of `data` objects in place
+  // of the data argument; options.chains stays the total, dataset d owns the chains [d * cpd, (d + 1) * cpd), cpd = chains / datasets.length
+  const datasets = opt('datasets', null);
+  if (datasets !== null) {
+    if (!Array.isArray(datasets) || datasets.length < 1) throw 'AmwgSampler (MI355X): options.datasets must be a non-empty array of data objects';
+    if (data !== null && data !== undefined) throw 'AmwgSampler (MI355X): options.datasets takes the place of the data argument, which must then be null or undefined';
+    if (shared) throw 'AmwgSampler (MI355X): options.datasets is not available to the stand-alone steppers';
+    data = datasets[0];      // (the host-side log_post() evaluates against dataset 0, the dataset of chain 0)
+  }
+  this.n_datasets = datasets ? datasets.length : 1;
   this.data = data;
   this.params = shared ? params : complete_params(params, this.param_init_fun);   // steppers take completed params (mcmc.js:419-421)
 
@@ -203,6 +213,10 @@ function AmwgSampler(params, log_post, data, options) {
     if (!ok) recog = null;
   }
   this.model = recog ? recog.family : 'translated';
+  // (the translator folds data-dependent constants and storage types into the generated source: one source per dataset is not one sampler)
+  if (datasets && !recog)
+    throw 'AmwgSampler (MI355X): options.datasets needs a closure that is recognised as a built-in family (normal, beta_bern, pois_glm); this one goes through the translator, ' +
+          'which folds data-dependent constants and storage types into the generated source, and is not supported with options.datasets';
 
   // flatten params / init / options in Object.keys order (the stepper order of mcmc.js:839)
   const descs = [], init = [], compOpts = [];
@@ -244,7 +258,12 @@ function AmwgSampler(params, log_post, data, options) {
   // the model: a built-in family, or the closure translated to HIP (compiled by the addon with hiprtc)
   let desc = null, user = null;
   this.derived = [];
-  if (recog) desc = buildModelDesc(recog, data, this.params);
+  let dsDescs = null;      // options.datasets: one description per dataset (same family and hyper-parameters: one closure)
+  if (recog && datasets) {
+    if (this.chains % datasets.length !== 0) throw 'AmwgSampler (MI355X): options.chains (' + this.chains + ', the total) must be a multiple of the ' + datasets.length + ' datasets';
+    dsDescs = datasets.map((d) => buildModelDesc(recog, d, this.params));
+    this.chains_per_dataset = this.chains / datasets.length;
+  } else if (recog) desc = buildModelDesc(recog, data, this.params);
   else {
     const tr = translator.translate(log_post, translatedParams, data, { constants: options.constants, helpers: options.helpers,
       lds_budget: options.lds_budget, max_threads: options.max_threads, unroll: options.unroll, state_object: shared ? shared.state : undefined });
@@ -258,17 +277,21 @@ function AmwgSampler(params, log_post, data, options) {
   // contiguous shards of global chain ids, one native sampler per device (SURVEY.md §8e)
   const N = native();
   this._shards = [];
-  const D = Math.min(devices.length, this.chains), per = Math.floor(this.chains / D), rem = this.chains % D;
-  let offset = 0;
+  // (options.datasets: whole datasets are dealt to the shards in contiguous slices; a shard is a dataset sampler over its slice)
+  const units = dsDescs ? dsDescs.length : this.chains, unit = dsDescs ? this.chains_per_dataset : 1;
+  const D = Math.min(devices.length, units), per = Math.floor(units / D), rem = units % D;
+  let offset = 0, firstDataset = 0;
   let lanes = opt('lanes_per_chain', 0);
   for (let r = 0; r < D; r++) {
-    const count = per + (r < rem ? 1 : 0);
-    const handle = (user ? N.createUser : N.create)(user || desc, descs, Float64Array.from(init), compOpts, {
+    const nUnits = per + (r < rem ? 1 : 0), count = nUnits * unit;
+    const create = user ? N.createUser : (dsDescs ? N.createDatasets : N.create);
+    const handle = create(user || (dsDescs ? dsDescs.slice(firstDataset, firstDataset + nUnits) : desc), descs, Float64Array.from(init), compOpts, {
       chains: count, seed: this.seed, chain_offset: opt('chain_offset', 0) + offset, device: devices[r],
       lanes_per_chain: lanes, block_threads: opt('block_threads', 0),
       steps_per_launch: opt('steps_per_launch', 0), exact_division: opt('exact_division', 0), group_local: opt('group_local', 0) ? 1 : 0, full_evaluation: Number(opt('full_evaluation', 0)) | 0, test_bound_shift: Number(opt('test_bound_shift', 0)) | 0,
       sufficient_statistics: opt('sufficient_statistics', 0) ? 1 : 0 });
-    this._shards.push({ handle, offset, count, device: devices[r] });
+    this._shards.push({ handle, offset, count, device: devices[r], datasets: dsDescs ? nUnits : 0 });
+    firstDataset += nUnits;
     // one summation order for the whole job: what the first shard picked (cost model, or the measurement of lanes_per_chain: -2)
     // is what the other shards get -- a chain's draws must not depend on the shard it landed in
     if (r === 0 && D > 1 && lanes <= 0) lanes = N.launchInfo(handle).lanes_per_chain;
@@ -316,7 +339,7 @@ AmwgSampler.prototype.sample = function (n_iterations) {
       const L = found[m];
       if (!L) { out[name] = []; return; }
       const arr = arrays[k++];
-      Object.defineProperty(arr, 'layout', { value: { kept, len: L.len, chains: C, dim: L.dim }, enumerable: false });
+      Object.defineProperty(arr, 'layout', { value: this._drawLayout(kept, L), enumerable: false });
       out[name] = arr;
     });
     return out;
@@ -340,11 +363,18 @@ AmwgSampler.prototype.sample = function (n_iterations) {
     } else {
       const arr = new Float64Array(kept * L.len * C);
       for (let t = 0; t < kept; t++) arr.set(flat.subarray((t * P + L.base) * C, (t * P + L.base + L.len) * C), t * L.len * C);
-      Object.defineProperty(arr, 'layout', { value: { kept, len: L.len, chains: C, dim: L.dim }, enumerable: false });
+      Object.defineProperty(arr, 'layout', { value: this._drawLayout(kept, L), enumerable: false });
       out[name] = arr;
     }
   }
   return out;
+};
+
+// the hidden `layout` of an array sample() returns; a dataset sampler says which chains belong together
+AmwgSampler.prototype._drawLayout = function (kept, L) {
+  const layout = { kept, len: L.len, chains: this.chains, dim: L.dim };
+  if (this.options && this.options.datasets) { layout.datasets = this.n_datasets; layout.chains_per_dataset = this.chains_per_dataset; }
+  return layout;
 };
 
 /** Like sample(n), but the draws stay in HBM: nothing is copied to the host; moments(), quantiles() and convergence()
@@ -404,6 +434,7 @@ AmwgSampler.prototype.info = function () {
  *  `options.devices` every device reduces its shard and the partial sums meet in an RCCL all-reduce (amwg_group_moments). */
 AmwgSampler.prototype.moments = function () {
   const N = native();
+  this._refusePooled('moments');
   const m = this._shards.length === 1 ? N.moments(this._shards[0].handle) : N.groupMoments(this._shards.map((sh) => sh.handle)), out = {};
   for (const L of this._layout) out[L.name] = { mean: Array.from(m.mean.subarray(L.base, L.base + L.len)), sd: Array.from(m.sd.subarray(L.base, L.base + L.len)) };
   this.derived.forEach((name, q) => { out[name] = { mean: [m.mean[this.P + q]], sd: [m.sd[this.P + q]] }; });
@@ -415,6 +446,7 @@ AmwgSampler.prototype.moments = function () {
  *  sums, amwg_group_diagnostics). */
 AmwgSampler.prototype.convergence = function () {
   const N = native();
+  this._refusePooled('convergence');
   const d = this._shards.length === 1 ? N.convergence(this._shards[0].handle) : N.groupConvergence(this._shards.map((sh) => sh.handle)), out = {};
   for (const L of this._layout) out[L.name] = { rhat: Array.from(d.rhat.subarray(L.base, L.base + L.len)), ess: Array.from(d.ess.subarray(L.base, L.base + L.len)) };
   this.derived.forEach((name, q) => { out[name] = { rhat: [d.rhat[this.P + q]], ess: [d.ess[this.P + q]] }; });
@@ -425,6 +457,7 @@ AmwgSampler.prototype.convergence = function () {
  *  device radix sort, R's default (type 7) interpolation.  quantiles([0.025, 0.5, 0.975]) -> {name: [[q...] per element]} */
 AmwgSampler.prototype.quantiles = function (probs) {
   const N = native();
+  this._refusePooled('quantiles');
   const pr = Float64Array.from(probs), out = {};
   const q = this._shards.length === 1 ? N.quantiles(this._shards[0].handle, pr) : N.groupQuantiles(this._shards.map((sh) => sh.handle), pr);   // several devices: RCCL gather to the first, sorted there
   const row = (c) => Array.from(q.subarray(c * pr.length, (c + 1) * pr.length));
@@ -432,6 +465,34 @@ AmwgSampler.prototype.quantiles = function (probs) {
   this.derived.forEach((name, k) => { out[name] = [row(this.P + k)]; });
   return out;
 };
+
+// A dataset sampler (options.datasets) holds a posterior per dataset: a summary pooled over all chains is refused -- with the library's own message where a
+// shard is a dataset sampler itself (a shard that was dealt a single dataset is an ordinary sampler)
+AmwgSampler.prototype._refusePooled = function (what) {
+  if (!(this.options && this.options.datasets)) return;
+  const N = native(), sh = this._shards.find((q) => q.datasets > 1);
+  if (sh) N.moments(sh.handle);      // throws: amwg_last_sample_moments on a dataset sampler
+  throw 'AmwgSampler (MI355X): ' + what + '() pools all chains, and this sampler runs ' + this.n_datasets + ' datasets, a posterior each: use dataset_moments() / dataset_convergence()';
+};
+
+// per-dataset summaries of the last sample(): an array of one object per dataset, each shaped like the result of moments() / convergence()
+AmwgSampler.prototype._datasetSummary = function (call, k0, k1) {
+  const out = [];
+  for (const sh of this._shards) {
+    const r = call(sh.handle), PR = this.PR;
+    for (let d = 0; d < r.datasets; d++) {
+      const o = {}, a = r[k0].subarray(d * PR, (d + 1) * PR), b = r[k1].subarray(d * PR, (d + 1) * PR);
+      for (const L of this._layout) o[L.name] = { [k0]: Array.from(a.subarray(L.base, L.base + L.len)), [k1]: Array.from(b.subarray(L.base, L.base + L.len)) };
+      this.derived.forEach((name, q) => { o[name] = { [k0]: [a[this.P + q]], [k1]: [b[this.P + q]] }; });
+      out.push(o);
+    }
+  }
+  return out;
+};
+/** moments() per dataset (options.datasets): [{name: {mean, sd}}, ...], device-side reduction over each dataset's chains x kept draws. */
+AmwgSampler.prototype.dataset_moments = function () { const N = native(); return this._datasetSummary((h) => N.datasetMoments(h), 'mean', 'sd'); };
+/** convergence() per dataset (options.datasets): [{name: {rhat, ess}}, ...]; needs >= 2 chains per dataset. */
+AmwgSampler.prototype.dataset_convergence = function () { const N = native(); return this._datasetSummary((h) => N.datasetConvergence(h), 'rhat', 'ess'); };
 
 /** Per-chain starting points: f(chainIndex) -> state object shaped like sampler.state of one chain ({name: number | nested array}).
  *  The reference starts from the completed `init` (mcmc.js:954-957); many chains want over-dispersed starts. */

@@ -157,6 +157,32 @@ typedef struct amwg_sampler amwg_sampler;
 int amwg_create(const amwg_model_desc *model, const amwg_param_desc *params, int32_t n_params, const double *init,
                 const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
 
+/* MANY DATASETS IN ONE SAMPLER: the same built-in model on n_datasets datasets, a posterior per dataset, one launch (what the reference's users loop over
+ * in JavaScript: one A/B test per segment, one fit per bootstrap replicate, per sensor, per simulated dataset of a calibration study).
+ * options->chains is the TOTAL and must be a multiple of n_datasets; with cpd = chains / n_datasets, dataset d owns the local chains [d * cpd, (d + 1) * cpd)
+ * and everywhere else chain c means dataset c / cpd: amwg_burn, amwg_sample*, amwg_fetch_draws*, amwg_get/set_state, amwg_info, amwg_chain_diag and the
+ * gathers of draws work unchanged.  Chain c draws from the stream of global id chain_offset + c as ever, so dataset d's chains are bit for bit the chains
+ * of an amwg_create sampler on models[d] with chain_offset + d * cpd at the same lanes_per_chain and block_threads -- and a shard of a larger job is a dataset
+ * sampler over a contiguous slice of the datasets with chain_offset = first dataset * cpd.
+ * A workgroup serves one dataset: the launch geometry is chosen among those whose chains per workgroup (block_threads / lanes_per_chain; 1 for a chain on
+ * several wavefronts) divide cpd -- small cpd means more lanes per chain or smaller workgroups --, and a fixed lanes_per_chain / block_threads pair that does
+ * not divide cpd is AMWG_EINVAL.  The kernel is the twin of the ordinary one (amwg_kernel_name: "amwg_step_kernel_ds<...>", "amwg_step_kernel_cert_ds<...>").
+ * All descriptions must agree in model, n_obs, K, G and hyper: RAGGED DATASETS ARE NOT SUPPORTED.  Refused with AMWG_EINVAL, before a device is opened:
+ * AMWG_MODEL_HIER_NORMAL (its launch plan depends on properties of the group labels), options->group_local, AMWG_LANES_AUTOTUNE.  Supported:
+ * AMWG_MODEL_NORMAL, AMWG_MODEL_BETA_BERN, AMWG_MODEL_POIS_GLM with every other option.  n_datasets == 1 is amwg_create(models, ...).
+ * The pooled summaries (amwg_last_sample_moments / _diagnostics / _quantiles, amwg_group_moments / _diagnostics / _quantiles, amwg_comm_moments) return
+ * AMWG_EINVAL on such a sampler -- a pooled mean over unrelated posteriors is a bug the caller did not mean to write --; the per-dataset ones are below.
+ * Per-dataset quantiles (a segmented sort) are not provided. */
+int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                         const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
+/* Datasets of a sampler: 1 for every sampler not made by amwg_create_datasets with n_datasets > 1. */
+int amwg_num_datasets(const amwg_sampler *s);
+/* amwg_last_sample_moments per dataset, computed on the device over the dataset's chains x kept draws: mean[D][P], sd[D][P]. */
+int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd);
+/* amwg_last_sample_diagnostics per dataset (the same definitions over the dataset's chains; one workgroup per recorded value and dataset):
+ * rhat[D][P], ess[D][P].  Needs >= 2 chains per dataset and >= 4 kept draws. */
+int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess);
+
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,
  * "translated closure"); amwg_create_user compiles it with hiprtc for the device's gfx target,

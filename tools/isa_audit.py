@@ -37,6 +37,9 @@ FLAGS = "--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-
 # names beside them are what options.full_evaluation = 1 / 2 runs)
 DEFAULT_GATE = ["NormalModel,1,256,cert", "NormalModel,1,256", "HierNormalModel,sweep,512,cert", "HierNormalModel,sweep,512", "HierNormalModel,64,512", "HierNormalModel,32,1024",
                 "PoisGlmModel,16,256,cert", "PoisGlmModel,16,256", "PoisGlmModel,64,256", "BetaBernModel,1,1024", "HierGlModel,512"]
+# (",ds": the dataset twins of the two certified kernels above -- amwg_step_kernel_cert_ds, csrc/amwg_dataset.h: the same body behind a workgroup's view of its
+# dataset --, under the same rules and allowances as the kernels they are twins of)
+DEFAULT_GATE += ["NormalModel,1,256,cert,ds", "PoisGlmModel,16,256,cert,ds"]
 # Spills tolerated OUTSIDE the passes, in the two certified kernels that keep 256 registers busy (two wavefronts per SIMD): the 16-lane Poisson kernel (the certified
 # pass for four chains to a wavefront, the stepper, and the out-of-line expression in the reference's order) spills 6 VGPRs around its pass; the certified sweep kernel
 # (the stepper, the window stream, the sweep's all-at-once decisions and the walk update by update) ~36 loop-invariant words.  No kernel may have a scratch
@@ -47,12 +50,13 @@ DEFAULT_GATE = ["NormalModel,1,256,cert", "NormalModel,1,256", "HierNormalModel,
 SPILL_ALLOW = {"NormalModel,1,256,cert": {"vgpr_spill": 8, "loop_scratch": 0},
                "PoisGlmModel,16,256,cert": {"vgpr_spill": 8, "loop_scratch": 8},
                "HierNormalModel,sweep,512,cert": {"vgpr_spill": 40, "loop_scratch": 56}}
+SPILL_ALLOW.update({k + ",ds": v for k, v in SPILL_ALLOW.items() if not k.startswith("Hier")})
 
 
 # v_readlane / v_writelane that are NOT spilled scalars: the certified pass of the Normal family broadcasts the 64 chains' means with 2 x 64 v_readlane per block of
 # observations (csrc/amwg_pass.h norm_sq_pass_wave); since round 6 the rest of a pass is walked in blocks of half the length each -- 16, 8, 4, 2, 1 rounds, a loop of
 # single rounds and the masked last one: seven static copies of the 128 broadcasts
-LANE_MOVE_LIMITS = {"NormalModel,1,256,cert": 1500}
+LANE_MOVE_LIMITS = {"NormalModel,1,256,cert": 1500, "NormalModel,1,256,cert,ds": 1500}
 
 
 def compile_asm(family):
@@ -163,7 +167,7 @@ def loop_stats(lines):
 # `s_waitcnt lgkmcnt(0)` of its own: the compiler's wait-count pass does not track loads it did not emit.  Rule: every s_load_dwordx16 inside an inline-asm region
 # (;;#ASMSTART .. ;;#ASMEND) reaches an s_waitcnt with lgkmcnt(0) before any instruction that reads or writes one of its destination SGPRs, and before any label or
 # branch; a checked kernel must contain at least one such load.
-INLINE_SMEM_KERNELS = ["NormalModel,1,256,cert", "NormalModel,1,512,cert"]
+INLINE_SMEM_KERNELS = ["NormalModel,1,256,cert", "NormalModel,1,512,cert", "NormalModel,1,256,cert,ds", "NormalModel,1,512,cert,ds"]
 _SREG = re.compile(r"\bs\[(\d+):(\d+)\]|\bs(\d+)\b")
 
 
@@ -277,11 +281,13 @@ def main():
         meta, bodies = kernel_metadata(txt), kernel_bodies(txt)
         names = [n for n in meta if "amwg_step_kernel" in n or "amwg_user_step" in n or "amwg_gl_kernel" in n or "amwg_sweep_kernel" in n]
         for n, d in zip(names, demangle(names)):
-            short = re.sub(r"^void amwg::amwg_(?:step|gl|sweep)_kernel(?:_cert)?<amwg::(.*)>\(.*$", r"\1", d).replace(" ", "")
+            short = re.sub(r"^void amwg::amwg_(?:step|gl|sweep)_kernel(?:_cert)?(?:_ds)?<amwg::(.*)>\(.*$", r"\1", d).replace(" ", "")
             if "amwg_sweep_kernel" in d:
                 short = short.replace("HierNormalModel,", "HierNormalModel,sweep,")
-            if "_kernel_cert<" in d:
+            if "_kernel_cert<" in d or "_kernel_cert_ds<" in d:
                 short += ",cert"
+            if "_ds<" in d:
+                short += ",ds"
             st = loop_stats(bodies.get(n, []))
             row = {"kernel": short, **meta[n], **{"loop_" + k: v for k, v in st["in_loops"].items()}, "total_instructions": st["whole_kernel"]["instructions"]}
             rows.append(row)
