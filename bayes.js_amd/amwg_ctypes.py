@@ -46,8 +46,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_create_datasets", "amwg_num_datasets", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_create_datasets", "amwg_num_datasets", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -68,6 +68,7 @@ def lib():
         L.amwg_num_datasets.argtypes = [vp]
         L.amwg_last_sample_dataset_moments.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_diagnostics.argtypes = [vp, pd, pd]
+        L.amwg_last_sample_dataset_quantiles.argtypes = [vp, pd, i32, pd]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -154,6 +155,7 @@ def selftest_lib():
         L.amwg_ld_host.argtypes = [i32, dbl, dbl, dbl, dbl]
         L.amwg_ld_device.argtypes = [i32, i64, pd, pd]
         L.amwg_prefault_selftest.argtypes = [C.c_void_p, C.c_size_t, i32, i32]
+        L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         _selftest = L
     return _selftest
 
@@ -363,6 +365,13 @@ class Sampler:
         _check(lib().amwg_last_sample_dataset_diagnostics(self.h, _dp(r), _dp(e)))
         return r, e
 
+    def dataset_quantiles(self, probs):
+        """-> array [datasets][P + derived][len(probs)]: quantiles() per dataset, a radix select on the device (amwg_last_sample_dataset_quantiles)"""
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        out = np.empty((self.D, self.PR, pr.size))
+        _check(lib().amwg_last_sample_dataset_quantiles(self.h, _dp(pr), pr.size, _dp(out)))
+        return out
+
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)
         assert st.shape == (self.P, self.C)
@@ -395,6 +404,19 @@ class Sampler:
         return {"lanes_per_chain": v[0].value, "block_threads": v[1].value, "grid_blocks": v[2].value,
                 "lds_bytes": v[3].value, "n_launches": v[4].value, "kernel_ms": ms.value, "kernel": (lib().amwg_kernel_name(self.h) or b"").decode(),
                 "summation_order": lib().amwg_summation_order(self.h), "datasets": lib().amwg_num_datasets(self.h)}
+
+
+def dataset_quantiles_check(draws, D, probs, device=0):
+    """libamwg_selftest.so: the kernel of Sampler.dataset_quantiles on any array draws [rows][PR][C], D datasets of C / D columns each
+    -> array [D][PR][len(probs)] (amwg_dataset_quantiles_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    pr = np.ascontiguousarray(probs, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    out = np.empty((D, PR, pr.size))
+    L = selftest_lib()
+    if L.amwg_dataset_quantiles_check(device, _dp(dr), rows, PR, Cn, D, _dp(pr), pr.size, _dp(out)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
 
 
 def _group(samplers):

@@ -130,7 +130,7 @@ int amwg_fail(int code, const char *fmt, ...) {
 // a pooled summary over the chains of a dataset sampler would mix posteriors that have nothing to do with each other
 int amwg_refuse_pooled(const amwg_sampler *s, const char *call) {
   if (s && s->n_datasets > 1)
-    return amwg_fail(AMWG_EINVAL, "%s: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_moments / amwg_last_sample_dataset_diagnostics", call, s->n_datasets);
+    return amwg_fail(AMWG_EINVAL, "%s: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_moments / amwg_last_sample_dataset_diagnostics / amwg_last_sample_dataset_quantiles", call, s->n_datasets);
   return AMWG_OK;
 }
 

@@ -625,6 +625,28 @@ static napi_value Quantiles(napi_env env, napi_callback_info info) {
   return rc == AMWG_OK ? out : throw_amwg(env, rc);
 }
 
+/* datasetQuantiles(handle, Float64Array probs) -> {datasets, q}: q a Float64Array [datasets][recorded][n_probs] over the last sample() */
+static napi_value DatasetQuantiles(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t np = 0;
+  const double *probs = (const double *)typed_data(env, a[1], napi_float64_array, &np);
+  if (!probs || np < 1) { napi_throw_type_error(env, NULL, "amwg_napi.datasetQuantiles: probs must be a non-empty Float64Array"); return NULL; }
+  double *q = NULL;
+  napi_value v = new_f64(env, (size_t)amwg_num_datasets(s) * (size_t)amwg_num_recorded(s) * np, &q);
+  if (!v) return NULL;
+  int rc = amwg_last_sample_dataset_quantiles(s, probs, (int32_t)np, q);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "q", v);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  return o;
+}
+
 /* the shards of a multi-device sampler: JS array of handles -> C array (caller frees) */
 static amwg_sampler **unwrap_group(napi_env env, napi_value arr, uint32_t *n) {
   *n = 0;
@@ -827,7 +849,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

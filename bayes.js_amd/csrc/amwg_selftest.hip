@@ -1,6 +1,7 @@
 // amwg_selftest.hip -- the test-only entry points of include/amwg_selftest.h: the building blocks one by one, for the test suite.  Linked into
 // libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
 #include "../../include/amwg_selftest.h"
+#include "amwg_dataset_quantiles.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
@@ -100,6 +101,18 @@ int amwg_device_eval(int32_t device, int32_t op, int64_t n, const double *a, con
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
   return AMWG_OK;
+}
+
+int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *probs, int32_t n_probs, double *out) {
+  if (!draws || !probs || !out) return amwg_fail(AMWG_EINVAL, "amwg_dataset_quantiles_check: null argument");
+  TRYB(amwg_dataset_quantiles_shape("amwg_dataset_quantiles_check", rows, PR, C, D, n_probs));      // (bounds rows * C / D, and with it the bytes below unless PR * D is absurd)
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "amwg_dataset_quantiles_check: array too large");
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  return amwg_dataset_quantiles_launch("amwg_dataset_quantiles_check", dd.as<double>(), rows, PR, C, D, probs, n_probs, out, nullptr);
 }
 
 }  // extern "C"

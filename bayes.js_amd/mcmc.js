@@ -472,7 +472,7 @@ AmwgSampler.prototype._refusePooled = function (what) {
   if (!(this.options && this.options.datasets)) return;
   const N = native(), sh = this._shards.find((q) => q.datasets > 1);
   if (sh) N.moments(sh.handle);      // throws: amwg_last_sample_moments on a dataset sampler
-  throw 'AmwgSampler (MI355X): ' + what + '() pools all chains, and this sampler runs ' + this.n_datasets + ' datasets, a posterior each: use dataset_moments() / dataset_convergence()';
+  throw 'AmwgSampler (MI355X): ' + what + '() pools all chains, and this sampler runs ' + this.n_datasets + ' datasets, a posterior each: use dataset_moments() / dataset_convergence() / dataset_quantiles()';
 };
 
 // per-dataset summaries of the last sample(): an array of one object per dataset, each shaped like the result of moments() / convergence()
@@ -493,6 +493,22 @@ AmwgSampler.prototype._datasetSummary = function (call, k0, k1) {
 AmwgSampler.prototype.dataset_moments = function () { const N = native(); return this._datasetSummary((h) => N.datasetMoments(h), 'mean', 'sd'); };
 /** convergence() per dataset (options.datasets): [{name: {rhat, ess}}, ...]; needs >= 2 chains per dataset. */
 AmwgSampler.prototype.dataset_convergence = function () { const N = native(); return this._datasetSummary((h) => N.datasetConvergence(h), 'rhat', 'ess'); };
+
+/** quantiles(probs) per dataset (options.datasets): [{name: [[q...] per element]}, ...]; a radix select on the device over each dataset's chains x kept
+ *  draws, R's default (type 7) interpolation.  A dataset lives wholly on one shard: no collective. */
+AmwgSampler.prototype.dataset_quantiles = function (probs) {
+  const N = native(), pr = Float64Array.from(probs), out = [], PR = this.PR;
+  for (const sh of this._shards) {
+    const r = N.datasetQuantiles(sh.handle, pr);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = {}, row = (c) => Array.from(r.q.subarray((d * PR + c) * pr.length, (d * PR + c + 1) * pr.length));
+      for (const L of this._layout) o[L.name] = Array.from({ length: L.len }, (_, e) => row(L.base + e));
+      this.derived.forEach((name, k) => { o[name] = [row(this.P + k)]; });
+      out.push(o);
+    }
+  }
+  return out;
+};
 
 /** Per-chain starting points: f(chainIndex) -> state object shaped like sampler.state of one chain ({name: number | nested array}).
  *  The reference starts from the completed `init` (mcmc.js:954-957); many chains want over-dispersed starts. */

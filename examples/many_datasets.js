@@ -34,9 +34,11 @@ var sampler = new mcmc.AmwgSampler(params, log_post, null, { datasets: datasets,
 sampler.burn(1000);
 sampler.sample_on_device(200);
 var moments = sampler.dataset_moments(), conv = sampler.dataset_convergence();
+var quant = sampler.dataset_quantiles([0.025, 0.5, 0.975]);      // a 95 % credible interval and the median per dataset, selected on the device
 [0, 1, 128, 255].forEach(function (d) {
-  console.log('dataset %d (true mean %s): mean(mu) = %s  mean(sigma) = %s  Rhat(mu) = %s', d, (160 + 0.1 * d).toFixed(1),
-    moments[d].mu.mean[0].toFixed(2), moments[d].sigma.mean[0].toFixed(2), conv[d].mu.rhat[0].toFixed(4));
+  var q = quant[d].mu[0];
+  console.log('dataset %d (true mean %s): mean(mu) = %s  median(mu) = %s  95%% interval [%s, %s]  mean(sigma) = %s  Rhat(mu) = %s', d, (160 + 0.1 * d).toFixed(1),
+    moments[d].mu.mean[0].toFixed(2), q[1].toFixed(2), q[0].toFixed(2), q[2].toFixed(2), moments[d].sigma.mean[0].toFixed(2), conv[d].mu.rhat[0].toFixed(4));
 });
 console.log('kernel:', sampler.info().launch[0].kernel, ' datasets per launch:', sampler.info().launch[0].datasets);
 sampler.close();

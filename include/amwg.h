@@ -172,7 +172,7 @@ int amwg_create(const amwg_model_desc *model, const amwg_param_desc *params, int
  * AMWG_MODEL_NORMAL, AMWG_MODEL_BETA_BERN, AMWG_MODEL_POIS_GLM with every other option.  n_datasets == 1 is amwg_create(models, ...).
  * The pooled summaries (amwg_last_sample_moments / _diagnostics / _quantiles, amwg_group_moments / _diagnostics / _quantiles, amwg_comm_moments) return
  * AMWG_EINVAL on such a sampler -- a pooled mean over unrelated posteriors is a bug the caller did not mean to write --; the per-dataset ones are below.
- * Per-dataset quantiles (a segmented sort) are not provided. */
+ * Per-dataset quantiles are a radix select over each dataset's draws where they lie (amwg_last_sample_dataset_quantiles). */
 int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
                          const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
 /* Datasets of a sampler: 1 for every sampler not made by amwg_create_datasets with n_datasets > 1. */
@@ -182,6 +182,12 @@ int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd);
 /* amwg_last_sample_diagnostics per dataset (the same definitions over the dataset's chains; one workgroup per recorded value and dataset):
  * rhat[D][P], ess[D][P].  Needs >= 2 chains per dataset and >= 4 kept draws. */
 int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess);
+/* amwg_last_sample_quantiles per dataset: out[D][P + derived][n_probs].  R's default (type 7) rule over the dataset's chains x kept draws: h = (n - 1) q,
+ * x[floor h] + (h - floor h) (x[floor h + 1] - x[floor h]); a q outside [0, 1] or NaN gives NaN.  Nothing is gathered or sorted: one workgroup per (recorded
+ * value, dataset) selects the order statistics by radix, most significant digit first, and the result comes to the host in one copy.  Any n_probs >= 1 (the
+ * kernel runs once per 24 probabilities).  Works on an ordinary sampler too (D = 1: the pooled call's result).  AMWG_EINVAL: a null argument or n_probs < 1
+ * (before any device call), no sample() yet, more than 2^31 - 1 values per dataset and component, more than 65535 datasets. */
+int amwg_last_sample_dataset_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,

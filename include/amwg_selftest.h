@@ -30,6 +30,11 @@ int amwg_ld_device(int32_t device, int64_t n, const double *records, double *out
 int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_t m, const double *acc0, const double *l1, const double *l0,
                               double *out_fast_forward, double *out_term_by_term);
 
+/* the kernel of amwg_last_sample_dataset_quantiles on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each: out[D][PR][n_probs] (host).
+ * The arguments are checked before a device is opened. */
+int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D,
+                                 const double *probs, int32_t n_probs, double *out);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);
