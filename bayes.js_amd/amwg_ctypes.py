@@ -46,7 +46,7 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_create_datasets", "amwg_num_datasets", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+EXPORTS = ["amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
 SELFTEST_EXPORTS = ["amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
@@ -65,7 +65,9 @@ def lib():
                                   C.POINTER(Options), C.POINTER(vp)]
         L.amwg_create_datasets.argtypes = [C.POINTER(ModelDesc), i32, C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt),
                                            C.POINTER(Options), C.POINTER(vp)]
+        L.amwg_create_datasets_ragged.argtypes = L.amwg_create_datasets.argtypes
         L.amwg_num_datasets.argtypes = [vp]
+        L.amwg_dataset_n_obs.argtypes = [vp, pi32]
         L.amwg_last_sample_dataset_moments.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_diagnostics.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_quantiles.argtypes = [vp, pd, i32, pd]
@@ -179,11 +181,13 @@ class Sampler:
     comp_opts[]) for a closure translated by bayes.js_amd/translate.js (amwg_create_user)."""
 
     def __init__(self, spec, chains, seed, chain_offset=0, device=0, lanes_per_chain=0, block_threads=0,
-                 steps_per_launch=0, exact_division=0, group_local=0, full_evaluation=0, test_bound_shift=0, sufficient_statistics=0):
+                 steps_per_launch=0, exact_division=0, group_local=0, full_evaluation=0, test_bound_shift=0, sufficient_statistics=0, ragged=False):
         L = lib()
         keep = []
         specs = None
-        if isinstance(spec, (list, tuple)):      # one spec per dataset: amwg_create_datasets (the parameters, init and stepper options are those of the first)
+        # one spec per dataset: amwg_create_datasets, which insists on equal sizes, or with ragged=True amwg_create_datasets_ragged (the parameters, init and
+        # stepper options are those of the first)
+        if isinstance(spec, (list, tuple)):
             specs = list(spec)
             if not specs or any(q.get("user") is not None for q in specs):
                 raise AmwgError("a list of specs is one built-in family on several datasets: it must not be empty or hold translated closures")
@@ -263,7 +267,8 @@ class Sampler:
         op.sufficient_statistics = sufficient_statistics
         h = C.c_void_p()
         if specs is not None:
-            _check(L.amwg_create_datasets(mds, len(specs), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
+            create = L.amwg_create_datasets_ragged if ragged else L.amwg_create_datasets
+            _check(create(mds, len(specs), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
         elif user is None:
             _check(L.amwg_create(C.byref(md), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
         else:
@@ -352,6 +357,12 @@ class Sampler:
         m, s = np.empty(self.PR), np.empty(self.PR)
         _check(lib().amwg_last_sample_moments(self.h, _dp(m), _dp(s)))
         return m, s
+
+    def dataset_n_obs(self):
+        """-> list of the datasets' sizes (amwg_dataset_n_obs); an ordinary sampler: its one size"""
+        out = np.zeros(max(1, self.D), dtype=np.int32)
+        _check(lib().amwg_dataset_n_obs(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out.tolist()
 
     def dataset_moments(self):
         """-> mean, sd, arrays [datasets][P + derived]: moments() per dataset (amwg_last_sample_dataset_moments)"""

@@ -246,6 +246,11 @@ static int check_family_args(const amwg_model_desc *m, const amwg_param_desc *pa
   return amwg_fail(AMWG_EINVAL, "unknown model id %d", m->model);
 }
 
+// the constants that depend on a dataset's SIZE alone: the Poisson family's prior ld.unif(cp, 0, n - 1) (per dataset in a dataset sampler: DatasetConsts)
+static void size_constants(int n_obs, double *cp_upper, double *lunif_cp) {
+  *cp_upper = (double)(n_obs - 1);
+  *lunif_cp = log_v8(1 / (*cp_upper - 0.0));
+}
 // model constants, with the kernel's own log (same roundings as the reference expression trees)
 static void model_constants(const amwg_model_desc *m, const amwg_options *options, ModelConsts &mc) {
   mc.neg_half_log_2pi = -0.5 * log_v8(2 * kPi);
@@ -271,8 +276,7 @@ static void model_constants(const amwg_model_desc *m, const amwg_options *option
   const Reciprocal y0 = make_reciprocal(mc.den0), y1 = make_reciprocal(mc.den1);
   mc.y0_hi = y0.hi; mc.y0_lo = y0.lo; mc.den0_ok = (!options->exact_division && mid_range(mc.den0)) ? 1 : 0;
   mc.y1_hi = y1.hi; mc.y1_lo = y1.lo; mc.den1_ok = (!options->exact_division && mid_range(mc.den1)) ? 1 : 0;
-  mc.cp_upper = (double)(m->n_obs - 1);
-  mc.lunif_cp = log_v8(1 / (mc.cp_upper - 0.0));
+  size_constants(m->n_obs, &mc.cp_upper, &mc.lunif_cp);
   mc.exact_division = options->exact_division ? 1 : 0;
   mc.group_local = 0, mc.sufficient = 0;
   mc.suff_xbar_hi = mc.suff_xbar_lo = mc.suff_ss = 0.0;
@@ -313,15 +317,17 @@ static int group_local_setup(amwg_sampler *s, const amwg_model_desc *m, const am
   return AMWG_OK;
 }
 
-// A dataset sampler (amwg_create_datasets) keeps the arrays of its D datasets back to back at a fixed stride, one allocation per array: the stride of an
-// array of n elements (rounded up so that every dataset's copy starts on a 256-byte boundary, like an allocation of its own; D == 1: n, the ordinary sampler's
-// allocation).  `packed` receives the D copies; -> what to upload and how many elements.
-static size_t dataset_stride(size_t n, int D, size_t align) { return D > 1 ? (n + align - 1) / align * align : n; }
-template <class T, class Get>
-static int upload_datasets(amwg_sampler *s, int D, size_t n, size_t stride, Get get, T **dev) {      // get(d): dataset d's n elements on the host
-  if (D == 1) return upload(s, get(0), n, dev);
-  std::vector<T> packed(stride * (size_t)D, T(0));
-  for (int d = 0; d < D; ++d) { const T *src = get(d); for (size_t i = 0; i < n; ++i) packed[(size_t)d * stride + i] = src[i]; }
+// A dataset sampler (amwg_create_datasets, amwg_create_datasets_ragged) keeps the copies of its D datasets back to back, one allocation per array: dataset d's
+// len(d) elements begin at the element offset this records in consts[d].*off, every copy on a 256-byte boundary like an allocation of its own (the sizes may
+// differ, so these are running sums, not multiples of a stride).  D == 1: the ordinary sampler's allocation.  get(d): dataset d's elements on the host.
+template <class T, class Len, class Get>
+static int upload_datasets(amwg_sampler *s, int D, Len len, Get get, std::vector<DatasetConsts> &consts, int64_t DatasetConsts::*off, T **dev) {
+  if (D == 1) return upload(s, get(0), len(0), dev);
+  constexpr size_t align = 256 / sizeof(T);
+  size_t total = 0;
+  for (int d = 0; d < D; ++d) { consts[d].*off = (int64_t)total; total += (len(d) + align - 1) / align * align; }
+  std::vector<T> packed(total, T(0));
+  for (int d = 0; d < D; ++d) { const T *src = get(d); const size_t n = len(d); T *dst = packed.data() + (size_t)(consts[d].*off); for (size_t i = 0; i < n; ++i) dst[i] = src[i]; }
   return upload(s, packed.data(), packed.size(), dev);
 }
 
@@ -333,13 +339,12 @@ static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *models, in
   DataRef &d = s->d;
   for (int k = 0; k < D; ++k) {
     bool mid = true;
-    for (int i = 0; i < N; ++i) mid = mid && (models[k].x[i] == 0.0 || mid_range(std::fabs(models[k].x[i])));
+    for (int i = 0; i < models[k].n_obs; ++i) mid = mid && (models[k].x[i] == 0.0 || mid_range(std::fabs(models[k].x[i])));
     consts[k].data_mid_range = mid ? 1 : 0;
   }
   s->mc.data_mid_range = consts[0].data_mid_range;
   double *dx = nullptr;
-  s->ds_stride[0] = (int64_t)dataset_stride((size_t)N, D, 32);
-  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[0], [&](int k) { return models[k].x; }, &dx));
+  TRYB(upload_datasets(s, D, [&](int k) { return (size_t)models[k].n_obs; }, [&](int k) { return models[k].x; }, consts, &DatasetConsts::off_x, &dx));
   d.x = dx;
   if (m->model != AMWG_MODEL_HIER_NORMAL) return AMWG_OK;
   std::vector<uint8_t> gb((size_t)N);
@@ -361,13 +366,14 @@ static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *models, in
   d.K = gl.n_min;
   return AMWG_OK;
 }
-// Bernoulli family: the observations as bytes and as bits, and the tables of two_valued_sum -- per dataset, as is has_invalid
+// Bernoulli family: the observations as bytes and as bits, and the tables of two_valued_sum -- per dataset, in that dataset's own sizes, as is has_invalid
 static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *models, int D, std::vector<DatasetConsts> &consts) {
-  const int N = models[0].n_obs;
-  const size_t W = BetaBernModel::words(N), T = 6 * two_valued_words(N);
-  std::vector<std::vector<uint8_t>> xb((size_t)D, std::vector<uint8_t>((size_t)N));
-  std::vector<std::vector<uint32_t>> xw((size_t)D, std::vector<uint32_t>(W, 0u)), tab((size_t)D);
+  std::vector<std::vector<uint8_t>> xb((size_t)D);
+  std::vector<std::vector<uint32_t>> xw((size_t)D), tab((size_t)D);
   for (int k = 0; k < D; ++k) {
+    const int N = models[k].n_obs;
+    xb[k].assign((size_t)N, 0);
+    xw[k].assign(BetaBernModel::words(N), 0u);
     bool invalid = false;
     for (int i = 0; i < N; ++i) {
       const bool one = models[k].x[i] == 1;
@@ -377,30 +383,29 @@ static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *models,
     }
     consts[k].has_invalid = invalid ? 1 : 0;
     tab[k] = two_valued_tables(xb[k].data(), N);
-    if (tab[k].size() != T) return amwg_fail(AMWG_EINVAL, "internal: two_valued_tables of %zu words, expected %zu", tab[k].size(), T);
+    if (tab[k].size() != 6 * two_valued_words(N)) return amwg_fail(AMWG_EINVAL, "internal: two_valued_tables of %zu words, expected %zu", tab[k].size(), 6 * two_valued_words(N));
   }
   s->mc.has_invalid = consts[0].has_invalid;
-  s->ds_stride[3] = (int64_t)dataset_stride((size_t)N, D, 256);
-  s->ds_stride[4] = (int64_t)dataset_stride(W, D, 64);
-  s->ds_stride[5] = (int64_t)dataset_stride(T, D, 64);
   uint8_t *dxb = nullptr;
   uint32_t *dxw = nullptr, *dtab = nullptr;
-  TRYB(upload_datasets(s, D, T, (size_t)s->ds_stride[5], [&](int k) { return tab[k].data(); }, &dtab));
+  TRYB(upload_datasets(s, D, [&](int k) { return tab[k].size(); }, [&](int k) { return tab[k].data(); }, consts, &DatasetConsts::off_arr0, &dtab));
   s->d.arr[0] = dtab;
-  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[3], [&](int k) { return xb[k].data(); }, &dxb));
-  TRYB(upload_datasets(s, D, W, (size_t)s->ds_stride[4], [&](int k) { return xw[k].data(); }, &dxw));
+  TRYB(upload_datasets(s, D, [&](int k) { return xb[k].size(); }, [&](int k) { return xb[k].data(); }, consts, &DatasetConsts::off_xb, &dxb));
+  TRYB(upload_datasets(s, D, [&](int k) { return xw[k].size(); }, [&](int k) { return xw[k].data(); }, consts, &DatasetConsts::off_xw, &dxw));
   s->d.xb = dxb;
   s->d.xw = dxw;
   return AMWG_OK;
 }
-// Poisson family: the design matrix column-major, the counts, log(y_i!), and what the bounds of the certified pass are made of (PoisGlmModel::log_post_approx) --
-// per dataset
+// Poisson family: the design matrix column-major [7][n_d] (a dataset's column stride is its own size), the counts, log(y_i!), and what the bounds of the certified
+// pass are made of (PoisGlmModel::log_post_approx) -- per dataset
 static int upload_poisson_data(amwg_sampler *s, const amwg_model_desc *models, int D, std::vector<DatasetConsts> &consts) {
-  const int N = models[0].n_obs;
-  std::vector<std::vector<double>> lf((size_t)D, std::vector<double>((size_t)N)), Xt((size_t)D, std::vector<double>((size_t)N * 7));
+  std::vector<std::vector<double>> lf((size_t)D), Xt((size_t)D);
   for (int d = 0; d < D; ++d) {
     const amwg_model_desc *m = &models[d];
+    const int N = m->n_obs;
     DatasetConsts &mc = consts[d];
+    lf[d].assign((size_t)N, 0.0);
+    Xt[d].assign((size_t)N * 7, 0.0);
     for (int i = 0; i < N; ++i) lf[d][i] = m->y[i] < 0 ? (double)INFINITY : lfactorial_js(m->y[i]);
     for (int i = 0; i < N; ++i) for (int k = 0; k < 7; ++k) Xt[d][(size_t)k * N + i] = m->x[(size_t)i * 7 + k];   // row-major [N][7] -> column-major [7][N]
     for (int k = 0; k < 7; ++k) { double mx = 0; for (int i = 0; i < N; ++i) { const double v = std::fabs(m->x[(size_t)i * 7 + k]); mx = (v > mx || v != v) ? v : mx; } mc.glm_xmax[k] = mx; }
@@ -409,12 +414,10 @@ static int upload_poisson_data(amwg_sampler *s, const amwg_model_desc *models, i
   }
   for (int k = 0; k < 7; ++k) s->mc.glm_xmax[k] = consts[0].glm_xmax[k];
   s->mc.glm_sum_y = consts[0].glm_sum_y; s->mc.glm_sum_lf = consts[0].glm_sum_lf;
-  s->ds_stride[0] = (int64_t)dataset_stride((size_t)N * 7, D, 32);
-  s->ds_stride[1] = s->ds_stride[2] = (int64_t)dataset_stride((size_t)N, D, 32);
   double *dX = nullptr, *dy = nullptr, *dlf = nullptr;
-  TRYB(upload_datasets(s, D, (size_t)N * 7, (size_t)s->ds_stride[0], [&](int d) { return Xt[d].data(); }, &dX));
-  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[1], [&](int d) { return models[d].y; }, &dy));
-  TRYB(upload_datasets(s, D, (size_t)N, (size_t)s->ds_stride[2], [&](int d) { return lf[d].data(); }, &dlf));
+  TRYB(upload_datasets(s, D, [&](int d) { return Xt[d].size(); }, [&](int d) { return Xt[d].data(); }, consts, &DatasetConsts::off_x, &dX));
+  TRYB(upload_datasets(s, D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d) { return models[d].y; }, consts, &DatasetConsts::off_y, &dy));
+  TRYB(upload_datasets(s, D, [&](int d) { return lf[d].size(); }, [&](int d) { return lf[d].data(); }, consts, &DatasetConsts::off_lfact, &dlf));
   s->d.x = dX; s->d.y = dy; s->d.lfact = dlf;
   return AMWG_OK;
 }
@@ -515,13 +518,13 @@ static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *m) {
   return AMWG_OK;
 }
 
-// ---- amwg_create and amwg_create_datasets from here on: D datasets of one built-in family (D == 1: the ordinary sampler).  What depends on the data is computed
-// per dataset (DatasetConsts) and, for D > 1, travels to the kernels in a device table beside the arrays laid back to back (amwg_dataset.h).
+// ---- amwg_create, amwg_create_datasets and amwg_create_datasets_ragged from here on: D datasets of one built-in family, of any sizes (D == 1: the ordinary
+// sampler; equal sizes: the special case the second entry insists on).  What depends on the data or its size is computed per dataset (DatasetConsts) and, for D > 1, travels to the kernels in a device table beside the arrays laid back to back (amwg_dataset.h).
 static int create_builtin(const amwg_model_desc *models, int D, const amwg_param_desc *params, int32_t n_params, const double *init,
                           const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
   const amwg_model_desc *m = &models[0];
   if (n_params < 1 || n_params > kMaxIndex) return amwg_fail(AMWG_EINVAL, "amwg_create: %d named parameters (supported: 1..%d)", n_params, kMaxIndex);
-  if (m->n_obs < 0) return amwg_fail(AMWG_EINVAL, "amwg_create: n_obs < 0");
+  for (int d = 0; d < D; ++d) if (models[d].n_obs < 0) return amwg_fail(AMWG_EINVAL, "amwg_create: n_obs < 0");
   const FamilyRow *family = family_of(m->model);      // (an unknown model is reported by check_family_args, after the options and the layout)
   TRYB(check_options(options, family ? family->max_threads : 64));
   SamplerGuard guard(options, m->model);
@@ -535,7 +538,15 @@ static int create_builtin(const amwg_model_desc *models, int D, const amwg_param
   clk.mark("open device (HIP runtime)");
   model_constants(m, options, s->mc);
   std::vector<DatasetConsts> consts((size_t)D, DatasetConsts{});
-  for (DatasetConsts &k : consts) { k.data_mid_range = s->mc.data_mid_range; k.has_invalid = s->mc.has_invalid; }
+  s->ds_n_obs.resize((size_t)D);
+  int n_max = 0;
+  for (int d = 0; d < D; ++d) {
+    DatasetConsts &k = consts[d];
+    k.data_mid_range = s->mc.data_mid_range; k.has_invalid = s->mc.has_invalid;
+    k.n_obs = s->ds_n_obs[d] = models[d].n_obs;
+    size_constants(k.n_obs, &k.cp_upper, &k.lunif_cp);
+    n_max = k.n_obs > n_max ? k.n_obs : n_max;
+  }
   if (options->sufficient_statistics)
     for (int d = D - 1; d >= 0; --d) {      // (dataset 0 last: its numbers are the ones s->mc keeps)
       TRYB(sufficient_statistics(s, &models[d], options));
@@ -543,7 +554,7 @@ static int create_builtin(const amwg_model_desc *models, int D, const amwg_param
     }
   GlLayoutHost gl;
   if (options->group_local) TRYB(group_local_setup(s, m, params, n_params, options, &gl));
-  s->d.n_obs = m->n_obs; s->d.G = m->G; s->d.K = m->K;
+  s->d.n_obs = n_max; s->d.G = m->G; s->d.K = m->K;      // (D > 1: the LARGEST dataset's size -- a workgroup's own arrives through the table, amwg_dataset.h; the plan reads ds_n_obs)
   if (m->model == AMWG_MODEL_NORMAL || m->model == AMWG_MODEL_HIER_NORMAL) TRYB(upload_normal_data(s, models, D, gl, consts));
   else if (m->model == AMWG_MODEL_BETA_BERN) TRYB(upload_bernoulli_data(s, models, D, consts));
   else TRYB(upload_poisson_data(s, models, D, consts));
@@ -572,27 +583,39 @@ int amwg_create(const amwg_model_desc *m, const amwg_param_desc *params, int32_t
   return create_builtin(m, 1, params, n_params, init, comp_opts, options, out);
 }
 
-int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
-                         const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
-  if (!models || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: null argument");
-  if (n_datasets < 1) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: n_datasets must be >= 1, got %d", n_datasets);
+// what both dataset entries check before a device is opened; `ragged`: the sizes may differ
+static int create_datasets(const char *entry, bool ragged, const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                           const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  if (!models || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "%s: null argument", entry);
+  if (n_datasets < 1) return amwg_fail(AMWG_EINVAL, "%s: n_datasets must be >= 1, got %d", entry, n_datasets);
   if (n_datasets == 1) return amwg_create(models, params, n_params, init, comp_opts, options, out);
   if (options->chains % n_datasets != 0)
-    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: chains (%lld, the total) must be a multiple of n_datasets (%d)", (long long)options->chains, n_datasets);
+    return amwg_fail(AMWG_EINVAL, "%s: chains (%lld, the total) must be a multiple of n_datasets (%d)", entry, (long long)options->chains, n_datasets);
   for (int d = 1; d < n_datasets; ++d) {
-    if (models[d].model != models[0].model) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d is of model %d, dataset 0 of model %d (one family per sampler)", d, models[d].model, models[0].model);
-    if (models[d].n_obs != models[0].n_obs) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has n_obs = %d, dataset 0 has %d (ragged datasets are not supported)", d, models[d].n_obs, models[0].n_obs);
-    if (models[d].K != models[0].K || models[d].G != models[0].G) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has K = %d, G = %d, dataset 0 has K = %d, G = %d", d, models[d].K, models[d].G, models[0].K, models[0].G);
+    if (models[d].model != models[0].model) return amwg_fail(AMWG_EINVAL, "%s: dataset %d is of model %d, dataset 0 of model %d (one family per sampler)", entry, d, models[d].model, models[0].model);
+    if (!ragged && models[d].n_obs != models[0].n_obs)
+      return amwg_fail(AMWG_EINVAL, "%s: dataset %d has n_obs = %d, dataset 0 has %d (ragged datasets are not supported); datasets of unequal sizes: amwg_create_datasets_ragged", entry, d, models[d].n_obs, models[0].n_obs);
+    if (models[d].K != models[0].K || models[d].G != models[0].G) return amwg_fail(AMWG_EINVAL, "%s: dataset %d has K = %d, G = %d, dataset 0 has K = %d, G = %d", entry, d, models[d].K, models[d].G, models[0].K, models[0].G);
     for (int k = 0; k < 8; ++k)
       if (memcmp(&models[d].hyper[k], &models[0].hyper[k], sizeof(double)) != 0)
-        return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: dataset %d has hyper[%d] = %g, dataset 0 has %g (the hyper-parameters are shared)", d, k, models[d].hyper[k], models[0].hyper[k]);
+        return amwg_fail(AMWG_EINVAL, "%s: dataset %d has hyper[%d] = %g, dataset 0 has %g (the hyper-parameters are shared)", entry, d, k, models[d].hyper[k], models[0].hyper[k]);
   }
   if (models[0].model == AMWG_MODEL_HIER_NORMAL)
-    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: the hierarchical family is not supported (its launch plan depends on properties of the group labels, which differ between datasets)");
-  if (options->group_local) return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: group_local is an evaluation of the hierarchical family, which dataset samplers do not support");
+    return amwg_fail(AMWG_EINVAL, "%s: the hierarchical family is not supported (its launch plan depends on properties of the group labels, which differ between datasets)", entry);
+  if (options->group_local) return amwg_fail(AMWG_EINVAL, "%s: group_local is an evaluation of the hierarchical family, which dataset samplers do not support", entry);
   if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE)
-    return amwg_fail(AMWG_EINVAL, "amwg_create_datasets: AMWG_LANES_AUTOTUNE is not supported (the timing runs would have to search the geometries that serve whole datasets); give lanes_per_chain or leave it 0");
+    return amwg_fail(AMWG_EINVAL, "%s: AMWG_LANES_AUTOTUNE is not supported (the timing runs would have to search the geometries that serve whole datasets); give lanes_per_chain or leave it 0", entry);
   return create_builtin(models, n_datasets, params, n_params, init, comp_opts, options, out);
+}
+
+int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                         const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  return create_datasets("amwg_create_datasets", false, models, n_datasets, params, n_params, init, comp_opts, options, out);
+}
+
+int amwg_create_datasets_ragged(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                                const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  return create_datasets("amwg_create_datasets_ragged", true, models, n_datasets, params, n_params, init, comp_opts, options, out);
 }
 
 int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, int32_t n_params, const double *init,

@@ -8,6 +8,10 @@
 // wave_scratch_of and the Philox key (seed, chain_offset + c) are those of an ordinary sampler, which is why dataset d's chains equal the chains of an
 // ordinary sampler on dataset d with chain_offset = d * cpd, bit for bit (tests/test_gpu_datasets.py).
 //
+// The datasets need not have one size (amwg_create_datasets_ragged): n_obs is one more per-dataset constant.  The stepper state lies behind the data in
+// LDS, so its offset then differs between workgroups, which is harmless; the launch's dynamic LDS covers the largest layout (amwg_plan.hip lds_of).
+// tests/test_gpu_ragged_datasets.py holds the same parity statement for unequal sizes.
+//
 // StepArgs stays the kernels' FIRST parameter and keeps its size: cold_args() (amwg_kernel.h) reads it through the kernel-argument pointer, and what is
 // read that way -- the per-chain arrays, the draws, the hyper-parameters of the Normal prior -- is the same for every dataset.
 #pragma once
@@ -15,18 +19,21 @@
 
 namespace amwg {
 
-// what the host computes per dataset instead of once (amwg_create.hip); the rest of ModelConsts follows from the hyper-parameters, which all datasets share
+// what the host computes per dataset instead of once (amwg_create.hip); the rest of ModelConsts follows from the hyper-parameters, which all datasets share.
+// Datasets may differ in SIZE (amwg_create_datasets_ragged): n_obs and what is formed from it -- the Poisson family's prior ld.unif(cp, 0, n - 1) -- are
+// per-dataset constants like the others, and so is the place of the dataset's copy inside each of the six arrays.
 struct DatasetConsts {
-  int32_t data_mid_range, has_invalid;
+  int32_t data_mid_range, has_invalid, n_obs, reserved;
+  double cp_upper, lunif_cp;
   double glm_xmax[7], glm_sum_y, glm_sum_lf;
   double suff_xbar_hi, suff_xbar_lo, suff_ss;
+  // the datasets' copies lie back to back, one allocation per array, each copy starting on a 256-byte boundary: dataset d's begins at base + off_* (in ELEMENTS
+  // of the array's type; 0 for an array the family does not have).  Offsets, not a stride: a dataset of 10^6 beside a thousand of 10^2 costs its own size once.
+  int64_t off_x, off_y, off_lfact, off_xb, off_xw, off_arr0;      // (arr[0]: the beta-Bernoulli family's tables of two_valued_sum, 32-bit words)
 };
 
-// The datasets' arrays lie back to back at a fixed stride, one allocation per array: dataset d's begin at base + d * stride (strides in ELEMENTS of the
-// array's type; 0 for an array the family does not have).
 struct DatasetArgs {
   int32_t blocks_per_dataset, n_datasets;
-  int64_t stride_x, stride_y, stride_lfact, stride_xb, stride_xw, stride_arr0;      // (arr[0]: the beta-Bernoulli family's tables of two_valued_sum, 32-bit words)
   const DatasetConsts *consts;                                                      // [n_datasets], device memory
 };
 
@@ -38,15 +45,18 @@ __device__ __forceinline__ void dataset_view(StepArgs &v, const DatasetArgs &ds)
 #else
   const int64_t d = 0;
 #endif
-  v.d.x += d * ds.stride_x;
-  v.d.y += d * ds.stride_y;
-  v.d.lfact += d * ds.stride_lfact;
-  v.d.xb += d * ds.stride_xb;
-  v.d.xw += d * ds.stride_xw;
-  v.d.arr[0] = static_cast<const uint32_t *>(v.d.arr[0]) + d * ds.stride_arr0;
   const DatasetConsts &k = ds.consts[d];      // (a uniform address: scalar loads)
+  v.d.n_obs = k.n_obs;                        // (wave-uniform, from a scalar load: log_post's fresh_uniform keeps it in a scalar register)
+  v.d.x += k.off_x;
+  v.d.y += k.off_y;
+  v.d.lfact += k.off_lfact;
+  v.d.xb += k.off_xb;
+  v.d.xw += k.off_xw;
+  v.d.arr[0] = static_cast<const uint32_t *>(v.d.arr[0]) + k.off_arr0;
   v.mc.data_mid_range = k.data_mid_range;
   v.mc.has_invalid = k.has_invalid;
+  v.mc.cp_upper = k.cp_upper;
+  v.mc.lunif_cp = k.lunif_cp;
 #pragma unroll
   for (int j = 0; j < 7; ++j) v.mc.glm_xmax[j] = k.glm_xmax[j];
   v.mc.glm_sum_y = k.glm_sum_y;

@@ -149,6 +149,12 @@ double amwg_uniform(uint64_t seed, uint64_t chain, uint64_t index) {
 }
 
 int amwg_num_datasets(const amwg_sampler *s) { return s ? s->n_datasets : 0; }
+int amwg_dataset_n_obs(const amwg_sampler *s, int32_t *n_obs) {
+  if (!s || !n_obs) return amwg_fail(AMWG_EINVAL, "amwg_dataset_n_obs: null argument");
+  if (s->ds_n_obs.size() != (size_t)s->n_datasets) { n_obs[0] = s->d.n_obs; return AMWG_OK; }      // (a translated closure: one dataset, whose arrays carry their own lengths -- 0)
+  for (int d = 0; d < s->n_datasets; ++d) n_obs[d] = s->ds_n_obs[d];
+  return AMWG_OK;
+}
 
 int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: null argument");

@@ -230,8 +230,9 @@ static napi_value Create(napi_env env, napi_callback_info info) {
 }
 
 /* createDatasets(models[], params[], init Float64Array, compOpts[], options) -> external handle: one built-in family on several datasets
- * (amwg_create_datasets; options.chains is the total) */
-static napi_value CreateDatasets(napi_env env, napi_callback_info info) {
+ * (amwg_create_datasets; options.chains is the total); createDatasetsRagged: the same, the datasets' n_obs free to differ (amwg_create_datasets_ragged) */
+typedef int (*create_datasets_fn)(const amwg_model_desc *, int32_t, const amwg_param_desc *, int32_t, const double *, const amwg_comp_opt *, const amwg_options *, amwg_sampler **);
+static napi_value create_datasets_with(napi_env env, napi_callback_info info, create_datasets_fn create) {
   napi_value a[5];
   if (!get_args(env, info, 5, a)) return NULL;
   uint32_t n_models = 0;
@@ -248,13 +249,15 @@ static napi_value CreateDatasets(napi_env env, napi_callback_info info) {
   amwg_param_desc *pd; amwg_comp_opt *co; uint32_t n_params; const double *init; amwg_options op;
   if (!parse_common(env, a, &pd, &co, &n_params, &init, &op)) { free(md); return NULL; }
   amwg_sampler *s = NULL;
-  int rc = amwg_create_datasets(md, (int32_t)n_models, pd, (int32_t)n_params, init, co, &op, &s);
+  int rc = create(md, (int32_t)n_models, pd, (int32_t)n_params, init, co, &op, &s);
   free(md);
   free(pd);
   free(co);
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   return wrap_sampler(env, s);
 }
+static napi_value CreateDatasets(napi_env env, napi_callback_info info) { return create_datasets_with(env, info, amwg_create_datasets); }
+static napi_value CreateDatasetsRagged(napi_env env, napi_callback_info info) { return create_datasets_with(env, info, amwg_create_datasets_ragged); }
 
 /* datasetMoments(handle) -> {mean, sd}, datasetConvergence(handle) -> {rhat, ess}: Float64Arrays [datasets][recorded] over the last sample() */
 static napi_value dataset_summary(napi_env env, napi_callback_info info, int (*fn)(amwg_sampler *, double *, double *), const char *k0, const char *k1) {
@@ -849,7 +852,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

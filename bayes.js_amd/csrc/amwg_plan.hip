@@ -133,22 +133,37 @@ static bool row_layout(const amwg_sampler *s, const LaunchPlan &p) {
   return p.variant == Variant::HierSweep || p.variant == Variant::HierSweepCert || (s->user && p.pad > 0);
 }
 
-// LDS bytes of a workgroup of the plan: the data its variant stages, then the stepper state of `cpb` chains (0: block / lanes).  cpb < block / lanes
+// LDS bytes of a workgroup of the plan on data of n_obs observations: the data its variant stages, then the stepper state of `cpb` chains (0: block / lanes).  cpb < block / lanes
 // (one-wavefront workgroups only) is the fallback for models whose per-chain state is so large that 64 / G copies do not fit: the spare lane groups
 // replicate the last chain.
-static uint32_t lds_of(const amwg_sampler *s, const LaunchPlan &p, int cpb = 0) {
+static uint32_t lds_of_size(const amwg_sampler *s, const LaunchPlan &p, int cpb, int n_obs) {
   const int G = p.lanes, bt = p.block;
   size_t data = 0;
   switch (p.variant) {
     case Variant::GroupLocal: data = HierGlModel::gl_lds_bytes(p.pad, bt / 64); break;
     case Variant::HierSweep: case Variant::HierSweepCert: data = HierNormalModel::rows_lds_bytes(p.pad, bt / 64, s->d.G); break;
     case Variant::Step: case Variant::StepCert:
-      data = (s->model == AMWG_MODEL_NORMAL && G == 1) ? (p.pad ? NormalModel::one_lane_tile_bytes(s->d.n_obs) : 0) : family_of(s->model)->lds_bytes(s->d.n_obs, s->d.G, G);
+      data = (s->model == AMWG_MODEL_NORMAL && G == 1) ? (p.pad ? NormalModel::one_lane_tile_bytes(n_obs) : 0) : family_of(s->model)->lds_bytes(n_obs, s->d.G, G);
       break;
     default:      // a translated closure: its row plan, else the translator's figure
       data = p.pad ? HierNormalModel::rows_lds_bytes(p.pad, bt / 64, s->user_rows_groups) : (size_t)(G == 1 ? s->user_lds_one_lane : s->user_lds);
   }
   return G > 64 ? lds_layout(data, s->P, G / 64, s->pl.max_top, s->n_params, true).total : lds_layout(data, s->P, cpb ? cpb : bt / G, s->pl.max_top, s->n_params).total;
+}
+
+// A dataset sampler whose sizes differ (amwg_create_datasets_ragged): every workgroup lays its LDS out for ITS dataset (amwg_kernel.h DataBytesOf), the launch's
+// dynamic LDS has to cover the largest of those layouts -- the maximum over the sizes, not the layout of the largest size: the one-lane tiles of the Normal and
+// the Bernoulli family are dropped beyond a limit, so the bytes are not monotone in n_obs.
+static uint32_t lds_of(const amwg_sampler *s, const LaunchPlan &p, int cpb = 0) {
+  if (s->n_datasets <= 1) return lds_of_size(s, p, cpb, s->d.n_obs);
+  uint32_t most = 0;
+  int last = -1;
+  for (int n : s->ds_n_obs) {      // (a run of equal sizes is priced once: the common case is all of them equal)
+    if (n == last) continue;
+    most = std::max(most, lds_of_size(s, p, cpb, n));
+    last = n;
+  }
+  return most;
 }
 
 // Geometry.  For every lanes-per-chain G take the largest workgroup that still gives every CU a workgroup (more waves
@@ -160,10 +175,18 @@ static uint32_t lds_of(const amwg_sampler *s, const LaunchPlan &p, int cpb = 0) 
 // G wins, ties go to the smaller G.  The choice depends only on the model, the data size and the chain count, so a
 // given sampler configuration always gets the same G (the lane count fixes the summation order, hence the draws).
 // W is priced for the kernel G lanes would run in 256-thread workgroups with 160 KB of LDS, whatever the device.
+// A dataset sampler has ONE geometry (the lanes fix the summation order); LDS is fitted with its largest dataset (lds_of), the work priced with the mean size
+// ceil(sum n_d / D): the launch's work is the sum over the datasets.  Still a function of (model, sizes, chains) alone.
+static int priced_n_obs(const amwg_sampler *s) {
+  if (s->n_datasets <= 1) return s->d.n_obs;
+  int64_t sum = 0;
+  for (int n : s->ds_n_obs) sum += n;
+  return (int)((sum + s->n_datasets - 1) / s->n_datasets);
+}
 static int log2_of(int lanes) { int lg = 0; for (int g = lanes; g > 1; g >>= 1) ++lg; return lg; }      // (lane counts are powers of two)
 static double model_work(const amwg_sampler *s, int G) {
   const LaunchPlan q = variant_for(s, G, 256, (size_t)160 * 1024);
-  const double N = (double)s->d.n_obs;
+  const double N = (double)priced_n_obs(s);
   switch (s->model) {
     // (one lane per chain: accept tests are decided from the certified pass -- two operations per observation -- unless the caller asked for the expression in every update)
     case AMWG_MODEL_NORMAL: return q.variant == Variant::StepCert ? (s->opt.sufficient_statistics ? 40.0 : 2.6 * N) : 9.0 * N;
@@ -236,10 +259,12 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
   const int max_bt = s->user ? s->user_max_threads : family_of(s->model)->max_threads;
   // a dataset sampler: a workgroup serves ONE dataset, so the chains per workgroup divide the chains per dataset -- only such geometries are searched
   const int64_t cpd = chains_per_dataset(s);
+  bool lds_short = false;      // (a dataset sampler: some geometry that serves whole datasets was given up for LDS alone)
   auto fits = [&](int bt, int G) {
     if (bt > max_bt || bt % G != 0) return false;
     if (cpd && cpd % chains_per_workgroup(G, bt) != 0) return false;
     const LaunchPlan p = variant_for(s, G, bt, max_lds);
+    if (cpd && lds_of(s, p) > max_lds) lds_short = true;
     // (the sweep kernels -- row layout, 64 lanes per chain -- keep the window stream and the sweep's per-lane values in registers: compiled for at most 512 threads,
     // where a lane has 256 of them; with the 128 of a 1024-thread workgroup the hierarchical family's ran from scratch memory, five times slower)
     if (lds_of(s, p) > max_lds || (bt > 512 && row_layout(s, variant_for(s, G, 512, max_lds)))) return false;
@@ -309,6 +334,12 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
   // (tested), the doubles are those of the G-lane order.  Unless the caller asked for a lane count (or for AMWG_LANES_FASTEST),
   // take one lane per chain whenever the model prices it within 12 % of the cheapest geometry.
   if (lanes == 0 && best.lanes > 1 && cost1 > 0 && cost1 <= 1.12 * best_cost) best = one;
+  if (!best.lanes && cpd && lds_short) {      // (s->d.n_obs is the largest size: name the dataset that has it)
+    int d_max = 0;
+    for (int d = 1; d < s->n_datasets; ++d) if (s->ds_n_obs[d] > s->ds_n_obs[d_max]) d_max = d;
+    return amwg_fail(AMWG_EINVAL, "no launch geometry fits dataset %d, the largest (n_obs = %d): every workgroup is given the LDS of the largest dataset, and with lanes %d (0 = any), block %d (0 = any) "
+                     "that is more than %zu bytes", d_max, s->ds_n_obs[d_max], lanes, o.block_threads, max_lds);
+  }
   if (!best.lanes && cpd)
     return amwg_fail(AMWG_EINVAL, "no launch geometry serves whole datasets: the chains of a workgroup (block_threads / lanes_per_chain, or 1 for a chain on several wavefronts) must divide "
                      "cpd = %lld chains per dataset; asked for lanes %d (0 = any), block %d (0 = any), %zu bytes of LDS", (long long)cpd, lanes, o.block_threads, max_lds);

@@ -88,8 +88,6 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
       return amwg_fail(AMWG_EINVAL, "internal: %d workgroups for %d datasets of %d workgroups each", p.grid, s->n_datasets, s->ds_blocks_per_dataset);
     ds.blocks_per_dataset = s->ds_blocks_per_dataset;
     ds.n_datasets = s->n_datasets;
-    ds.stride_x = s->ds_stride[0]; ds.stride_y = s->ds_stride[1]; ds.stride_lfact = s->ds_stride[2];
-    ds.stride_xb = s->ds_stride[3]; ds.stride_xw = s->ds_stride[4]; ds.stride_arr0 = s->ds_stride[5];
     ds.consts = s->d_ds_consts;
   }
   // (a 0-step finalize launch on chains that have stepped -- amwg_chain_diag asking for the expression's value after a certified kernel ran -- is not "the latest call":

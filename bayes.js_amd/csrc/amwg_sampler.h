@@ -50,7 +50,7 @@ struct amwg_sampler {
   // many datasets in one sampler (amwg_create_datasets; amwg_dataset.h): D > 1 datasets of cpd = C / D chains each, the kernel's second argument as far as it
   // is fixed at construction (blocks_per_dataset follows the plan: adopt_plan), and the twin that takes it
   int n_datasets = 1;
-  int64_t ds_stride[6] = {0, 0, 0, 0, 0, 0};      // elements: x, y, lfact, xb, xw, arr[0]
+  std::vector<int32_t> ds_n_obs;                  // n_obs of every dataset (a built-in family; D == 1: the one size).  With D > 1, d.n_obs is the LARGEST of them
   amwg::DatasetConsts *d_ds_consts = nullptr;
   int ds_blocks_per_dataset = 0;
   dataset_kernel_t ds_kernel = nullptr;

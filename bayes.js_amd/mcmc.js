@@ -184,7 +184,8 @@ function AmwgSampler(params, log_post, data, options) {
   this.thin(opt('thin', 1));
   this.monitor(opt('monitor', null));
   this.options = options;
-  // options.datasets: the same model on many datasets, a posterior per dataset, in ONE sampler (amwg_create_datasets).  An array of `data` objects in place
+  // options.datasets: the same model on many datasets, a posterior per dataset, in ONE sampler (amwg_create_datasets; datasets of unequal sizes:
+  // amwg_create_datasets_ragged, chosen here from the sizes -- there is nothing for the caller to say).  An array of `data` objects in place
   // of the data argument; options.chains stays the total, dataset d owns the chains [d * cpd, (d + 1) * cpd), cpd = chains / datasets.length
   const datasets = opt('datasets', null);
   if (datasets !== null) {
@@ -263,6 +264,7 @@ function AmwgSampler(params, log_post, data, options) {
     if (this.chains % datasets.length !== 0) throw 'AmwgSampler (MI355X): options.chains (' + this.chains + ', the total) must be a multiple of the ' + datasets.length + ' datasets';
     dsDescs = datasets.map((d) => buildModelDesc(recog, d, this.params));
     this.chains_per_dataset = this.chains / datasets.length;
+    this.dataset_n_obs = dsDescs.map((d) => d.n_obs);
   } else if (recog) desc = buildModelDesc(recog, data, this.params);
   else {
     const tr = translator.translate(log_post, translatedParams, data, { constants: options.constants, helpers: options.helpers,
@@ -284,8 +286,11 @@ function AmwgSampler(params, log_post, data, options) {
   let lanes = opt('lanes_per_chain', 0);
   for (let r = 0; r < D; r++) {
     const nUnits = per + (r < rem ? 1 : 0), count = nUnits * unit;
-    const create = user ? N.createUser : (dsDescs ? N.createDatasets : N.create);
-    const handle = create(user || (dsDescs ? dsDescs.slice(firstDataset, firstDataset + nUnits) : desc), descs, Float64Array.from(init), compOpts, {
+    // (a shard of a dataset sampler is a dataset sampler over its slice: ragged where the sizes of ITS slice differ, else the entry that insists on equal sizes)
+    const slice = dsDescs ? dsDescs.slice(firstDataset, firstDataset + nUnits) : null;
+    const unequal = slice !== null && slice.some((d) => d.n_obs !== slice[0].n_obs);
+    const create = user ? N.createUser : (dsDescs ? (unequal ? N.createDatasetsRagged : N.createDatasets) : N.create);
+    const handle = create(user || (dsDescs ? slice : desc), descs, Float64Array.from(init), compOpts, {
       chains: count, seed: this.seed, chain_offset: opt('chain_offset', 0) + offset, device: devices[r],
       lanes_per_chain: lanes, block_threads: opt('block_threads', 0),
       steps_per_launch: opt('steps_per_launch', 0), exact_division: opt('exact_division', 0), group_local: opt('group_local', 0) ? 1 : 0, full_evaluation: Number(opt('full_evaluation', 0)) | 0, test_bound_shift: Number(opt('test_bound_shift', 0)) | 0,
@@ -374,6 +379,8 @@ AmwgSampler.prototype.sample = function (n_iterations) {
 AmwgSampler.prototype._drawLayout = function (kept, L) {
   const layout = { kept, len: L.len, chains: this.chains, dim: L.dim };
   if (this.options && this.options.datasets) { layout.datasets = this.n_datasets; layout.chains_per_dataset = this.chains_per_dataset; }
+  // (the datasets' sizes, not enumerable: a layout of equal sizes lists and compares as it always did)
+  if (this.options && this.options.datasets) Object.defineProperty(layout, 'n_obs', { value: this.dataset_n_obs.slice(), enumerable: false });
   return layout;
 };
 
