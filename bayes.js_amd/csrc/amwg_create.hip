@@ -246,12 +246,14 @@ static int check_family_args(const amwg_model_desc *m, const amwg_param_desc *pa
   return amwg_fail(AMWG_EINVAL, "unknown model id %d", m->model);
 }
 
-// the constants that depend on a dataset's SIZE alone: the Poisson family's prior ld.unif(cp, 0, n - 1) (per dataset in a dataset sampler: DatasetConsts)
-static void size_constants(int n_obs, double *cp_upper, double *lunif_cp) {
-  *cp_upper = (double)(n_obs - 1);
-  *lunif_cp = log_v8(1 / (*cp_upper - 0.0));
+// the constants that depend on a dataset's SIZE alone: the Poisson family's prior ld.unif(cp, 0, n - 1)
+static void size_constants(int n_obs, DatasetConsts &k) {
+  k.n_obs = n_obs;
+  k.cp_upper = (double)(n_obs - 1);
+  k.lunif_cp = log_v8(1 / (k.cp_upper - 0.0));
 }
-// model constants, with the kernel's own log (same roundings as the reference expression trees)
+// the model constants that follow from the hyper-parameters and the options, with the kernel's own log (same roundings as the reference expression trees).
+// What follows from a dataset's data or size is not formed here: DatasetConsts (create_builtin).
 static void model_constants(const amwg_model_desc *m, const amwg_options *options, ModelConsts &mc) {
   mc.neg_half_log_2pi = -0.5 * log_v8(2 * kPi);
   const double *h = m->hyper;
@@ -276,29 +278,28 @@ static void model_constants(const amwg_model_desc *m, const amwg_options *option
   const Reciprocal y0 = make_reciprocal(mc.den0), y1 = make_reciprocal(mc.den1);
   mc.y0_hi = y0.hi; mc.y0_lo = y0.lo; mc.den0_ok = (!options->exact_division && mid_range(mc.den0)) ? 1 : 0;
   mc.y1_hi = y1.hi; mc.y1_lo = y1.lo; mc.den1_ok = (!options->exact_division && mid_range(mc.den1)) ? 1 : 0;
-  size_constants(m->n_obs, &mc.cp_upper, &mc.lunif_cp);
   mc.exact_division = options->exact_division ? 1 : 0;
   mc.group_local = 0, mc.sufficient = 0;
-  mc.suff_xbar_hi = mc.suff_xbar_lo = mc.suff_ss = 0.0;
-  mc.data_mid_range = 1;      // (the Normal and hierarchical families look at their observations: upload_normal_data)
 }
 
 // amwg_options::sufficient_statistics: the two sufficient statistics of the Normal likelihood, in quad precision -- xbar as a double-double (its error must stay
 // far below an ulp of xbar - mu when mu sits next to the data: 2^-106 |xbar|), SS = sum (x_i - xbar)^2 rounded once
-static int sufficient_statistics(amwg_sampler *s, const amwg_model_desc *m, const amwg_options *options) {
+static void sufficient_statistics(const double *x, int N, DatasetConsts &k) {
+  __float128 sum = 0;
+  for (int i = 0; i < N; ++i) sum += (__float128)x[i];
+  const __float128 xbar = N > 0 ? sum / (__float128)N : (__float128)0;
+  __float128 ss = 0;
+  for (int i = 0; i < N; ++i) { const __float128 t = (__float128)x[i] - xbar; ss += t * t; }
+  k.suff_xbar_hi = (double)xbar;
+  k.suff_xbar_lo = (double)(xbar - (__float128)k.suff_xbar_hi);
+  k.suff_ss = (double)ss;
+}
+// what the option asks of the call, and what it sets for the sampler: the one-lane certified kernel, told to read the statistics
+static int use_sufficient_statistics(amwg_sampler *s, const amwg_model_desc *m, const amwg_options *options) {
   if (m->model != AMWG_MODEL_NORMAL) return amwg_fail(AMWG_EINVAL, "sufficient_statistics: only the Normal family has a pass-free certified value");
   // (AMWG_LANES_AUTOTUNE would time -- and could keep -- a multi-lane kernel, which never reads mc.sufficient; AMWG_LANES_FASTEST is taken as 1 below)
   if (options->lanes_per_chain > 1 || options->lanes_per_chain == AMWG_LANES_AUTOTUNE)
     return amwg_fail(AMWG_EINVAL, "sufficient_statistics decides from the one-lane certified kernel: lanes_per_chain must be 0, 1 or AMWG_LANES_FASTEST, got %d", options->lanes_per_chain);
-  const int N = m->n_obs;
-  __float128 sum = 0;
-  for (int i = 0; i < N; ++i) sum += (__float128)m->x[i];
-  const __float128 xbar = N > 0 ? sum / (__float128)N : (__float128)0;
-  __float128 ss = 0;
-  for (int i = 0; i < N; ++i) { const __float128 t = (__float128)m->x[i] - xbar; ss += t * t; }
-  s->mc.suff_xbar_hi = (double)xbar;
-  s->mc.suff_xbar_lo = (double)(xbar - (__float128)s->mc.suff_xbar_hi);
-  s->mc.suff_ss = (double)ss;
   s->mc.sufficient = 1;
   s->opt.lanes_per_chain = 1;
   return AMWG_OK;
@@ -342,7 +343,6 @@ static int upload_normal_data(amwg_sampler *s, const amwg_model_desc *models, in
     for (int i = 0; i < models[k].n_obs; ++i) mid = mid && (models[k].x[i] == 0.0 || mid_range(std::fabs(models[k].x[i])));
     consts[k].data_mid_range = mid ? 1 : 0;
   }
-  s->mc.data_mid_range = consts[0].data_mid_range;
   double *dx = nullptr;
   TRYB(upload_datasets(s, D, [&](int k) { return (size_t)models[k].n_obs; }, [&](int k) { return models[k].x; }, consts, &DatasetConsts::off_x, &dx));
   d.x = dx;
@@ -385,7 +385,6 @@ static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *models,
     tab[k] = two_valued_tables(xb[k].data(), N);
     if (tab[k].size() != 6 * two_valued_words(N)) return amwg_fail(AMWG_EINVAL, "internal: two_valued_tables of %zu words, expected %zu", tab[k].size(), 6 * two_valued_words(N));
   }
-  s->mc.has_invalid = consts[0].has_invalid;
   uint8_t *dxb = nullptr;
   uint32_t *dxw = nullptr, *dtab = nullptr;
   TRYB(upload_datasets(s, D, [&](int k) { return tab[k].size(); }, [&](int k) { return tab[k].data(); }, consts, &DatasetConsts::off_arr0, &dtab));
@@ -412,8 +411,6 @@ static int upload_poisson_data(amwg_sampler *s, const amwg_model_desc *models, i
     mc.glm_sum_y = 0; mc.glm_sum_lf = 0;
     for (int i = 0; i < N; ++i) { mc.glm_sum_y += std::fabs(m->y[i]); mc.glm_sum_lf += std::fabs(lf[d][i]); }
   }
-  for (int k = 0; k < 7; ++k) s->mc.glm_xmax[k] = consts[0].glm_xmax[k];
-  s->mc.glm_sum_y = consts[0].glm_sum_y; s->mc.glm_sum_lf = consts[0].glm_sum_lf;
   double *dX = nullptr, *dy = nullptr, *dlf = nullptr;
   TRYB(upload_datasets(s, D, [&](int d) { return Xt[d].size(); }, [&](int d) { return Xt[d].data(); }, consts, &DatasetConsts::off_x, &dX));
   TRYB(upload_datasets(s, D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d) { return models[d].y; }, consts, &DatasetConsts::off_y, &dy));
@@ -519,7 +516,9 @@ static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *m) {
 }
 
 // ---- amwg_create, amwg_create_datasets and amwg_create_datasets_ragged from here on: D datasets of one built-in family, of any sizes (D == 1: the ordinary
-// sampler; equal sizes: the special case the second entry insists on).  What depends on the data or its size is computed per dataset (DatasetConsts) and, for D > 1, travels to the kernels in a device table beside the arrays laid back to back (amwg_dataset.h).
+// sampler; equal sizes: the special case the second entry insists on).  What depends on ONE dataset's data or size is written into that dataset's DatasetConsts and
+// nowhere else.  From there it goes one way: dataset 0's into the sampler's own ModelConsts (dataset_constants, amwg_dataset.h -- what an ordinary sampler's kernel
+// reads), and for D > 1 the whole table to the device, beside the arrays laid back to back, where every workgroup takes its dataset's row (dataset_view).
 static int create_builtin(const amwg_model_desc *models, int D, const amwg_param_desc *params, int32_t n_params, const double *init,
                           const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
   const amwg_model_desc *m = &models[0];
@@ -541,23 +540,22 @@ static int create_builtin(const amwg_model_desc *models, int D, const amwg_param
   s->ds_n_obs.resize((size_t)D);
   int n_max = 0;
   for (int d = 0; d < D; ++d) {
-    DatasetConsts &k = consts[d];
-    k.data_mid_range = s->mc.data_mid_range; k.has_invalid = s->mc.has_invalid;
-    k.n_obs = s->ds_n_obs[d] = models[d].n_obs;
-    size_constants(k.n_obs, &k.cp_upper, &k.lunif_cp);
-    n_max = k.n_obs > n_max ? k.n_obs : n_max;
+    consts[d].data_mid_range = 1;      // (the Normal and hierarchical families look at their observations: upload_normal_data)
+    size_constants(models[d].n_obs, consts[d]);
+    s->ds_n_obs[d] = models[d].n_obs;
+    n_max = models[d].n_obs > n_max ? models[d].n_obs : n_max;
   }
-  if (options->sufficient_statistics)
-    for (int d = D - 1; d >= 0; --d) {      // (dataset 0 last: its numbers are the ones s->mc keeps)
-      TRYB(sufficient_statistics(s, &models[d], options));
-      consts[d].suff_xbar_hi = s->mc.suff_xbar_hi; consts[d].suff_xbar_lo = s->mc.suff_xbar_lo; consts[d].suff_ss = s->mc.suff_ss;
-    }
+  if (options->sufficient_statistics) {
+    TRYB(use_sufficient_statistics(s, m, options));
+    for (int d = 0; d < D; ++d) sufficient_statistics(models[d].x, models[d].n_obs, consts[d]);
+  }
   GlLayoutHost gl;
   if (options->group_local) TRYB(group_local_setup(s, m, params, n_params, options, &gl));
   s->d.n_obs = n_max; s->d.G = m->G; s->d.K = m->K;      // (D > 1: the LARGEST dataset's size -- a workgroup's own arrives through the table, amwg_dataset.h; the plan reads ds_n_obs)
   if (m->model == AMWG_MODEL_NORMAL || m->model == AMWG_MODEL_HIER_NORMAL) TRYB(upload_normal_data(s, models, D, gl, consts));
   else if (m->model == AMWG_MODEL_BETA_BERN) TRYB(upload_bernoulli_data(s, models, D, consts));
   else TRYB(upload_poisson_data(s, models, D, consts));
+  dataset_constants(s->mc, consts[0]);
   if (D > 1) {
     TRYB(upload(s, consts.data(), consts.size(), &s->d_ds_consts));
     s->n_datasets = D;

@@ -19,7 +19,8 @@
 
 namespace amwg {
 
-// what the host computes per dataset instead of once (amwg_create.hip); the rest of ModelConsts follows from the hyper-parameters, which all datasets share.
+// what the host derives from ONE dataset's data or size (amwg_create.hip fills it, for an ordinary sampler too: its one dataset); the rest of ModelConsts
+// follows from the hyper-parameters and the options, which all datasets share.
 // Datasets may differ in SIZE (amwg_create_datasets_ragged): n_obs and what is formed from it -- the Poisson family's prior ld.unif(cp, 0, n - 1) -- are
 // per-dataset constants like the others, and so is the place of the dataset's copy inside each of the six arrays.
 struct DatasetConsts {
@@ -37,6 +38,23 @@ struct DatasetArgs {
   const DatasetConsts *consts;                                                      // [n_datasets], device memory
 };
 
+// One dataset's constants where the kernels read them, ModelConsts.  THE list of the fields of DatasetConsts that are constants of the model -- the
+// rest are the size and the offsets, which dataset_view below applies to DataRef.  Both sides go through it: the device per workgroup (dataset_view),
+// the host once, for dataset 0, into the sampler's own ModelConsts (amwg_create.hip create_builtin: an ordinary sampler is dataset 0 of one).
+__host__ __device__ __forceinline__ void dataset_constants(ModelConsts &mc, const DatasetConsts &k) {
+  mc.data_mid_range = k.data_mid_range;
+  mc.has_invalid = k.has_invalid;
+  mc.cp_upper = k.cp_upper;
+  mc.lunif_cp = k.lunif_cp;
+#pragma unroll
+  for (int j = 0; j < 7; ++j) mc.glm_xmax[j] = k.glm_xmax[j];
+  mc.glm_sum_y = k.glm_sum_y;
+  mc.glm_sum_lf = k.glm_sum_lf;
+  mc.suff_xbar_hi = k.suff_xbar_hi;
+  mc.suff_xbar_lo = k.suff_xbar_lo;
+  mc.suff_ss = k.suff_ss;
+}
+
 // the argument block as the workgroup of dataset blockIdx.x / blocks_per_dataset sees it
 __device__ __forceinline__ void dataset_view(StepArgs &v, const DatasetArgs &ds) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -53,17 +71,7 @@ __device__ __forceinline__ void dataset_view(StepArgs &v, const DatasetArgs &ds)
   v.d.xb += k.off_xb;
   v.d.xw += k.off_xw;
   v.d.arr[0] = static_cast<const uint32_t *>(v.d.arr[0]) + k.off_arr0;
-  v.mc.data_mid_range = k.data_mid_range;
-  v.mc.has_invalid = k.has_invalid;
-  v.mc.cp_upper = k.cp_upper;
-  v.mc.lunif_cp = k.lunif_cp;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) v.mc.glm_xmax[j] = k.glm_xmax[j];
-  v.mc.glm_sum_y = k.glm_sum_y;
-  v.mc.glm_sum_lf = k.glm_sum_lf;
-  v.mc.suff_xbar_hi = k.suff_xbar_hi;
-  v.mc.suff_xbar_lo = k.suff_xbar_lo;
-  v.mc.suff_ss = k.suff_ss;
+  dataset_constants(v.mc, k);
 }
 
 template <class Model, int G, int BT>

@@ -1,5 +1,6 @@
 // amwg_diag.hip -- what a caller can ask about a sampler and its draws (moments, R-hat / ESS, stepper state, launch geometry, kernel name), about the
-// library (version, last error) and about the device (fp64 peak); the host build of the kernel arithmetic; the three small kernels these need.
+// library (version, last error) and about the device (fp64 peak); the host build of the kernel arithmetic; the small kernels these need.  A summary has ONE
+// launcher, over D datasets of C / D chains each: the pooled call of an ordinary sampler is its case D = 1.
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -12,25 +13,6 @@
 using namespace amwg;
 
 namespace {
-__global__ void moments_kernel(const double *draws, int64_t rows, int P, int64_t C, double *mean, double *sd) {
-  __shared__ double red[1024];
-  const int p = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int64_t n = rows * C;
-  double sum = 0;
-  for (int64_t i = tid; i < n; i += nt) sum += draws[((i / C) * P + p) * C + (i % C)];
-  red[tid] = sum;
-  __syncthreads();
-  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-  const double m = red[0] / (double)n;
-  __syncthreads();
-  double ss = 0;
-  for (int64_t i = tid; i < n; i += nt) { const double dlt = draws[((i / C) * P + p) * C + (i % C)] - m; ss += dlt * dlt; }
-  red[tid] = ss;
-  __syncthreads();
-  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-  if (tid == 0) { mean[p] = m; sd[p] = n > 1 ? sqrt(red[0] / (double)(n - 1)) : 0.0; }
-}
-
 // per chain and recorded value: mean and (n-1) variance of each half of the chain's kept draws
 // out[((h*2 + stat) * PR + p) * C + c], stat 0 = mean, 1 = variance; draws [row][PR][C] (coalesced over chains)
 __global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, int64_t C, double *out) {
@@ -52,8 +34,8 @@ __global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, i
   }
 }
 
-// ---- a dataset sampler (amwg_create_datasets): the same summaries per dataset, one workgroup per (recorded value, dataset); dataset d owns the chains
-// [d * cpd, (d + 1) * cpd)
+// ---- summaries per dataset, one workgroup per (recorded value, dataset); dataset d owns the chains [d * cpd, (d + 1) * cpd).  An ordinary sampler is
+// one dataset of all its chains (cpd = C).
 __device__ inline double block_sum(double v, double *red) {      // sum over the workgroup (a power-of-two size), in every thread
   const int tid = threadIdx.x, nt = blockDim.x;
   __syncthreads();
@@ -62,7 +44,8 @@ __device__ inline double block_sum(double v, double *red) {      // sum over the
   for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
   return red[0];
 }
-// mean and sd (n - 1 denominator) over the dataset's chains x kept draws: the order of moments_kernel over the dataset's own columns; out [D][PR] each
+// mean and sd (n - 1 denominator) over the dataset's chains x kept draws, in a fixed order: thread t sums the values i = t, t + 1024, ... of the dataset's
+// rows laid end to end, a halving tree adds the 1024 partial sums; a second pass for the squares about the mean.  out [D][PR] each
 __global__ void __launch_bounds__(1024) dataset_moments_kernel(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, double *mean, double *sd) {
   __shared__ double red[1024];
   const int p = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
@@ -134,6 +117,33 @@ int amwg_refuse_pooled(const amwg_sampler *s, const char *call) {
   return AMWG_OK;
 }
 
+// ---- the launchers behind the summaries of the last sample call, over D datasets of C / D chains each (D = 1: pooled over all chains)
+// mean and sd, [D][PR] each
+static int last_sample_moments(amwg_sampler *s, int D, double *mean, double *sd) {
+  HIP_TRY(hipSetDevice(s->device));
+  const int PR = s->P + s->D;
+  const size_t n = (size_t)D * PR;
+  DevBuf buf;
+  HIP_TRY(buf.alloc(n * 16));
+  double *dm = buf.as<double>();
+  hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return AMWG_OK;
+}
+// the halves of every chain (chain_halves_kernel's layout, 4 PR C doubles) in a scratch buffer, queued on the sampler's stream
+static int last_sample_halves(amwg_sampler *s, DevBuf *halves) {
+  HIP_TRY(hipSetDevice(s->device));
+  const int PR = s->P + s->D;
+  const size_t C = (size_t)s->C;
+  HIP_TRY(halves->alloc(4 * (size_t)PR * C * 8));
+  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves->as<double>());
+  HIP_TRY(hipGetLastError());
+  return AMWG_OK;
+}
+
 extern "C" {
 
 const char *amwg_last_error(void) { return g_err.c_str(); }
@@ -159,33 +169,19 @@ int amwg_dataset_n_obs(const amwg_sampler *s, int32_t *n_obs) {
 int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: null argument");
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: no sample() call yet");
-  HIP_TRY(hipSetDevice(s->device));
-  const int PR = s->P + s->D, D = s->n_datasets;
-  const size_t n = (size_t)D * PR;
-  DevBuf buf;
-  HIP_TRY(buf.alloc(n * 16));
-  double *dm = buf.as<double>();
-  hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return AMWG_OK;
+  return last_sample_moments(s, s->n_datasets, mean, sd);
 }
 
 int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: null argument");
   const int D = s->n_datasets;
   if (!s->last_draws || s->last_rows < 4 || s->C / D < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains per dataset");
-  HIP_TRY(hipSetDevice(s->device));
   const int PR = s->P + s->D;
-  const size_t C = (size_t)s->C, n_halves = 4 * (size_t)PR * C, n = (size_t)D * PR;
+  const size_t n = (size_t)D * PR;
   DevBuf halves, out;
-  HIP_TRY(halves.alloc(n_halves * 8));
+  TRYB(last_sample_halves(s, &halves));
   HIP_TRY(out.alloc(n * 16));
   double *dr = out.as<double>();
-  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves.as<double>());
-  HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(dataset_diagnostics_kernel, dim3(PR, D), dim3(256), 0, s->stream, halves.as<double>(), s->last_rows, PR, s->C, s->C / D, dr, dr + n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(rhat, dr, n * 8, hipMemcpyDeviceToHost, s->stream));
@@ -198,14 +194,11 @@ int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: null argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_diagnostics"));
   if (!s->last_draws || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
-  HIP_TRY(hipSetDevice(s->device));
   const int PR = s->P + s->D;
   const size_t C = (size_t)s->C, n_out = 4 * (size_t)PR * C;
   DevBuf dout;
-  HIP_TRY(dout.alloc(n_out * 8));
-  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, dout.as<double>());
+  TRYB(last_sample_halves(s, &dout));
   std::vector<double> h(n_out);
-  HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h.data(), dout.p, n_out * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   const double n = (double)(s->last_rows / 2), m = 2.0 * (double)C;   // 2C half-chains of n draws
@@ -277,17 +270,7 @@ int amwg_last_sample_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: null argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_moments"));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: no sample() call yet");
-  HIP_TRY(hipSetDevice(s->device));
-  DevBuf buf;
-  const int PR = s->P + s->D;
-  HIP_TRY(buf.alloc((size_t)PR * 16));
-  double *dm = buf.as<double>();
-  hipLaunchKernelGGL(moments_kernel, dim3(PR), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, dm, dm + PR);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(mean, dm, (size_t)PR * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(sd, dm + PR, (size_t)PR * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return AMWG_OK;
+  return last_sample_moments(s, 1, mean, sd);      // (one dataset of all the chains: cpd = C)
 }
 
 int amwg_tuning(const amwg_sampler *s, int32_t *lanes, double *ms, int32_t cap) {

@@ -45,11 +45,11 @@ int dev_alloc(amwg_sampler *s, T **p, size_t n) {
 }
 
 // ---- amwg_kernels.hip: a built-in family is one row of facts, exported by the family's own translation unit (AMWG_FAMILY = AMWG_MODEL_* - 1)
+struct KernelPair { step_kernel_t plain = nullptr; dataset_kernel_t ds = nullptr; };      // a kernel and its dataset twin (amwg_dataset.h); nullptr: none
 struct FamilyRow {
-  step_kernel_t (*kernel)(int lanes, int block), (*certified)(int lanes, int block);      // the step kernel of a geometry, and the one that decides from certified values (kCert); nullptr: none
+  KernelPair (*kernel)(int lanes, int block), (*certified)(int lanes, int block);      // the step kernel of a geometry, and the one that decides from certified values (kCert)
   size_t (*lds_bytes)(int n_obs, int groups, int lanes);      // LDS bytes of the data the family stages
   int max_threads;                                            // the family's largest workgroup
-  dataset_kernel_t (*dataset_kernel)(int lanes, int block), (*dataset_certified)(int lanes, int block);      // their dataset twins (amwg_dataset.h); nullptr: none
 };
 template <int Family> FamilyRow amwg_family_row();
 

@@ -122,7 +122,7 @@ static LaunchPlan variant_for(const amwg_sampler *s, int G, int bt, size_t max_l
   const bool rows = s->model == AMWG_MODEL_HIER_NORMAL && rows_wanted && ((s->hier_periodic_mask >> 6) & 1u) && s->d.G <= 64 && s->d.n_obs >= 64 &&
                     rows_fit(HierNormalModel::row_pitch(s->d.n_obs), s->d.G);
   const bool cert = decide_certified && ((s->model == AMWG_MODEL_NORMAL && G == 1) || (s->model == AMWG_MODEL_POIS_GLM && G == 16) || rows) &&
-                    family_of(s->model)->certified(G, bt) != nullptr;
+                    family_of(s->model)->certified(G, bt).plain != nullptr;
   p.variant = rows ? (cert ? Variant::HierSweepCert : Variant::HierSweep) : (cert ? Variant::StepCert : Variant::Step);
   p.pad = rows ? HierNormalModel::row_pitch(s->d.n_obs) : ((cert && s->model == AMWG_MODEL_NORMAL && bt <= 512 && !o.sufficient_statistics) ? 1 : 0);
   return p;
@@ -352,30 +352,31 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
 }
 
 // Everything that goes with a plan: the sampler's geometry, DataRef::pad, the constant-mean pass of the hierarchical family (HierNormalModel::pass_fast:
-// the labels repeat with the lane stride), the built-in kernel and the wave scratch.  A translated closure's kernel is compiled and loaded afterwards
-// (amwg_create_user, prepare).
+// the labels repeat with the lane stride), the built-in kernel with its dataset twin (the family's row is asked once: KernelPair) and the wave scratch.
+// A translated closure's kernel is compiled and loaded afterwards (amwg_create_user, prepare).
 int adopt_plan(amwg_sampler *s, const LaunchPlan &p) {
   s->plan = p;
   s->d.pad = p.pad;
   if (s->user) return size_wave_scratch(s);
-  if (s->n_datasets > 1) {      // the dataset twin (amwg_dataset.h), and how many workgroups serve one dataset
+  if (s->model == AMWG_MODEL_HIER_NORMAL) s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> log2_of(p.lanes)) & 1u);
+  KernelPair k;
+  switch (p.variant) {
+    case Variant::StepCert: case Variant::HierSweepCert: k = family_of(s->model)->certified(p.lanes, p.block); break;
+    case Variant::HierSweep: k.plain = amwg_kernel_hier_sweep(p.block); break;
+    case Variant::GroupLocal: k.plain = amwg_kernel_hier_gl(p.block); break;
+    default: k = family_of(s->model)->kernel(p.lanes, p.block);
+  }
+  s->kernel = k.plain;
+  s->ds_kernel = k.ds;
+  if (s->n_datasets > 1) {      // a dataset sampler launches the twin (amwg_dataset.h); how many workgroups serve one dataset
     const int cpw = chains_per_workgroup(p.lanes, p.block);
     const int64_t cpd = chains_per_dataset(s);
     if (p.cpb || (p.variant != Variant::Step && p.variant != Variant::StepCert) || cpd % cpw != 0)
       return amwg_fail(AMWG_EINVAL, "internal: a plan of %d lanes in workgroups of %d (cpb %d) for datasets of %lld chains", p.lanes, p.block, p.cpb, (long long)cpd);
     s->ds_blocks_per_dataset = (int)(cpd / cpw);
-    s->ds_kernel = p.variant == Variant::StepCert ? family_of(s->model)->dataset_certified(p.lanes, p.block) : family_of(s->model)->dataset_kernel(p.lanes, p.block);
     if (!s->ds_kernel) return amwg_fail(AMWG_EINVAL, "no dataset kernel for model %d with %d lanes per chain in workgroups of %d", s->model, p.lanes, p.block);
-    return size_wave_scratch(s);
   }
-  if (s->model == AMWG_MODEL_HIER_NORMAL) s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> log2_of(p.lanes)) & 1u);
-  switch (p.variant) {
-    case Variant::StepCert: case Variant::HierSweepCert: s->kernel = family_of(s->model)->certified(p.lanes, p.block); break;
-    case Variant::HierSweep: s->kernel = amwg_kernel_hier_sweep(p.block); break;
-    case Variant::GroupLocal: s->kernel = amwg_kernel_hier_gl(p.block); break;
-    default: s->kernel = family_of(s->model)->kernel(p.lanes, p.block);
-  }
-  if (!s->kernel) return amwg_fail(AMWG_EINVAL, "no kernel for model %d with %d lanes per chain in workgroups of %d", s->model, p.lanes, p.block);
+  if (s->n_datasets <= 1 && !s->kernel) return amwg_fail(AMWG_EINVAL, "no kernel for model %d with %d lanes per chain in workgroups of %d", s->model, p.lanes, p.block);
   return size_wave_scratch(s);
 }
 // ---- AMWG_LANES_AUTOTUNE: measure instead of model.  Every lane count whose geometry fits is adopted (adopt_plan) and prepared (`prepare`: kernel

@@ -35,41 +35,32 @@ __global__ void pick_quantiles_kernel(const double *sorted, int64_t n, const dou
 
 }  // namespace
 
-#define HIP_TRYQ(expr)                                                                                   \
-  do {                                                                                                   \
-    hipError_t e_ = (expr);                                                                              \
-    if (e_ != hipSuccess) { cleanup(); return amwg_fail(AMWG_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } \
-  } while (0)
-
 extern "C" int amwg_last_sample_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: bad argument");
-  { const int rp = amwg_refuse_pooled(s, "amwg_last_sample_quantiles"); if (rp != AMWG_OK) return rp; }
+  TRYB(amwg_refuse_pooled(s, "amwg_last_sample_quantiles"));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: no sample() call yet");
   const int PR = s->P + s->D;
   const int64_t n = s->last_rows * s->C;
-  double *vals = nullptr, *sorted = nullptr, *dprobs = nullptr, *dout = nullptr;
-  void *tmp = nullptr;
-  auto cleanup = [&]() { (void)hipFree(vals); (void)hipFree(sorted); (void)hipFree(dprobs); (void)hipFree(dout); (void)hipFree(tmp); };
-  HIP_TRYQ(hipSetDevice(s->device));
-  HIP_TRYQ(hipMalloc(reinterpret_cast<void **>(&vals), (size_t)n * 8));
-  HIP_TRYQ(hipMalloc(reinterpret_cast<void **>(&sorted), (size_t)n * 8));
-  HIP_TRYQ(hipMalloc(reinterpret_cast<void **>(&dprobs), (size_t)n_probs * 8));
-  HIP_TRYQ(hipMalloc(reinterpret_cast<void **>(&dout), (size_t)n_probs * 8));
-  HIP_TRYQ(hipMemcpyAsync(dprobs, probs, (size_t)n_probs * 8, hipMemcpyHostToDevice, s->stream));
+  if (n > 2147483647) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: more than 2^31 values per component");      // (the sort counts in int)
+  DevBuf vals, sorted, dprobs, dout, tmp;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(vals.alloc((size_t)n * 8));
+  HIP_TRY(sorted.alloc((size_t)n * 8));
+  HIP_TRY(dprobs.alloc((size_t)n_probs * 8));
+  HIP_TRY(dout.alloc((size_t)n_probs * 8));
+  HIP_TRY(hipMemcpyAsync(dprobs.p, probs, (size_t)n_probs * 8, hipMemcpyHostToDevice, s->stream));
   size_t tmp_bytes = 0;
-  HIP_TRYQ(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, vals, sorted, (int)n, 0, 64, s->stream));
-  HIP_TRYQ(hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 8));
-  if (n > 2147483647) { cleanup(); return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: more than 2^31 values per component"); }
+  HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, vals.as<double>(), sorted.as<double>(), (int)n, 0, 64, s->stream));
+  HIP_TRY(tmp.alloc(tmp_bytes));
   for (int p = 0; p < PR; ++p) {
-    hipLaunchKernelGGL(gather_component_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, p, vals);
-    HIP_TRYQ(hipGetLastError());
-    HIP_TRYQ(hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, vals, sorted, (int)n, 0, 64, s->stream));
-    hipLaunchKernelGGL(pick_quantiles_kernel, dim3((unsigned)((n_probs + 63) / 64)), dim3(64), 0, s->stream, sorted, n, dprobs, n_probs, dout);
-    HIP_TRYQ(hipGetLastError());
-    HIP_TRYQ(hipMemcpyAsync(out + (size_t)p * n_probs, dout, (size_t)n_probs * 8, hipMemcpyDeviceToHost, s->stream));
+    hipLaunchKernelGGL(gather_component_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, p, vals.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceRadixSort::SortKeys(tmp.p, tmp_bytes, vals.as<double>(), sorted.as<double>(), (int)n, 0, 64, s->stream));
+    hipLaunchKernelGGL(pick_quantiles_kernel, dim3((unsigned)((n_probs + 63) / 64)), dim3(64), 0, s->stream, sorted.as<double>(), n, dprobs.as<double>(), n_probs, dout.as<double>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out + (size_t)p * n_probs, dout.p, (size_t)n_probs * 8, hipMemcpyDeviceToHost, s->stream));
   }
-  HIP_TRYQ(hipStreamSynchronize(s->stream));
-  cleanup();
+  HIP_TRY(hipStreamSynchronize(s->stream));
   return AMWG_OK;
 }
 

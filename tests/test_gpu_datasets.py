@@ -1,11 +1,8 @@
 """Many datasets in one sampler (amwg_create_datasets; csrc/amwg_dataset.h), on the GPU.  The bar is the project's own: every bit.
 
-A dataset sampler over D datasets is compared with D ordinary samplers (amwg_create), one per dataset, with chain_offset = d * cpd, the same seed and the
-same lanes_per_chain and block_threads, over ALL chains: the draws as bytes, every array of info(), state(), and diag()'s uniforms, named_order and
-log_post.  Schedule: burn 120 (adaptation crosses two batches), then sample(40, thin=3).  Data: synth with a different data_seed per dataset.  The
-shapes are the smallest at which the new code can still go wrong (one case per row of the table in the pull request's issue); launch_info() of the two
-sides must agree -- the kernel's name modulo the twin's marker "_ds", lanes, block and summation order.  Two chains are anchored to the CPU oracle
-directly, independent of the library's own single-dataset path."""
+Every dataset's chains against an ordinary sampler on that dataset, with the harness of tests/dataset_harness.py (which states what is compared and on
+which schedule).  Data: synth with a different data_seed per dataset.  The shapes are the smallest at which the new code can still go wrong (one case per
+row of the table in the pull request's issue).  Two chains are anchored to the CPU oracle directly, independent of the library's own single-dataset path."""
 import os
 import shutil
 import subprocess
@@ -17,11 +14,10 @@ import amwg_ctypes
 import gpu_util
 import model_spec
 import oracle_lib
+from dataset_harness import BURN, SAMPLE, SEED, THIN, against_twins, assert_same_bits, run
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 20261018
-BURN, SAMPLE, THIN = 120, 40, 3
 
 
 def dataset_specs(model, n_obs, D, tweak=None):
@@ -34,51 +30,6 @@ def dataset_specs(model, n_obs, D, tweak=None):
             tweak(d, data)
         out.append(model_spec.build_spec(model, data))
     return out
-
-
-def run(s):
-    s.burn(BURN)
-    draws = s.sample(SAMPLE, THIN)
-    return {"draws": draws, "info": s.info(), "state": s.state(), "diag": s.diag()}
-
-
-def assert_same_bits(a, b, what):
-    assert a["draws"].tobytes() == b["draws"].tobytes(), what + ": draws"
-    for k in a["info"]:
-        assert a["info"][k].tobytes() == b["info"][k].tobytes(), what + ": info " + k
-    assert a["state"].tobytes() == b["state"].tobytes(), what + ": state"
-    for k in ("uniforms", "named_order", "log_post"):
-        assert a["diag"][k].tobytes() == b["diag"][k].tobytes(), what + ": diag " + k
-
-
-def slice_chains(r, c0, c1):
-    return {"draws": np.ascontiguousarray(r["draws"][:, :, c0:c1]), "info": {k: np.ascontiguousarray(v[:, c0:c1]) for k, v in r["info"].items()},
-            "state": np.ascontiguousarray(r["state"][:, c0:c1]), "diag": {k: np.ascontiguousarray(v[c0:c1]) for k, v in r["diag"].items()}}
-
-
-def same_launch(ds, twin):
-    a, b = ds.launch_info(), twin.launch_info()
-    assert "_ds<" in a["kernel"] and a["kernel"].replace("_ds<", "<") == b["kernel"], (a["kernel"], b["kernel"])
-    for k in ("lanes_per_chain", "block_threads", "summation_order"):
-        assert a[k] == b[k], (k, a, b)
-    assert a["datasets"] > 1 and b["datasets"] == 1
-
-
-def against_twins(specs, cpd, lanes, block, kernel=None, **opts):
-    """-> the dataset sampler's results, after comparing every dataset's chains with an ordinary sampler on that dataset"""
-    D = len(specs)
-    ds = amwg_ctypes.Sampler(specs, chains=D * cpd, seed=SEED, lanes_per_chain=lanes, block_threads=block, **opts)
-    assert ds.D == D and ds.launch_info()["datasets"] == D
-    if kernel:
-        assert ds.launch_info()["kernel"].startswith(kernel), ds.launch_info()
-    got = run(ds)
-    for d in range(D):
-        twin = amwg_ctypes.Sampler(specs[d], chains=cpd, seed=SEED, chain_offset=d * cpd, lanes_per_chain=lanes, block_threads=block, **opts)
-        same_launch(ds, twin)
-        assert_same_bits(slice_chains(got, d * cpd, (d + 1) * cpd), run(twin), "dataset %d" % d)
-        twin.close()
-    ds.close()
-    return got
 
 
 @pytest.mark.parametrize("block,cpd", [(256, 256), (64, 64)])
@@ -178,8 +129,9 @@ def test_one_chain_of_dataset_one_equals_the_oracle(model, n_obs, cpd, lanes, bl
 
 
 def test_summaries_per_dataset():
-    """dataset_moments()[d] / dataset_convergence()[d] against the twin sampler's moments() / convergence(): two summation orders over ~1e4 values, the
-    tolerances of tests/test_gpu_moments.py.  The pooled calls are refused."""
+    """dataset_moments()[d] equals the twin sampler's moments() byte for byte: the same kernel over the same values in the same order.
+    dataset_convergence()[d] against the twin's convergence(): two summation orders (the pooled call reduces on the host), the tolerances of
+    tests/test_gpu_moments.py.  The pooled calls are refused."""
     specs = dataset_specs("normal", 300, 3)
     cpd = 64
     ds = amwg_ctypes.Sampler(specs, chains=3 * cpd, seed=SEED, lanes_per_chain=1, block_threads=64)
@@ -198,8 +150,7 @@ def test_summaries_per_dataset():
         twin.sample(SAMPLE * 4, THIN)
         m, s = twin.moments()
         r, e = twin.convergence()
-        np.testing.assert_allclose(mean[d], m, rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(sd[d], s, rtol=1e-10)
+        assert mean[d].tobytes() == m.tobytes() and sd[d].tobytes() == s.tobytes(), (d, mean[d], m, sd[d], s)
         np.testing.assert_allclose(rhat[d], r, rtol=1e-10)
         np.testing.assert_allclose(ess[d], e, rtol=1e-10)
         twin.close()

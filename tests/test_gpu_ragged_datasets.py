@@ -1,10 +1,8 @@
 """Datasets of unequal sizes in one sampler (amwg_create_datasets_ragged; csrc/amwg_dataset.h), on the GPU.  The bar is the one of
-tests/test_gpu_datasets.py, whose harness is repeated here: every bit.
+tests/test_gpu_datasets.py, with the same harness (tests/dataset_harness.py): every bit.
 
-A ragged sampler over D datasets is compared with D ordinary samplers (amwg_create), one per dataset, with chain_offset = d * cpd, the same seed, the same
-lanes_per_chain and block_threads and the parameters of the FIRST spec (the list constructor passes one params array for the whole sampler), over ALL
-chains: the draws as bytes, every array of info(), state(), and diag()'s uniforms, named_order and log_post.  Schedule: burn 120 (adaptation crosses two
-batches), then sample(40, thin=3).  The sizes are the smallest at which a per-dataset size can go wrong, one case per row of the table in
+Every dataset's chains against an ordinary sampler on that dataset with the parameters of the FIRST spec (the list constructor passes one params array
+for the whole sampler).  The sizes are the smallest at which a per-dataset size can go wrong, one case per row of the table in
 tests/README.ragged_datasets.md.  The Poisson family's sizes start at 2: with n = 1 the reference's own prior is log(1 / 0)."""
 import os
 import shutil
@@ -14,14 +12,19 @@ import numpy as np
 import pytest
 
 import amwg_ctypes
+import dataset_harness
 import gpu_util
 import model_spec
 import oracle_lib
+from dataset_harness import BURN, SAMPLE, SEED, THIN, assert_same_bits, run
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SEED = 20261018
-BURN, SAMPLE, THIN = 120, 40, 3
+
+
+def against_twins(case, specs, cpd, lanes, block, **kw):
+    """through the ragged entry; the twins' runs are kept under the case's name"""
+    return dataset_harness.against_twins(specs, cpd, lanes, block, case=case, ragged=True, **kw)
 
 
 def ragged_specs(model, sizes, tweak=None):
@@ -39,63 +42,6 @@ def ragged_specs(model, sizes, tweak=None):
             spec = dict(spec, params=out[0]["params"], P=out[0]["P"], init=out[0]["init"], comp_opts=out[0]["comp_opts"])
         out.append(spec)
     return out
-
-
-def run(s):
-    s.burn(BURN)
-    draws = s.sample(SAMPLE, THIN)
-    return {"draws": draws, "info": s.info(), "state": s.state(), "diag": s.diag()}
-
-
-def assert_same_bits(a, b, what):
-    assert a["draws"].tobytes() == b["draws"].tobytes(), what + ": draws"
-    for k in a["info"]:
-        assert a["info"][k].tobytes() == b["info"][k].tobytes(), what + ": info " + k
-    assert a["state"].tobytes() == b["state"].tobytes(), what + ": state"
-    for k in ("uniforms", "named_order", "log_post"):
-        assert a["diag"][k].tobytes() == b["diag"][k].tobytes(), what + ": diag " + k
-
-
-def slice_chains(r, c0, c1):
-    return {"draws": np.ascontiguousarray(r["draws"][:, :, c0:c1]), "info": {k: np.ascontiguousarray(v[:, c0:c1]) for k, v in r["info"].items()},
-            "state": np.ascontiguousarray(r["state"][:, c0:c1]), "diag": {k: np.ascontiguousarray(v[c0:c1]) for k, v in r["diag"].items()}}
-
-
-_twin_runs = {}
-
-
-def twin_run(key, spec, cpd, offset, lanes, block, opts):
-    """the ordinary sampler on one dataset at one offset, run once per (case, dataset, offset, options) and shared by the tests that compare against it"""
-    k = (key, cpd, offset, lanes, block, tuple(sorted(opts.items())))
-    if k not in _twin_runs:
-        twin = amwg_ctypes.Sampler(spec, chains=cpd, seed=SEED, chain_offset=offset, lanes_per_chain=lanes, block_threads=block, **opts)
-        _twin_runs[k] = (run(twin), twin.launch_info())
-        assert twin.dataset_n_obs() == [spec["n_obs"]]
-        twin.close()
-    return _twin_runs[k]
-
-
-def against_twins(case, specs, cpd, lanes, block, kernel=None, order=None, **opts):
-    """-> the ragged sampler's results, after comparing every dataset's chains with an ordinary sampler on that dataset.  order: the datasets as the ragged
-    sampler gets them (a permutation of range(D)); dataset order[j] then sits at offset j * cpd, and so does its twin"""
-    D = len(specs)
-    order = list(range(D)) if order is None else list(order)
-    ds = amwg_ctypes.Sampler([specs[d] for d in order], chains=D * cpd, seed=SEED, lanes_per_chain=lanes, block_threads=block, ragged=True, **opts)
-    li = ds.launch_info()
-    assert ds.D == D and li["datasets"] == D
-    assert ds.dataset_n_obs() == [specs[d]["n_obs"] for d in order]
-    if kernel:
-        assert li["kernel"].startswith(kernel), li
-    got = run(ds)
-    for j, d in enumerate(order):
-        want, twin_li = twin_run((case, d), specs[d], cpd, j * cpd, lanes, block, opts)
-        assert "_ds<" in li["kernel"] and li["kernel"].replace("_ds<", "<") == twin_li["kernel"], (li["kernel"], twin_li["kernel"])
-        for k in ("lanes_per_chain", "block_threads", "summation_order"):
-            assert li[k] == twin_li[k], (k, li, twin_li)
-        assert twin_li["datasets"] == 1
-        assert_same_bits(slice_chains(got, j * cpd, (j + 1) * cpd), want, "dataset %d (n_obs = %d) at offset %d" % (d, specs[d]["n_obs"], j * cpd))
-    ds.close()
-    return got
 
 
 NORMAL_ONE_LANE = (1, 2, 63, 64, 65, 1023, 1024, 1025, 1100)
@@ -215,7 +161,8 @@ def test_chains_of_a_small_and_an_odd_sized_dataset_equal_the_oracle(model, size
 
 def test_summaries_per_dataset():
     """dataset_quantiles() == numpy's sort over each dataset's slice of sample() (R's type 7 rule, as tests/test_gpu_dataset_quantiles.py states it);
-    dataset_moments()[d] against the twin sampler's moments() with the tolerances of tests/test_gpu_datasets.py; dataset_n_obs() returns the sizes."""
+    dataset_moments()[d] equals the twin sampler's moments() byte for byte (the same kernel over the same values in the same order); dataset_n_obs()
+    returns the sizes."""
     sizes = (2, 65, 300)
     specs = ragged_specs("normal", sizes)
     cpd = 64
@@ -239,8 +186,7 @@ def test_summaries_per_dataset():
         twin.burn(BURN)
         twin.sample(SAMPLE * 4, THIN)
         m, s = twin.moments()
-        np.testing.assert_allclose(mean[d], m, rtol=1e-12, atol=1e-13)
-        np.testing.assert_allclose(sd[d], s, rtol=1e-10)
+        assert mean[d].tobytes() == m.tobytes() and sd[d].tobytes() == s.tobytes(), (d, mean[d], m, sd[d], s)
         twin.close()
     ds.close()
 
