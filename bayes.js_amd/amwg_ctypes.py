@@ -46,7 +46,7 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+EXPORTS = ["amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
 SELFTEST_EXPORTS = ["amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
@@ -104,6 +104,8 @@ def lib():
         L.amwg_code_cache_stats.argtypes = [pi64, pi64, C.c_char_p, C.c_size_t]
         L.amwg_create_user.argtypes = [C.POINTER(UserModel), C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt),
                                        C.POINTER(Options), C.POINTER(vp)]
+        L.amwg_create_user_datasets.argtypes = [C.POINTER(UserModel), i32, C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt), C.POINTER(Options), C.POINTER(vp)]
+        L.amwg_compile_user_datasets.argtypes = L.amwg_compile_user.argtypes
         L.amwg_num_recorded.argtypes = [vp]
         L.amwg_set_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_fp64_peak.argtypes = [i32, pd]
@@ -189,10 +191,30 @@ class Sampler:
         # stepper options are those of the first)
         if isinstance(spec, (list, tuple)):
             specs = list(spec)
-            if not specs or any(q.get("user") is not None for q in specs):
-                raise AmwgError("a list of specs is one built-in family on several datasets: it must not be empty or hold translated closures")
+            n_user = sum(1 for q in specs if q.get("user") is not None)
+            if not specs or (n_user and n_user != len(specs)):
+                raise AmwgError("a list of specs is one built-in family, or one translated closure, on several datasets: it must not be empty or mix the two")
             spec = specs[0]
         user = spec.get("user")
+
+        def user_model(um, user):
+            src = user["source"].encode() if isinstance(user["source"], str) else user["source"]
+            keep.append(src)
+            um.source = src
+            arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in user["arrays"]]
+            keep.append(arrs)
+            um.n_arrays = len(arrs)
+            ptrs = (C.POINTER(C.c_double) * max(1, len(arrs)))(*[_dp(a) for a in arrs])
+            lens = (C.c_int64 * max(1, len(arrs)))(*[a.size for a in arrs])
+            types = (C.c_int32 * max(1, len(arrs)))(*[int(t) for t in user.get("array_types", [0] * len(arrs))])
+            keep.extend([ptrs, lens, types])
+            um.arrays, um.array_len, um.array_type = ptrs, lens, types
+            um.n_derived, um.lds_bytes = int(user.get("n_derived", 0)), int(user.get("lds_bytes", 0))
+            um.lds_bytes_one_lane = int(user.get("lds_bytes_one_lane", 0))
+            um.parallel, um.max_threads = int(user.get("parallel", 0)), int(user.get("max_threads", 0))
+            um.work_per_eval = float(user.get("work_per_eval", 0.0))
+            um.work_one_lane = float(user.get("work_one_lane", 0.0))
+            um.rows_n_obs, um.rows_groups, um.rows_sweep = int(user.get("rows_n_obs", 0)), int(user.get("rows_groups", 0)), int(user.get("rows_sweep", 0))
 
         def model_desc(md, q):
             d = q["data"]
@@ -214,7 +236,11 @@ class Sampler:
             for i, v in enumerate(q.get("hyper") or DEFAULT_HYPER[q["model"]]):
                 md.hyper[i] = float(v)
 
-        if specs is not None:
+        if specs is not None and user is not None:      # one translated closure on several datasets: amwg_create_user_datasets
+            ums = (UserModel * len(specs))()
+            for k, q in enumerate(specs):
+                user_model(ums[k], q["user"])
+        elif specs is not None:
             mds = (ModelDesc * len(specs))()
             for k, q in enumerate(specs):
                 model_desc(mds[k], q)
@@ -223,23 +249,7 @@ class Sampler:
             model_desc(md, spec)
         else:
             um = UserModel()
-            src = user["source"].encode() if isinstance(user["source"], str) else user["source"]
-            keep.append(src)
-            um.source = src
-            arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in user["arrays"]]
-            keep.append(arrs)
-            um.n_arrays = len(arrs)
-            ptrs = (C.POINTER(C.c_double) * max(1, len(arrs)))(*[_dp(a) for a in arrs])
-            lens = (C.c_int64 * max(1, len(arrs)))(*[a.size for a in arrs])
-            types = (C.c_int32 * max(1, len(arrs)))(*[int(t) for t in user.get("array_types", [0] * len(arrs))])
-            keep += [ptrs, lens, types]
-            um.arrays, um.array_len, um.array_type = ptrs, lens, types
-            um.n_derived, um.lds_bytes = int(user.get("n_derived", 0)), int(user.get("lds_bytes", 0))
-            um.lds_bytes_one_lane = int(user.get("lds_bytes_one_lane", 0))
-            um.parallel, um.max_threads = int(user.get("parallel", 0)), int(user.get("max_threads", 0))
-            um.work_per_eval = float(user.get("work_per_eval", 0.0))
-            um.work_one_lane = float(user.get("work_one_lane", 0.0))
-            um.rows_n_obs, um.rows_groups, um.rows_sweep = int(user.get("rows_n_obs", 0)), int(user.get("rows_groups", 0)), int(user.get("rows_sweep", 0))
+            user_model(um, user)
         n = len(spec["params"])
         pa = (ParamDesc * n)()
         TYPE = {"real": 0, "int": 1, "binary": 2}
@@ -266,7 +276,9 @@ class Sampler:
         op.test_bound_shift = test_bound_shift
         op.sufficient_statistics = sufficient_statistics
         h = C.c_void_p()
-        if specs is not None:
+        if specs is not None and user is not None:
+            _check(L.amwg_create_user_datasets(ums, len(specs), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
+        elif specs is not None:
             create = L.amwg_create_datasets_ragged if ragged else L.amwg_create_datasets
             _check(create(mds, len(specs), pa, n, _dp(init), oa, C.byref(op), C.byref(h)))
         elif user is None:

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 
 #include "amwg_host.h"
 #include "amwg_dataset.h"
@@ -474,43 +475,57 @@ static int adopt_user_model(amwg_sampler *s, const amwg_user_model *m, int max_t
   return AMWG_OK;
 }
 
-// array j of a closure stored as the integer type T, with `pad` spare elements behind it; elements that T cannot hold are refused
+// array j of a closure stored as the type T (the doubles themselves, or an integer type: elements that it cannot hold are refused), with `pad` spare elements behind
+// it.  D > 1 (amwg_create_user_datasets): the D copies back to back in ONE allocation, each starting on a 256-byte boundary like an allocation of its own and followed by
+// its own spare elements; dev[d] = dataset d's copy.
 template <class T>
-static int upload_user_ints(amwg_sampler *s, const amwg_user_model *m, int j, const char *type_name, size_t pad, const void **dev) {
-  const int64_t n = m->array_len[j];
-  std::vector<T> tmp((size_t)n);
-  for (int64_t i = 0; i < n; ++i) {
-    const double v = m->arrays[j][i];
-    if (!(v >= (double)std::numeric_limits<T>::min() && v <= (double)std::numeric_limits<T>::max() && v == (double)(T)v))
-      return amwg_fail(AMWG_EINVAL, "amwg_create_user: array %d element %lld (%g) does not fit %s", j, (long long)i, v, type_name);
-    tmp[(size_t)i] = (T)v;
-  }
+static int upload_user_array(amwg_sampler *s, const amwg_user_model *models, int D, int j, const char *type_name, size_t pad, const void **dev) {
+  const size_t n = (size_t)models[0].array_len[j];
+  constexpr size_t align = 256 / sizeof(T);
+  const size_t stride = D == 1 ? n + pad : (n + pad + align - 1) / align * align;
+  std::vector<T> tmp(stride * (size_t)D, T(0));
+  for (int d = 0; d < D; ++d)
+    for (size_t i = 0; i < n; ++i) {
+      const double v = models[d].arrays[j][i];
+      if constexpr (!std::is_same<T, double>::value) {
+        if (!(v >= (double)std::numeric_limits<T>::min() && v <= (double)std::numeric_limits<T>::max() && v == (double)(T)v)) {
+          if (D == 1) return amwg_fail(AMWG_EINVAL, "amwg_create_user: array %d element %lld (%g) does not fit %s", j, (long long)i, v, type_name);
+          return amwg_fail(AMWG_EINVAL, "amwg_create_user_datasets: dataset %d: array %d element %lld (%g) does not fit %s", d, j, (long long)i, v, type_name);
+        }
+      }
+      tmp[(size_t)d * stride + i] = (T)v;
+    }
   T *p = nullptr;
-  TRYB(dev_alloc(s, &p, (size_t)n + pad));
-  if (n) HIP_TRY(hipMemcpy(p, tmp.data(), (size_t)n * sizeof(T), hipMemcpyHostToDevice));
-  *dev = p;
+  TRYB(dev_alloc(s, &p, tmp.size()));
+  if (D == 1 ? n > 0 : !tmp.empty()) HIP_TRY(hipMemcpy(p, tmp.data(), (D == 1 ? n : tmp.size()) * sizeof(T), hipMemcpyHostToDevice));
+  for (int d = 0; d < D; ++d) dev[d] = p + (size_t)d * stride;
   return AMWG_OK;
 }
 
-// every array the closure reads, row-major, in the storage type the translator chose
-static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *m) {
+// every array the closure reads, row-major, in the storage type the translator chose.  D > 1: of every dataset, and the device table [D][row_stride] of their
+// places (amwg_user_dataset.h); the sampler's own DataRef then holds dataset 0's, as an ordinary sampler's would.
+static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *models, int D) {
+  const amwg_user_model *m = &models[0];
   s->d.n_obs = 0;
-  std::vector<const void *> ext;      // arrays beyond the kInlineUserArrays pointers of the kernel arguments
+  const int row_stride = m->n_arrays > kInlineUserArrays ? m->n_arrays : kInlineUserArrays;
+  std::vector<const void *> table((size_t)D * row_stride, nullptr), at((size_t)D);
   for (int j = 0; j < m->n_arrays; ++j) {
-    if (m->array_len[j] < 0 || (m->array_len[j] && !m->arrays[j])) return amwg_fail(AMWG_EINVAL, "amwg_create_user: array %d is null or has a negative length", j);
+    for (int d = 0; d < D; ++d)
+      if (models[d].array_len[j] < 0 || (models[d].array_len[j] && !models[d].arrays[j])) return amwg_fail(AMWG_EINVAL, "amwg_create_user: array %d is null or has a negative length", j);
     const int ty = m->array_type ? m->array_type[j] : AMWG_F64;
-    const void *p = nullptr;
-    double *pd = nullptr;
-    if (ty == AMWG_F64) { TRYB(upload(s, m->arrays[j], (size_t)m->array_len[j], &pd)); p = pd; }
-    else if (ty == AMWG_U8) TRYB(upload_user_ints<uint8_t>(s, m, j, "u8", 16, &p));
-    else if (ty == AMWG_I32) TRYB(upload_user_ints<int32_t>(s, m, j, "i32", 4, &p));
+    if (ty == AMWG_F64 && D == 1) { double *pd = nullptr; TRYB(upload(s, m->arrays[j], (size_t)m->array_len[j], &pd)); at[0] = pd; }      // (as they lie: no packing)
+    else if (ty == AMWG_F64) TRYB(upload_user_array<double>(s, models, D, j, "f64", 0, at.data()));
+    else if (ty == AMWG_U8) TRYB(upload_user_array<uint8_t>(s, models, D, j, "u8", 16, at.data()));
+    else if (ty == AMWG_I32) TRYB(upload_user_array<int32_t>(s, models, D, j, "i32", 4, at.data()));
     else return amwg_fail(AMWG_EINVAL, "amwg_create_user: array %d has unknown storage type %d", j, ty);
-    if (j < kInlineUserArrays) s->d.arr[j] = p; else ext.push_back(p);
+    for (int d = 0; d < D; ++d) table[(size_t)d * row_stride + j] = at[d];
   }
-  if (!ext.empty()) {
-    const void **d_ext = nullptr;
-    TRYB(upload(s, ext.data(), ext.size(), &d_ext));
-    s->d.arr_ext = d_ext;
+  for (int j = 0; j < m->n_arrays && j < kInlineUserArrays; ++j) s->d.arr[j] = table[j];
+  if (m->n_arrays > kInlineUserArrays || D > 1) {      // (one table serves both: row d's entries from kInlineUserArrays on are dataset d's arr_ext)
+    const void **d_table = nullptr;
+    TRYB(upload(s, table.data(), table.size(), &d_table));
+    s->d.arr_ext = d_table + kInlineUserArrays;
+    if (D > 1) { s->d_user_ds_table = d_table; s->user_ds_row_stride = row_stride; s->user_ds_n_arrays = m->n_arrays; }
   }
   return AMWG_OK;
 }
@@ -616,9 +631,60 @@ int amwg_create_datasets_ragged(const amwg_model_desc *models, int32_t n_dataset
   return create_datasets("amwg_create_datasets_ragged", true, models, n_datasets, params, n_params, init, comp_opts, options, out);
 }
 
+// amwg_create_user and amwg_create_user_datasets from here on: one translated closure on D datasets (D == 1: the ordinary sampler).  `entry`: the name in the messages.
+static int create_user(const char *entry, const amwg_user_model *models, int D, const amwg_param_desc *params, int32_t n_params, const double *init,
+                       const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
+
 int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, int32_t n_params, const double *init,
                      const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
   if (!m || !m->source || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "amwg_create_user: null argument");
+  return create_user("amwg_create_user", m, 1, params, n_params, init, comp_opts, options, out);
+}
+
+// What the dataset entry of a closure checks before a device is opened: ONE source, ONE layout of the arrays, nothing in the source that is formed from one dataset's
+// values (the row plan's layout, the sums of the certified Poisson / logistic tails).
+int amwg_create_user_datasets(const amwg_user_model *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                              const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  const char *entry = "amwg_create_user_datasets";
+  if (!models || !params || !init || !comp_opts || !options || !out) return amwg_fail(AMWG_EINVAL, "%s: null argument", entry);
+  if (n_datasets < 1) return amwg_fail(AMWG_EINVAL, "%s: n_datasets must be >= 1, got %d", entry, n_datasets);
+  for (int d = 0; d < n_datasets; ++d) if (!models[d].source) return amwg_fail(AMWG_EINVAL, "%s: null argument (dataset %d: source)", entry, d);
+  if (n_datasets == 1) return amwg_create_user(models, params, n_params, init, comp_opts, options, out);
+  if (options->chains % n_datasets != 0)
+    return amwg_fail(AMWG_EINVAL, "%s: chains (%lld, the total) must be a multiple of n_datasets (%d)", entry, (long long)options->chains, n_datasets);
+  const amwg_user_model &m0 = models[0];
+  for (int d = 1; d < n_datasets; ++d) {
+    const amwg_user_model &m = models[d];
+    if (strcmp(m.source, m0.source) != 0)
+      return amwg_fail(AMWG_EINVAL, "%s: dataset %d: source differs from dataset 0's (one generated source serves all datasets: translate.js translate_datasets)", entry, d);
+    if (m.n_arrays != m0.n_arrays) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: n_arrays = %d, dataset 0 has %d", entry, d, m.n_arrays, m0.n_arrays);
+    if (m.n_arrays > 0 && (!m.arrays || !m.array_len || !m0.arrays || !m0.array_len)) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: arrays is null", entry, d);
+    for (int j = 0; j < m.n_arrays; ++j) {
+      if (m.array_len[j] != m0.array_len[j])
+        return amwg_fail(AMWG_EINVAL, "%s: dataset %d: array_len[%d] = %lld, dataset 0 has %lld (the datasets of a closure are of equal shape; ragged ones are not supported)", entry, d, j,
+                         (long long)m.array_len[j], (long long)m0.array_len[j]);
+      const int t = m.array_type ? m.array_type[j] : AMWG_F64, t0 = m0.array_type ? m0.array_type[j] : AMWG_F64;
+      if (t != t0) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: array_type[%d] = %d, dataset 0 has %d (one storage type per array: the widest over the datasets)", entry, d, j, t, t0);
+    }
+#define AMWG_SAME(field) if (m.field != m0.field) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: " #field " = %d, dataset 0 has %d", entry, d, (int)m.field, (int)m0.field)
+    AMWG_SAME(n_derived); AMWG_SAME(lds_bytes); AMWG_SAME(lds_bytes_one_lane); AMWG_SAME(parallel); AMWG_SAME(max_threads); AMWG_SAME(rows_n_obs); AMWG_SAME(rows_groups); AMWG_SAME(rows_sweep);
+#undef AMWG_SAME
+  }
+  const SourceTraits t = source_traits(m0.source);
+  if (t.row_n >= 0 || m0.rows_n_obs > 0)
+    return amwg_fail(AMWG_EINVAL, "%s: the source has a row plan (kRowN): its layout is formed from one dataset's labels; translate with no_row_plan (translate_datasets does)", entry);
+  if (t.pois_tail_n > 0 || t.logit_tail_n > 0)
+    return amwg_fail(AMWG_EINVAL, "%s: the source has a certified %s tail (%s): its bound holds sums over one dataset's values; translate with no_pois_tail / no_logit_tail (translate_datasets does)", entry,
+                     t.pois_tail_n > 0 ? "Poisson" : "logistic", t.pois_tail_n > 0 ? "kPoisTail" : "kLogitTail");
+  if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE)
+    return amwg_fail(AMWG_EINVAL, "%s: AMWG_LANES_AUTOTUNE is not supported (the timing runs would have to search the geometries that serve whole datasets); give lanes_per_chain or leave it 0", entry);
+  return create_user(entry, models, n_datasets, params, n_params, init, comp_opts, options, out);
+}
+
+static int create_user(const char *entry, const amwg_user_model *models, int D, const amwg_param_desc *params, int32_t n_params, const double *init,
+                       const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out) {
+  const amwg_user_model *m = &models[0];
+  (void)entry;
   if (n_params < 1 || n_params > (1 << 20)) return amwg_fail(AMWG_EINVAL, "amwg_create_user: %d parameter entries (supported: 1..%d, of which at most %d stepped)", n_params, 1 << 20, kMaxIndex);
   if (m->n_arrays < 0) return amwg_fail(AMWG_EINVAL, "amwg_create_user: %d data arrays", m->n_arrays);
   if (m->n_arrays && (!m->arrays || !m->array_len)) return amwg_fail(AMWG_EINVAL, "amwg_create_user: arrays is null");
@@ -634,8 +700,9 @@ int amwg_create_user(const amwg_user_model *m, const amwg_param_desc *params, in
   TRYB(build_layout(s, params, n_params, true));
   for (int p = 0; p < n_params; ++p) s->user_has_binary = s->user_has_binary || params[p].type == AMWG_BINARY;
   hipDeviceProp_t prop;
+  if (D > 1) { s->n_datasets = D; s->ds_n_obs.assign((size_t)D, 0); }      // (before the plan: only geometries that serve whole datasets are searched, amwg_plan.hip)
   TRYB(open_device(s, &prop));
-  TRYB(upload_user_arrays(s, m));
+  TRYB(upload_user_arrays(s, models, D));
   TRYB(alloc_chain_state(s, params, n_params, init, comp_opts));
   TRYB(plan_and_prepare(s, prop, clk, [&]() { return load_user_kernel(s, m->source, prop.gcnArchName); }));
   *out = guard.release();

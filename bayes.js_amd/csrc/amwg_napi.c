@@ -282,6 +282,84 @@ static napi_value dataset_summary(napi_env env, napi_callback_info info, int (*f
 static napi_value DatasetMoments(napi_env env, napi_callback_info info) { return dataset_summary(env, info, amwg_last_sample_dataset_moments, "mean", "sd"); }
 static napi_value DatasetConvergence(napi_env env, napi_callback_info info) { return dataset_summary(env, info, amwg_last_sample_dataset_diagnostics, "rhat", "ess"); }
 
+/* createUserDatasets({source, datasets: [[Float64Array...] per dataset], array_types, n_derived, lds_bytes, ...}, params[], init, compOpts[], options) -> external handle:
+ * one translated closure on several datasets of equal shape (amwg_create_user_datasets; options.chains is the total).  The fields are createUser's, with the arrays of
+ * every dataset under `datasets` in place of `arrays`. */
+static napi_value CreateUserDatasets(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  if (!get_args(env, info, 5, a)) return NULL;
+  napi_value v, sets;
+  if (!prop(env, a[0], "source", &v)) { napi_throw_type_error(env, NULL, "amwg_napi.createUserDatasets: source missing"); return NULL; }
+  size_t slen = 0;
+  if (napi_get_value_string_utf8(env, v, NULL, 0, &slen) != napi_ok) { napi_throw_type_error(env, NULL, "amwg_napi.createUserDatasets: source must be a string"); return NULL; }
+  uint32_t D = 0, n_arr = 0;
+  if (!prop(env, a[0], "datasets", &sets) || napi_get_array_length(env, sets, &D) != napi_ok || D < 1) {
+    napi_throw_type_error(env, NULL, "amwg_napi.createUserDatasets: datasets must be a non-empty array of arrays of Float64Arrays");
+    return NULL;
+  }
+  { napi_value e; napi_get_element(env, sets, 0, &e); if (napi_get_array_length(env, e, &n_arr) != napi_ok) n_arr = 0; }
+  char *src = (char *)malloc(slen + 1);
+  const size_t cells = (size_t)D * (n_arr ? n_arr : 1);
+  const double **arrs = (const double **)calloc(cells, sizeof *arrs);
+  int64_t *lens = (int64_t *)calloc(cells, sizeof *lens);
+  int32_t *types = (int32_t *)calloc(n_arr ? n_arr : 1, sizeof *types);
+  amwg_user_model *um = (amwg_user_model *)calloc(D, sizeof *um);
+  const char *bad = (!src || !arrs || !lens || !types || !um) ? "out of memory" : NULL;
+  if (!bad) napi_get_value_string_utf8(env, v, src, slen + 1, &slen);
+  for (uint32_t d = 0; d < D && !bad; d++) {
+    napi_value set;
+    uint32_t n_here = 0;
+    napi_get_element(env, sets, d, &set);
+    if (napi_get_array_length(env, set, &n_here) != napi_ok) { bad = "every dataset must be an array of Float64Arrays"; break; }
+    um[d].n_arrays = (int32_t)n_here;      /* (a count that differs from dataset 0's is the library's to refuse, with its message) */
+    for (uint32_t i = 0; i < n_here && i < n_arr; i++) {
+      napi_value e;
+      size_t n = 0;
+      napi_get_element(env, set, i, &e);
+      arrs[(size_t)d * n_arr + i] = (const double *)typed_data(env, e, napi_float64_array, &n);
+      lens[(size_t)d * n_arr + i] = (int64_t)n;
+      if (!arrs[(size_t)d * n_arr + i] && n) { bad = "arrays must be Float64Arrays"; break; }
+    }
+    if (n_here > n_arr) um[d].n_arrays = (int32_t)n_arr + 1;      /* (still unequal, and nothing past the n_arr cells is read) */
+  }
+  if (bad) {
+    free(src); free(arrs); free(lens); free(types); free(um);
+    char msg[160];
+    snprintf(msg, sizeof msg, "amwg_napi.createUserDatasets: %s", bad);
+    napi_throw_type_error(env, NULL, msg);
+    return NULL;
+  }
+  {
+    napi_value tv;
+    uint32_t nt = 0;
+    if (prop(env, a[0], "array_types", &tv) && napi_get_array_length(env, tv, &nt) == napi_ok)
+      for (uint32_t i = 0; i < nt && i < n_arr; i++) { napi_value e; napi_get_element(env, tv, i, &e); types[i] = (int32_t)arg_i64(env, e); }
+  }
+  for (uint32_t d = 0; d < D; d++) {
+    um[d].source = src;
+    um[d].arrays = arrs + (size_t)d * n_arr;
+    um[d].array_len = lens + (size_t)d * n_arr;
+    um[d].array_type = types;
+    um[d].n_derived = (int32_t)prop_i64(env, a[0], "n_derived", 0);
+    um[d].lds_bytes = (int32_t)prop_i64(env, a[0], "lds_bytes", 0);
+    um[d].lds_bytes_one_lane = (int32_t)prop_i64(env, a[0], "lds_bytes_one_lane", 0);
+    um[d].parallel = (int32_t)prop_i64(env, a[0], "parallel", 0);
+    um[d].max_threads = (int32_t)prop_i64(env, a[0], "max_threads", 0);
+    um[d].work_per_eval = prop_double(env, a[0], "work_per_eval", 0.0);
+    um[d].work_one_lane = prop_double(env, a[0], "work_one_lane", 0.0);
+    um[d].rows_n_obs = (int32_t)prop_double(env, a[0], "rows_n_obs", 0.0);
+    um[d].rows_groups = (int32_t)prop_double(env, a[0], "rows_groups", 0.0);
+    um[d].rows_sweep = (int32_t)prop_double(env, a[0], "rows_sweep", 0.0);
+  }
+  amwg_param_desc *pd; amwg_comp_opt *co; uint32_t n_params; const double *init; amwg_options op;
+  if (!parse_common(env, a, &pd, &co, &n_params, &init, &op)) { free(src); free(arrs); free(lens); free(types); free(um); return NULL; }
+  amwg_sampler *s = NULL;
+  int rc = amwg_create_user_datasets(um, (int32_t)D, pd, (int32_t)n_params, init, co, &op, &s);
+  free(pd); free(co); free(src); free(arrs); free(lens); free(types); free(um);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  return wrap_sampler(env, s);
+}
+
 /* createUser({source, arrays: [Float64Array...], n_derived, lds_bytes, parallel, max_threads}, params[], init, compOpts[], options)
  * -- a closure translated by bayes.js_amd/translate.js (amwg_create_user) */
 static napi_value CreateUser(napi_env env, napi_callback_info info) {
@@ -852,7 +930,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

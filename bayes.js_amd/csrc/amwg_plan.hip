@@ -357,7 +357,16 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
 int adopt_plan(amwg_sampler *s, const LaunchPlan &p) {
   s->plan = p;
   s->d.pad = p.pad;
-  if (s->user) return size_wave_scratch(s);
+  if (s->user) {
+    if (s->n_datasets > 1) {      // a closure on many datasets launches the twin (amwg_user_dataset.h); how many workgroups serve one dataset
+      const int cpw = chains_per_workgroup(p.lanes, p.block);
+      const int64_t cpd = chains_per_dataset(s);
+      if (p.cpb || p.pad || (p.variant != Variant::UserStep && p.variant != Variant::UserStepCert) || cpd % cpw != 0)
+        return amwg_fail(AMWG_EINVAL, "internal: a plan of %d lanes in workgroups of %d (cpb %d, pad %d) for a closure on datasets of %lld chains", p.lanes, p.block, p.cpb, p.pad, (long long)cpd);
+      s->ds_blocks_per_dataset = (int)(cpd / cpw);
+    }
+    return size_wave_scratch(s);
+  }
   if (s->model == AMWG_MODEL_HIER_NORMAL) s->mc.group_lane_const = (int32_t)((s->hier_periodic_mask >> log2_of(p.lanes)) & 1u);
   KernelPair k;
   switch (p.variant) {

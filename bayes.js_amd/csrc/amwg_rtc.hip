@@ -18,7 +18,7 @@
 extern "C" {
 extern const char amwg_hdr_stdint[], amwg_hdr_types[], amwg_hdr_math[], amwg_hdr_div[], amwg_hdr_ld[], amwg_hdr_philox[],
     amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[], amwg_hdr_ltail[],
-    amwg_hdr_user_kernels[];
+    amwg_hdr_user_kernels[], amwg_hdr_user_dataset[];
 }
 
 // ---- hiprtc: a translated closure + its step kernels (amwg_user_kernels.h) -> code object for one (lanes, workgroup) geometry
@@ -112,11 +112,12 @@ static void dump_code_object(const std::vector<char> &code) {      // developmen
 }
 
 // use_cache = false: compile even if the on-disk cache has the object (the caller found the cached one unloadable)
-static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool use_cache = true) {
+// datasets: with the dataset twins (amwg_user_dataset.h) compiled in -- one more compile option, hence one more part of the cache key
+static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool datasets, bool use_cache = true) {
   static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h", "amwg_kernel.h", "amwg_user.h",
-                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_ltail.h", "amwg_user_kernels.h"};
+                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_ltail.h", "amwg_user_kernels.h", "amwg_user_dataset.h"};
   const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox, amwg_hdr_kernel, amwg_hdr_user,
-                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_ltail, amwg_hdr_user_kernels};
+                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_ltail, amwg_hdr_user_kernels, amwg_hdr_user_dataset};
   constexpr int kHeaders = (int)(sizeof(texts) / sizeof(texts[0]));
   const std::string prog_src = user_program(source, lanes, block);
 #if defined(AMWG_AUDIT)      // (libamwg_audit.so: the certified kernels of translated closures record |A - E| / eps as the built-in families' do)
@@ -126,6 +127,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
 #else
   const char *const kOpts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value", "-falign-loops=64"};
 #endif
+  static const char *const kDatasetsOpt = "-DAMWG_USER_DATASETS=1";
   // the on-disk cache (see above)
   std::string dir = cache_dir(), file;
   CacheKey key{};
@@ -134,6 +136,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
     (void)hiprtcVersion(&rt_major, &rt_minor);
     std::vector<std::string> parts = {prog_src, arch, "hiprtc " + std::to_string(rt_major) + "." + std::to_string(rt_minor)};
     for (const char *o : kOpts) parts.push_back(o);
+    if (datasets) parts.push_back(kDatasetsOpt);
     for (const char *t : texts) parts.push_back(t);
     key = hash_key(parts);
     char name[64];
@@ -150,6 +153,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
   // same floating-point contract as the Makefile: one rounding per operation, no fused contraction
   std::vector<const char *> opts = {arch_opt.c_str()};
   for (const char *o : kOpts) opts.push_back(o);
+  if (datasets) opts.push_back(kDatasetsOpt);
   r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
   if (r != HIPRTC_SUCCESS) {
     size_t n = 0;
@@ -187,18 +191,20 @@ int load_user_kernel(amwg_sampler *s, const char *source, const char *arch) {
   static std::mutex mu;
   static std::map<std::string, std::vector<char>> cache;
   const LaunchPlan &p = s->plan;
-  const std::string key = std::string(arch) + "|" + std::to_string(p.lanes) + "|" + std::to_string(p.block) + "|" + source;
+  const bool datasets = s->n_datasets > 1;      // (a dataset sampler: the code object with the twins, and the twin of the plan's kernel)
+  const std::string key = std::string(arch) + "|" + std::to_string(p.lanes) + "|" + std::to_string(p.block) + (datasets ? "|ds|" : "|") + source;
+  const std::string fn_name = std::string(info(p.variant).name) + (datasets ? "_ds" : "");
   std::lock_guard<std::mutex> lock(mu);
   auto it = cache.find(key);
   if (it == cache.end()) {
     std::vector<char> code;
-    TRYB(compile_user(source, p.lanes, p.block, arch, &code));
+    TRYB(compile_user(source, p.lanes, p.block, arch, &code, datasets));
     it = cache.emplace(key, std::move(code)).first;
   }
   if (s->user_module) return AMWG_OK;      // (autotune hands back the module it kept)
   auto load = [&]() {
     const hipError_t e = hipModuleLoadData(&s->user_module, it->second.data());
-    return e == hipSuccess ? hipModuleGetFunction(&s->user_fn, s->user_module, info(p.variant).name) : e;
+    return e == hipSuccess ? hipModuleGetFunction(&s->user_fn, s->user_module, fn_name.c_str()) : e;
   };
   hipError_t e = load();
   if (e != hipSuccess) {
@@ -206,7 +212,7 @@ int load_user_kernel(amwg_sampler *s, const char *source, const char *arch) {
     // driver) is dropped and the closure compiled afresh, once
     (void)hipGetLastError();
     if (s->user_module) { (void)hipModuleUnload(s->user_module); s->user_module = nullptr; }
-    TRYB(compile_user(source, p.lanes, p.block, arch, &it->second, false));
+    TRYB(compile_user(source, p.lanes, p.block, arch, &it->second, datasets, false));
     e = load();
     if (e != hipSuccess) return amwg_fail(AMWG_EHIP, "loading the compiled log_post failed: %s", hipGetErrorString(e));
   }
@@ -228,7 +234,15 @@ int amwg_code_cache_stats(int64_t *hits, int64_t *misses, char *dir, size_t dir_
 int amwg_compile_user(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes) {
   if (!source || !arch) return amwg_fail(AMWG_EINVAL, "amwg_compile_user: null argument");
   std::vector<char> code;
-  int rc = compile_user(source, lanes_per_chain, block_threads, arch, &code);
+  int rc = compile_user(source, lanes_per_chain, block_threads, arch, &code, false);
+  if (rc == AMWG_OK && code_bytes) *code_bytes = code.size();
+  return rc;
+}
+
+int amwg_compile_user_datasets(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes) {
+  if (!source || !arch) return amwg_fail(AMWG_EINVAL, "amwg_compile_user_datasets: null argument");
+  std::vector<char> code;
+  int rc = compile_user(source, lanes_per_chain, block_threads, arch, &code, true);
   if (rc == AMWG_OK && code_bytes) *code_bytes = code.size();
   return rc;
 }

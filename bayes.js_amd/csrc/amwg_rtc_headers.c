@@ -21,3 +21,4 @@ AMWG_TEXT(amwg_hdr_window, "amwg_window.h");
 AMWG_TEXT(amwg_hdr_ptail, "amwg_ptail.h");
 AMWG_TEXT(amwg_hdr_ltail, "amwg_ltail.h");
 AMWG_TEXT(amwg_hdr_user_kernels, "amwg_user_kernels.h");
+AMWG_TEXT(amwg_hdr_user_dataset, "amwg_user_dataset.h");

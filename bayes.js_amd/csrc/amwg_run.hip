@@ -4,12 +4,14 @@
 #include <sys/mman.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
 #include "amwg_host.h"
 #include "amwg_kernel.h"      // (StepArgs, and the kErr* bits the step kernels report)
 #include "amwg_dataset.h"     // (DatasetArgs: the second argument of a dataset sampler's kernel)
+#include "amwg_user_dataset.h"      // (UserDatasetArgs: the same for a translated closure)
 
 using namespace amwg;
 
@@ -83,12 +85,24 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
   if (p.lanes != 1) a.d.wave_scratch = nullptr;      // (sized for one-lane geometries only; no other kernel reads it)
   a.ch = s->ch;
   DatasetArgs ds{};      // (a dataset sampler: which workgroups serve which dataset, and where its data and constants lie)
-  if (s->n_datasets > 1) {
+  if (s->n_datasets > 1 && !s->user) {
     if (!s->ds_kernel || s->ds_blocks_per_dataset < 1 || (int64_t)s->ds_blocks_per_dataset * s->n_datasets != p.grid)
       return amwg_fail(AMWG_EINVAL, "internal: %d workgroups for %d datasets of %d workgroups each", p.grid, s->n_datasets, s->ds_blocks_per_dataset);
     ds.blocks_per_dataset = s->ds_blocks_per_dataset;
     ds.n_datasets = s->n_datasets;
     ds.consts = s->d_ds_consts;
+  }
+  // (a closure on many datasets: StepArgs and UserDatasetArgs, in that order, are the twin's argument buffer)
+  struct { StepArgs a; UserDatasetArgs ds; } ua{};
+  static_assert(offsetof(decltype(ua), ds) == sizeof(StepArgs) && sizeof(StepArgs) % alignof(UserDatasetArgs) == 0, "the second kernel argument follows the first without padding");
+  if (s->n_datasets > 1 && s->user) {
+    if (!s->d_user_ds_table || s->ds_blocks_per_dataset < 1 || (int64_t)s->ds_blocks_per_dataset * s->n_datasets != p.grid || s->user_ds_row_stride < kInlineUserArrays)
+      return amwg_fail(AMWG_EINVAL, "internal: %d workgroups for %d datasets of %d workgroups each (closure; table rows of %d entries)", p.grid, s->n_datasets, s->ds_blocks_per_dataset, s->user_ds_row_stride);
+    ua.ds.blocks_per_dataset = s->ds_blocks_per_dataset;
+    ua.ds.n_datasets = s->n_datasets;
+    ua.ds.row_stride = s->user_ds_row_stride;
+    ua.ds.n_arrays = s->user_ds_n_arrays;
+    ua.ds.table = s->d_user_ds_table;
   }
   // (a 0-step finalize launch on chains that have stepped -- amwg_chain_diag asking for the expression's value after a certified kernel ran -- is not "the latest call":
   // the sample call's launch count, its per-launch marks and its event pair stay, so that a diag() between sample_async and fetch_draws neither loses the copy overlap
@@ -110,7 +124,9 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     a.row0 = row;
     if (s->user) {
       size_t arg_bytes = sizeof a;
-      void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_bytes, HIP_LAUNCH_PARAM_END};
+      void *arg_buf = &a;
+      if (s->n_datasets > 1) { ua.a = a; arg_buf = &ua; arg_bytes = sizeof ua; }
+      void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, arg_buf, HIP_LAUNCH_PARAM_BUFFER_SIZE, &arg_bytes, HIP_LAUNCH_PARAM_END};
       HIP_TRY(hipModuleLaunchKernel(s->user_fn, (unsigned)p.grid, 1, 1, (unsigned)p.block, 1, 1, (unsigned)p.lds, s->stream, nullptr, extra));
     } else if (s->n_datasets > 1) {
       hipLaunchKernelGGL(s->ds_kernel, dim3(p.grid), dim3(p.block), (size_t)p.lds, s->stream, a, ds);

@@ -54,6 +54,9 @@ struct amwg_sampler {
   amwg::DatasetConsts *d_ds_consts = nullptr;
   int ds_blocks_per_dataset = 0;
   dataset_kernel_t ds_kernel = nullptr;
+  // ... of a translated closure (amwg_create_user_datasets; amwg_user_dataset.h): the device table [n_datasets][row_stride] of the datasets' arrays
+  const void *const *d_user_ds_table = nullptr;
+  int user_ds_row_stride = 0, user_ds_n_arrays = 0;
   int gl_rounds = 0;                // group_local: rows of the lane-major tile (GlLayoutHost::rounds; the group-local kernel's DataRef::pad)
   std::string kernel_name;          // amwg_kernel_name(): filled on first request
   uint32_t hier_periodic_mask = 0;   // HIER: bit j set = the group labels repeat with a lane stride of 2^j (g[i] == g[i mod 2^j])

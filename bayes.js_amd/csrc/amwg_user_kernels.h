@@ -35,3 +35,9 @@ extern "C" __global__ void __launch_bounds__(AMWG_USER_BLOCK) amwg_user_step_cer
     amwg::step_body<amwg::UserModel, AMWG_USER_LANES, (AMWG_USER_BLOCK <= 256 ? 256 : 1024), false, false, true>(a, smem);
   else amwg::device_error(a, amwg::kErrNoKernelBody);
 }
+
+// a dataset sampler (amwg_create_user_datasets) launches the twins of the two step kernels; the host defines the macro in the compile options of such a sampler
+// only, so an ordinary closure's code object stays what it was
+#if defined(AMWG_USER_DATASETS)
+#include "amwg_user_dataset.h"
+#endif

@@ -215,9 +215,12 @@ function AmwgSampler(params, log_post, data, options) {
   }
   this.model = recog ? recog.family : 'translated';
   // (the translator folds data-dependent constants and storage types into the generated source: one source per dataset is not one sampler)
-  if (datasets && !recog)
+  // options.translate: true beside options.datasets asks for one source for all datasets (translate.js translate_datasets): opt-in, so that a call that threw keeps throwing
+  const translatedDatasets = !!datasets && !recog && !!opt('translate', false);
+  if (datasets && !recog && !translatedDatasets)
     throw 'AmwgSampler (MI355X): options.datasets needs a closure that is recognised as a built-in family (normal, beta_bern, pois_glm); this one goes through the translator, ' +
-          'which folds data-dependent constants and storage types into the generated source, and is not supported with options.datasets';
+          'which folds data-dependent constants and storage types into the generated source, and is not supported with options.datasets unless options.translate: true asks for it: ' +
+          'every dataset is then translated and all must give ONE source, which needs datasets of equal shape (every data array of the same dimensions in every dataset)';
 
   // flatten params / init / options in Object.keys order (the stepper order of mcmc.js:839)
   const descs = [], init = [], compOpts = [];
@@ -260,6 +263,7 @@ function AmwgSampler(params, log_post, data, options) {
   let desc = null, user = null;
   this.derived = [];
   let dsDescs = null;      // options.datasets: one description per dataset (same family and hyper-parameters: one closure)
+  let userSets = null;     // ... of a translated closure: the arrays of every dataset, [datasets][n_arrays] (one source)
   if (recog && datasets) {
     if (this.chains % datasets.length !== 0) throw 'AmwgSampler (MI355X): options.chains (' + this.chains + ', the total) must be a multiple of the ' + datasets.length + ' datasets';
     dsDescs = datasets.map((d) => buildModelDesc(recog, d, this.params));
@@ -267,11 +271,19 @@ function AmwgSampler(params, log_post, data, options) {
     this.dataset_n_obs = dsDescs.map((d) => d.n_obs);
   } else if (recog) desc = buildModelDesc(recog, data, this.params);
   else {
-    const tr = translator.translate(log_post, translatedParams, data, { constants: options.constants, helpers: options.helpers,
-      lds_budget: options.lds_budget, max_threads: options.max_threads, unroll: options.unroll, state_object: shared ? shared.state : undefined });
+    const trOpts = { constants: options.constants, helpers: options.helpers,
+      lds_budget: options.lds_budget, max_threads: options.max_threads, unroll: options.unroll, state_object: shared ? shared.state : undefined };
+    if (translatedDatasets && this.chains % datasets.length !== 0) throw 'AmwgSampler (MI355X): options.chains (' + this.chains + ', the total) must be a multiple of the ' + datasets.length + ' datasets';
+    // (many datasets: ONE translation over all of them -- also with options.devices: the shards get slices of its arrays, and a chain's draws do not depend on its shard)
+    const tr = translatedDatasets ? translator.translate_datasets(log_post, translatedParams, datasets, trOpts) : translator.translate(log_post, translatedParams, data, trOpts);
+    if (translatedDatasets) {
+      userSets = tr.arrays;
+      this.chains_per_dataset = this.chains / datasets.length;
+      this.dataset_n_obs = datasets.map(() => 0);      // (a closure's arrays carry their own lengths: amwg_dataset_n_obs says 0)
+    }
     this.derived = tr.derived;
     this.translation = tr;
-    user = { source: tr.source, arrays: tr.arrays, array_types: tr.array_types, n_derived: tr.derived.length, lds_bytes: tr.lds_bytes, lds_bytes_one_lane: tr.lds_bytes_one_lane, parallel: tr.parallel,
+    user = { source: tr.source, arrays: translatedDatasets ? tr.arrays[0] : tr.arrays, array_types: tr.array_types, n_derived: tr.derived.length, lds_bytes: tr.lds_bytes, lds_bytes_one_lane: tr.lds_bytes_one_lane, parallel: tr.parallel,
              max_threads: tr.max_threads, work_per_eval: tr.work_per_eval, work_one_lane: tr.work_one_lane, rows_n_obs: tr.rows_n_obs, rows_groups: tr.rows_groups, rows_sweep: tr.rows_sweep };
   }
   this.PR = this.P + this.derived.length;   // values per recorded draw
@@ -280,7 +292,8 @@ function AmwgSampler(params, log_post, data, options) {
   const N = native();
   this._shards = [];
   // (options.datasets: whole datasets are dealt to the shards in contiguous slices; a shard is a dataset sampler over its slice)
-  const units = dsDescs ? dsDescs.length : this.chains, unit = dsDescs ? this.chains_per_dataset : 1;
+  const nSets = dsDescs ? dsDescs.length : (userSets ? userSets.length : 0);
+  const units = nSets ? nSets : this.chains, unit = nSets ? this.chains_per_dataset : 1;
   const D = Math.min(devices.length, units), per = Math.floor(units / D), rem = units % D;
   let offset = 0, firstDataset = 0;
   let lanes = opt('lanes_per_chain', 0);
@@ -289,13 +302,16 @@ function AmwgSampler(params, log_post, data, options) {
     // (a shard of a dataset sampler is a dataset sampler over its slice: ragged where the sizes of ITS slice differ, else the entry that insists on equal sizes)
     const slice = dsDescs ? dsDescs.slice(firstDataset, firstDataset + nUnits) : null;
     const unequal = slice !== null && slice.some((d) => d.n_obs !== slice[0].n_obs);
-    const create = user ? N.createUser : (dsDescs ? (unequal ? N.createDatasetsRagged : N.createDatasets) : N.create);
-    const handle = create(user || (dsDescs ? slice : desc), descs, Float64Array.from(init), compOpts, {
+    // (a translated closure: the shard's slice of the datasets' arrays under the one source; a shard that was dealt one dataset is an ordinary closure sampler on it)
+    const userHere = !userSets ? user : (nUnits > 1 ? Object.assign({}, user, { arrays: undefined, datasets: userSets.slice(firstDataset, firstDataset + nUnits) })
+                                                    : Object.assign({}, user, { arrays: userSets[firstDataset] }));
+    const create = user ? (userSets && nUnits > 1 ? N.createUserDatasets : N.createUser) : (dsDescs ? (unequal ? N.createDatasetsRagged : N.createDatasets) : N.create);
+    const handle = create(userHere || (dsDescs ? slice : desc), descs, Float64Array.from(init), compOpts, {
       chains: count, seed: this.seed, chain_offset: opt('chain_offset', 0) + offset, device: devices[r],
       lanes_per_chain: lanes, block_threads: opt('block_threads', 0),
       steps_per_launch: opt('steps_per_launch', 0), exact_division: opt('exact_division', 0), group_local: opt('group_local', 0) ? 1 : 0, full_evaluation: Number(opt('full_evaluation', 0)) | 0, test_bound_shift: Number(opt('test_bound_shift', 0)) | 0,
       sufficient_statistics: opt('sufficient_statistics', 0) ? 1 : 0 });
-    this._shards.push({ handle, offset, count, device: devices[r], datasets: dsDescs ? nUnits : 0 });
+    this._shards.push({ handle, offset, count, device: devices[r], datasets: nSets ? nUnits : 0 });
     firstDataset += nUnits;
     // one summation order for the whole job: what the first shard picked (cost model, or the measurement of lanes_per_chain: -2)
     // is what the other shards get -- a chain's draws must not depend on the shard it landed in

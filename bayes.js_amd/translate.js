@@ -346,8 +346,15 @@ Translator.prototype.registerArray = function (key, value) {
     if (v < -2147483648 || v > 2147483647) i32 = false;
     if (v !== 0 && v !== 1) is01 = false;
   }
-  const type = this.opts.f64_arrays ? 0 : (u8 ? 1 : (i32 ? 2 : 0));
-  this.arrays.push({ key, flat, dims, type, is01: is01 && type === 1, ctype: ['double', 'uint8_t', 'int32_t'][type], esize: [8, 1, 4][type] });
+  let type = this.opts.f64_arrays ? 0 : (u8 ? 1 : (i32 ? 2 : 0));
+  // translate_datasets (below): one source serves D datasets, so what the values of ONE dataset would decide -- the storage type, is01, the integer range that
+  // removes bounds checks -- is handed in per key, formed over all datasets (the widest type, is01 only if everywhere, the hull of the ranges)
+  const own = (o) => o && Object.prototype.hasOwnProperty.call(o, key);
+  if (own(this.opts.array_types)) type = this.opts.array_types[key];
+  if (own(this.opts.array_is01)) is01 = !!this.opts.array_is01[key];
+  const A = { key, flat, dims, type, is01: is01 && type === 1, ctype: ['double', 'uint8_t', 'int32_t'][type], esize: [8, 1, 4][type] };
+  if (own(this.opts.array_ranges)) A.range = this.opts.array_ranges[key] ? this.opts.array_ranges[key].slice() : null;
+  this.arrays.push(A);
   this.arrayIds.set(key, id);
   return id;
 };
@@ -429,6 +436,17 @@ Translator.prototype.lookup = function (name) {
 };
 
 Translator.prototype.dataValue = function (path, v) {
+  if (typeof v === 'number' && path && path[0] !== '#') {
+    // (a scalar field of the data: folded to a literal -- unless translate_datasets found that it differs between the datasets: then a one-element f64 array)
+    this.scalarsRead = this.scalarsRead || {};
+    this.scalarsRead[path] = v;
+    if (this.opts.varying_scalars && this.opts.varying_scalars.has(path)) {
+      const id = this.registerArray('#scalar:' + path, [v]);
+      if (this.arrays[id].type !== 0) { const A = this.arrays[id]; A.type = 0; A.ctype = 'double'; A.esize = 8; A.is01 = false; A.range = null; }      // always f64
+      (this.varyingIds = this.varyingIds || new Set()).add(id);
+      return num('A' + id + '[0]', false);
+    }
+  }
   if (typeof v === 'number') return cnum(v);
   if (typeof v === 'boolean') return cnum(v ? 1 : 0);
   if (typeof v === 'string') return { t: 'strlit', v };
@@ -554,12 +572,12 @@ Translator.prototype.index = function (objV, idxV) {
   const guarded = (code) => { const v = num('((' + guards.join(' && ') + ') ? ' + code + ' : __builtin_nan(""))', false); v.undef = '!(' + guards.join(' && ') + ')'; return v; };
   if (objV.t === 'dataArr') {
     // a constant element of a data array is a constant
-    if (/^\d+$/.test(sum) && !G) return cnum(this.arrays[objV.id].flat[Number(sum)]);
+    if (/^\d+$/.test(sum) && !G && !this.opts.no_const_element_fold) return cnum(this.arrays[objV.id].flat[Number(sum)]);
     const A = this.arrays[objV.id];
     if (G) return guarded((A.type === 0 ? '' : '(double)') + 'A' + objV.id + '[' + sum + ']');
     const v = A.type === 0 ? num('A' + objV.id + '[' + sum + ']', false) : num('(int)A' + objV.id + '[' + sum + ']', true, undefined, '(double)A' + objV.id + '[' + sum + ']');
     if (A.type !== 0) {        // an element of an integer array lies between the array's extremes
-      if (!A.range) { let lo = Infinity, hi = -Infinity; for (let q = 0; q < A.flat.length; q++) { if (A.flat[q] < lo) lo = A.flat[q]; if (A.flat[q] > hi) hi = A.flat[q]; } A.range = A.flat.length ? [lo, hi] : null; }
+      if (A.range === undefined) { let lo = Infinity, hi = -Infinity; for (let q = 0; q < A.flat.length; q++) { if (A.flat[q] < lo) lo = A.flat[q]; if (A.flat[q] > hi) hi = A.flat[q]; } A.range = A.flat.length ? [lo, hi] : null; }
       withRange(v, A.range);
     }
     v.src = { id: objV.id, off: sum };
@@ -1329,6 +1347,11 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
   const ind2 = indent + '    ';
   if (canon) {
     const startV = this.expr(canon.startAst), boundV = this.expr(canon.boundAst);
+    // (translate_datasets: a loop's extent is part of the one source -- the unrolled and staged forms, the LDS copies and the work estimate carry it as a constant)
+    if (this.varyingIds && this.varyingIds.size)
+      for (const bv of [startV, boundV])
+        for (const id of this.varyingIds) if (bv.cst === undefined && new RegExp('\\bA' + id + '\\[0\\]').test(String(bv.code) + ' ' + String(bv.dcode || '')))
+          this.fail('the bound of the loop over ' + canon.name + ' is data' + this.arrays[id].key.slice('#scalar:'.length) + ', whose value differs between the datasets of options.datasets: a loop bound must be the same constant in every dataset');
     this.flush(out, indent);
     this.setLocal(canon.name, startV);
     const isInt = this.localTypes[canon.name] === 'int';
@@ -2191,6 +2214,17 @@ Translator.prototype.run = function () {
     arrays: this.arrays.map((a) => a.flat),
     array_types: this.arrays.map((a) => a.type),
     array_keys: this.arrays.map((a) => a.key),
+    // what the VALUES of this data decided (translate_datasets forms the union over the datasets): dimensions, is01, the extremes of an integer-typed array
+    // (null: not integer-typed, or empty) and every scalar field of the data that was read, with its value
+    array_dims: this.arrays.map((a) => a.dims.slice()),
+    array_is01: this.arrays.map((a) => !!a.is01),
+    array_ranges: this.arrays.map((a) => {
+      if (a.type === 0 || !a.flat.length) return null;
+      let lo = Infinity, hi = -Infinity;
+      for (let q = 0; q < a.flat.length; q++) { if (a.flat[q] < lo) lo = a.flat[q]; if (a.flat[q] > hi) hi = a.flat[q]; }
+      return [lo, hi];
+    }),
+    scalars_read: Object.assign({}, this.scalarsRead || {}),
     derived: this.derived.slice(),
     lds_bytes: off,
     lds_bytes_one_lane: P1.bytes,
@@ -2469,4 +2503,91 @@ function translate(fn, params, data, options) {
   return new Translator(fn, params, data, options).run();
 }
 
-module.exports = { translate, parseFunctionSource, hexFloat, tokenize, foldConstantNormInv };
+// ---- MANY DATASETS, ONE SOURCE (include/amwg.h amwg_create_user_datasets; csrc/amwg_user_dataset.h).
+// translate_datasets(log_post, completedParams, datasets[, options]) -> the result of translate() once, with `arrays` as [D][n_arrays].
+// The generated source folds facts about the data's VALUES into its text in many places (storage types, index ranges, is01, constant elements, scalar fields, the
+// predicates and tables of the fast paths).  Which places is not what soundness rests on: every dataset is translated ON ITS OWN VALUES, under options that replace
+// the per-dataset facts by their union over all datasets, and the D texts must come out byte-identical.  Dataset d then runs a text that IS its own translation --
+// with a wider storage type, a weaker is01, a larger index range than its values alone would give, each of which is a sound translation of the same closure.
+//   pass 1: every dataset alone (no row plan, no Poisson / logistic tail: those write layouts and sums over the data into the source) -> per array key the type, is01,
+//           range and dimensions; per scalar field its value.  Union: the widest type (u8 < i32 < f64), is01 if everywhere, the hull; a scalar that differs is VARYING.
+//   pass 2: every dataset again with array_types / array_is01 / array_ranges by key, varying_scalars (read from a one-element array `#scalar:<path>`; where the
+//           translator needs such a value as a constant its own failure is the refusal) and no_const_element_fold.
+//   the check: D identical texts.  If not, once more without the K-valued fast-forward, the staged normal pass and the certified tail, whose tables and predicates
+//           may legitimately differ between datasets; then the refusal.
+const DATASET_BASE_OPTS = { no_row_plan: true, no_pois_tail: true, no_logit_tail: true, no_const_element_fold: true };
+const DATASET_RETRY_OPTS = { no_fast_forward: true, no_cert_tail: true, no_staged_norm: true, no_tail_rows: true, no_tail_linear: true };
+const TYPE_RANK = [2, 0, 1];      // AMWG_F64 = 0, AMWG_U8 = 1, AMWG_I32 = 2 -> u8 < i32 < f64
+function translate_datasets(fn, params, datasets, options) {
+  if (!Array.isArray(datasets) || datasets.length < 1) throw 'translate_datasets: datasets must be a non-empty array of data objects';
+  const D = datasets.length, user = Object.assign({}, options || {});
+  const run = (d, extra) => {
+    try { return new Translator(fn, params, datasets[d], Object.assign({}, user, DATASET_BASE_OPTS, extra)).run(); }
+    catch (e) {
+      const msg = typeof e === 'string' ? e : (e && e.message) || String(e);
+      const vs = extra && extra.varying_scalars && extra.varying_scalars.size ? '; in dataset mode data' + Array.from(extra.varying_scalars).join(', data') +
+        ' is read at run time because its value differs between the datasets, so it cannot stand where the translator needs a constant (a loop bound, a dimension, a constant index)' : '';
+      throw msg + ' [options.datasets, dataset ' + d + ']' + vs;
+    }
+  };
+  // pass 1
+  const first = [];
+  for (let d = 0; d < D; d++) first.push(run(d, null));
+  const types = {}, is01 = {}, ranges = {}, dims = {}, scalars = {}, varying = new Set();
+  let derivedDiffer = false;
+  for (let d = 0; d < D; d++) {
+    const r = first[d];
+    r.array_keys.forEach((key, j) => {
+      const rg = r.array_ranges[j];
+      if (!Object.prototype.hasOwnProperty.call(types, key)) {
+        types[key] = r.array_types[j]; is01[key] = r.array_is01[j]; ranges[key] = rg ? rg.slice() : null; dims[key] = { d, dims: r.array_dims[j] };
+        return;
+      }
+      if (dims[key].dims.join('x') !== r.array_dims[j].join('x')) {
+        if (key[0] === '#') { derivedDiffer = true; return; }      // (a table the translator derived: its size may follow the values -- the retry below drops those)
+        throw 'AmwgSampler (MI355X): options.datasets with a translated closure needs datasets of equal shape: data' + key + ' has dimensions [' + r.array_dims[j].join(', ') + '] in dataset ' + d +
+              ' and [' + dims[key].dims.join(', ') + '] in dataset ' + dims[key].d + ' (ragged closure datasets are not supported: the generated loops and LDS copies carry the lengths as constants)';
+      }
+      if (TYPE_RANK[r.array_types[j]] > TYPE_RANK[types[key]]) types[key] = r.array_types[j];
+      is01[key] = is01[key] && r.array_is01[j];
+      ranges[key] = ranges[key] && rg ? [Math.min(ranges[key][0], rg[0]), Math.max(ranges[key][1], rg[1])] : null;
+    });
+    for (const path of Object.keys(r.scalars_read)) {
+      const v = r.scalars_read[path];
+      if (!Object.prototype.hasOwnProperty.call(scalars, path)) scalars[path] = v;
+      else if (!Object.is(scalars[path], v)) varying.add(path);
+    }
+  }
+  for (const key of Object.keys(types)) { if (types[key] === 0) ranges[key] = null; if (types[key] !== 1) is01[key] = false; }
+  // pass 2 and the check
+  const union = { array_types: types, array_is01: is01, array_ranges: ranges, varying_scalars: varying };
+  const META = ['derived', 'lds_bytes', 'lds_bytes_one_lane', 'parallel', 'max_threads', 'array_types', 'array_keys', 'array_dims', 'rows_n_obs', 'cert_tail_n', 'pois_tail_n', 'logit_tail_n'];
+  const differs = (rs) => {      // -> null, or {d, why}
+    for (let d = 1; d < D; d++) {
+      if (rs[d].source !== rs[0].source) return { d, text: true };
+      for (const f of META) if (JSON.stringify(rs[d][f]) !== JSON.stringify(rs[0][f])) return { d, field: f };
+    }
+    return null;
+  };
+  let second = null, bad = derivedDiffer ? { d: 0 } : null;
+  if (!bad) { second = []; for (let d = 0; d < D; d++) second.push(run(d, union)); bad = differs(second); }
+  if (bad) { second = []; for (let d = 0; d < D; d++) second.push(run(d, Object.assign({}, union, DATASET_RETRY_OPTS))); bad = differs(second); }
+  if (bad) {
+    const a = second[0].source.split('\n'), b = second[bad.d].source.split('\n');
+    let ln = 0;
+    while (ln < a.length && ln < b.length && a[ln] === b[ln]) ln++;
+    throw 'AmwgSampler (MI355X): options.datasets with a translated closure needs ONE generated source for all datasets, and the source of dataset ' + bad.d + ' differs from dataset 0\'s' +
+          (bad.text ? ' at line ' + (ln + 1) + ':\n  dataset 0: ' + (a[ln] || '(end)').trim() + '\n  dataset ' + bad.d + ': ' + (b[ln] || '(end)').trim() + '\n' : ' in ' + bad.field + ' (' + JSON.stringify(second[0][bad.field]) + ' against ' + JSON.stringify(second[bad.d][bad.field]) + '). ') +
+          'The usual cause: the text of the closure depends on a value of the data -- a loop bound, an array of records or of strings with different levels, a constant that is read from the data.';
+  }
+  const out = Object.assign({}, second[0]);
+  out.arrays = second.map((r) => r.arrays);
+  out.n_datasets = D;
+  out.array_is01 = second[0].array_keys.map((k) => !!is01[k]);
+  out.array_ranges = second[0].array_keys.map((k) => (Object.prototype.hasOwnProperty.call(ranges, k) ? ranges[k] : null));
+  out.varying_scalars = Array.from(varying);
+  delete out.scalars_read;
+  return out;
+}
+
+module.exports = { translate, translate_datasets, parseFunctionSource, hexFloat, tokenize, foldConstantNormInv };

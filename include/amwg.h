@@ -190,9 +190,9 @@ int amwg_create_datasets(const amwg_model_desc *models, int32_t n_datasets, cons
  * sum, smallest first 1.17, a shuffled order 1.53.  With one workgroup per CU or fewer the order does not matter: the launch lasts as long as the largest dataset. */
 int amwg_create_datasets_ragged(const amwg_model_desc *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
                                 const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
-/* Datasets of a sampler: 1 for every sampler not made by amwg_create_datasets / amwg_create_datasets_ragged with n_datasets > 1. */
+/* Datasets of a sampler: 1 for every sampler not made by amwg_create_datasets / amwg_create_datasets_ragged / amwg_create_user_datasets with n_datasets > 1. */
 int amwg_num_datasets(const amwg_sampler *s);
-/* n_obs of every dataset, n_obs[amwg_num_datasets(s)] (an ordinary sampler: its one size; a translated closure, whose arrays carry their own lengths: 0). */
+/* n_obs of every dataset, n_obs[amwg_num_datasets(s)] (an ordinary sampler: its one size; a translated closure, whose arrays carry their own lengths: 0, one per dataset). */
 int amwg_dataset_n_obs(const amwg_sampler *s, int32_t *n_obs);
 /* amwg_last_sample_moments per dataset, computed on the device over the dataset's chains x kept draws: mean[D][P], sd[D][P]. */
 int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd);
@@ -243,9 +243,28 @@ typedef struct {
 int amwg_create_user(const amwg_user_model *model, const amwg_param_desc *params, int32_t n_params, const double *init,
                      const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
 
+/* MANY DATASETS IN ONE SAMPLER FOR A TRANSLATED CLOSURE: amwg_create_datasets for amwg_create_user.  models[0..n_datasets) describe the SAME closure on n_datasets
+ * datasets OF EQUAL SHAPE -- every array has the same length and storage type in every dataset, the values are free -- and carry the SAME source: bayes.js_amd/translate.js
+ * translate_datasets translates every dataset under the union of what the values decide (the widest storage type, the hull of the index ranges, scalar fields that differ
+ * read from one-element arrays) and insists that all texts come out identical.  Chains, cpd, the geometries that serve whole datasets, the pooled summaries' refusal and
+ * the per-dataset summaries are those of amwg_create_datasets above; derived quantities are recorded and summarised per dataset like the components.  Dataset d's chains are
+ * bit for bit the chains of an amwg_create_user sampler compiled from the same source on models[d]'s arrays with chain_offset + d * cpd at the same lanes_per_chain and
+ * block_threads.  The kernel is the twin of the ordinary one (amwg_kernel_name: "amwg_user_step_ds", "amwg_user_step_cert_ds"; csrc/amwg_user_dataset.h): a workgroup takes
+ * its dataset's arrays from a device table of pointers [n_datasets][n_arrays]; per array the copies lie back to back in one allocation, each on a 256-byte boundary.
+ * n_datasets == 1 is amwg_create_user(models, ...).  amwg_dataset_n_obs fills n_datasets zeros (a closure's arrays carry their own lengths).
+ * Refused with AMWG_EINVAL before a device is opened, with a message that names the dataset and the field: a null argument, n_datasets < 1, chains % n_datasets != 0,
+ * models[d].source not string-equal to models[0].source, a difference in n_arrays, any array_len or array_type, n_derived, lds_bytes, lds_bytes_one_lane, parallel,
+ * max_threads or rows_*; a source with a row plan (kRowN) or a certified Poisson / logistic tail (kPoisTail / kLogitTail) -- their layout and bounds are formed from one
+ * dataset's values; such closures run with the expression in every update here, per-dataset versions are follow-ups --; AMWG_LANES_AUTOTUNE; sufficient_statistics.
+ * NOT SUPPORTED: ragged closure datasets (the generated loops and LDS copies carry the lengths as constants), autotune, the stand-alone steppers. */
+int amwg_create_user_datasets(const amwg_user_model *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
+                              const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);
+
 /* hiprtc compilation of a translated closure without a device (build-time / CPU-test check).
  * arch e.g. "gfx950".  On failure returns AMWG_EINVAL and amwg_last_error() carries the compiler log. */
 int amwg_compile_user(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes);
+/* The same with the dataset twins compiled in (amwg_user_step_ds, amwg_user_step_cert_ds): the code object of an amwg_create_user_datasets sampler. */
+int amwg_compile_user_datasets(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes);
 
 /* Compiled closures are kept on disk ($AMWG_CACHE_DIR, else $XDG_CACHE_HOME/amwg, else $HOME/.cache/amwg; AMWG_CACHE_DIR="" disables), keyed by
  * program text + kernel headers + compile options + target + hiprtc version: a second process constructing the same sampler loads the
