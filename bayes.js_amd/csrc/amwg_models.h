@@ -180,7 +180,15 @@ struct NormalModel {
       S2 = __builtin_fma((double)d.n_obs, dm * dm, mc.suff_ss);
     } else
     // (the wavefront's pass in the 256- and 512-thread classes: blocks of 16 observations per lane where a lane has 512 registers, of 8 where it has 256)
-    if constexpr (BT <= 512) S2 = norm_sq_pass_wave<(BT <= 256 ? kWaveBlock : 8)>(lds_bytes_of(d, 1, 0) ? reinterpret_cast<const double *>(smem) : d.x, kc.mu, d.n_obs, wave_scratch_of(d));
+    // (the tile's address space is the pass's at compile time -- ds_read from the tile; the array in global memory, or no wave scratch, through the generic
+    // instantiation --: one wave-uniform branch here)
+    if constexpr (BT <= 512) {
+      constexpr int B = BT <= 256 ? kWaveBlock : 8;
+      double *scr = wave_scratch_of(d);
+      const bool tile = lds_bytes_of(d, 1, 0) != 0;
+      if (tile && scr != nullptr) S2 = norm_sq_pass_wave<B, true>((amwg_lds_f64_ptr)smem, kc.mu, d.n_obs, scr);
+      else S2 = norm_sq_pass_wave<B>(tile ? reinterpret_cast<const double *>(smem) : d.x, kc.mu, d.n_obs, scr);
+    }
     else S2 = norm_sq_pass_uniform<8>(d.x, kc.mu, d.n_obs);
     const double n = (double)d.n_obs;
     const double Q = S2 * kc.n.y.hi, nc = n * kc.n.c;

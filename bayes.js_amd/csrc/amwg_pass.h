@@ -357,6 +357,14 @@ AMWG_HD double norm_sq_pass_uniform(const double *x_global, double mean, int n_o
 // chains' worth at a time), every lane keeps 64 partial sums -- one per chain -- and a transposing butterfly (v_permlane32_swap / v_permlane16_swap /
 // DPP: 63 exchange-and-add steps) leaves chain c's total in lane c.  Same count of fp64 operations, no load on the critical path.  The order of the
 // additions is whatever this schedule gives: the value is used with its rounding bound only (NormalModel::log_post_approx).
+// THE ROW PLAN of the wavefront's pass (norm_sq_pass_wave below; a row = 64 consecutive observations, one per lane).  n_obs observations are `blocks` full blocks of B
+// full rows, then ONE remainder of `full` (0 .. B-1) full rows and, when n_obs is no multiple of 64, a partly filled last row (`masked`).  The remainder's rows sit in
+// one register set of B slots: the parts p = B/2, B/4, .., 1 that make up `full` (its binary digits) take, in that order, the rows pass_part_row .. + p - 1 of the
+// remainder into the slots pass_part_slot .. + p - 1; slot B - 1 belongs to no part and holds the partly filled row.
+struct PassRows { int blocks, full, masked; };
+AMWG_HD PassRows pass_rows(int n_obs, int B) { const int rows = n_obs / 64; return PassRows{rows / B, rows % B, (n_obs % 64) != 0 ? 1 : 0}; }
+AMWG_HD constexpr int pass_part_slot(int B, int p) { return B - 2 * p; }
+AMWG_HD constexpr int pass_part_row(int full, int p) { return full & ~(2 * p - 1); }      // (the rows that the larger parts have taken)
 #if defined(__HIPCC__) || defined(__HIPCC_RTC__)      // (device code only; the host builds of these headers -- tests/host -- never call it)
 #ifndef AMWG_WAVE_BLOCK
 #define AMWG_WAVE_BLOCK 16
@@ -381,10 +389,20 @@ __device__ __forceinline__ double *wave_scratch_of(const DataRef &d) {
   (void)d; return nullptr;
 #endif
 }
-template <int B>
-__device__ __forceinline__ double norm_sq_pass_wave(const double *x, double mu, int n_obs, double *scr = nullptr) {
+// the tile's address space at compile time: through a pointer that may be LDS or global the reads are flat_load, which count on vmcnt AND lgkmcnt -- every wait for
+// them also drains the scalar loads of the means in flight.  The callers branch once, wave-uniformly, on "tile in LDS" (amwg_lds_f64_ptr: ds_read_b64) or "array in
+// global memory" (const double *: global_load).
 #if defined(__HIP_DEVICE_COMPILE__)
-  const int lane = (int)(threadIdx.x & 63u);
+typedef const double __attribute__((address_space(3))) *amwg_lds_f64_ptr;
+#else
+typedef const double *amwg_lds_f64_ptr;
+#endif
+// SCALAR_ONLY: the caller has checked scr != nullptr; the v_readlane fallback is not compiled into this instantiation (the callers keep it in the generic one only)
+template <int B, bool SCALAR_ONLY = false, class XP = const double *>
+__device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, double *scr = nullptr) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  int lane = (int)(threadIdx.x & 63u);
+  asm volatile("" : "+v"(lane));      // (a value of THIS pass: the rows' addresses are formed here -- a few instructions -- and not kept in registers through the stepper's loop)
   double a[64];
 #pragma unroll
   for (int c = 0; c < 64; ++c) a[c] = 0.0;
@@ -392,57 +410,101 @@ __device__ __forceinline__ double norm_sq_pass_wave(const double *x, double mu, 
   auto mean_of = [&](int c) { return bits_f64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(mu_hi, c) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane(mu_lo, c)); };
   bool smem_done = false;
 #if !defined(AMWG_X_NO_SMEM_MEANS)
-  if (scr != nullptr) {      // (wave-uniform)
+  if (SCALAR_ONLY || scr != nullptr) {      // (wave-uniform)
+    // SCHEDULE (a lane's additions per chain stay in increasing row order: the same bits as one block after the other).
+    //   * ONE register set of B rows, refilled in place: in a block's LAST group a row's register is free once that group has used it, so the first half of the
+    //     next block's rows is requested in the middle of that group and the second half at its end -- half a group of arithmetic (B/2 x 16 instructions) before the
+    //     wait that follows.  No block waits for its own rows, no second set of registers, no copies, and the loop body is one basic block.
+    //   * every group requests the means of the NEXT group -- the last group of a block those of group 0, which whatever comes next needs first -- and waits for them
+    //     at its END, behind its own arithmetic: no wait at a block's top, and no scalar load in flight across a branch (tools/isa_audit.py checks that).
+    //   * the rows after the full blocks are ONE set of reads (pass_rows above) into the same registers, worked through part by part.
+    const PassRows pr = pass_rows(n_obs, B);
+    double xv[B];
+    auto read_rows = [&](int blk, int b0, int b1) {
+#pragma unroll
+      for (int b = b0; b < b1; ++b) xv[b] = x[(blk * B + b) * 64 + lane];
+    };
+    if (pr.blocks > 0) read_rows(0, 0, B);      // (the first block's rows travel while the means' stores do)
     scr[lane] = mu;
     asm volatile("s_waitcnt vmcnt(0)\n\ts_dcache_inv\n\ts_waitcnt lgkmcnt(0)" ::: "memory");      // (the stores have reached L2; this wavefront's line of the scalar cache, if an earlier pass left one, is dropped)
     auto fetch = [&](int g) { amwg_v16i r; asm volatile("s_load_dwordx16 %0, %1, %2" : "=&s"(r) : "s"(scr), "s"(g * 8)); return r; };
     auto landed = [&](amwg_v16i &r) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(r)); };
     auto mean_in = [&](const amwg_v16i &r, int j) { return bits_f64(((uint64_t)(uint32_t)r[2 * j + 1] << 32) | (uint64_t)(uint32_t)r[2 * j]); };
-    auto block_s = [&](auto tag, int at) {
-      constexpr int BB = decltype(tag)::value;
-      double xv[BB];
-      amwg_v16i cur = fetch(0);
-#pragma unroll
-      for (int b = 0; b < BB; ++b) xv[b] = x[at + b * 64 + lane];
+    amwg_v16i cur = fetch(0);
+    landed(cur);
+    // rows [R0, R0 + RN) of xv against all 64 means; on entry `cur` holds group 0, on exit again.  refill(b0, b1), called twice in the last group, may request
+    // what those registers hold next
+    auto rows_s = [&](auto r0, auto rn, auto refill) {
+      constexpr int R0 = decltype(r0)::value, RN = decltype(rn)::value, RH = R0 + RN / 2;
 #pragma unroll
       for (int g = 0; g < 64; g += 8) {
-        landed(cur);
-        amwg_v16i nxt = cur;
-        if (g + 8 < 64) nxt = fetch(g + 8);
+        amwg_v16i nxt = fetch(g + 8 < 64 ? g + 8 : 0);
+        AMWG_STAGE_FENCE();      // (the request stays at the group's top: the scheduler would sink it to its wait)
 #pragma unroll
-        for (int b = 0; b < BB; ++b) {
+        for (int b = R0; b < RH; ++b) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) { const double t = xv[b] - mean_in(cur, j); a[g + j] = __builtin_fma(t, t, a[g + j]); }
         }
+        if (g + 8 == 64) { AMWG_STAGE_FENCE(); refill(R0, RH); AMWG_STAGE_FENCE(); }
+#pragma unroll
+        for (int b = RH; b < R0 + RN; ++b) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const double t = xv[b] - mean_in(cur, j); a[g + j] = __builtin_fma(t, t, a[g + j]); }
+        }
+        if (g + 8 == 64) AMWG_STAGE_FENCE();
+        landed(nxt);
+        if (g + 8 == 64) { AMWG_STAGE_FENCE(); refill(RH, R0 + RN); AMWG_STAGE_FENCE(); }
         cur = nxt;
       }
     };
-    int base = 0;
-    for (; base + 64 * B <= n_obs; base += 64 * B) block_s(PassBlock<B>{}, base);
-    if constexpr (B >= 32) { if (base + 64 * 16 <= n_obs) { block_s(PassBlock<16>{}, base); base += 64 * 16; } }
-    if constexpr (B >= 16) { if (base + 64 * 8 <= n_obs) { block_s(PassBlock<8>{}, base); base += 64 * 8; } }
-    if constexpr (B >= 8) { if (base + 64 * 4 <= n_obs) { block_s(PassBlock<4>{}, base); base += 64 * 4; } }
-    if constexpr (B >= 4) { if (base + 64 * 2 <= n_obs) { block_s(PassBlock<2>{}, base); base += 64 * 2; } }
-    for (; base + 64 <= n_obs; base += 64) block_s(PassBlock<1>{}, base);
-    if (base < n_obs) {
-      const int i = base + lane;
-      const bool has = i < n_obs;
-      const double xv = x[has ? i : base];
-      amwg_v16i cur = fetch(0);
+    // (the last full block requests itself again: harmless, and the loop body stays one basic block)
+    for (int k = 0; k < pr.blocks; ++k) {
+      const int nb = k + 1 < pr.blocks ? k + 1 : k;
+      rows_s(PassBlock<0>{}, PassBlock<B>{}, [&](int b0, int b1) { read_rows(nb, b0, b1); });
+    }
+    if (pr.full > 0 || pr.masked) {
+      const int rbase = pr.blocks * B * 64 + lane;
+      const bool has = pr.masked && rbase + pr.full * 64 < n_obs;
+      // every row of the remainder is requested before its first part starts: part p (B/2, B/4, .., 1: the binary digits of pr.full) into the slots pass_part_slot
+      auto read_part = [&](auto pt) {
+        constexpr int P = decltype(pt)::value;
+        if (pr.full & P) {
 #pragma unroll
-      for (int g = 0; g < 64; g += 8) {
-        landed(cur);
-        amwg_v16i nxt = cur;
-        if (g + 8 < 64) nxt = fetch(g + 8);
+          for (int b = 0; b < P; ++b) xv[pass_part_slot(B, P) + b] = x[rbase + (pass_part_row(pr.full, P) + b) * 64];
+        }
+      };
+      if constexpr (B >= 32) read_part(PassBlock<16>{});
+      if constexpr (B >= 16) read_part(PassBlock<8>{});
+      if constexpr (B >= 8) read_part(PassBlock<4>{});
+      if constexpr (B >= 4) read_part(PassBlock<2>{});
+      if constexpr (B >= 2) read_part(PassBlock<1>{});
+      if (pr.masked) xv[B - 1] = x[has ? rbase + pr.full * 64 : 0];
+      auto part = [&](auto pt) {
+        constexpr int P = decltype(pt)::value;
+        if (pr.full & P) rows_s(PassBlock<pass_part_slot(B, P)>{}, pt, [](int, int) {});
+      };
+      if constexpr (B >= 32) part(PassBlock<16>{});
+      if constexpr (B >= 16) part(PassBlock<8>{});
+      if constexpr (B >= 8) part(PassBlock<4>{});
+      if constexpr (B >= 4) part(PassBlock<2>{});
+      if constexpr (B >= 2) part(PassBlock<1>{});
+      if (pr.masked) {      // the partly filled last row: the only selects of the pass
+        const double xm = xv[B - 1];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) { const double t = has ? xv - mean_in(cur, j) : 0.0; a[g + j] = __builtin_fma(t, t, a[g + j]); }
-        cur = nxt;
+        for (int g = 0; g < 64; g += 8) {
+          amwg_v16i nxt = cur;
+          if (g + 8 < 64) nxt = fetch(g + 8);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { const double t = has ? xm - mean_in(cur, j) : 0.0; a[g + j] = __builtin_fma(t, t, a[g + j]); }
+          if (g + 8 < 64) landed(nxt);
+          cur = nxt;
+        }
       }
     }
     smem_done = true;
   }
 #endif
-  if (!smem_done) {
+  if constexpr (!SCALAR_ONLY) if (!smem_done) {
   // a block of BB observations per lane against all 64 means: the means travel eight at a time into scalar registers (16 v_readlane per 8 BB subtract-fma pairs, so
   // the longer the block the smaller their share: 2 + 2 / BB vector instructions per observation and chain -- 2.25 at eight, 2.06 at 32), the eight running sums interleave
   auto block = [&](auto tag, int at) {

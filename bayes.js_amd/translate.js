@@ -2076,6 +2076,7 @@ Translator.prototype.run = function () {
     src.push('  __device__ __forceinline__ static const double *tail_x_global(const DataRef &d) { return static_cast<const double *>(user_arr<' + tail.x + '>(d)); }');
     src.push('  __device__ __forceinline__ static const double *tail_x(const DataRef &d, const unsigned char *smem) { (void)smem; return ' +
              (tx.lds ? 'reinterpret_cast<const double *>(smem + ' + tx.off + ')' : 'tail_x_global(d)') + '; }      // (the one-lane plan of the arrays)');
+    src.push('  static constexpr bool kTailXLds = ' + (tx.lds ? 'true' : 'false') + ';      // (tail_x points into LDS: the pass reads it with ds_read)');
     src.push('  // the closure up to that loop: what its accumulator holds when the loop begins');
     src.push('  template <int G>');
     src.push('  __device__ static double tail_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
