@@ -673,7 +673,9 @@ int amwg_create_user_datasets(const amwg_user_model *models, int32_t n_datasets,
   const SourceTraits t = source_traits(m0.source);
   if (t.row_n >= 0 || m0.rows_n_obs > 0)
     return amwg_fail(AMWG_EINVAL, "%s: the source has a row plan (kRowN): its layout is formed from one dataset's labels; translate with no_row_plan (translate_datasets does)", entry);
-  if (t.pois_tail_n > 0 || t.logit_tail_n > 0)
+  // (a certified Poisson / logistic tail: accepted when its sums and column maxima are slots of each dataset's own constants array -- kTailPerDataset --, refused when
+  // they are literals of the text, formed from ONE dataset's values)
+  if ((t.pois_tail_n > 0 || t.logit_tail_n > 0) && !t.tail_per_dataset)
     return amwg_fail(AMWG_EINVAL, "%s: the source has a certified %s tail (%s): its bound holds sums over one dataset's values; translate with no_pois_tail / no_logit_tail (translate_datasets does)", entry,
                      t.pois_tail_n > 0 ? "Poisson" : "logistic", t.pois_tail_n > 0 ? "kPoisTail" : "kLogitTail");
   if (options->lanes_per_chain == AMWG_LANES_AUTOTUNE)

@@ -70,7 +70,7 @@ int adopt_plan(amwg_sampler *s, const LaunchPlan &p);
 int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, const std::function<int()> &prepare);
 
 // ---- amwg_rtc.hip: what the generated source of a translated closure states about itself; compile (hiprtc, cached) and load of the kernel of s->plan
-struct SourceTraits { long row_n, row_groups; bool row_sweep, row_cert; int cert_tail_n, pois_tail_n, logit_tail_n; };
+struct SourceTraits { long row_n, row_groups; bool row_sweep, row_cert; int cert_tail_n, pois_tail_n, logit_tail_n; bool tail_per_dataset; };
 SourceTraits source_traits(const char *src);
 int load_user_kernel(amwg_sampler *s, const char *source, const char *arch);
 

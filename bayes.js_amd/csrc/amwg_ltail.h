@@ -26,6 +26,8 @@
 //   (the same count and the same 1.25 as the Poisson tail's; L enters through this pass's own sum, whose relative error ~n u the slack covers many times over).
 // H > 690 (exp_v8 nears its overflow, softplus_bounded leaves the range its bound is stated for), any non-finite value: eps is not finite and the stepper evaluates
 // the expression.  (A NaN eta: fmax / fmin skip it, sum eta y carries it -- fma(NaN, y, .) is NaN whatever y.)  A non-finite y: the translator does not emit this plan.
+// PER-DATASET CONSTANTS (M::kTailPerDataset, amwg_ptail.h TailPerDataset: translate_datasets, many datasets under ONE source): Y is not a literal of the text but the
+// one slot of the f64 data array M::kTailConsts (key `#tail:consts`), formed by the translator from THAT dataset's values, rounded up the same way; M::ltail_sum_abs_y(d).
 // Checked like the other bounds: tests/host/logit_bound_replay.cpp (the derivation in __float128) and tools/bound_audit.py --only logit (libamwg_audit.so
 // evaluates the expression beside every certified value).
 #pragma once
@@ -144,7 +146,10 @@ __device__ __forceinline__ TailApprox logit_tail_approx(const StateView &S, cons
     tot = mine == c ? t : tot;
     L = mine == c ? l : L;
   }
-  const double Y = M::ltail_sum_abs_y(), H = hm;
+  double Y;
+  if constexpr (TailPerDataset<M>::value) Y = M::ltail_sum_abs_y(d);
+  else Y = M::ltail_sum_abs_y();
+  const double H = hm;
   const double W = Hm + H * Y + L + (double)n;
   const double eps = (H <= 690.0) ? (W * ((double)n + (double)(n / 32) + 2.0 * Hc + 200.0) * 0x1p-53 + (double)n * kSoftplusBoundedAbs) * 1.25 : __builtin_inf();
   return TailApprox{P + tot, eps};

@@ -258,6 +258,8 @@ int choose_geometry(const amwg_sampler *s, int lanes, int n_cus, size_t max_lds,
   const amwg_options &o = s->opt;
   const int max_bt = s->user ? s->user_max_threads : family_of(s->model)->max_threads;
   // a dataset sampler: a workgroup serves ONE dataset, so the chains per workgroup divide the chains per dataset -- only such geometries are searched
+  // (a closure with a certified Poisson / logistic tail in its per-dataset form -- kTailPerDataset -- is searched like any other: G = 16 is among those geometries when
+  // block / 16 divides cpd, variant_for gives it UserStepCert and model_work prices it with the tail terms; a fixed (16, block) that does not divide cpd is the EINVAL below)
   const int64_t cpd = chains_per_dataset(s);
   bool lds_short = false;      // (a dataset sampler: some geometry that serves whole datasets was given up for LDS alone)
   auto fits = [&](int bt, int G) {

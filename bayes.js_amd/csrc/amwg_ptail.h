@@ -28,6 +28,10 @@
 // 36 operations per observation and chain against the generic 44, and no running maximum.
 // H > 690 (exp and log leave their ordinary range), any non-finite value: eps is not finite and the stepper evaluates the expression.  A negative count makes the
 // reference's term -inf: the translator does not emit this plan for such data.
+// PER-DATASET CONSTANTS (M::kTailPerDataset: translate_datasets, many datasets under ONE source): Y, F and the column maxima inside H are not literals of the text but
+// slots of one more f64 data array (M::kTailConsts, key `#tail:consts`: [sum y, sum lfactorial(y), colmax_0 ...]), each formed by the translator from THAT dataset's
+// values by the code that forms the literals; the accessors then take the data reference -- M::ptail_sum_y(d), M::ptail_sum_lf(d), M::ptail_hlin(S, d).  A workgroup
+// serves one dataset, so the address is wave-uniform and the loads are scalar.  The pass, the derivation and eps are the same.
 // Checked like the other bounds: tools/bound_audit.py case user_pois_glm_closure (libamwg_audit.so evaluates the expression beside every certified value).
 #pragma once
 #include "amwg_user.h"      // (which includes this file at its end: TailApprox, ld_pois_pre_exp)
@@ -52,6 +56,20 @@ __device__ __forceinline__ double wave_uniform(double x) {
   return bits_f64(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
 #else
   return x;
+#endif
+}
+
+// does the source read its tails' data-dependent constants from the data reference (translate.js tail_consts_array)?  Ordinary sources lack the member.
+template <class M, class = void> struct TailPerDataset { static constexpr bool value = false; };
+template <class M> struct TailPerDataset<M, void_of<decltype(M::kTailPerDataset)>> { static constexpr bool value = M::kTailPerDataset; };
+
+// slot k of a per-dataset constants array: a wave-uniform address in memory that no kernel writes -- a scalar load through the constant address space
+__device__ __forceinline__ double tail_const(const void *consts, int k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef __attribute__((address_space(4))) const double *const_f64;
+  return ((const_f64)(uintptr_t)consts)[k];
+#else
+  return static_cast<const double *>(consts)[k];
 #endif
 }
 
@@ -162,7 +180,8 @@ __device__ __forceinline__ TailApprox pois_tail_approx(const StateView &S, const
   // every chain's totals over the wavefront; a lane keeps its own chain's.  H: the largest |eta| any of the four chains met (fmax skips a NaN: the sums carry it)
   double cH = 23.0;      // (slack for the closure's own eta on both sides; the hand-written family's coefficient)
   if constexpr (kLinear) {
-    hm = M::ptail_hlin(S);      // this lane's own chain
+    if constexpr (TailPerDataset<M>::value) hm = M::ptail_hlin(S, d);      // this lane's own chain; the column maxima are the workgroup's dataset's
+    else hm = M::ptail_hlin(S);      // this lane's own chain
     cH = 1.1 * (double)M::kTailLinearRoundings + 1.0;      // eta's roundings on the two sides, each below u H: |eta_fused - eta_reference| <= kTailLinearRoundings u H 1.05
   } else {
 #pragma unroll
@@ -176,7 +195,10 @@ __device__ __forceinline__ TailApprox pois_tail_approx(const StateView &S, const
     tot = mine == c ? t : tot;
     L = mine == c ? l : L;
   }
-  const double Y = M::ptail_sum_y(), F = M::ptail_sum_lf(), H = hm;
+  double Y, F;
+  if constexpr (TailPerDataset<M>::value) { Y = M::ptail_sum_y(d); F = M::ptail_sum_lf(d); }
+  else { Y = M::ptail_sum_y(); F = M::ptail_sum_lf(); }
+  const double H = hm;
   const double W = Hm + (1.0 + H) * Y + L + __builtin_fabs(F);
   const double eps = (H <= 690.0) ? W * ((double)n + (double)(n / 32) + 2.0 * Hc + cH * H + 200.0) * 1.25 * 0x1p-53 : __builtin_inf();
   return TailApprox{(P + tot) - F, eps};

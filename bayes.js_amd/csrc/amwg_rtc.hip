@@ -175,7 +175,8 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
 }
 
 // What the generated source of a translated closure (translate.js) states about itself, read off its markers: the row plan (kRowN, kRowGroups, kRowSweep,
-// kRowCert; -1 = no such marker), the certified tail (kCertifiedTail, kTailN), the certified Poisson tail (kPoisTail, kTailN) and the certified logistic tail (kLogitTail, kTailN); 0 = none.
+// kRowCert; -1 = no such marker), the certified tail (kCertifiedTail, kTailN), the certified Poisson tail (kPoisTail, kTailN) and the certified logistic tail (kLogitTail, kTailN); 0 = none;
+// and whether those two tails read their data-dependent constants from an array of the dataset (kTailPerDataset: translate.js tail_consts_array) rather than from the text.
 SourceTraits source_traits(const char *src) {
   auto int_after = [&](const char *key) -> long {
     const char *q = strstr(src, key);
@@ -183,7 +184,7 @@ SourceTraits source_traits(const char *src) {
   };
   auto tail_n = [&](const char *marker) { const long n = strstr(src, marker) ? int_after("kTailN = ") : 0; return n > 0 && n < (1l << 28) ? (int)n : 0; };
   return SourceTraits{int_after("kRowN = "), int_after("kRowGroups = "), strstr(src, "kRowSweep = true") != nullptr, strstr(src, "kRowCert = true") != nullptr,
-                      tail_n("kCertifiedTail = true"), tail_n("kPoisTail = true"), tail_n("kLogitTail = true")};
+                      tail_n("kCertifiedTail = true"), tail_n("kPoisTail = true"), tail_n("kLogitTail = true"), strstr(src, "kTailPerDataset = true") != nullptr};
 }
 
 // ---- compile for the adopted plan (cached per process by source text + geometry + arch) and load on the sampler's device

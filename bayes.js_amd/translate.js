@@ -1529,7 +1529,9 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
       if (mp && mp[3] === canon.name && startV.cst === 0 && !canon.le && L.preamble.length === 0 && !this.isHelper && !this.opts.no_cert_tail && !this.linear && this.acc &&
           loopAcc === this.acc && indent === '    ' && !this.condDepth) {
         const ya = this.arrays[Number(mp[2])], la = ml ? ya : this.arrays[Number(mp[5])], text = bodyText + ' ' + mp[4];
-        let ok = (ml || ya.type !== 0) && boundV.cst === ya.flat.length && boundV.cst === la.flat.length && boundV.cst >= 64 && !/\b(sub|G|dq_\w+|dv|return|goto|tb_\w*|it_\w*|u_|rr_)\b/.test(text);
+        // (per-dataset constants -- tail_consts_array, translate_datasets --: any number of observations.  Segments are short, and the pass has a ragged last round anyway.)
+        const minN = this.opts.tail_consts_array && !(ml ? this.opts.no_logit_tail : this.opts.no_pois_tail) ? 1 : 64;
+        let ok = (ml || ya.type !== 0) && boundV.cst === ya.flat.length && boundV.cst === la.flat.length && boundV.cst >= minN && !/\b(sub|G|dq_\w+|dv|return|goto|tb_\w*|it_\w*|u_|rr_)\b/.test(text);
         if (ml) for (let i = 0; ok && i < ya.flat.length; i++) ok = Number.isFinite(ya.flat[i]);
         else
         for (let i = 0; ok && i < ya.flat.length; i++) ok = ya.flat[i] >= 0 && Number.isFinite(la.flat[i]);      // (a negative count: the reference's term is -inf)
@@ -1602,6 +1604,9 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
           }
           const colmax = (j, stride, o) => { let m = 0; const f = this.arrays[j].flat; for (let i = 0; i < boundV.cst; i++) m = Math.max(m, Math.abs(f[i * stride + o])); return m; };
           const terms = [];      // [text of one summand of H]
+          // tail_consts_array: the column maxima are slots 2, 3, ... of the dataset's constants array (read through c_), EVERY column's -- a zero maximum is a zero
+          // factor, so that the text does not depend on the values
+          const perDs = !!this.opts.tail_consts_array, cms = [];
           let refRound = 0, fusedRound = 0;
           const reAsg = new RegExp(Ee + ' = ([^;]+);', 'g');
           let fused = '', last = 0, ma;
@@ -1631,7 +1636,8 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
                   if (o < per.lo || o >= per.hi || si < 0 || si >= this.P) { good = false; break; }
                   const cm = colmax(j, per.stride, o) * mult;
                   if (!Number.isFinite(cm)) { good = false; break; }
-                  if (cm > 0) terms.push(hexFloat(cm) + ' * __builtin_fabs(S(' + si + '))');
+                  if (perDs) { terms.push('tail_const(c_, ' + (2 + cms.length) + ') * __builtin_fabs(S(' + si + '))'); cms.push(cm); }
+                  else if (cm > 0) terms.push(hexFloat(cm) + ' * __builtin_fabs(S(' + si + '))');
                 }
                 refRound += 2 * trips; fusedRound += trips;
                 out = E + ' = __builtin_fma(' + (sign === '-' ? '-' : '') + rd + ', ' + sv + ', ' + E + ');';
@@ -1658,7 +1664,7 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
             const rest = T.replace(reAsg, ';');
             if (new RegExp('\\b' + Ee + '\\b').test(rest) || !terms.length || terms.length > 64 || refRound + fusedRound > 200) good = false;
           }
-          if (good) linInfo = { body: fused, hlin: terms.join(' + '), roundings: refRound + fusedRound };
+          if (good) linInfo = { body: fused, hlin: terms.join(' + '), roundings: refRound + fusedRound, colmax: cms };
         }
         if (ok && ml) {
           ptailCand = true;
@@ -1997,6 +2003,17 @@ Translator.prototype.run = function () {
   const tail = rows ? null : this.tailPlan(body);
   const ptail0 = (rows || tail) ? null : this.poisTailPlan(body);
   const ltail = (rows || tail || ptail0) ? null : this.logitTailPlan(body);
+  // PER-DATASET CONSTANTS (options.tail_consts_array; translate_datasets): what the two plans form from the data's values -- sum y, sum lfactorial(y) and the column
+  // maxima of H; sum |y| -- goes into one more f64 array, appended last, instead of into the text.  Its layout follows from the closure's text alone, so D datasets
+  // give D equal texts and D arrays.  Never staged: a handful of scalar loads per pass.
+  let tailConsts = -1;
+  if ((ptail0 || ltail) && this.opts.tail_consts_array) {
+    const vals = ltail ? [ltail.sumAbsY] : [ptail0.sumY, ptail0.sumLF].concat(ptail0.linear ? ptail0.linear.colmax : []);
+    tailConsts = this.arrays.length;
+    this.arrays.push({ key: '#tail:consts', flat: Float64Array.from(vals), dims: [vals.length], type: 0, is01: false, ctype: 'double', esize: 8 });
+    plan.push({ lds: false, off: 0 });
+    if (P1 !== PG) P1.plan.push({ lds: false, off: 0 });
+  }
   // (the logistic candidate's markers are the plan's alone: the text of the closure's evaluation stays what it was)
   body = body.filter((ln) => !/^\/\/@LTAIL(_END)?$/.test(ln.trim()));
   const src = [];
@@ -2110,6 +2127,17 @@ Translator.prototype.run = function () {
     src.push('  static constexpr int kCertifiedLanes = 16, kTailN = ' + ptail.n + ', kStateN = ' + this.P + ';');
     src.push('  static constexpr bool kTailUniformState = ' + (ptail.uniform && this.P <= 12 ? 'true' : 'false') + ';      // the entries of the state the loop reads do not depend on the observation (and are few): scalar registers');
     src.push('  typedef TailApprox Approx;');
+    if (tailConsts >= 0) {
+      const slot = (k) => 'tail_const(user_arr<' + tailConsts + '>(d), ' + k + ')';
+      src.push('  // the data-dependent constants of the bound are slots of THIS dataset\'s array A' + tailConsts + ' (`#tail:consts`): one source serves every dataset');
+      src.push('  static constexpr bool kTailPerDataset = true;');
+      src.push('  static constexpr int kTailConsts = ' + tailConsts + ';');
+      if (ltail) src.push('  __device__ __forceinline__ static double ltail_sum_abs_y(const DataRef &d) { return ' + slot(0) + '; }      // >= sum |y[i]|');
+      else {
+        src.push('  __device__ __forceinline__ static double ptail_sum_y(const DataRef &d) { return ' + slot(0) + '; }      // sum y[i]');
+        src.push('  __device__ __forceinline__ static double ptail_sum_lf(const DataRef &d) { return ' + slot(1) + '; }      // sum lfactorial(y[i])');
+      }
+    } else
     if (ltail) src.push('  __device__ __forceinline__ static double ltail_sum_abs_y() { return ' + hexFloat(ptail.sumAbsY) + '; }      // >= sum |y[i]| = ' + ptail.sumAbsY);
     else {
     src.push('  __device__ __forceinline__ static double ptail_sum_y() { return ' + hexFloat(ptail.sumY) + '; }      // sum y[i] = ' + ptail.sumY);
@@ -2164,6 +2192,8 @@ Translator.prototype.run = function () {
       src.push('    return ' + ptail.rows.eta + ';');
       src.push('  }');
       src.push('  // H >= sum of the magnitudes of eta\'s summands for every observation (column maxima of the data x |state entry|): bounds |eta| and both etas\' roundings');
+      if (tailConsts >= 0) src.push('  __device__ __forceinline__ static double ptail_hlin(const StateView &S, const DataRef &d) { const void *c_ = user_arr<' + tailConsts + '>(d); (void)c_; return ' + ptail.linear.hlin + '; }');
+      else
       src.push('  __device__ __forceinline__ static double ptail_hlin(const StateView &S) { return ' + ptail.linear.hlin + '; }');
     }
     src.push('  // the closure up to that loop: what its accumulator holds when the loop begins (this lane\'s share)');
@@ -2296,6 +2326,7 @@ Translator.prototype.poisTailPlan = function (body) {
     cF += Math.abs(sF) >= Math.abs(lf[i]) ? (sF - t) + lf[i] : (lf[i] - t) + sF;
     sF = t;
   }
+  if (this.opts.tail_consts_array && !(Number.isFinite(sumY) && Number.isFinite(sF + cF))) return null;      // (a literal would carry it into the text; a slot must be a number the bound can use)
   return Object.assign({}, info, { decls, head, headMag: hm.mag, sumY, sumLF: sF + cF });
 };
 
@@ -2514,16 +2545,21 @@ function translate(fn, params, data, options) {
 //           range and dimensions; per scalar field its value.  Union: the widest type (u8 < i32 < f64), is01 if everywhere, the hull; a scalar that differs is VARYING.
 //   pass 2: every dataset again with array_types / array_is01 / array_ranges by key, varying_scalars (read from a one-element array `#scalar:<path>`; where the
 //           translator needs such a value as a constant its own failure is the refusal) and no_const_element_fold.
+//           First WITH the certified Poisson / logistic tail in its per-dataset form (tail_consts_array: the sums and column maxima of the bound are slots of one more
+//           array `#tail:consts`, formed from each dataset's own values, and the text holds none of them); a dataset that cannot take the plan -- a negative or
+//           fractional count, a non-finite sum, a derived quantity -- makes the texts differ, and the pass is run as before, without those tails.
 //   the check: D identical texts.  If not, once more without the K-valued fast-forward, the staged normal pass and the certified tail, whose tables and predicates
 //           may legitimately differ between datasets; then the refusal.
+// The caller's own no_pois_tail / no_logit_tail / no_cert_tail hold in every pass.
 const DATASET_BASE_OPTS = { no_row_plan: true, no_pois_tail: true, no_logit_tail: true, no_const_element_fold: true };
+const DATASET_TAIL_OPTS = { no_row_plan: true, no_const_element_fold: true, tail_consts_array: true };
 const DATASET_RETRY_OPTS = { no_fast_forward: true, no_cert_tail: true, no_staged_norm: true, no_tail_rows: true, no_tail_linear: true };
 const TYPE_RANK = [2, 0, 1];      // AMWG_F64 = 0, AMWG_U8 = 1, AMWG_I32 = 2 -> u8 < i32 < f64
 function translate_datasets(fn, params, datasets, options) {
   if (!Array.isArray(datasets) || datasets.length < 1) throw 'translate_datasets: datasets must be a non-empty array of data objects';
   const D = datasets.length, user = Object.assign({}, options || {});
   const run = (d, extra) => {
-    try { return new Translator(fn, params, datasets[d], Object.assign({}, user, DATASET_BASE_OPTS, extra)).run(); }
+    try { return new Translator(fn, params, datasets[d], Object.assign({}, user, extra && extra.tail_consts_array ? null : DATASET_BASE_OPTS, extra)).run(); }
     catch (e) {
       const msg = typeof e === 'string' ? e : (e && e.message) || String(e);
       const vs = extra && extra.varying_scalars && extra.varying_scalars.size ? '; in dataset mode data' + Array.from(extra.varying_scalars).join(', data') +
@@ -2570,8 +2606,13 @@ function translate_datasets(fn, params, datasets, options) {
     }
     return null;
   };
-  let second = null, bad = derivedDiffer ? { d: 0 } : null;
-  if (!bad) { second = []; for (let d = 0; d < D; d++) second.push(run(d, union)); bad = differs(second); }
+  let second = null, bad = derivedDiffer ? { d: 0 } : null, tails = false;
+  if (!bad && !user.no_cert_tail && !(user.no_pois_tail && user.no_logit_tail)) {
+    // (a dataset whose translation fails here fails in the pass below too, which words the refusal)
+    try { second = []; for (let d = 0; d < D; d++) second.push(run(d, Object.assign({}, union, DATASET_TAIL_OPTS))); } catch (e) { second = null; }
+    tails = !!second && !differs(second) && (second[0].pois_tail_n > 0 || second[0].logit_tail_n > 0);
+  }
+  if (!tails && !bad) { second = []; for (let d = 0; d < D; d++) second.push(run(d, union)); bad = differs(second); }
   if (bad) { second = []; for (let d = 0; d < D; d++) second.push(run(d, Object.assign({}, union, DATASET_RETRY_OPTS))); bad = differs(second); }
   if (bad) {
     const a = second[0].source.split('\n'), b = second[bad.d].source.split('\n');
@@ -2587,6 +2628,7 @@ function translate_datasets(fn, params, datasets, options) {
   out.array_is01 = second[0].array_keys.map((k) => !!is01[k]);
   out.array_ranges = second[0].array_keys.map((k) => (Object.prototype.hasOwnProperty.call(ranges, k) ? ranges[k] : null));
   out.varying_scalars = Array.from(varying);
+  out.tail_per_dataset = tails;
   delete out.scalars_read;
   return out;
 }

@@ -235,7 +235,9 @@ typedef struct {
    * (kRowN, kRowGroups, kRowSweep) and refuses a mismatch -- a caller built against an older, shorter struct cannot switch a layout on that the source has
    * no code for.  Everything the translator added since is read from the source alone: kRowCert (certified decisions in the row layout: amwg_user_sweep_cert),
    * kCertifiedTail / kTailN (certified decisions for a closure ending in a constant-mean normal loop: amwg_user_step_cert at one lane per chain), kPoisTail / kTailN
-   * and kLogitTail / kTailN (the same for a closure ending in a log-link Poisson loop or in a logistic-regression loop: amwg_user_step_cert at 16 lanes per chain). */
+   * and kLogitTail / kTailN (the same for a closure ending in a log-link Poisson loop or in a logistic-regression loop: amwg_user_step_cert at 16 lanes per chain),
+   * kTailPerDataset / kTailConsts (those two tails read the data-dependent constants of their bound -- sum y, sum lfactorial(y) and the column maxima of the linear
+   * predictor; sum |y| -- from the f64 array kTailConsts of the model, `#tail:consts`, instead of from literals of the text: translate.js tail_consts_array). */
   int32_t rows_n_obs, rows_groups, rows_sweep;
 } amwg_user_model;
 
@@ -254,8 +256,13 @@ int amwg_create_user(const amwg_user_model *model, const amwg_param_desc *params
  * n_datasets == 1 is amwg_create_user(models, ...).  amwg_dataset_n_obs fills n_datasets zeros (a closure's arrays carry their own lengths).
  * Refused with AMWG_EINVAL before a device is opened, with a message that names the dataset and the field: a null argument, n_datasets < 1, chains % n_datasets != 0,
  * models[d].source not string-equal to models[0].source, a difference in n_arrays, any array_len or array_type, n_derived, lds_bytes, lds_bytes_one_lane, parallel,
- * max_threads or rows_*; a source with a row plan (kRowN) or a certified Poisson / logistic tail (kPoisTail / kLogitTail) -- their layout and bounds are formed from one
- * dataset's values; such closures run with the expression in every update here, per-dataset versions are follow-ups --; AMWG_LANES_AUTOTUNE; sufficient_statistics.
+ * max_threads or rows_*; a source with a row plan (kRowN) -- its layout is formed from one dataset's labels --; a source with a certified Poisson / logistic tail
+ * (kPoisTail / kLogitTail) whose bound holds LITERALS, i.e. sums over one dataset's values; AMWG_LANES_AUTOTUNE; sufficient_statistics.
+ * A Poisson / logistic tail IS accepted when the source states kTailPerDataset = true: the constants of its bound are then the slots of models[d]'s own array
+ * kTailConsts (the last one, `#tail:consts`), which translate_datasets forms from dataset d's values by the code that forms the literals of an ordinary translation --
+ * the library takes them as data and checks nothing about them.  Such a sampler runs "amwg_user_step_cert_ds" at 16 lanes per chain (block_threads / 16 must divide cpd;
+ * lanes_per_chain = 0 finds such a geometry where it is priced cheapest) with amwg_summation_order 1: every dataset's chains are the reference's, bit for bit.
+ * amwg_create_user takes a marked source too: the constants are its one dataset's array.
  * NOT SUPPORTED: ragged closure datasets (the generated loops and LDS copies carry the lengths as constants), autotune, the stand-alone steppers. */
 int amwg_create_user_datasets(const amwg_user_model *models, int32_t n_datasets, const amwg_param_desc *params, int32_t n_params, const double *init,
                               const amwg_comp_opt *comp_opts, const amwg_options *options, amwg_sampler **out);

@@ -20,6 +20,7 @@ verdict goes wrong or a chain differs from the expression-in-every-update run.
     python tools/bound_audit.py --out profiles/r06_bound_audit.json            # everything (a few minutes of GPU)
     python tools/bound_audit.py --quick                                        # the small cases only (what tests/test_gpu_bound_audit.py asserts)
     python tools/bound_audit.py --only logit                                   # the certified logistic tail's cases alone (tests/test_gpu_logit_tail.py)
+    python tools/bound_audit.py --only dstail                                  # the certified tails of closures on MANY datasets (tests/test_gpu_user_dataset_tails.py)
 """
 import argparse
 import ctypes as C
@@ -210,6 +211,23 @@ def logit_cases():
     return out
 
 
+def dstail_cases():
+    """The certified Poisson / logistic tails of a translated closure on MANY datasets (translate.js translate_datasets with tail_consts_array; kTailPerDataset:
+    amwg_user_step_cert_ds at 16 lanes per chain): the dataset samplers of tests/js/dataset_tail_models.js, three datasets whose constants all differ, 64 chains each.
+    The ratios are reported per dataset as well (the per-chain rows of amwg_audit_fetch, dataset d = chains [d cpd, (d + 1) cpd)): a dataset whose bound was formed
+    from another's values shows there.  Names begin with dstail_: part of the full run and of --only dstail, not of --quick."""
+    out = []
+    if not shutil.which("node"):
+        return out
+    import user_dataset_tails_lib as tl
+    for tag in tl.MARKED:
+        specs = tl.specs(tag)
+        for q in specs:
+            q["n_obs"] = int(tl.load(tag)[1]["array_len"][0])
+        out.append(dict(name="dstail_" + tag, spec=specs, chains=64 * len(specs), steps=150, lanes=16, state=None, seed=21, datasets=len(specs)))
+    return out
+
+
 def run_case(c, shift=0, full_evaluation=0):
     s = A.Sampler(c["spec"], chains=c["chains"], seed=c["seed"], lanes_per_chain=c["lanes"], test_bound_shift=shift, full_evaluation=full_evaluation,
                   sufficient_statistics=(c.get("suff", 0) if full_evaluation == 0 else 0))
@@ -241,7 +259,7 @@ def main():
     rec = {"library": A.lib().amwg_version().decode(), "cases": [], "shrink": []}
     worst_v = worst_d = 0.0
     wrong = 0
-    for c in (logit_cases() if a.only.startswith("logit") else cases(a.quick) + ([] if a.quick else logit_cases())):
+    for c in (logit_cases() if a.only.startswith("logit") else dstail_cases() if a.only.startswith("dstail") else cases(a.quick) + ([] if a.quick else logit_cases() + dstail_cases())):
         if a.only and a.only not in c["name"]:
             continue
         r = run_case(c)
@@ -249,9 +267,15 @@ def main():
         mv, md = float(np.nanmax(per[0])) if not np.isnan(per[0]).all() else float("nan"), float(np.nanmax(per[1])) if not np.isnan(per[1]).all() else float("nan")
         if np.isnan(per[0]).any() or np.isnan(per[1]).any():
             mv = md = float("nan")
-        e = dict(name=c["name"], kernel=r["kernel"], chains=c["chains"], steps=c["steps"], n_obs=c["spec"]["n_obs"], in_bounds_proposals=r["inbounds"],
+        spec0 = c["spec"][0] if isinstance(c["spec"], list) else c["spec"]
+        e = dict(name=c["name"], kernel=r["kernel"], chains=c["chains"], steps=c["steps"], n_obs=spec0["n_obs"], in_bounds_proposals=r["inbounds"],
                  audited_decisions=int(per[2].sum()), wrong_verdicts=int(per[3].sum()), max_value_ratio=mv, max_difference_ratio=md,
                  value_ratio_hist=hist_summary(r["hist"][0]), difference_ratio_hist=hist_summary(r["hist"][1]), seconds=round(r["wall"], 2))
+        if c.get("datasets"):      # the worst ratios of every dataset's own chains
+            cpd = c["chains"] // c["datasets"]
+            e["datasets"] = [dict(dataset=d, audited_decisions=int(per[2, d * cpd:(d + 1) * cpd].sum()), wrong_verdicts=int(per[3, d * cpd:(d + 1) * cpd].sum()),
+                                  max_value_ratio=float(np.max(per[0, d * cpd:(d + 1) * cpd])), max_difference_ratio=float(np.max(per[1, d * cpd:(d + 1) * cpd])))
+                             for d in range(c["datasets"])]
         rec["cases"].append(e)
         if "_cert" in r["kernel"]:
             worst_v, worst_d, wrong = max(worst_v, mv if mv == mv else INF), max(worst_d, md if md == md else INF), wrong + e["wrong_verdicts"]
