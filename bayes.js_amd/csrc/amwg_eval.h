@@ -106,7 +106,7 @@ __global__ void amwg_eval_kernel(int op, int64_t n, const double *a, const doubl
     case 34: r = log1p_v8(exp_v8_full(x)); break;             // ... and the full fdlibm control flow it replaces
     case 35: { bool rare = false; r = log1p_exp_v8_open(rare, x); if (rare) r = log1p_exp_cold(x); } break;   // the branch-free form of unrolled loops
     case 36: r = softplus_bounded(x); break;                  // the certified logistic pass's softplus (NOT V8's bits: a value with a bound) ...
-    case 37: r = softplus_bounded(x, softplus_regs()); break; // ... with its coefficients in registers, as amwg_ltail.h calls it
+    case 37: r = softplus_bounded(x, softplus_regs()); break; // ... with its coefficients in registers, as amwg_gtail.h calls it
   }
   out[i] = r;
 }

@@ -461,7 +461,7 @@ AMWG_HD double exp_bounded(double x, const C &c) {
 constexpr double kExpBoundedRel = 0x1p-46;
 
 // softplus(x) = log(1 + e^x) = max(x, 0) + log1p(e^-|x|), |x| <= 690, to an ABSOLUTE error below kSoftplusBoundedAbs -- NOT the reference's
-// log1p_v8(exp_v8(x)) (log1p_exp_v8 below is), for the certified pass of a logistic likelihood, which uses the value with its bound only (amwg_ltail.h).  One
+// log1p_v8(exp_v8(x)) (log1p_exp_v8 below is), for the certified pass of a logistic likelihood, which uses the value with its bound only (amwg_gtail.h).  One
 // straight line: no branch on the data, no IEEE division.  a = min(|x|, 64) (what the cut drops is below e^-64 < 2^-92); t = exp_bounded(-a) in [2^-93, 1];
 // s = t / (2 + t) in (0, 1/3] by quot_plain (reciprocal, two Newton steps, quotient, residual: 2 + t in (2, 3] and t need no exponent juggling -- the correctly
 // rounded quotient, so the host build, which divides, gives the same bits); log1p(t) = 2 atanh(s) = 2 s + s z Q(z), z = s s <= 1/9, Q the polynomial of degree 9

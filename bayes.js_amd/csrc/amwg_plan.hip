@@ -89,7 +89,7 @@ static int chains_per_workgroup(int lanes, int block) { return lanes > 64 ? 1 : 
 // The kernel G lanes per chain in workgroups of bt threads with max_lds bytes of LDS run, and its DataRef::pad: the plan's lanes, block, variant and pad.
 //   * certified decisions unless full_evaluation or exact_division ask for the expression: the Normal family at one lane per chain, the Poisson family at
 //     16, the hierarchical family's sweep kernel; a closure without binary parameters with a certified tail (amwg_user.h norm_tail_approx: one lane;
-//     amwg_ptail.h pois_tail_approx / amwg_ltail.h logit_tail_approx: 16 lanes, four chains sharing every row they read) or a row plan marked kRowCert
+//     amwg_gtail.h glm_tail_approx<PoisLink | LogitLink>: 16 lanes, four chains sharing every row they read) or a row plan marked kRowCert
 //     (amwg_rows.h);
 //   * the row layout (lane-local re-evaluation) of the hierarchical family and of a closure's row plan (amwg_rows.h): a chain on one wavefront, not
 //     switched off, the tile, the label bytes and the per-wavefront term rows beside the stepper state.  Its sweep kernels are compiled for at most 512

@@ -17,7 +17,7 @@
 // together with the very same step kernel source the built-in models are compiled from.
 extern "C" {
 extern const char amwg_hdr_stdint[], amwg_hdr_types[], amwg_hdr_math[], amwg_hdr_div[], amwg_hdr_ld[], amwg_hdr_philox[],
-    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_ptail[], amwg_hdr_ltail[],
+    amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_gtail[],
     amwg_hdr_user_kernels[], amwg_hdr_user_dataset[];
 }
 
@@ -115,9 +115,9 @@ static void dump_code_object(const std::vector<char> &code) {      // developmen
 // datasets: with the dataset twins (amwg_user_dataset.h) compiled in -- one more compile option, hence one more part of the cache key
 static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool datasets, bool use_cache = true) {
   static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h", "amwg_kernel.h", "amwg_user.h",
-                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_ptail.h", "amwg_ltail.h", "amwg_user_kernels.h", "amwg_user_dataset.h"};
+                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_gtail.h", "amwg_user_kernels.h", "amwg_user_dataset.h"};
   const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox, amwg_hdr_kernel, amwg_hdr_user,
-                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_ptail, amwg_hdr_ltail, amwg_hdr_user_kernels, amwg_hdr_user_dataset};
+                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_gtail, amwg_hdr_user_kernels, amwg_hdr_user_dataset};
   constexpr int kHeaders = (int)(sizeof(texts) / sizeof(texts[0]));
   const std::string prog_src = user_program(source, lanes, block);
 #if defined(AMWG_AUDIT)      // (libamwg_audit.so: the certified kernels of translated closures record |A - E| / eps as the built-in families' do)

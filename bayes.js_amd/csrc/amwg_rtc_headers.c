@@ -18,7 +18,6 @@ AMWG_TEXT(amwg_hdr_trig, "amwg_trig.h");
 AMWG_TEXT(amwg_hdr_pass, "amwg_pass.h");
 AMWG_TEXT(amwg_hdr_rows, "amwg_rows.h");
 AMWG_TEXT(amwg_hdr_window, "amwg_window.h");
-AMWG_TEXT(amwg_hdr_ptail, "amwg_ptail.h");
-AMWG_TEXT(amwg_hdr_ltail, "amwg_ltail.h");
+AMWG_TEXT(amwg_hdr_gtail, "amwg_gtail.h");
 AMWG_TEXT(amwg_hdr_user_kernels, "amwg_user_kernels.h");
 AMWG_TEXT(amwg_hdr_user_dataset, "amwg_user_dataset.h");

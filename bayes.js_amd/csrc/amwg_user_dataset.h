@@ -43,7 +43,7 @@ __device__ __forceinline__ void user_dataset_view(StepArgs &v, const UserDataset
 // the dataset twins of amwg_user_step / amwg_user_step_cert (amwg_user_kernels.h): the same step_body on the workgroup's dataset.  (The host units include this
 // header for UserDatasetArgs alone: no geometry, no kernels.)
 // The certified twin instantiates the certified step_body for ANY CertifiedAt<UserModel, AMWG_USER_LANES> without rows: one lane per chain (the constant-mean normal
-// tail) and 16 lanes per chain (the Poisson / logistic tails of a source marked kTailPerDataset: amwg_ptail.h, amwg_ltail.h).  At 16 lanes the four chains of a
+// tail) and 16 lanes per chain (the Poisson / logistic tails of a source marked kTailPerDataset: amwg_gtail.h).  At 16 lanes the four chains of a
 // wavefront share every row of the data they read; a workgroup serves one dataset, so they share the constants of the bound too -- slots of that dataset's array
 // `#tail:consts`, read through the same redirected user_arr<J>(d).
 #if defined(AMWG_USER_LANES) && defined(AMWG_USER_BLOCK)

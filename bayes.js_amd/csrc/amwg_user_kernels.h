@@ -27,7 +27,7 @@ extern "C" __global__ void __launch_bounds__(AMWG_USER_BLOCK) amwg_user_sweep_ce
   else amwg::device_error(a, amwg::kErrNoKernelBody);
 }
 
-// a closure with a certified tail (amwg_user.h norm_tail_approx, amwg_ptail.h pois_tail_approx: UserModel::kCertified) at the lane count it has one for: the stepper
+// a closure with a certified tail (amwg_user.h norm_tail_approx, amwg_gtail.h glm_tail_approx<PoisLink>: UserModel::kCertified) at the lane count it has one for: the stepper
 // that decides accept tests from it (amwg_step_kernel_cert's twin; BT: the wavefront's pass needs the 512 registers of a workgroup of at most 256 threads)
 extern "C" __global__ void __launch_bounds__(AMWG_USER_BLOCK) amwg_user_step_cert(const amwg::StepArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

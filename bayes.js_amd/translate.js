@@ -1520,12 +1520,12 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
         return;
       }
       // `for (i = 0; i < y.length; i++) { <eta from the state and row i>; lp += ld.pois(y[i], Math.exp(eta)); }` over whole arrays of counts: CERTIFIED POISSON TAIL
-      // candidate (csrc/amwg_ptail.h).  run() decides (it must be the LAST statement: poisTailPlan); the loop itself is emitted as any other lane-split loop.
-      // ... and `{ <eta>; lp += y[i] * eta - Math.log1p(Math.exp(eta)); }` over whole arrays, every y[i] finite: CERTIFIED LOGISTIC TAIL candidate (csrc/amwg_ltail.h;
-      // logitTailPlan), under the same conditions and with the same analyses of the statements -- except the linear predictor's: eta stays the reference's bits.
+      // candidate (csrc/amwg_gtail.h PoisLink).  run() decides (it must be the LAST statement: glmTailPlan); the loop itself is emitted as any other lane-split loop.
+      // ... and `{ <eta>; lp += y[i] * eta - Math.log1p(Math.exp(eta)); }` over whole arrays, every y[i] finite: CERTIFIED LOGISTIC TAIL candidate (LogitLink), under
+      // the same conditions and with the same analyses of the statements -- except the linear predictor's: eta stays the reference's bits.
       const ml = logitTerm(term.code);
       const mp = ml || /^ld_pois_pre_exp\(((?:\(double\))?)A(\d+)\[v_(\w+)\], (.+), A(\d+)\[v_\3\]\)$/.exec(term.code);
-      let ptailCand = false;
+      let gtailCand = false;
       if (mp && mp[3] === canon.name && startV.cst === 0 && !canon.le && L.preamble.length === 0 && !this.isHelper && !this.opts.no_cert_tail && !this.linear && this.acc &&
           loopAcc === this.acc && indent === '    ' && !this.condDepth) {
         const ya = this.arrays[Number(mp[2])], la = ml ? ya : this.arrays[Number(mp[5])], text = bodyText + ' ' + mp[4];
@@ -1552,7 +1552,7 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
           if (/\bS\b(?!\()/.test(text)) ok = false;      // (the state handed on as a whole)
         }
         // ROW CACHE: does every read of a data array in the statements address observation i's own row -- `A[i]`, `A[i * K + c]`, `A[i * K + counter]` (c, the counter's
-        // range inside [0, K))?  Then the pass loads a row into registers a round AHEAD of its use (ptail_load / ptail_eta_row: the statements with the reads replaced by
+        // range inside [0, K))?  Then the pass loads a row into registers a round AHEAD of its use (gtail_load / gtail_eta_row: the statements with the reads replaced by
         // the row's entries) instead of waiting for every row where its first product needs it.
         let rowInfo = null;
         if (ok && uniform && !this.opts.no_tail_rows) {
@@ -1590,7 +1590,7 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
         }
         // LINEAR PREDICTOR: is eta nothing but a sum of products (row entry) x (state entry), state entries and literals -- `eta = 0; for (k) eta += X[i K + k] * b[k];
         // if (...) eta += b[7]`?  Then the pass forms it by fused steps (one rounding per product instead of two) and bounds |eta| AND the distance between the two
-        // etas by H = sum |b_k| max_i |x_ik| + ..., once per pass, instead of taking max |eta_i| over the rows (csrc/amwg_ptail.h, kTailLinear).
+        // etas by H = sum |b_k| max_i |x_ik| + ..., once per pass, instead of taking max |eta_i| over the rows (csrc/amwg_gtail.h, kTailLinear).
         let linInfo = null;
         if (!ml && rowInfo && /^v_\w+$/.test(rowInfo.eta) && !this.opts.no_tail_linear) {
           const E = rowInfo.eta, Ee = E.replace(/[$]/g, '\\$'), T = rowInfo.body;
@@ -1666,19 +1666,16 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
           }
           if (good) linInfo = { body: fused, hlin: terms.join(' + '), roundings: refRound + fusedRound, colmax: cms };
         }
-        if (ok && ml) {
-          ptailCand = true;
-          this.ltailInfo = { y: Number(mp[2]), cast: mp[1], n: boundV.cst, acc: loopAcc, i: canon.name, uniform, eta: mp[4], body: bodyText, rows: rowInfo };
-          out.push(indent + '//@LTAIL');
-        } else if (ok) {
-          ptailCand = true;
-          this.ptailInfo = { y: Number(mp[2]), lf: Number(mp[5]), cast: mp[1], n: boundV.cst, acc: loopAcc, i: canon.name, uniform, eta: mp[4], body: bodyText, rows: rowInfo, linear: linInfo };
-          out.push(indent + '//@PTAIL');
+        if (ok) {      // (the last candidate of each kind: glmTailPlan wants it to be the only one)
+          gtailCand = true;
+          const kind = ml ? 'logit' : 'pois';
+          (this.gtailInfo = this.gtailInfo || {})[kind] = { kind, y: Number(mp[2]), lf: ml ? null : Number(mp[5]), cast: mp[1], n: boundV.cst, acc: loopAcc, i: canon.name, uniform, eta: mp[4], body: bodyText, rows: rowInfo, linear: linInfo };
+          out.push(indent + GTAIL_MARK[kind]);
         }
       }
       this.otherSplitLoops = (this.otherSplitLoops || 0) + 1;
       this.emitSplit(out, indent, L.preamble, head, loop, [loopAcc]);
-      if (ptailCand) out.push(indent + (ml ? '//@LTAIL_END' : '//@PTAIL_END'));
+      if (gtailCand) out.push(indent + GTAIL_MARK[ml ? 'logit' : 'pois'] + '_END');
       return;
     }
     this.loopLabels.push({ native: true });
@@ -2001,14 +1998,14 @@ Translator.prototype.run = function () {
   const maxThreads = this.opts.max_threads || (this.heavyLoop ? (off > 73728 ? 512 : 256) : 1024);
   const rows = this.rowPlan(body);
   const tail = rows ? null : this.tailPlan(body);
-  const ptail0 = (rows || tail) ? null : this.poisTailPlan(body);
-  const ltail = (rows || tail || ptail0) ? null : this.logitTailPlan(body);
+  const gtail = (rows || tail) ? null : (this.glmTailPlan(body, 'pois') || this.glmTailPlan(body, 'logit'));      // (the Poisson plan first)
+  const logit = !!gtail && gtail.kind === 'logit';
   // PER-DATASET CONSTANTS (options.tail_consts_array; translate_datasets): what the two plans form from the data's values -- sum y, sum lfactorial(y) and the column
   // maxima of H; sum |y| -- goes into one more f64 array, appended last, instead of into the text.  Its layout follows from the closure's text alone, so D datasets
   // give D equal texts and D arrays.  Never staged: a handful of scalar loads per pass.
   let tailConsts = -1;
-  if ((ptail0 || ltail) && this.opts.tail_consts_array) {
-    const vals = ltail ? [ltail.sumAbsY] : [ptail0.sumY, ptail0.sumLF].concat(ptail0.linear ? ptail0.linear.colmax : []);
+  if (gtail && this.opts.tail_consts_array) {
+    const vals = logit ? [gtail.sumY] : [gtail.sumY, gtail.sumLF].concat(gtail.linear ? gtail.linear.colmax : []);
     tailConsts = this.arrays.length;
     this.arrays.push({ key: '#tail:consts', flat: Float64Array.from(vals), dims: [vals.length], type: 0, is01: false, ctype: 'double', esize: 8 });
     plan.push({ lds: false, off: 0 });
@@ -2110,117 +2107,113 @@ Translator.prototype.run = function () {
     src.push('    return norm_tail_approx<UserModel, G, BT>(S, d, smem, sub);');
     src.push('  }');
   }
-  if (ptail0 || ltail) {
-    // CERTIFIED POISSON TAIL (csrc/amwg_ptail.h; amwg_kernel.h "certified decisions"): with 16 lanes per chain the stepper decides accept tests from
+  if (gtail) {
+    // CERTIFIED POISSON TAIL (csrc/amwg_gtail.h PoisLink; amwg_kernel.h "certified decisions"): with 16 lanes per chain the stepper decides accept tests from
     // head + sum eta y - sum e^eta - sum lfactorial(y) and its bound, and evaluates the closure in the reference's order where that does not decide
-    // CERTIFIED LOGISTIC TAIL (csrc/amwg_ltail.h): the same for head + sum eta y - sum softplus(eta); its members are ltail_*, and eta is never fused
-    const ptail = ptail0 || ltail, pf = ltail ? 'ltail' : 'ptail';
+    // CERTIFIED LOGISTIC TAIL (LogitLink): the same for head + sum eta y - sum softplus(eta), through the same members; eta is never fused
+    const link = logit ? 'LogitLink' : 'PoisLink';
     const arrDecl = (j) => { const a = this.arrays[j], pl = plan[j];
       return '    const ' + a.ctype + ' *A' + j + ' = ' + (pl.lds ? 'reinterpret_cast<const ' + a.ctype + ' *>(smem + ' + pl.off + ')' : 'static_cast<const ' + a.ctype + ' *>(user_arr<' + j + '>(d))') + ';'; };
-    if (ltail) {
-      src.push('  // ---- certified logistic tail: `' + ptail.acc + '` ends in  for (i < ' + ptail.n + ') { ...; ' + ptail.acc + ' += A' + ptail.y + '[i] * eta - Math.log1p(Math.exp(eta)) }');
+    if (logit) {
+      src.push('  // ---- certified logistic tail: `' + gtail.acc + '` ends in  for (i < ' + gtail.n + ') { ...; ' + gtail.acc + ' += A' + gtail.y + '[i] * eta - Math.log1p(Math.exp(eta)) }');
       src.push('  static constexpr bool kLogitTail = true, kCertified = true, kReferenceOrder = true;');
     } else {
-    src.push('  // ---- certified Poisson tail: `' + ptail.acc + '` ends in  for (i < ' + ptail.n + ') { ...; ' + ptail.acc + ' += ld.pois(A' + ptail.y + '[i], Math.exp(eta)) }');
+    src.push('  // ---- certified Poisson tail: `' + gtail.acc + '` ends in  for (i < ' + gtail.n + ') { ...; ' + gtail.acc + ' += ld.pois(A' + gtail.y + '[i], Math.exp(eta)) }');
     src.push('  static constexpr bool kPoisTail = true, kCertified = true, kReferenceOrder = true;');
     }
-    src.push('  static constexpr int kCertifiedLanes = 16, kTailN = ' + ptail.n + ', kStateN = ' + this.P + ';');
-    src.push('  static constexpr bool kTailUniformState = ' + (ptail.uniform && this.P <= 12 ? 'true' : 'false') + ';      // the entries of the state the loop reads do not depend on the observation (and are few): scalar registers');
+    src.push('  static constexpr int kCertifiedLanes = 16, kTailN = ' + gtail.n + ', kStateN = ' + this.P + ';');
+    src.push('  static constexpr bool kTailUniformState = ' + (gtail.uniform && this.P <= 12 ? 'true' : 'false') + ';      // the entries of the state the loop reads do not depend on the observation (and are few): scalar registers');
     src.push('  typedef TailApprox Approx;');
+    const yNote = logit ? '>= sum |y[i]|' : 'sum y[i]';      // the bound's Y
     if (tailConsts >= 0) {
       const slot = (k) => 'tail_const(user_arr<' + tailConsts + '>(d), ' + k + ')';
       src.push('  // the data-dependent constants of the bound are slots of THIS dataset\'s array A' + tailConsts + ' (`#tail:consts`): one source serves every dataset');
       src.push('  static constexpr bool kTailPerDataset = true;');
       src.push('  static constexpr int kTailConsts = ' + tailConsts + ';');
-      if (ltail) src.push('  __device__ __forceinline__ static double ltail_sum_abs_y(const DataRef &d) { return ' + slot(0) + '; }      // >= sum |y[i]|');
-      else {
-        src.push('  __device__ __forceinline__ static double ptail_sum_y(const DataRef &d) { return ' + slot(0) + '; }      // sum y[i]');
-        src.push('  __device__ __forceinline__ static double ptail_sum_lf(const DataRef &d) { return ' + slot(1) + '; }      // sum lfactorial(y[i])');
-      }
-    } else
-    if (ltail) src.push('  __device__ __forceinline__ static double ltail_sum_abs_y() { return ' + hexFloat(ptail.sumAbsY) + '; }      // >= sum |y[i]| = ' + ptail.sumAbsY);
-    else {
-    src.push('  __device__ __forceinline__ static double ptail_sum_y() { return ' + hexFloat(ptail.sumY) + '; }      // sum y[i] = ' + ptail.sumY);
-    src.push('  __device__ __forceinline__ static double ptail_sum_lf() { return ' + hexFloat(ptail.sumLF) + '; }      // sum lfactorial(y[i]) = ' + ptail.sumLF);
+      src.push('  __device__ __forceinline__ static double gtail_sum_y(const DataRef &d) { return ' + slot(0) + '; }      // ' + yNote);
+      if (!logit) src.push('  __device__ __forceinline__ static double gtail_sum_lf(const DataRef &d) { return ' + slot(1) + '; }      // sum lfactorial(y[i])');
+    } else {
+      src.push('  __device__ __forceinline__ static double gtail_sum_y() { return ' + hexFloat(gtail.sumY) + '; }      // ' + yNote + ' = ' + gtail.sumY);
+      if (!logit) src.push('  __device__ __forceinline__ static double gtail_sum_lf() { return ' + hexFloat(gtail.sumLF) + '; }      // sum lfactorial(y[i]) = ' + gtail.sumLF);
     }
-    src.push('  __device__ __forceinline__ static double ' + pf + '_y(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
-    src.push(arrDecl(ptail.y));
-    src.push('    return (double)A' + ptail.y + '[i]; }');
-    if (!ltail) {
-    src.push('  __device__ __forceinline__ static double ptail_lf(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
-    src.push(arrDecl(ptail.lf));
-    src.push('    return A' + ptail.lf + '[i]; }');
+    src.push('  __device__ __forceinline__ static double gtail_y(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
+    src.push(arrDecl(gtail.y));
+    src.push('    return (double)A' + gtail.y + '[i]; }');
+    if (!logit) {
+    src.push('  __device__ __forceinline__ static double gtail_lf(const DataRef &d, const unsigned char *smem, int i) { (void)d; (void)smem;');
+    src.push(arrDecl(gtail.lf));
+    src.push('    return A' + gtail.lf + '[i]; }');
     }
-    src.push('  // the loop\'s statements up to the term: eta of observation v_' + ptail.i + ' for the chain whose state is S');
+    src.push('  // the loop\'s statements up to the term: eta of observation v_' + gtail.i + ' for the chain whose state is S');
     src.push('  template <class SV>');
-    src.push('  __device__ __forceinline__ static double ' + pf + '_eta(const SV &S, const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ') {');
+    src.push('  __device__ __forceinline__ static double gtail_eta(const SV &S, const DataRef &d, const unsigned char *smem, const int v_' + gtail.i + ') {');
     this.arrays.forEach((a, j) => src.push(arrDecl(j)));
     src.push('    (void)smem; (void)d; (void)S;');
-    for (const dl of ptail.decls) src.push('    ' + dl);
-    src.push('    ' + ptail.body);
-    src.push('    return ' + ptail.eta + ';');
+    for (const dl of gtail.decls) src.push('    ' + dl);
+    src.push('    ' + gtail.body);
+    src.push('    return ' + gtail.eta + ';');
     src.push('  }');
-    src.push('  static constexpr bool kTailRows = ' + (ptail.rows ? 'true' : 'false') + ';      // every data read of the statements addresses the observation\'s own row: loaded a round ahead (' + pf + '_load)');
-    if (ptail.rows) {
-      const per = ptail.rows.per, js = Object.keys(per).map(Number).sort((a, b) => a - b);
+    src.push('  static constexpr bool kTailRows = ' + (gtail.rows ? 'true' : 'false') + ';      // every data read of the statements addresses the observation\'s own row: loaded a round ahead (gtail_load)');
+    if (gtail.rows) {
+      const per = gtail.rows.per, js = Object.keys(per).map(Number).sort((a, b) => a - b);
       src.push('  struct TailRow { ' + js.map((j) => this.arrays[j].ctype + ' a' + j + '[' + (per[j].hi - per[j].lo) + '];').join(' ') + ' };');
-      src.push('  __device__ __forceinline__ static void ' + pf + '_load(const DataRef &d, const unsigned char *smem, const int v_' + ptail.i + ', TailRow &R) {');
+      src.push('  __device__ __forceinline__ static void gtail_load(const DataRef &d, const unsigned char *smem, const int v_' + gtail.i + ', TailRow &R) {');
       for (const j of js) src.push(arrDecl(j));
       src.push('    (void)smem; (void)d;');
       for (const j of js) {
         src.push('#pragma unroll');
-        src.push('    for (int q_ = 0; q_ < ' + (per[j].hi - per[j].lo) + '; ++q_) R.a' + j + '[q_] = A' + j + '[v_' + ptail.i + ' * ' + per[j].stride + ' + ' + per[j].lo + ' + q_];');
+        src.push('    for (int q_ = 0; q_ < ' + (per[j].hi - per[j].lo) + '; ++q_) R.a' + j + '[q_] = A' + j + '[v_' + gtail.i + ' * ' + per[j].stride + ' + ' + per[j].lo + ' + q_];');
       }
       src.push('  }');
-      src.push('  __device__ __forceinline__ static double ' + pf + '_y_row(const TailRow &R) { return (double)R.a' + ptail.y + '[0]; }');
+      src.push('  __device__ __forceinline__ static double gtail_y_row(const TailRow &R) { return (double)R.a' + gtail.y + '[0]; }');
       src.push('  template <class SV>');
-      src.push('  __device__ __forceinline__ static double ' + pf + '_eta_row(const SV &S, const TailRow &R, const int v_' + ptail.i + ') {');
+      src.push('  __device__ __forceinline__ static double gtail_eta_row(const SV &S, const TailRow &R, const int v_' + gtail.i + ') {');
       src.push('    (void)S; (void)R;');
-      for (const dl of ptail.decls) src.push('    ' + dl);
-      src.push('    ' + ptail.rows.body);
-      src.push('    return ' + ptail.rows.eta + ';');
+      for (const dl of gtail.decls) src.push('    ' + dl);
+      src.push('    ' + gtail.rows.body);
+      src.push('    return ' + gtail.rows.eta + ';');
       src.push('  }');
     }
-    src.push('  static constexpr bool kTailLinear = ' + (ptail.linear ? 'true' : 'false') + ';      // eta is a sum of (row entry) x (state entry) products, state entries and literals: formed by fused steps');
-    if (ptail.linear) {
-      src.push('  static constexpr int kTailLinearRoundings = ' + ptail.linear.roundings + ';      // roundings of eta in the closure\'s statements + in the fused form');
+    src.push('  static constexpr bool kTailLinear = ' + (gtail.linear ? 'true' : 'false') + ';      // eta is a sum of (row entry) x (state entry) products, state entries and literals: formed by fused steps');
+    if (gtail.linear) {
+      src.push('  static constexpr int kTailLinearRoundings = ' + gtail.linear.roundings + ';      // roundings of eta in the closure\'s statements + in the fused form');
       src.push('  template <class SV>');
-      src.push('  __device__ __forceinline__ static double ptail_eta_fused(const SV &S, const TailRow &R, const int v_' + ptail.i + ') {');
+      src.push('  __device__ __forceinline__ static double gtail_eta_fused(const SV &S, const TailRow &R, const int v_' + gtail.i + ') {');
       src.push('    (void)S; (void)R;');
-      for (const dl of ptail.decls) src.push('    ' + dl);
-      src.push('    ' + ptail.linear.body);
-      src.push('    return ' + ptail.rows.eta + ';');
+      for (const dl of gtail.decls) src.push('    ' + dl);
+      src.push('    ' + gtail.linear.body);
+      src.push('    return ' + gtail.rows.eta + ';');
       src.push('  }');
       src.push('  // H >= sum of the magnitudes of eta\'s summands for every observation (column maxima of the data x |state entry|): bounds |eta| and both etas\' roundings');
-      if (tailConsts >= 0) src.push('  __device__ __forceinline__ static double ptail_hlin(const StateView &S, const DataRef &d) { const void *c_ = user_arr<' + tailConsts + '>(d); (void)c_; return ' + ptail.linear.hlin + '; }');
+      if (tailConsts >= 0) src.push('  __device__ __forceinline__ static double gtail_hlin(const StateView &S, const DataRef &d) { const void *c_ = user_arr<' + tailConsts + '>(d); (void)c_; return ' + gtail.linear.hlin + '; }');
       else
-      src.push('  __device__ __forceinline__ static double ptail_hlin(const StateView &S) { return ' + ptail.linear.hlin + '; }');
+      src.push('  __device__ __forceinline__ static double gtail_hlin(const StateView &S) { return ' + gtail.linear.hlin + '; }');
     }
     src.push('  // the closure up to that loop: what its accumulator holds when the loop begins (this lane\'s share)');
     src.push('  template <int G>');
     src.push('  __device__ static double tail_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
     this.arrays.forEach((a, j) => src.push(arrDecl(j)));
     src.push('    (void)smem; (void)sub; (void)d;');
-    for (const ln of ptail.head) src.push(ln);
-    src.push('    return v_' + ptail.acc + ';');
+    for (const ln of gtail.head) src.push(ln);
+    src.push('    return v_' + gtail.acc + ';');
     src.push('  }');
-    src.push('  __device__ static double ' + pf + '_head_sequence(const StateView &S, const DataRef &d, const unsigned char *smem) { return tail_head<1>(S, d, smem, 0); }      // (one lane\'s walk: the reference\'s order)');
+    src.push('  __device__ static double gtail_head_sequence(const StateView &S, const DataRef &d, const unsigned char *smem) { return tail_head<1>(S, d, smem, 0); }      // (one lane\'s walk: the reference\'s order)');
     src.push('  // ... with the magnitudes of what it adds up and the number of additions');
     src.push('  template <int G>');
-    src.push('  __device__ __forceinline__ static HeadPair ' + pf + '_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
+    src.push('  __device__ __forceinline__ static HeadPair gtail_head(const StateView &S, const DataRef &d, const unsigned char *smem, int sub) {');
     this.arrays.forEach((a, j) => src.push(arrDecl(j)));
     src.push('    (void)smem; (void)sub; (void)d;');
     src.push('    double mag_ = 0.0, cnt_ = 0.0;');
-    for (const ln of ptail.headMag) src.push(ln);
-    src.push('    return HeadPair{v_' + ptail.acc + ', mag_, cnt_};');
+    for (const ln of gtail.headMag) src.push(ln);
+    src.push('    return HeadPair{v_' + gtail.acc + ', mag_, cnt_};');
     src.push('  }');
     src.push('  template <int G, int BT, class C>');
     src.push('  __device__ __forceinline__ static Approx log_post_approx(C &, const StateView &S, const ModelConsts &, const DataRef &d, const unsigned char *smem, int sub) {');
-    src.push('    return ' + (ltail ? 'logit' : 'pois') + '_tail_approx<UserModel, G, BT>(S, d, smem, sub);');
+    src.push('    return glm_tail_approx<UserModel, ' + link + ', G, BT>(S, d, smem, sub);');
     src.push('  }');
     src.push('  template <int G, class C>');
     src.push('  __device__ __forceinline__ static double reference_order(C &, const StateView &S, const ModelConsts &, const DataRef &d, const unsigned char *smem, int sub) {');
-    src.push('    return ' + (ltail ? 'logit' : 'pois') + '_tail_reference<UserModel, G>(S.base, &d, smem, sub);');
+    src.push('    return glm_tail_reference<UserModel, ' + link + ', G>(S.base, &d, smem, sub);');
     src.push('  }');
   }
   src.push('#endif');
@@ -2275,10 +2268,10 @@ Translator.prototype.run = function () {
     // same fact off the generated source -- kCertifiedTail / kTailN -- so no field of amwg_user_model carries it.)
     cert_tail_n: tail ? tail.n : 0,
     rows_cert: rows && rows.cert ? 1 : 0,
-    // certified Poisson tail (csrc/amwg_ptail.h): observations of the closure's final log-link Poisson loop; 0 = none (the host library reads kPoisTail / kTailN off the source)
-    pois_tail_n: ptail0 ? ptail0.n : 0,
-    // certified logistic tail (csrc/amwg_ltail.h): observations of the closure's final logistic-regression loop; 0 = none (kLogitTail / kTailN of the source)
-    logit_tail_n: ltail ? ltail.n : 0,
+    // certified Poisson tail (csrc/amwg_gtail.h PoisLink): observations of the closure's final log-link Poisson loop; 0 = none (the host library reads kPoisTail / kTailN off the source)
+    pois_tail_n: gtail && !logit ? gtail.n : 0,
+    // certified logistic tail (csrc/amwg_gtail.h LogitLink): observations of the closure's final logistic-regression loop; 0 = none (kLogitTail / kTailN of the source)
+    logit_tail_n: logit ? gtail.n : 0,
   };
 };
 
@@ -2299,15 +2292,17 @@ Translator.prototype.tailPlan = function (body) {
   return { x: Number(m[1]), n: Number(m[2]), acc: m[3], mean: m[4], sd: m[5], head };
 };
 
-// The CERTIFIED POISSON TAIL of a closure (csrc/amwg_ptail.h): its LAST statement before `return acc` is the log-link Poisson loop forLoop() marked with //@PTAIL;
-// everything before is the head -- it must not return early, must be nothing but accumulations (headMagnitude), and the closure must not write derived quantities.
-// -> {y, lf (array indices), n, acc, i, uniform, eta, body, decls, head, headMag, sumY, sumLF} or null
-Translator.prototype.poisTailPlan = function (body) {
-  if (!this.ptailInfo || this.derived.length || this.isHelper || this.opts.no_cert_tail || this.opts.no_pois_tail || this.hasBinary) return null;
+// The CERTIFIED GLM TAIL of a closure (csrc/amwg_gtail.h), kind 'pois' or 'logit': its LAST statement before `return acc` is the log-link Poisson loop / the
+// logistic-regression loop forLoop() marked with //@PTAIL / //@LTAIL; everything before is the head -- it must not return early, must be nothing but accumulations
+// (headMagnitude), and the closure must not write derived quantities.  Switched off by no_cert_tail and by no_pois_tail / no_logit_tail.
+// -> {kind, y, lf (array indices; lf: Poisson only), n, acc, i, uniform, eta, body, rows, linear, decls, head, headMag, sumY (the bound's Y), sumLF (Poisson only)} or null
+const GTAIL_MARK = { pois: '//@PTAIL', logit: '//@LTAIL' };
+Translator.prototype.glmTailPlan = function (body, kind) {
+  const info = this.gtailInfo && this.gtailInfo[kind], mark = GTAIL_MARK[kind];
+  if (!info || this.derived.length || this.isHelper || this.opts.no_cert_tail || this.opts['no_' + kind + '_tail'] || this.hasBinary) return null;
   let iB = -1, iE = -1, nB = 0;
-  body.forEach((ln, i) => { const t = ln.trim(); if (t === '//@PTAIL') { iB = i; nB++; } else if (t === '//@PTAIL_END') iE = i; });
-  if (nB !== 1 || iE < iB) return null;      // (ptailInfo describes the last candidate: it must be the only one)
-  const info = this.ptailInfo;
+  body.forEach((ln, i) => { const t = ln.trim(); if (t === mark) { iB = i; nB++; } else if (t === mark + '_END') iE = i; });
+  if (nB !== 1 || iE < iB) return null;      // (info describes the last candidate: it must be the only one)
   const tailLines = body.slice(iE + 1).map((ln) => ln.trim()).filter((t) => t && t.indexOf('//') !== 0);
   if (!(tailLines.length === 2 && /^if constexpr \(DERIVE\) \{ \(void\)dv; \}$/.test(tailLines[0]) && tailLines[1] === 'return v_' + info.acc + ';')) return null;
   const head = body.slice(0, iB);
@@ -2317,43 +2312,27 @@ Translator.prototype.poisTailPlan = function (body) {
   // the closure's locals (declared at the top of the body): the loop's statements use them as scratch
   const decls = [];
   for (const ln of head) { const m = /^(double|int) (v_\w+) = 0;$/.exec(ln.trim()); if (m && m[2] !== 'v_' + info.i) decls.push(ln.trim()); }
-  // sum y (integers: exact) and sum lfactorial(y) (Neumaier's compensated sum: within an ulp or two of the real sum of the stored values)
-  let sumY = 0, sF = 0, cF = 0;
-  const yf = this.arrays[info.y].flat, lf = this.arrays[info.lf].flat;
-  for (let i = 0; i < info.n; i++) {
-    sumY += yf[i];
-    const t = sF + lf[i];
-    cF += Math.abs(sF) >= Math.abs(lf[i]) ? (sF - t) + lf[i] : (lf[i] - t) + sF;
-    sF = t;
-  }
-  if (this.opts.tail_consts_array && !(Number.isFinite(sumY) && Number.isFinite(sF + cF))) return null;      // (a literal would carry it into the text; a slot must be a number the bound can use)
-  return Object.assign({}, info, { decls, head, headMag: hm.mag, sumY, sumLF: sF + cF });
-};
-
-// The CERTIFIED LOGISTIC TAIL of a closure (csrc/amwg_ltail.h): its LAST statement before `return acc` is the logistic-regression loop forLoop() marked with //@LTAIL;
-// the head under the Poisson tail's conditions.  Switched off by no_cert_tail and no_logit_tail.
-// -> {y (array index), n, acc, i, uniform, eta, body, rows, decls, head, headMag, sumAbsY} or null
-Translator.prototype.logitTailPlan = function (body) {
-  if (!this.ltailInfo || this.derived.length || this.isHelper || this.opts.no_cert_tail || this.opts.no_logit_tail || this.hasBinary) return null;
-  let iB = -1, iE = -1, nB = 0;
-  body.forEach((ln, i) => { const t = ln.trim(); if (t === '//@LTAIL') { iB = i; nB++; } else if (t === '//@LTAIL_END') iE = i; });
-  if (nB !== 1 || iE < iB) return null;      // (ltailInfo describes the last candidate: it must be the only one)
-  const info = this.ltailInfo;
-  const tailLines = body.slice(iE + 1).map((ln) => ln.trim()).filter((t) => t && t.indexOf('//') !== 0);
-  if (!(tailLines.length === 2 && /^if constexpr \(DERIVE\) \{ \(void\)dv; \}$/.test(tailLines[0]) && tailLines[1] === 'return v_' + info.acc + ';')) return null;
-  const head = body.slice(0, iB);
-  if (head.some((ln) => /\breturn\b|\bdv\[|\bdq_/.test(ln))) return null;
-  const hm = this.headMagnitude(head, info.acc);
-  if (hm.why) return null;
-  const decls = [];
-  for (const ln of head) { const m = /^(double|int) (v_\w+) = 0;$/.exec(ln.trim()); if (m && m[2] !== 'v_' + info.i) decls.push(ln.trim()); }
-  // sum |y| (the bound's Y), pushed up by more than a plain sum's rounding so that it is not below the real sum
-  let sumAbsY = 0;
   const yf = this.arrays[info.y].flat;
-  for (let i = 0; i < info.n; i++) sumAbsY += Math.abs(yf[i]);
-  if (!Number.isInteger(sumAbsY) || sumAbsY > 9007199254740992) sumAbsY *= 1 + info.n * Math.pow(2, -52);
-  if (!Number.isFinite(sumAbsY)) return null;
-  return Object.assign({}, info, { decls, head, headMag: hm.mag, sumAbsY });
+  let sumY = 0, sumLF;
+  if (kind === 'pois') {
+    // sum y (integers: exact) and sum lfactorial(y) (Neumaier's compensated sum: within an ulp or two of the real sum of the stored values)
+    let sF = 0, cF = 0;
+    const lf = this.arrays[info.lf].flat;
+    for (let i = 0; i < info.n; i++) {
+      sumY += yf[i];
+      const t = sF + lf[i];
+      cF += Math.abs(sF) >= Math.abs(lf[i]) ? (sF - t) + lf[i] : (lf[i] - t) + sF;
+      sF = t;
+    }
+    sumLF = sF + cF;
+    if (this.opts.tail_consts_array && !(Number.isFinite(sumY) && Number.isFinite(sumLF))) return null;      // (a literal would carry it into the text; a slot must be a number the bound can use)
+  } else {
+    // sum |y| (the bound's Y), pushed up by more than a plain sum's rounding so that it is not below the real sum
+    for (let i = 0; i < info.n; i++) sumY += Math.abs(yf[i]);
+    if (!Number.isInteger(sumY) || sumY > 9007199254740992) sumY *= 1 + info.n * Math.pow(2, -52);
+    if (!Number.isFinite(sumY)) return null;
+  }
+  return Object.assign({}, info, { decls, head, headMag: hm.mag, sumY, sumLF });
 };
 
 // The head of a plan (everything before the closure's final loop) as value + MAGNITUDES: the certified values bound the two orders the head's terms are summed in

@@ -187,7 +187,7 @@ static void pois_case(const char *name, const std::vector<double> &Xm, const std
   const double bE = U * (2.02 * (1 + H) * Y + 2 * L + 4 * (H * Y + L + F) + 14.3 * HYL + (n + 9.0) * W);
   const double bA = U * (7.7 * HYL + 128 * L + 2 * (n / 64.0 + 9.0) * W);
   note(name, E, A, Rq, bE, bA, eps);
-  // ---- the same model as a TRANSLATED closure with a certified Poisson tail (csrc/amwg_ptail.h pois_tail_approx): eta by the closure's own statements -- the
+  // ---- the same model as a TRANSLATED closure with a certified Poisson tail (csrc/amwg_gtail.h glm_tail_approx<PoisLink>): eta by the closure's own statements -- the
   // reference's fp64 eta on both sides, so the real number the two are measured against is the one formed FROM that eta --, H = max |eta_i| over the rows, the head's
   // nine additions with their magnitudes (Hc = 9, Hm = sum |term|), eps = u W (n + n / 32 + 2 Hc + 23 H + 200) 1.25
   {
@@ -223,7 +223,7 @@ static void pois_case(const char *name, const std::vector<double> &Xm, const std
     const double W2 = Hm + (1.0 + H2) * Y + L2 + std::fabs(F2);
     const double eps2 = (H2 <= 690.0) ? W2 * ((double)n + (double)(n / 32) + 2.0 * Hc + 23.0 * H2 + 200.0) * 1.25 * U : INFINITY;
     const double A2 = (P + e1[0]) - F2;
-    // amwg_ptail.h, the pieces: E -- the terms (log of exp against eta, exp_v8, three roundings) and the running sum of Hc + n additions;  A -- exp_bounded, the head in
+    // amwg_gtail.h, the pieces: E -- the terms (log of exp against eta, exp_v8, three roundings) and the running sum of Hc + n additions;  A -- exp_bounded, the head in
     // the lanes' order, the lanes' sums and butterflies, the closing three roundings, F
     const double bE2 = U * (2.02 * (1 + H2) * Y + 2 * L2 + 4 * (H2 * Y + L2 + F2) + (Hc + n) * W2);
     const double bA2 = U * (128 * L2 + Hc * Hm + (n / 64.0 + 7.0) * (H2 * Y + L2) + 3 * W2 + 2 * F2);

@@ -1,11 +1,11 @@
-// logit_bound_replay.cpp -- TEST INFRASTRUCTURE (host only): the derivation behind the certified logistic tail (csrc/amwg_ltail.h logit_tail_approx and its eps),
+// logit_bound_replay.cpp -- TEST INFRASTRUCTURE (host only): the derivation behind the certified logistic tail (csrc/amwg_gtail.h glm_tail_approx<LogitLink> and its eps),
 // replayed in QUAD precision, in the manner of bound_replay.cpp.
 //
 // The derivation says: the reference's expression E (fp64: the head, then one running sum over the terms y eta - log1p_exp_v8(eta)) and the pass's value A (fp64:
 // per-lane sums of eta y by fused steps and of softplus_bounded(eta), butterflies, their difference) both approximate one REAL number R -- formed from the same fp64
 // eta_i, which are the reference's own on both sides -- within |E - R| <= bE and |A - R| <= bA, and the bound handed to the stepper is eps >= 2 (bE + bA).  Here E
 // and A are computed in fp64 with those operations and orders, R in __float128, and the three inequalities are checked with the constants AS WRITTEN in the comment
-// of amwg_ltail.h: random states and adversarial ones (eta next to 0, +-36, +-690; y in {0, 1}, all zero, all one, real weights of both signs; n in {64, 65, 517, 1e4}).
+// of amwg_gtail.h: random states and adversarial ones (eta next to 0, +-36, +-690; y in {0, 1}, all zero, all one, real weights of both signs; n in {64, 65, 517, 1e4}).
 // Prints the worst ratios; exit 1 if a half exceeds 1, |A - E| / eps exceeds 0.5 (the bar tests/test_gpu_bound_audit.py sets), or the pieces exceed eps.
 //   g++ -std=c++17 -O2 -ffp-contract=off -fno-fast-math -I bayes.js_amd/csrc tests/host/logit_bound_replay.cpp -lquadmath
 #include <quadmath.h>
@@ -72,7 +72,7 @@ static void logit_case(const char *name, const std::vector<double> &x1, const st
   Y *= 1 + n * 0x1p-52;      // (the translator's Y: pushed up)
   const double W = Hm + H * Y + L + (double)n;
   const double eps = (H <= 690.0) ? (W * ((double)n + (double)(n / 32) + 2.0 * Hc + 200.0) * U + (double)n * kSoftplusBoundedAbs) * 1.25 : INFINITY;
-  // amwg_ltail.h, the pieces: E -- the reference's softplus 2 u (n + L), the product u H Y, the subtraction u (H Y + L), the running sum of Hc + n additions;
+  // amwg_gtail.h, the pieces: E -- the reference's softplus 2 u (n + L), the product u H Y, the subtraction u (H Y + L), the running sum of Hc + n additions;
   // A -- softplus_bounded n kAbs, the head in the lanes' order Hc u Hm, the lanes' sums and butterflies (n / 64 + 7) u (H Y + L), the difference and the closing sum 2 u W
   const double bE = U * (2 * ((double)n + L) + H * Y + (H * Y + L) + (Hc + n) * W);
   const double bA = (double)n * kSoftplusBoundedAbs + U * (Hc * Hm + (n / 64.0 + 7.0) * (H * Y + L) + 2 * W);

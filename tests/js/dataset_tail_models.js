@@ -1,7 +1,7 @@
 // (sloppy mode on purpose, like dataset_models.js: the closures are written against a global `ld`)
 /*
  * dataset_tail_models.js -- TEST FIXTURES: closures that end in a logistic-regression loop or in a log-link Poisson loop, on D = 3 datasets of equal shape, for the
- * certified tails of options.datasets with a translated closure (translate.js translate_datasets with tail_consts_array; csrc/amwg_ptail.h, amwg_ltail.h:
+ * certified tails of options.datasets with a translated closure (translate.js translate_datasets with tail_consts_array; csrc/amwg_gtail.h:
  * kTailPerDataset).  build(name[, n_obs[, n_datasets]]) -> {params, datasets, log_post}; the data comes from fixed seeds.  Used by
  * tests/js/translate_dataset_tails_cli.js, tests/js/test_gpu_user_dataset_tails.js, tools/bound_audit.py (dstail) and tools/time_user_dataset_tails.py.
  * Every slot of a dataset's constants differs between the datasets: a bound formed from dataset 0's values for everyone shows in the host test.

@@ -1,6 +1,6 @@
 'use strict';
-// logit_models.js -- TEST FIXTURES: closures that end in a logistic-regression loop, for the certified logistic tail (bayes.js_amd/translate.js logitTailPlan,
-// csrc/amwg_ltail.h) on and off its fast path, and the closures for which the translator must NOT emit that plan.  Kept apart from user_models.js, whose closures
+// logit_models.js -- TEST FIXTURES: closures that end in a logistic-regression loop, for the certified logistic tail (bayes.js_amd/translate.js glmTailPlan,
+// csrc/amwg_gtail.h) on and off its fast path, and the closures for which the translator must NOT emit that plan.  Kept apart from user_models.js, whose closures
 // have goldens of the reference; these are compared with the same closure at one lane per chain with the expression in every update.
 //   build(name, n, ymode) -> { params, data, log_post }     n observations (default 517: a ragged last round); ymode 'zeros' | 'ones' | undefined (drawn)
 const { lcg } = require('./user_models.js');

@@ -358,7 +358,7 @@ const BENCH = {
     } },
   bench_hier: { params: CASES.hier_normal_closure.params, data: () => synth.hier(10000, 32, 20260925), log_post: CASES.hier_normal_closure.log_post },
   bench_glm: { params: CASES.pois_glm_closure.params, data: () => synth.glm(50000, 20260925), log_post: CASES.pois_glm_closure.log_post },
-  // (round 6, the certified Poisson tail of translate.js poisTailPlan on its FALLBACK paths -- csrc/amwg_ptail.h: a predictor that is not linear (a product of two
+  // (round 6, the certified Poisson tail of translate.js glmTailPlan on its FALLBACK paths -- csrc/amwg_gtail.h: a predictor that is not linear (a product of two
   // coefficients: the closure's own statements for eta, H = max |eta| over the rows), a coefficient gathered by the data (per-lane LDS reads of the state, the plain
   // loop), a read of the NEXT observation's row (scalar-register state, no row cache), and a ragged 517 observations)
   pois_tail_nonlinear: { params: CASES.pois_glm_closure.params, data: () => synth.glm(517, 20260929),

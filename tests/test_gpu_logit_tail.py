@@ -1,4 +1,4 @@
-"""-m gpu: certified decisions for closures that end in a logistic-regression loop (translate.js logitTailPlan, csrc/amwg_ltail.h): the 16-lane certified kernel
+"""-m gpu: certified decisions for closures that end in a logistic-regression loop (translate.js glmTailPlan, csrc/amwg_gtail.h): the 16-lane certified kernel
 decides like the expression in the REFERENCE's order -- every byte of the one-lane run that evaluates the expression in every update, the reference's golden
 chains for logit_n10k --, on and off the pass's fast path, beyond the reference's straight-line range and beyond the bound's cut-off; the device's
 softplus_bounded is the host's; the bound audited on the device (tools/bound_audit.py --only logit)."""
@@ -114,7 +114,7 @@ def _four_runs_agree(spec, kw, shifts=(10, 34)):
 @pytest.mark.parametrize("label,flags", [("logit_tail_gather", ("false", "false", "false")), ("logit_tail_next_row", ("true", "false", "false")),
                                          ("logit_tail_small", ("true", "true", "false")), ("logit_tail_weights", ("true", "true", "false"))])
 def test_certified_logistic_tail_fallback_paths_equal_the_expression(label, flags):
-    """csrc/amwg_ltail.h off its fast path -- a coefficient gathered by the data (per-lane LDS reads of the state, the plain loop), a read of the next observation's
+    """csrc/amwg_gtail.h off its fast path -- a coefficient gathered by the data (per-lane LDS reads of the state, the plain loop), a read of the next observation's
     row (no row cache) --, 517 observations (a ragged last round) and real-valued weights in the place of y: the 16-lane certified kernel against the same closure at
     ONE lane per chain with the expression in every update, and against narrowed / widened bounds: every bit of every chain, cached log_post included."""
     spec, src, meta = logit_host.spec(label)

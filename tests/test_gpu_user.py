@@ -300,7 +300,7 @@ def test_a_closure_kernel_without_a_body_at_its_geometry_fails_the_call():
 
 
 def test_certified_poisson_tail_of_a_translated_closure_reproduces_the_reference_and_the_full_evaluation():
-    """translate.js poisTailPlan + csrc/amwg_ptail.h: a closure that ends in `lp += ld.pois(y[i], Math.exp(eta))` runs amwg_user_step_cert at 16 lanes per chain (four
+    """translate.js glmTailPlan + csrc/amwg_gtail.h: a closure that ends in `lp += ld.pois(y[i], Math.exp(eta))` runs amwg_user_step_cert at 16 lanes per chain (four
     chains of a wavefront share every row).  Its decisions are the expression's in the REFERENCE's order: chain by chain the reference's golden trajectory, and every bit
     of the run that evaluates the expression in every update at one lane per chain; widened and narrowed bounds change nothing."""
     from gpu_util import run_schedule
@@ -331,7 +331,7 @@ def test_certified_poisson_tail_of_a_translated_closure_reproduces_the_reference
 
 @pytest.mark.parametrize("name,flags", [("pois_tail_nonlinear", ("true", "true", "false")), ("pois_tail_gather", ("false", "false", "false")), ("pois_tail_next_row", ("true", "false", "false"))])
 def test_certified_poisson_tail_fallback_paths_equal_the_expression(name, flags):
-    """csrc/amwg_ptail.h off its fast path -- a predictor that is not linear (eta by the closure's own statements, H = max |eta| over the rows), a coefficient gathered
+    """csrc/amwg_gtail.h off its fast path -- a predictor that is not linear (eta by the closure's own statements, H = max |eta| over the rows), a coefficient gathered
     by the data (per-lane LDS reads of the state, the plain loop), a read of the next observation's row (no row cache) --, 517 observations (a ragged last round): the
     16-lane certified kernel against the same closure at ONE lane per chain with the expression in every update, and against narrowed / widened bounds: every bit of
     every chain, cached log_post included (the certified kernel evaluates the expression in the reference's order)."""

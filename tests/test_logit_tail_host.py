@@ -1,6 +1,6 @@
-"""Certified decisions for closures that end in a logistic-regression loop, without a GPU: the translator's plan (translate.js logitTailPlan) is found where it
+"""Certified decisions for closures that end in a logistic-regression loop, without a GPU: the translator's plan (translate.js glmTailPlan) is found where it
 must be and refused where it must be, the generated sources compile for gfx950 (hiprtc needs no device), softplus_bounded keeps the absolute error its comment
-derives (tests/host/softplus_bounded_fuzz.cpp against __float128) and the bound of csrc/amwg_ltail.h holds with a factor of two when its derivation is replayed in
+derives (tests/host/softplus_bounded_fuzz.cpp against __float128) and the bound of csrc/amwg_gtail.h holds with a factor of two when its derivation is replayed in
 quad precision (tests/host/logit_bound_replay.cpp)."""
 import ctypes as C
 import os
@@ -23,20 +23,20 @@ def _flags(src):
 def test_logit_n10k_gets_the_certified_logistic_tail():
     src, _, _ = user_host.translated("logit_n10k")
     for token in ("kLogitTail = true, kCertified = true, kReferenceOrder = true", "kCertifiedLanes = 16, kTailN = 10000, kStateN = 4", "kTailUniformState = true", "kTailRows = true",
-                  "logit_tail_approx<UserModel, G, BT>", "logit_tail_reference<UserModel, G>", "ltail_sum_abs_y() { return 4366.0; }",
+                  "glm_tail_approx<UserModel, LogitLink, G, BT>", "glm_tail_reference<UserModel, LogitLink, G>", "gtail_sum_y() { return 4366.0; }",
                   "struct TailRow { uint8_t a0[1]; double a1[1]; double a2[1]; double a3[1]; };"):
         assert token in src, token
     assert "kPoisTail" not in src and "kCertifiedTail" not in src and "@LTAIL" not in src
     # the lane-split loop of the expression is emitted as it was: one device function for the softplus, its branch-free form in the unrolled body
     assert "log1p_exp_v8_open(rr_, v_eta)" in src and "log1p_exp_cold(v_eta)" in src
     # eta is the closure's own statements, never the fused form
-    assert "ltail_eta_fused" not in src and "(((S(0) + (S(1) * R.a1[(0) - 0])) + (S(2) * R.a2[(0) - 0])) + (S(3) * R.a3[(0) - 0]))" in src
+    assert "gtail_eta_fused" not in src and "(((S(0) + (S(1) * R.a1[(0) - 0])) + (S(2) * R.a2[(0) - 0])) + (S(3) * R.a3[(0) - 0]))" in src
 
 
 @pytest.mark.parametrize("name", ["logit_bern_n10k", "logistic_softplus", "records_logistic"])
 def test_other_logistic_spellings_and_loops_that_are_not_last_get_no_plan(name):
     src, _, _ = user_host.translated(name)
-    assert "kLogitTail" not in src and "logit_tail_approx" not in src and "@LTAIL" not in src
+    assert "kLogitTail" not in src and "LogitLink" not in src and "@LTAIL" not in src
 
 
 def test_the_poisson_closure_keeps_its_own_plan():
@@ -120,7 +120,7 @@ def test_softplus_bounded_keeps_its_derived_absolute_error(tmp_path):
 
 
 def test_logistic_tail_bound_holds_with_a_factor_of_two_in_quad_precision(tmp_path):
-    """the derivation of csrc/amwg_ltail.h replayed in __float128 on random and adversarial inputs: both halves hold, the pieces add up to no more than eps, and the
+    """the derivation of csrc/amwg_gtail.h replayed in __float128 on random and adversarial inputs: both halves hold, the pieces add up to no more than eps, and the
     worst |A - E| / eps is at most 0.5"""
     exe = _build_host(tmp_path, "logit_bound_replay")
     r = subprocess.run([str(exe), "8"], capture_output=True, text=True, timeout=600)

@@ -331,7 +331,7 @@ console.log(JSON.stringify(out));
 
 
 def test_poisson_tail_plan_is_found_and_refused_where_it_must_be(tmp_path):
-    """translate.js poisTailPlan (csrc/amwg_ptail.h): a closure that ENDS in `lp += ld.pois(y[i], Math.exp(eta))` over all observations gets certified values at 16 lanes
+    """translate.js glmTailPlan (csrc/amwg_gtail.h): a closure that ENDS in `lp += ld.pois(y[i], Math.exp(eta))` over all observations gets certified values at 16 lanes
     per chain.  Scalar-register state only if every state index is the same for all observations, the row cache only if every data read is of the observation's own row;
     no plan at all for a negative count (the reference's term is -inf), a loop that is not the last statement, a head that does more than add, an early return."""
     import ctypes as C
@@ -340,7 +340,7 @@ def test_poisson_tail_plan_is_found_and_refused_where_it_must_be(tmp_path):
     m = user_host.host_model("pois_glm_closure")
     assert m.meta["pois_tail_n"] == 500 and m.meta["cert_tail_n"] == 0 and m.meta["rows_cert"] == 0
     for token in ("kPoisTail = true, kCertified = true, kReferenceOrder = true", "kCertifiedLanes = 16, kTailN = 500, kStateN = 9", "kTailUniformState = true", "kTailRows = true", "kTailLinear = true", "kTailLinearRoundings = 23", "__builtin_fma(R.a1[(v___b1_k) - 0], S(v___b1_k), v_eta)",
-                  "struct TailRow { uint8_t a0[1]; double a1[7]; };", "R.a1[(v___b1_k) - 0] * S(v___b1_k)", "pois_tail_approx<UserModel, G, BT>", "pois_tail_reference<UserModel, G>"):
+                  "struct TailRow { uint8_t a0[1]; double a1[7]; };", "R.a1[(v___b1_k) - 0] * S(v___b1_k)", "glm_tail_approx<UserModel, PoisLink, G, BT>", "glm_tail_reference<UserModel, PoisLink, G>"):
         assert token in m.source, token
     L = A.lib()
     n = C.c_size_t(0)

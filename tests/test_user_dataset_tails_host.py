@@ -1,5 +1,5 @@
-"""Certified Poisson / logistic tails for a translated closure on MANY datasets (translate.js translate_datasets with tail_consts_array; csrc/amwg_ptail.h and
-amwg_ltail.h: kTailPerDataset), the part that needs no GPU: the one source carries the tail and the marker, the data-dependent constants of its bound are slots of one
+"""Certified Poisson / logistic tails for a translated closure on MANY datasets (translate.js translate_datasets with tail_consts_array; csrc/amwg_gtail.h:
+kTailPerDataset), the part that needs no GPU: the one source carries the tail and the marker, the data-dependent constants of its bound are slots of one
 more array per dataset -- EACH dataset's own, which is what a device run cannot see: a bound formed from dataset 0's values for everyone still decides nearly every test
 the same way --, a dataset that cannot take the plan sends all of them back to the expression, the source compiles for gfx950 with the certified dataset twin, evaluates
 to the closure's value under Node on every dataset, and what the library refuses it refuses before a device is opened.  Fixtures: tests/js/dataset_tail_models.js.
@@ -60,11 +60,11 @@ def test_one_source_with_the_tail_and_the_per_dataset_marker(tag):
     assert meta["lds_bytes"] == off["lds_bytes"] and meta["lds_bytes_one_lane"] == off["lds_bytes_one_lane"]
     assert off["array_keys"] == meta["array_keys"][:-1]
     # no literal of the bound in the text, and the accessors take the data reference
-    assert "ptail_sum_y()" not in source and "ptail_sum_lf()" not in source and "ltail_sum_abs_y()" not in source and "ptail_hlin(const StateView &S)" not in source
+    assert "gtail_sum_y()" not in source and "gtail_sum_lf()" not in source and "gtail_hlin(const StateView &S)" not in source
     if is_logit(tag):
-        assert "ltail_sum_abs_y(const DataRef &d)" in source
+        assert "gtail_sum_y(const DataRef &d)" in source
     else:
-        assert "ptail_sum_y(const DataRef &d)" in source and "ptail_sum_lf(const DataRef &d)" in source and "ptail_hlin(const StateView &S, const DataRef &d)" in source
+        assert "gtail_sum_y(const DataRef &d)" in source and "gtail_sum_lf(const DataRef &d)" in source and "gtail_hlin(const StateView &S, const DataRef &d)" in source
 
 
 def neumaier(values):
@@ -108,12 +108,12 @@ def test_the_constants_are_each_datasets_own(tag):
         own = tl.load_own(tag, d)[0]
         if N_OBS[tag] >= 64:      # (the ordinary translation has the plan, with literals)
             if is_logit(tag):
-                m = re.search(r"ltail_sum_abs_y\(\) \{ return ([^;]+); \}", own)
+                m = re.search(r"gtail_sum_y\(\) \{ return ([^;]+); \}", own)
                 assert m and bits(literal(m.group(1))) == bits(got[0]), (tag, d)
             else:
-                my, mf = re.search(r"ptail_sum_y\(\) \{ return ([^;]+); \}", own), re.search(r"ptail_sum_lf\(\) \{ return ([^;]+); \}", own)
+                my, mf = re.search(r"gtail_sum_y\(\) \{ return ([^;]+); \}", own), re.search(r"gtail_sum_lf\(\) \{ return ([^;]+); \}", own)
                 assert my and mf and bits(literal(my.group(1))) == bits(got[0]) and bits(literal(mf.group(1))) == bits(got[1]), (tag, d)
-                hl = re.search(r"ptail_hlin\(const StateView &S\) \{ return ([^;]+); \}", own).group(1)
+                hl = re.search(r"gtail_hlin\(const StateView &S\) \{ return ([^;]+); \}", own).group(1)
                 factors = {int(si): literal(lit) for lit, si in re.findall(r"([-+.\w]+) \* __builtin_fabs\(S\((\d+)\)\)", hl)}
                 for si, slot in slot_of_state.items():
                     assert bits(got[slot]) == bits(factors.get(si, 0.0)), (tag, d, si)      # (a column whose own translation pruned the term: slot 0)

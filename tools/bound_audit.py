@@ -160,7 +160,7 @@ def cases(quick):
             hspec = {"user": user_host.user_spec_part(hsrc, harrays, hmeta), "params": hparams, "P": G + 2, "init": [0.5] * G + [0.5, 1.0],
                      "comp_opts": [dict(model_spec.DEFAULT_OPT) for _ in range(G + 2)], "n_obs": nobs}
             out.append(dict(name="user_" + nm, spec=hspec, chains=ch, steps=st, lanes=64, state=None, seed=16))
-        # ... and one with a certified POISSON TAIL (translate.js poisTailPlan, csrc/amwg_ptail.h pois_tail_approx: amwg_user_step_cert at 16 lanes per chain): the small
+        # ... and one with a certified POISSON TAIL (translate.js glmTailPlan, csrc/amwg_gtail.h glm_tail_approx<PoisLink>: amwg_user_step_cert at 16 lanes per chain): the small
         # closure of the goldens, the same pressed against the 690 cut-off's neighbourhood by a large intercept, and BASELINE configs[4] as a plain closure
         for nm, nobs, ch, st, state in (("pois_glm_closure", 500, 64 if quick else 256, 150, None), ("pois_glm_closure", 500, 64, 100, [3.0, 0.2, -0.1, 0.05, 0.1, -0.2, 0.15, 0.3, 160.0]),
                                         ("bench_glm", 50000, 64 if quick else 2048, 20 if quick else 40, None)):
@@ -169,7 +169,7 @@ def cases(quick):
             pspec = {"user": user_host.user_spec_part(psrc, parrays, pmeta), "params": pparams, "P": 9, "init": [0.0] * 8 + [float(nobs // 2)],
                      "comp_opts": [dict(model_spec.DEFAULT_OPT) for _ in range(9)], "n_obs": nobs}
             out.append(dict(name="user_" + nm + ("_large_rates" if state else ""), spec=pspec, chains=ch, steps=st, lanes=16, state=state, seed=17))
-        # ... and the tail's fallback paths (amwg_ptail.h: eta by the closure's own statements with H taken over the rows; per-lane state reads; no row cache)
+        # ... and the tail's fallback paths (amwg_gtail.h: eta by the closure's own statements with H taken over the rows; per-lane state reads; no row cache)
         for nm in ("pois_tail_nonlinear", "pois_tail_gather", "pois_tail_next_row"):
             psrc, parrays, pmeta = user_host.translated(nm)
             pparams = [{"type": "real", "len": 8, "top": 8, "multidim": 1, "lower": -inf, "upper": inf}, {"type": "int", "len": 1, "top": 1, "multidim": 0, "lower": 0.0, "upper": 516.0}]
@@ -187,7 +187,7 @@ def cases(quick):
 
 
 def logit_cases():
-    """The certified LOGISTIC TAIL of a translated closure (translate.js logitTailPlan, csrc/amwg_ltail.h logit_tail_approx: amwg_user_step_cert at 16 lanes per chain):
+    """The certified LOGISTIC TAIL of a translated closure (translate.js glmTailPlan, csrc/amwg_gtail.h glm_tail_approx<LogitLink>: amwg_user_step_cert at 16 lanes per chain):
     the closures of tests/js/logit_models.js -- the small one at n in {64, 65, 517}, its fallback paths, real weights for y --, predictors at +-36 (where the
     reference's softplus leaves its straight line) and on either side of the 690 cut-off (x1 holds 2 and -2: a start state b1 puts max |eta| at 2 b1), all-zero and
     all-one y.  Names begin with logit_: part of the full run and of --only logit, not of --quick."""

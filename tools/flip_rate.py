@@ -28,7 +28,7 @@ CAMPAIGN = [
     ("cfg4_size", 16_384, 4_000, {"lanes_per_chain": 64, "group_local": 1}),
     ("cfg4_size", 16_384, 4_000, {"lanes_per_chain": 32}),
     ("normal_n1000", 65_536, 20_000, {"lanes_per_chain": 64}),
-    # (round 6) TRANSLATED closures whose certified kernels decide in the reference's order (translate.js rowPlan / poisTailPlan; docs/CERTIFIED.md): against the same closure
+    # (round 6) TRANSLATED closures whose certified kernels decide in the reference's order (translate.js rowPlan / glmTailPlan; docs/CERTIFIED.md): against the same closure
     # at one lane per chain -- not one chain may differ, cached log_post included
     ("user:hier_normal_closure", 65_536, 10_000, {"lanes_per_chain": 64}),
     ("user:pois_glm_closure", 16_384, 10_000, {"lanes_per_chain": 16}),

@@ -2,7 +2,7 @@
 """tools/user_isa.py NAME [LANES | LANESxBLOCK ...] -- what the gfx950 compiler makes of a TRANSLATED closure's step kernels (no GPU needed).
 Translates tests/js/user_models.js:NAME, compiles the program csrc/amwg_rtc.hip would hand to hiprtc (isa_audit.user_asm) with hipcc -S and lists
 the innermost loops of amwg_user_step by VALU count (the likelihood loop's unrolled body is the largest) -- and of amwg_user_step_cert where the closure has
-certified decisions at that lane count (csrc/amwg_ptail.h, csrc/amwg_ltail.h: the wavefront's pass is its largest loop)."""
+certified decisions at that lane count (csrc/amwg_gtail.h: the wavefront's pass is its largest loop)."""
 import os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests"), os.path.join(ROOT, "bayes.js_amd")]
