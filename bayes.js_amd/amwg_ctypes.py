@@ -46,8 +46,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_sample_summarize", "amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_fold_check", "amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -78,6 +78,9 @@ def lib():
         L.amwg_fetch_draws_slices.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_size_t)]
         L.amwg_sample.argtypes = [vp, i64, i64, pd, C.c_size_t]
         L.amwg_sample_device.argtypes = [vp, i64, i64, vp, C.c_size_t]
+        L.amwg_sample_summarize.argtypes = [vp, i64, i64, i64]
+        L.amwg_sample_summarize_async.argtypes = [vp, i64, i64, i64]
+        L.amwg_summary_info.argtypes = [vp, pi64, pi64, pi64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.amwg_set_adapting.argtypes = [vp, i32]
         L.amwg_get_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_info.argtypes = [vp, pd, pi32, pi32, pi32, pi64, pi64]
@@ -160,6 +163,7 @@ def selftest_lib():
         L.amwg_ld_device.argtypes = [i32, i64, pd, pd]
         L.amwg_prefault_selftest.argtypes = [C.c_void_p, C.c_size_t, i32, i32]
         L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
+        L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         _selftest = L
     return _selftest
 
@@ -332,6 +336,20 @@ class Sampler:
         _check(lib().amwg_fetch_draws_slices(self.h, n, base, ln, ptrs, sizes))
         return outs
 
+    def summarize(self, n, thin=1, window_rows=0):
+        """The steps of sample_async(n, thin) + sync(), the kept draws folded window by window into per-chain accumulators instead of stored
+        (amwg_sample_summarize): moments(), convergence() and their dataset_ forms then answer from those.  -> kept draws"""
+        _check(lib().amwg_sample_summarize(self.h, n, thin, window_rows))
+        self._pending = -(-n // thin)
+        return self._pending
+
+    def summary_info(self):
+        """What the last summarize() held (amwg_summary_info)"""
+        r, w, k = C.c_int64(), C.c_int64(), C.c_int64()
+        wb, ab = C.c_size_t(), C.c_size_t()
+        _check(lib().amwg_summary_info(self.h, C.byref(r), C.byref(w), C.byref(k), C.byref(wb), C.byref(ab)))
+        return {"rows": r.value, "window_rows": w.value, "windows": k.value, "window_bytes": wb.value, "accumulator_bytes": ab.value}
+
     def sample_device(self, n, thin, dev_ptr, nbytes):
         _check(lib().amwg_sample_device(self.h, n, thin, C.c_void_p(dev_ptr), nbytes))
 
@@ -440,6 +458,19 @@ def dataset_quantiles_check(draws, D, probs, device=0):
     if L.amwg_dataset_quantiles_check(device, _dp(dr), rows, PR, Cn, D, _dp(pr), pr.size, _dp(out)) != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return out
+
+
+def fold_check(draws, D, window_rows, device=0):
+    """libamwg_selftest.so: the fold of Sampler.summarize on any array draws [rows][PR][C], in windows of window_rows, beside chain_halves_kernel on the whole
+    array -> halves_folded, halves_direct (arrays [2 halves][mean | variance][PR][C]), mean, sd ([D][PR], D datasets of C / D columns each) (amwg_fold_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    hf, hd = np.empty((2, 2, PR, Cn)), np.empty((2, 2, PR, Cn))
+    m, sd = np.empty((D, PR)), np.empty((D, PR))
+    L = selftest_lib()
+    if L.amwg_fold_check(device, _dp(dr), rows, PR, Cn, D, window_rows, _dp(hf), _dp(hd), _dp(m), _dp(sd)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return hf, hd, m, sd
 
 
 def _group(samplers):

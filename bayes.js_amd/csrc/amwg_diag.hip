@@ -6,6 +6,7 @@
 #include <cstdio>
 
 #include "amwg_build_id.h"
+#include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_math.h"
 #include "amwg_philox.h"
@@ -23,12 +24,7 @@ __global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, i
   for (int h = 0; h < 2; ++h) {
     const int64_t r0 = h * half, r1 = r0 + half;
     double m = 0, m2 = 0;   // Welford
-    for (int64_t r = r0; r < r1; ++r) {
-      const double x = draws[(r * PR + p) * C + c];
-      const double dlt = x - m;
-      m += dlt / (double)(r - r0 + 1);
-      m2 += dlt * (x - m);
-    }
+    for (int64_t r = r0; r < r1; ++r) welford_add(draws[(r * PR + p) * C + c], r - r0 + 1, m, m2);
     out[((size_t)(h * 2 + 0) * PR + p) * C + c] = m;
     out[((size_t)(h * 2 + 1) * PR + p) * C + c] = half > 1 ? m2 / (double)(half - 1) : 0.0;
   }
@@ -83,6 +79,62 @@ __global__ void __launch_bounds__(256) dataset_diagnostics_kernel(const double *
   }
 }
 
+// ---- summaries without stored draws (amwg_sample_summarize; amwg_fold.h).  One thread per (chain, recorded value), the chain the fastest index: a wavefront's 64
+// loads of one row are one contiguous 512-byte run.  The accumulators are read once into registers and written once.  The Welford chains are serial per thread and
+// carry an fp64 division, but the loads do not depend on them: kFoldAhead rows are fetched into registers ahead of the dependent updates, so a wavefront's time per
+// row is the arithmetic and not a load's latency.  Which half a row belongs to is decided per row from its global index -- the same for every lane of a wavefront --,
+// so a window may begin and end anywhere: a row crossing from the first half into the second, and the odd last row, need no special window.
+constexpr int kFoldAhead = 8;
+__global__ void __launch_bounds__(256) fold_window_kernel(const double *__restrict__ window, int64_t g0, int64_t nrows, int64_t half, int PR, int64_t C, double *__restrict__ acc) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = blockIdx.y;
+  if (c >= C) return;
+  const size_t stat = (size_t)PR * (size_t)C, at = (size_t)p * (size_t)C + (size_t)c;
+  double m0 = acc[0 * stat + at], s0 = acc[1 * stat + at], m1 = acc[2 * stat + at], s1 = acc[3 * stat + at], ma = acc[4 * stat + at], sa = acc[5 * stat + at];
+  const double *col = window + at;
+  for (int64_t r = 0; r < nrows; r += kFoldAhead) {
+    double x[kFoldAhead];
+#pragma unroll
+    for (int u = 0; u < kFoldAhead; ++u) x[u] = r + u < nrows ? col[(size_t)(r + u) * stat] : 0.0;
+#pragma unroll
+    for (int u = 0; u < kFoldAhead; ++u) {
+      if (r + u >= nrows) break;
+      const int64_t g = g0 + r + u;      // the row's index among the chain's kept draws
+      if (g < half) welford_add(x[u], g + 1, m0, s0);
+      else if (g < 2 * half) welford_add(x[u], g - half + 1, m1, s1);
+      welford_add(x[u], g + 1, ma, sa);
+    }
+  }
+  acc[0 * stat + at] = m0; acc[1 * stat + at] = s0; acc[2 * stat + at] = m1; acc[3 * stat + at] = s1; acc[4 * stat + at] = ma; acc[5 * stat + at] = sa;
+}
+// the accumulated halves in chain_halves_kernel's layout and with its last operation: out[((h*2 + stat) * PR + p) * C + c], the half M2 as (n-1) variances
+__global__ void __launch_bounds__(256) fold_halves_kernel(const double *__restrict__ acc, int64_t rows, int PR, int64_t C, double *__restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int p = blockIdx.y;
+  if (c >= C) return;
+  const int64_t half = rows / 2;
+  for (int h = 0; h < 2; ++h) {
+    const double m = acc[((size_t)(h * 2 + 0) * PR + p) * C + c], m2 = acc[((size_t)(h * 2 + 1) * PR + p) * C + c];
+    out[((size_t)(h * 2 + 0) * PR + p) * C + c] = m;
+    out[((size_t)(h * 2 + 1) * PR + p) * C + c] = half > 1 ? m2 / (double)(half - 1) : 0.0;
+  }
+}
+// mean and sd (n - 1 denominator) of a dataset's chains x kept draws from the whole-chain pairs (m_c, M2_c) of its cpd chains, every chain of `rows` draws, in a
+// fixed order (thread t takes the chains t, t + 256, ...; block_sum's halving tree): mean = sum m_c / cpd, SS = sum M2_c + rows sum (m_c - mean)^2.  out [D][PR] each
+__global__ void __launch_bounds__(256) fold_moments_kernel(const double *__restrict__ acc, int64_t rows, int PR, int64_t C, int64_t cpd, double *mean, double *sd) {
+  __shared__ double red[256];
+  const int p = blockIdx.x, d = blockIdx.y, tid = threadIdx.x, nt = blockDim.x;
+  const double *mc = acc + ((size_t)4 * PR + p) * C + (size_t)d * cpd, *m2c = acc + ((size_t)5 * PR + p) * C + (size_t)d * cpd;
+  double sm = 0, s2 = 0;
+  for (int64_t c = tid; c < cpd; c += nt) { sm += mc[c]; s2 += m2c[c]; }
+  const double m = block_sum(sm, red) / (double)cpd, within = block_sum(s2, red);
+  double sb = 0;
+  for (int64_t c = tid; c < cpd; c += nt) { const double dlt = mc[c] - m; sb += dlt * dlt; }
+  const double ss = within + (double)rows * block_sum(sb, red);
+  const double n = (double)rows * (double)cpd;
+  if (tid == 0) { mean[(size_t)d * PR + p] = m; sd[(size_t)d * PR + p] = n > 1 ? sqrt(ss / (n - 1)) : 0.0; }
+}
+
 // 8 independent fma chains per lane, no memory traffic: the fp64 issue rate the chip sustains
 __global__ void __launch_bounds__(1024) fp64_peak_kernel(double *out, int iters, double a, double b) {
   double x0 = threadIdx.x, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
@@ -126,8 +178,14 @@ static int last_sample_moments(amwg_sampler *s, int D, double *mean, double *sd)
   DevBuf buf;
   HIP_TRY(buf.alloc(n * 16));
   double *dm = buf.as<double>();
-  hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
-  HIP_TRY(hipGetLastError());
+  if (amwg_summarised(s)) {      // (amwg_sample_summarize: from the whole-chain accumulators)
+    const FoldSummary *f = amwg_summary_of(s);
+    if (!f || !f->acc) return amwg_fail(AMWG_EINVAL, "internal: a summarised sampler without accumulators");
+    TRYB(amwg_fold_moments(f->acc, s->last_rows, PR, s->C, D, dm, dm + n, s->stream));
+  } else {
+    hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -139,7 +197,36 @@ static int last_sample_halves(amwg_sampler *s, DevBuf *halves) {
   const int PR = s->P + s->D;
   const size_t C = (size_t)s->C;
   HIP_TRY(halves->alloc(4 * (size_t)PR * C * 8));
+  if (amwg_summarised(s)) {      // (amwg_sample_summarize: the halves were accumulated window by window, by the same recurrence)
+    const FoldSummary *f = amwg_summary_of(s);
+    if (!f || !f->acc) return amwg_fail(AMWG_EINVAL, "internal: a summarised sampler without accumulators");
+    return amwg_fold_halves(f->acc, s->last_rows, PR, s->C, halves->as<double>(), s->stream);
+  }
   hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves->as<double>());
+  HIP_TRY(hipGetLastError());
+  return AMWG_OK;
+}
+
+// ---- amwg_fold.h: the launchers of the fold kernels (the sampler's summarising call and the selftest entry share them)
+int amwg_fold_window(const double *window, int64_t g0, int64_t nrows, int64_t half, int PR, int64_t C, double *acc, hipStream_t stream) {
+  if (!window || !acc || g0 < 0 || nrows < 1 || half < 0 || PR < 1 || PR > 65535 || C < 1) return amwg_fail(AMWG_EINVAL, "internal: fold of rows [%lld, +%lld) of %d values x %lld chains", (long long)g0, (long long)nrows, PR, (long long)C);
+  hipLaunchKernelGGL(fold_window_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, stream, window, g0, nrows, half, PR, C, acc);
+  HIP_TRY(hipGetLastError());
+  return AMWG_OK;
+}
+int amwg_fold_halves(const double *acc, int64_t rows, int PR, int64_t C, double *halves, hipStream_t stream) {
+  hipLaunchKernelGGL(fold_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, stream, acc, rows, PR, C, halves);
+  HIP_TRY(hipGetLastError());
+  return AMWG_OK;
+}
+int amwg_fold_moments(const double *acc, int64_t rows, int PR, int64_t C, int D, double *mean, double *sd, hipStream_t stream) {
+  hipLaunchKernelGGL(fold_moments_kernel, dim3((unsigned)PR, (unsigned)D), dim3(256), 0, stream, acc, rows, PR, C, C / D, mean, sd);
+  HIP_TRY(hipGetLastError());
+  return AMWG_OK;
+}
+// the selftest entry's other half: chain_halves_kernel on a stored array
+int amwg_chain_halves(const double *draws, int64_t rows, int PR, int64_t C, double *halves, hipStream_t stream) {
+  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, stream, draws, rows, PR, C, halves);
   HIP_TRY(hipGetLastError());
   return AMWG_OK;
 }
@@ -168,14 +255,14 @@ int amwg_dataset_n_obs(const amwg_sampler *s, int32_t *n_obs) {
 
 int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: null argument");
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: no sample() call yet");
+  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_moments: no sample() call yet");
   return last_sample_moments(s, s->n_datasets, mean, sd);
 }
 
 int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: null argument");
   const int D = s->n_datasets;
-  if (!s->last_draws || s->last_rows < 4 || s->C / D < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains per dataset");
+  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 4 || s->C / D < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains per dataset");
   const int PR = s->P + s->D;
   const size_t n = (size_t)D * PR;
   DevBuf halves, out;
@@ -193,7 +280,7 @@ int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *
 int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: null argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_diagnostics"));
-  if (!s->last_draws || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
+  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
   const int PR = s->P + s->D;
   const size_t C = (size_t)s->C, n_out = 4 * (size_t)PR * C;
   DevBuf dout;
@@ -269,7 +356,7 @@ int amwg_chain_diag(amwg_sampler *s, uint64_t *uniforms, double *log_post_out, i
 int amwg_last_sample_moments(amwg_sampler *s, double *mean, double *sd) {
   if (!s || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: null argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_moments"));
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: no sample() call yet");
+  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_moments: no sample() call yet");
   return last_sample_moments(s, 1, mean, sd);      // (one dataset of all the chains: cpd = C)
 }
 

@@ -29,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "amwg_fold.h"
 #include "amwg_sampler.h"
 
 namespace {
@@ -137,6 +138,7 @@ int open_group(amwg_sampler *const *shards, int n, size_t buf_len, bool need_dra
     amwg_sampler *s = shards[i];
     if (!s) return amwg_fail(AMWG_EINVAL, "amwg_group: sampler %d is null", i);
     if (s->P + s->D != PR) return amwg_fail(AMWG_EINVAL, "amwg_group: sampler %d records %d values per draw, sampler 0 %d", i, s->P + s->D, PR);
+    if (need_draws) { const int rs = amwg_refuse_summarised(s, "amwg_group"); if (rs != AMWG_OK) return rs; }
     if (need_draws && (!s->last_draws || s->last_rows < 1)) return amwg_fail(AMWG_EINVAL, "amwg_group: sampler %d has no sample() call yet", i);
     if (need_draws && s->last_rows != shards[0]->last_rows) return amwg_fail(AMWG_EINVAL, "amwg_group: sampler %d kept %lld draws, sampler 0 %lld", i, (long long)s->last_rows, (long long)shards[0]->last_rows);
     g->shards.push_back(s);
@@ -243,12 +245,7 @@ __global__ void group_chain_halves_kernel(const double *draws, int64_t rows, int
   for (int h = 0; h < 2; ++h) {
     const int64_t r0 = h * half, r1 = r0 + half;
     double m = 0, m2 = 0;   // Welford
-    for (int64_t r = r0; r < r1; ++r) {
-      const double x = draws[(r * PR + p) * C + c];
-      const double dlt = x - m;
-      m += dlt / (double)(r - r0 + 1);
-      m2 += dlt * (x - m);
-    }
+    for (int64_t r = r0; r < r1; ++r) amwg::welford_add(draws[(r * PR + p) * C + c], r - r0 + 1, m, m2);
     out[((size_t)(h * 2 + 0) * PR + p) * C + c] = m;
     out[((size_t)(h * 2 + 1) * PR + p) * C + c] = half > 1 ? m2 / (double)(half - 1) : 0.0;
   }
@@ -612,6 +609,7 @@ int amwg_comm_gather_draws(amwg_sampler *s, amwg_comm *c, int32_t root, double *
   // a rank that cannot contribute all-gathers a count of -1, and every rank then returns an error without any send or receive posted.
   char why[200] = "";
   if (root < 0 || root >= c->n_ranks) snprintf(why, sizeof why, "root %d outside 0..%d", root, c->n_ranks - 1);
+  else if (amwg_summarised(s)) snprintf(why, sizeof why, "the last sample call was amwg_sample_summarize: its draws were not kept");
   else if (!s->last_draws || s->last_rows < 1) snprintf(why, sizeof why, "no sample() call yet");
   else if (s->device != c->device) snprintf(why, sizeof why, "the sampler is on device %d, the communicator on %d", s->device, c->device);
   else if (amwg_sync(s) != AMWG_OK) snprintf(why, sizeof why, "%.190s", amwg_last_error());      // (incl. the step kernels' device error word)
@@ -670,6 +668,7 @@ int amwg_comm_moments(amwg_sampler *s, amwg_comm *c, double *mean, double *sd) {
   char why[200] = "";
   if (!mean || !sd) snprintf(why, sizeof why, "null output");
   else if (s->n_datasets > 1) snprintf(why, sizeof why, "this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_moments", s->n_datasets);
+  else if (amwg_summarised(s)) snprintf(why, sizeof why, "the last sample call was amwg_sample_summarize: its draws were not kept");
   else if (!s->last_draws || s->last_rows < 1) snprintf(why, sizeof why, "no sample() call yet");
   else if (s->device != c->device) snprintf(why, sizeof why, "the sampler is on device %d, the communicator on %d", s->device, c->device);
   else if (amwg_sync(s) != AMWG_OK) snprintf(why, sizeof why, "%.190s", amwg_last_error());

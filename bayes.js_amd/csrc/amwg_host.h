@@ -77,7 +77,8 @@ int load_user_kernel(amwg_sampler *s, const char *source, const char *arch);
 // ---- amwg_create.hip (the tables of two_valued_sum), amwg_run.hip
 std::vector<uint32_t> two_valued_tables(const uint8_t *xb, int N);
 int use_device(int device);      // hipSetDevice for the helper entry points that take a device number; AMWG_EHIP where there is none
-int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool finalize = false);
+struct FoldWindow;      // (amwg_fold.h: the rows are folded window by window instead of kept -- amwg_sample_summarize)
+int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool finalize = false, FoldWindow *win = nullptr);
 int finish_timing(amwg_sampler *s);
 // Makes the destination of a sample call resident ahead of the device-to-host copies: helper threads walk it in copy order (amwg_run.hip)
 struct Prefaulter {

@@ -494,6 +494,33 @@ static napi_value SampleAsync(napi_env env, napi_callback_info info) {
   return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
 }
 
+/* sampleSummarizeAsync(handle, n, thin, windowRows): amwg_sample_summarize_async -- the steps of sampleAsync, the kept draws folded into per-chain accumulators */
+static napi_value SampleSummarizeAsync(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int rc = amwg_sample_summarize_async(s, arg_i64(env, a[1]), arg_i64(env, a[2]), arg_i64(env, a[3]));
+  return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
+}
+
+/* summaryInfo(handle) -> {rows, window_rows, windows, window_bytes, accumulator_bytes} of the last summarising call (amwg_summary_info) */
+static napi_value SummaryInfo(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int64_t v[3];
+  size_t b[2];
+  int rc = amwg_summary_info(s, &v[0], &v[1], &v[2], &b[0], &b[1]);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  static const char *names[5] = {"rows", "window_rows", "windows", "window_bytes", "accumulator_bytes"};
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  for (int i = 0; i < 5; i++) { napi_create_int64(env, i < 3 ? v[i] : (int64_t)b[i - 3], &t); napi_set_named_property(env, o, names[i], t); }
+  return o;
+}
+
 /* fetchDraws(handle, rows) -> Float64Array [rows][P][chains] */
 static napi_value FetchDraws(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -931,7 +958,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
       {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
-      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
+      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

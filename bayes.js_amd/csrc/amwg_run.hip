@@ -6,8 +6,11 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdlib>
+#include <mutex>
+#include <unordered_map>
 
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
+#include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_kernel.h"      // (StepArgs, and the kErr* bits the step kernels report)
 #include "amwg_dataset.h"     // (DatasetArgs: the second argument of a dataset sampler's kernel)
@@ -44,13 +47,17 @@ struct Roctx {
 Roctx &roctx() { static Roctx r; return r; }
 }  // namespace
 
-int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool finalize) {
+// `win` (amwg_sample_summarize): d_draws holds win->window_rows rows only.  A launch never records past the end of the window -- its steps are capped to the rows
+// left x thin, step0 / row0 as ever --, and each time the window is full, and again at the end of the call, its rows are folded into win->acc (amwg_fold.h) on the
+// same stream and the window is reused: no host synchronisation in between, and the call's launch count and event pair span all of it.
+int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool finalize, FoldWindow *win) {
   Roctx &rx = roctx();
   if (rx.push) rx.push(d_draws ? "amwg_sample" : "amwg_burn");
   struct PopOnExit { Roctx &r; ~PopOnExit() { if (r.pop) r.pop(); } } pop_on_exit{rx};
   // a launch counts its accepted / evaluated proposals in 16-bit fields (amwg_kernel.h, TOTme): at most 65535 steps per launch
   int64_t chunk = (s->opt.steps_per_launch > 0 && s->opt.steps_per_launch < 65535) ? s->opt.steps_per_launch : 65535;
-  if (d_draws && d_draws == s->d_draws && s->opt.steps_per_launch <= 0) {
+  if (win && (!d_draws || win->window_rows < 1 || !win->acc)) return amwg_fail(AMWG_EINVAL, "internal: a fold window of %lld rows", (long long)win->window_rows);
+  if (d_draws && d_draws == s->d_draws && s->opt.steps_per_launch <= 0 && !win) {
     // draws that will be fetched (amwg_sample / amwg_sample_async): launches of ~32 MB of recorded rows each, so that the rows of one launch
     // leave the device while the next launches run (amwg_fetch_draws_slices); results do not depend on how a call is cut into launches
     const double per_step = (double)(s->P + s->D) * (double)s->C * 8.0 / (double)thin;
@@ -113,15 +120,16 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     s->chunk_rows.clear();
     HIP_TRY(hipEventRecord(s->ev0, s->stream));
   }
-  int64_t done = 0, row = 0;
+  int64_t done = 0, row = 0, folded = 0;      // (with a window: `row` counts the rows in the window, `folded` those of the windows before it)
   do {
-    const int64_t m = (n - done < chunk) ? n - done : chunk;
-    a.n_steps = (int32_t)m;
+    int64_t m = (n - done < chunk) ? n - done : chunk;
     a.init_lp = s->lp_ready ? 0 : 1;
     a.finalize_lp = finalize ? 1 : 0;
     // steps until the first recorded step of this launch: smallest t >= 0 with (done + t) % thin == 0
     a.step0 = (thin - (done % thin)) % thin;
     a.row0 = row;
+    if (win && m > a.step0 + (win->window_rows - row) * thin) m = a.step0 + (win->window_rows - row) * thin;      // (the window has room for >= 1 row: m >= 1)
+    a.n_steps = (int32_t)m;
     if (s->user) {
       size_t arg_bytes = sizeof a;
       void *arg_buf = &a;
@@ -143,7 +151,7 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     // a mark for amwg_fetch_draws*: only for the library's own buffer, and only once >= 8 MB of new rows (or the end of the call) stand
     // behind it -- a caller who asks for one-step launches gets a handful of events, not one per launch
     const int64_t marked = s->chunk_rows.empty() ? 0 : s->chunk_rows.back();
-    if (d_draws && d_draws == s->d_draws && row > marked &&
+    if (!win && d_draws && d_draws == s->d_draws && row > marked &&
         (done + m >= n || (double)(row - marked) * (double)(s->P + s->D) * (double)s->C * 8.0 >= 8388608.0)) {
       const size_t j = s->chunk_rows.size();
       if (j >= s->chunk_ev.size()) {
@@ -155,6 +163,13 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
       s->chunk_rows.push_back(row);
     }
     done += m;
+    if (win && row > 0 && (row == win->window_rows || done >= n)) {
+      if (row > win->window_rows || folded + row > win->total_rows) return amwg_fail(AMWG_EINVAL, "internal: %lld rows in a window of %lld (%lld of %lld folded)", (long long)row, (long long)win->window_rows, (long long)folded, (long long)win->total_rows);
+      TRYB(amwg_fold_window(d_draws, folded, row, win->total_rows / 2, s->P + s->D, s->C, win->acc, s->stream));
+      win->windows++;
+      folded += row;
+      row = 0;
+    }
   } while (done < n);
   if (!quiet) HIP_TRY(hipEventRecord(s->ev1, s->stream));
   return AMWG_OK;
@@ -233,6 +248,32 @@ void Prefaulter::wait_chunk(size_t j) {
 }
 Prefaulter::~Prefaulter() { for (auto &w : workers) w.join(); }
 
+// ---- amwg_fold.h: what a summarising call left behind, per sampler.  Kept beside the handle, not in it: amwg_sampler.h is one of the sources the step kernels'
+// id is formed from (tools/build_id.py), and this feature changes no step kernel.  The accumulators themselves are the sampler's (dev_allocs); amwg_destroy forgets the entry.
+namespace {
+std::mutex g_summaries_mu;
+std::unordered_map<const amwg_sampler *, FoldSummary> g_summaries;
+FoldSummary &summary_slot(const amwg_sampler *s) {      // (references into an unordered_map stay valid while other entries come and go)
+  std::lock_guard<std::mutex> lock(g_summaries_mu);
+  return g_summaries[s];
+}
+}  // namespace
+bool amwg_summarised(const amwg_sampler *s) { return s && !s->last_draws && s->last_rows > 0; }
+const FoldSummary *amwg_summary_of(const amwg_sampler *s) {
+  std::lock_guard<std::mutex> lock(g_summaries_mu);
+  auto it = g_summaries.find(s);
+  return it == g_summaries.end() ? nullptr : &it->second;
+}
+void amwg_summary_forget(const amwg_sampler *s) {
+  std::lock_guard<std::mutex> lock(g_summaries_mu);
+  g_summaries.erase(s);
+}
+int amwg_refuse_summarised(const amwg_sampler *s, const char *call) {
+  if (amwg_summarised(s))
+    return amwg_fail(AMWG_EINVAL, "%s: the last sample call was amwg_sample_summarize: its draws were folded into per-chain accumulators and not kept (moments and diagnostics answer from those; this call needs the draws of amwg_sample*)", call);
+  return AMWG_OK;
+}
+
 // The rows of a sample call are final launch by launch (launch_steps records an event after each): the rows of launch j leave the
 // device on copy_stream while launches j + 1, ... run on the sampler's stream -- a pageable destination (a JavaScript typed array, a numpy
 // array) makes each copy block THIS thread, not the GPU.  65 536 chains x 1000 draws x 2 components are 1.05 GB: with the destination resident
@@ -281,8 +322,60 @@ int amwg_sample_async(amwg_sampler *s, int64_t n, int64_t thin) {
   }
   return amwg_sample_device(s, n, thin, s->d_draws, need);
 }
+
+// Summaries without stored draws: the steps of amwg_sample_async(n, thin), the recorded rows folded window by window into per-chain accumulators (amwg_fold.h)
+// instead of kept.  The window is the library's own draw buffer, grown only when too small: its size does not depend on n.
+int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_t window_rows) {
+  if (!s || n < 0 || thin < 1 || window_rows < 0) return amwg_fail(AMWG_EINVAL, "amwg_sample_summarize: bad argument (%s)", !s ? "null sampler" : n < 0 ? "n < 0" : thin < 1 ? "thin < 1" : "window_rows < 0");
+  const int64_t rows = (n + thin - 1) / thin;
+  const int PR = s->P + s->D;
+  const size_t row_bytes = (size_t)PR * (size_t)s->C * 8;
+  int64_t W = window_rows > 0 ? window_rows : (int64_t)(kFoldWindowBytes / row_bytes);
+  if (W > rows) W = rows;      // (no run needs a window longer than itself)
+  if (W < 1) W = 1;
+  const size_t need = (size_t)W * row_bytes, acc_bytes = (size_t)kFoldStats * row_bytes;
+  HIP_TRY(hipSetDevice(s->device));
+  if (need > s->d_draws_cap) {
+    if (s->d_draws) { (void)hipFree(s->d_draws); s->d_draws = nullptr; s->d_draws_cap = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_draws), need));
+    s->d_draws_cap = need;
+  }
+  s->last_draws = nullptr;      // (whatever stood in the buffer is overwritten)
+  s->last_rows = 0;
+  FoldSummary &f = summary_slot(s);
+  if (!f.acc) { TRYB(dev_alloc(s, &f.acc, (size_t)kFoldStats * (size_t)PR * (size_t)s->C)); f.acc_bytes = acc_bytes; }
+  f.rows = f.window_rows = f.windows = 0;
+  f.window_bytes = 0;
+  HIP_TRY(hipMemsetAsync(f.acc, 0, acc_bytes, s->stream));      // (each call starts afresh)
+  FoldWindow win;
+  win.window_rows = W;
+  win.total_rows = rows;
+  win.acc = f.acc;
+  TRYB(launch_steps(s, n, thin, s->d_draws, false, &win));
+  f.rows = rows; f.window_rows = W; f.windows = win.windows; f.window_bytes = need;
+  s->last_rows = rows;      // (rows > 0 without last_draws: the mark of a summary -- amwg_summarised)
+  return AMWG_OK;
+}
+
+int amwg_sample_summarize(amwg_sampler *s, int64_t n, int64_t thin, int64_t window_rows) {
+  TRYB(amwg_sample_summarize_async(s, n, thin, window_rows));
+  return amwg_sync(s);
+}
+
+int amwg_summary_info(const amwg_sampler *s, int64_t *rows, int64_t *window_rows, int64_t *windows, size_t *window_bytes, size_t *accumulator_bytes) {
+  const FoldSummary *f = (s && amwg_summarised(s)) ? amwg_summary_of(s) : nullptr;
+  if (!f) return amwg_fail(AMWG_EINVAL, "amwg_summary_info: %s", s ? "the last sample call of this sampler was not amwg_sample_summarize (or kept no draw)" : "null sampler");
+  if (rows) *rows = f->rows;
+  if (window_rows) *window_rows = f->window_rows;
+  if (windows) *windows = f->windows;
+  if (window_bytes) *window_bytes = f->window_bytes;
+  if (accumulator_bytes) *accumulator_bytes = f->acc_bytes;
+  return AMWG_OK;
+}
+
 int amwg_fetch_draws_slices(amwg_sampler *s, int32_t n_slices, const int32_t *base, const int32_t *len, double *const *out, const size_t *out_bytes) {
   if (!s) return amwg_fail(AMWG_EINVAL, "amwg_fetch_draws: null sampler");
+  TRYB(amwg_refuse_summarised(s, "amwg_fetch_draws"));
   if (s->last_draws != s->d_draws) return amwg_fail(AMWG_EINVAL, "amwg_fetch_draws: no amwg_sample_async pending");
   if (n_slices < 0 || (n_slices > 0 && (!base || !len || !out || !out_bytes))) return amwg_fail(AMWG_EINVAL, "amwg_fetch_draws_slices: bad argument");
   const int PR = s->P + s->D;

@@ -2,6 +2,7 @@
 // libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
 #include "../../include/amwg_selftest.h"
 #include "amwg_dataset_quantiles.h"
+#include "amwg_fold.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
@@ -113,6 +114,34 @@ int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t ro
   HIP_TRY(dd.alloc(bytes));
   HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
   return amwg_dataset_quantiles_launch("amwg_dataset_quantiles_check", dd.as<double>(), rows, PR, C, D, probs, n_probs, out, nullptr);
+}
+
+int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
+                    double *halves_folded, double *halves_direct, double *mean, double *sd) {
+  if (!draws || !halves_folded || !halves_direct || !mean || !sd) return amwg_fail(AMWG_EINVAL, "amwg_fold_check: null argument");
+  if (rows < 1 || PR < 1 || PR > 65535 || C < 1 || D < 1 || D > 65535 || C % D != 0 || window_rows < 1)
+    return amwg_fail(AMWG_EINVAL, "amwg_fold_check: bad shape (rows %lld, values %d, chains %lld, datasets %d -- dividing the chains --, window_rows %lld)", (long long)rows, PR, (long long)C, D, (long long)window_rows);
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "amwg_fold_check: array too large");
+  TRYB(use_device(device));
+  const size_t row_elems = (size_t)PR * (size_t)C, bytes = (size_t)rows * row_elems * 8, n_mom = (size_t)D * (size_t)PR;
+  DevBuf dd, acc, hf, hd, mom;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(acc.alloc(kFoldStats * row_elems * 8));
+  HIP_TRY(hf.alloc(4 * row_elems * 8));
+  HIP_TRY(hd.alloc(4 * row_elems * 8));
+  HIP_TRY(mom.alloc(2 * n_mom * 8));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemsetAsync(acc.p, 0, kFoldStats * row_elems * 8, nullptr));
+  for (int64_t g0 = 0; g0 < rows; g0 += window_rows)      // (window after window, as launch_steps folds them)
+    TRYB(amwg_fold_window(dd.as<double>() + (size_t)g0 * row_elems, g0, rows - g0 < window_rows ? rows - g0 : window_rows, rows / 2, PR, C, acc.as<double>(), nullptr));
+  TRYB(amwg_fold_halves(acc.as<double>(), rows, PR, C, hf.as<double>(), nullptr));
+  TRYB(amwg_fold_moments(acc.as<double>(), rows, PR, C, D, mom.as<double>(), mom.as<double>() + n_mom, nullptr));
+  TRYB(amwg_chain_halves(dd.as<double>(), rows, PR, C, hd.as<double>(), nullptr));
+  HIP_TRY(hipMemcpy(halves_folded, hf.p, 4 * row_elems * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(halves_direct, hd.p, 4 * row_elems * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(mean, mom.p, n_mom * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sd, mom.as<double>() + n_mom, n_mom * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
 }
 
 }  // extern "C"

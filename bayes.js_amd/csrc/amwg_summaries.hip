@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "amwg_dataset_quantiles.h"
+#include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_sampler.h"
 
@@ -38,6 +39,7 @@ __global__ void pick_quantiles_kernel(const double *sorted, int64_t n, const dou
 extern "C" int amwg_last_sample_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: bad argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_quantiles"));
+  TRYB(amwg_refuse_summarised(s, "amwg_last_sample_quantiles"));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: no sample() call yet");
   const int PR = s->P + s->D;
   const int64_t n = s->last_rows * s->C;
@@ -264,6 +266,7 @@ int amwg_dataset_quantiles_launch(const char *call, const double *draws, int64_t
 
 extern "C" int amwg_last_sample_dataset_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_quantiles: bad argument");
+  TRYB(amwg_refuse_summarised(s, "amwg_last_sample_dataset_quantiles"));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_quantiles: no sample() call yet");
   HIP_TRY(hipSetDevice(s->device));
   return amwg_dataset_quantiles_launch("amwg_last_sample_dataset_quantiles", s->last_draws, s->last_rows, s->P + s->D, s->C, s->n_datasets, probs, n_probs, out, s->stream);

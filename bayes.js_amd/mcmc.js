@@ -409,6 +409,21 @@ AmwgSampler.prototype.sample_on_device = function (n_iterations) {
   return Math.ceil(n_iterations / this.thinning_interval);
 };
 
+/** Like sample_on_device(n), but not even the device keeps the draws: they pass through a window of `options.window_rows` kept draws (default: what fits into
+ *  64 MiB) and are folded into per-chain accumulators, so the memory of a run does not grow with its length.  moments(), convergence(), dataset_moments() and
+ *  dataset_convergence() then answer from the accumulators -- R-hat and ESS bit for bit those of the stored run --; quantiles() and dataset_quantiles() need the
+ *  draws and throw the library's refusal.  One device only.  Returns the number of kept draws. */
+AmwgSampler.prototype.summarize = function (n_iterations, options) {
+  const N = native(), w = options && options.window_rows !== undefined ? options.window_rows : 0;
+  if (this._shards.length > 1 || (options && options.devices && options.devices.length > 1))
+    throw 'AmwgSampler (MI355X): summarize() runs on one device: summaries over several devices (options.devices) are formed from the stored draws -- use sample_on_device()';
+  this._each((sh) => N.sampleSummarizeAsync(sh.handle, n_iterations, this.thinning_interval, w));
+  this._each((sh) => N.sync(sh.handle));
+  return Math.ceil(n_iterations / this.thinning_interval);
+};
+/** What the last summarize() held on the device: {rows, window_rows, windows, window_bytes, accumulator_bytes}. */
+AmwgSampler.prototype.summary_info = function () { return native().summaryInfo(this._shards[0].handle); };
+
 Object.defineProperty(AmwgSampler.prototype, 'state', {
   get: function () {
     const N = native(), C = this.chains;

@@ -307,6 +307,27 @@ int amwg_fetch_draws_slices(amwg_sampler *s, int32_t n_slices, const int32_t *ba
  * until amwg_sync(). */
 int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_draws_dev, size_t out_bytes);
 
+/* SUMMARIES WITHOUT STORED DRAWS.  Runs the n steps of amwg_sample_async(s, n, thin) -- the same draws, Philox stream, adaptation and launches cut by
+ * steps_per_launch and the 65 535-step limit: afterwards the chains' state, amwg_info and amwg_chain_diag are those of that call, every byte -- but keeps no draw:
+ * the recorded rows go into a device window of window_rows rows, and each time the window is full, and again at the end of the call, a fold kernel adds its rows to
+ * per-chain accumulators (per recorded value and chain the Welford pair (mean, M2) of the first half of the kept draws, of the second half and of the whole chain:
+ * 6 x 8 bytes) and the window is reused.  Everything is enqueued on the sampler's stream, without a host synchronisation between windows; a launch never records past
+ * the end of the window (its steps are capped).  window_rows = 0: the rows that fit into 64 MiB; never more rows than the call keeps, never fewer than 1.  The device
+ * memory of a call is therefore the window and the accumulators, whatever n -- amwg_sample_async needs ceil(n/thin) rows.
+ * Afterwards amwg_last_sample_moments, amwg_last_sample_diagnostics, amwg_last_sample_dataset_moments and amwg_last_sample_dataset_diagnostics answer from the
+ * accumulators: the halves are accumulated by the recurrence of the stored path in the same row order, so split-R-hat and ESS equal those of the stored run BIT FOR BIT
+ * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
+ * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_fetch_draws*,
+ * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize.  A later amwg_sample* call replaces
+ * the summary, amwg_burn leaves it alone, and every summarising call starts its accumulators afresh.  n = 0 succeeds and leaves nothing to summarise.
+ * amwg_launch_info's n_launches (step-kernel launches) and kernel_ms (which includes the folds) cover the whole call.
+ * amwg_sample_summarize = the _async form + amwg_sync.  Refused before a device is opened: null sampler, n < 0, thin < 1, window_rows < 0.
+ * amwg_summary_info: the kept rows, the rows of the window, the number of folds, and the bytes of window and accumulators held by the last summarising call
+ * (any pointer may be NULL); AMWG_EINVAL when the sampler's last sample call was not a summarising one. */
+int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_t window_rows);
+int amwg_sample_summarize(amwg_sampler *s, int64_t n, int64_t thin, int64_t window_rows);
+int amwg_summary_info(const amwg_sampler *s, int64_t *rows, int64_t *window_rows, int64_t *windows, size_t *window_bytes, size_t *accumulator_bytes);
+
 /* Replaces sampler.start_adaptation() / .stop_adaptation() (mcmc.js:1060-1073). */
 int amwg_set_adapting(amwg_sampler *s, int32_t flag);
 

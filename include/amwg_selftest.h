@@ -35,6 +35,13 @@ int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_
 int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D,
                                  const double *probs, int32_t n_probs, double *out);
 
+/* The fold of amwg_sample_summarize on a caller's array draws[rows][PR][C] (host): the array is folded in windows of window_rows rows through the kernels and the
+ * launcher the sampler uses (halves_folded, 4 * PR * C doubles in chain_halves_kernel's layout [half][mean | variance][PR][C]), chain_halves_kernel runs on the whole
+ * array (halves_direct, the same size), and the moments of D datasets of C / D chains each come from the folded whole-chain pairs (mean, sd: [D][PR]).
+ * Refused before a device is opened: null pointers, non-positive shapes, C % D != 0, window_rows < 1. */
+int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
+                    double *halves_folded, double *halves_direct, double *mean, double *sd);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);
