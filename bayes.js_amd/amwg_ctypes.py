@@ -47,7 +47,7 @@ class UserModel(C.Structure):
 
 
 EXPORTS = ["amwg_sample_summarize", "amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_fold_check", "amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+SELFTEST_EXPORTS = ["amwg_summaries_check", "amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -164,6 +164,7 @@ def selftest_lib():
         L.amwg_prefault_selftest.argtypes = [C.c_void_p, C.c_size_t, i32, i32]
         L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
+        L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         _selftest = L
     return _selftest
 
@@ -471,6 +472,20 @@ def fold_check(draws, D, window_rows, device=0):
     if L.amwg_fold_check(device, _dp(dr), rows, PR, Cn, D, window_rows, _dp(hf), _dp(hd), _dp(m), _dp(sd)) != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return hf, hd, m, sd
+
+
+def summaries_check(draws, D, window_rows=0, device=0):
+    """libamwg_selftest.so: the stored-draw summaries on any array draws [rows][PR][C], D datasets of C / D columns each, through the launchers behind
+    Sampler.dataset_moments / dataset_convergence / convergence; window_rows > 0: the halves from the fold of Sampler.summarize instead of chain_halves_kernel
+    -> dict of mean, sd, rhat_ds, ess_ds ([D][PR]) and rhat_pooled, ess_pooled ([PR], over all C columns) (amwg_summaries_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    out = {k: np.empty((D, PR)) for k in ("mean", "sd", "rhat_ds", "ess_ds")}
+    out.update({k: np.empty(PR) for k in ("rhat_pooled", "ess_pooled")})
+    L = selftest_lib()
+    if L.amwg_summaries_check(device, _dp(dr), rows, PR, Cn, D, window_rows, *[_dp(out[k]) for k in ("mean", "sd", "rhat_ds", "ess_ds", "rhat_pooled", "ess_pooled")]) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
 
 
 def _group(samplers):

@@ -174,18 +174,14 @@ int amwg_refuse_pooled(const amwg_sampler *s, const char *call) {
 static int last_sample_moments(amwg_sampler *s, int D, double *mean, double *sd) {
   HIP_TRY(hipSetDevice(s->device));
   const int PR = s->P + s->D;
+  if (!amwg_summarised(s)) return amwg_moments_launch(s->last_draws, s->last_rows, PR, s->C, D, mean, sd, s->stream);
   const size_t n = (size_t)D * PR;
   DevBuf buf;
   HIP_TRY(buf.alloc(n * 16));
   double *dm = buf.as<double>();
-  if (amwg_summarised(s)) {      // (amwg_sample_summarize: from the whole-chain accumulators)
-    const FoldSummary *f = amwg_summary_of(s);
-    if (!f || !f->acc) return amwg_fail(AMWG_EINVAL, "internal: a summarised sampler without accumulators");
-    TRYB(amwg_fold_moments(f->acc, s->last_rows, PR, s->C, D, dm, dm + n, s->stream));
-  } else {
-    hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, s->C / D, dm, dm + n);
-    HIP_TRY(hipGetLastError());
-  }
+  const FoldSummary *f = amwg_summary_of(s);      // (amwg_sample_summarize: from the whole-chain accumulators)
+  if (!f || !f->acc) return amwg_fail(AMWG_EINVAL, "internal: a summarised sampler without accumulators");
+  TRYB(amwg_fold_moments(f->acc, s->last_rows, PR, s->C, D, dm, dm + n, s->stream));
   HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -202,8 +198,64 @@ static int last_sample_halves(amwg_sampler *s, DevBuf *halves) {
     if (!f || !f->acc) return amwg_fail(AMWG_EINVAL, "internal: a summarised sampler without accumulators");
     return amwg_fold_halves(f->acc, s->last_rows, PR, s->C, halves->as<double>(), s->stream);
   }
-  hipLaunchKernelGGL(chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves->as<double>());
+  return amwg_chain_halves(s->last_draws, s->last_rows, PR, s->C, halves->as<double>(), s->stream);
+}
+
+// ---- amwg_fold.h: the summaries over a device array (the sampler's calls above and below, and the selftest entry amwg_summaries_check)
+int amwg_diagnostics_refusal(const char *call, bool have, int64_t rows, int64_t C, int D, bool per_dataset) {
+  if (have && D >= 1 && rows >= 4 && C / D >= 2) return AMWG_OK;
+  return amwg_fail(AMWG_EINVAL, "%s: needs a sample() of >= 4 kept draws on >= 2 chains%s", call, per_dataset ? " per dataset" : "");
+}
+int amwg_moments_launch(const double *draws, int64_t rows, int PR, int64_t C, int D, double *mean, double *sd, hipStream_t stream) {
+  const size_t n = (size_t)D * PR;
+  DevBuf buf;
+  HIP_TRY(buf.alloc(n * 16));
+  double *dm = buf.as<double>();
+  hipLaunchKernelGGL(dataset_moments_kernel, dim3(PR, D), dim3(1024), 0, stream, draws, rows, PR, C, C / D, dm, dm + n);
   HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(mean, dm, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(sd, dm + n, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return AMWG_OK;
+}
+int amwg_dataset_diagnostics_launch(const double *halves, int64_t rows, int PR, int64_t C, int D, double *rhat, double *ess, hipStream_t stream) {
+  const size_t n = (size_t)D * PR;
+  DevBuf out;
+  HIP_TRY(out.alloc(n * 16));
+  double *dr = out.as<double>();
+  hipLaunchKernelGGL(dataset_diagnostics_kernel, dim3(PR, D), dim3(256), 0, stream, halves, rows, PR, C, C / D, dr, dr + n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rhat, dr, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(ess, dr + n, n * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return AMWG_OK;
+}
+int amwg_pooled_diagnostics(const double *halves, int64_t rows, int PR, int64_t Cn, double *rhat, double *ess, hipStream_t stream) {
+  const size_t C = (size_t)Cn, n_out = 4 * (size_t)PR * C;
+  std::vector<double> h(n_out);
+  HIP_TRY(hipMemcpyAsync(h.data(), halves, n_out * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  const double n = (double)(rows / 2), m = 2.0 * (double)C;   // 2C half-chains of n draws
+  for (int p = 0; p < PR; ++p) {
+    // W = mean within-sequence variance; B/n = variance of the sequence means (over the 2C halves)
+    long double sw = 0, sm = 0;
+    for (int hf = 0; hf < 2; ++hf)
+      for (size_t c = 0; c < C; ++c) { sm += h[((size_t)(hf * 2 + 0) * PR + p) * C + c]; sw += h[((size_t)(hf * 2 + 1) * PR + p) * C + c]; }
+    const double W = (double)(sw / m), gm = (double)(sm / m);
+    long double sb = 0, sbc = 0;
+    for (int hf = 0; hf < 2; ++hf)
+      for (size_t c = 0; c < C; ++c) { const double dlt = h[((size_t)(hf * 2 + 0) * PR + p) * C + c] - gm; sb += (long double)dlt * dlt; }
+    const double B_over_n = (double)(sb / (m - 1));
+    const double var_plus = (n - 1) / n * W + B_over_n;
+    rhat[p] = W > 0 ? std::sqrt(var_plus / W) : (double)NAN;
+    // whole-chain means: average of the two half means (equal lengths)
+    long double smc = 0;
+    for (size_t c = 0; c < C; ++c) smc += 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]);
+    const double gmc = (double)(smc / (double)C);
+    for (size_t c = 0; c < C; ++c) { const double dlt = 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]) - gmc; sbc += (long double)dlt * dlt; }
+    const double var_chain_mean = (double)(sbc / ((double)C - 1));
+    ess[p] = var_chain_mean > 0 ? (double)C * var_plus / var_chain_mean : (double)NAN;
+  }
   return AMWG_OK;
 }
 
@@ -262,54 +314,19 @@ int amwg_last_sample_dataset_moments(amwg_sampler *s, double *mean, double *sd) 
 int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: null argument");
   const int D = s->n_datasets;
-  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 4 || s->C / D < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains per dataset");
-  const int PR = s->P + s->D;
-  const size_t n = (size_t)D * PR;
-  DevBuf halves, out;
+  TRYB(amwg_diagnostics_refusal("amwg_last_sample_dataset_diagnostics", s->last_draws || amwg_summarised(s), s->last_rows, s->C, D, true));
+  DevBuf halves;
   TRYB(last_sample_halves(s, &halves));
-  HIP_TRY(out.alloc(n * 16));
-  double *dr = out.as<double>();
-  hipLaunchKernelGGL(dataset_diagnostics_kernel, dim3(PR, D), dim3(256), 0, s->stream, halves.as<double>(), s->last_rows, PR, s->C, s->C / D, dr, dr + n);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(rhat, dr, n * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(ess, dr + n, n * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return AMWG_OK;
+  return amwg_dataset_diagnostics_launch(halves.as<double>(), s->last_rows, s->P + s->D, s->C, D, rhat, ess, s->stream);
 }
 
 int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess) {
   if (!s || !rhat || !ess) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: null argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_diagnostics"));
-  if ((!s->last_draws && !amwg_summarised(s)) || s->last_rows < 4 || s->C < 2) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_diagnostics: needs a sample() of >= 4 kept draws on >= 2 chains");
-  const int PR = s->P + s->D;
-  const size_t C = (size_t)s->C, n_out = 4 * (size_t)PR * C;
+  TRYB(amwg_diagnostics_refusal("amwg_last_sample_diagnostics", s->last_draws || amwg_summarised(s), s->last_rows, s->C, 1, false));
   DevBuf dout;
   TRYB(last_sample_halves(s, &dout));
-  std::vector<double> h(n_out);
-  HIP_TRY(hipMemcpyAsync(h.data(), dout.p, n_out * 8, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  const double n = (double)(s->last_rows / 2), m = 2.0 * (double)C;   // 2C half-chains of n draws
-  for (int p = 0; p < PR; ++p) {
-    // W = mean within-sequence variance; B/n = variance of the sequence means (over the 2C halves)
-    long double sw = 0, sm = 0;
-    for (int hf = 0; hf < 2; ++hf)
-      for (size_t c = 0; c < C; ++c) { sm += h[((size_t)(hf * 2 + 0) * PR + p) * C + c]; sw += h[((size_t)(hf * 2 + 1) * PR + p) * C + c]; }
-    const double W = (double)(sw / m), gm = (double)(sm / m);
-    long double sb = 0, sbc = 0;
-    for (int hf = 0; hf < 2; ++hf)
-      for (size_t c = 0; c < C; ++c) { const double dlt = h[((size_t)(hf * 2 + 0) * PR + p) * C + c] - gm; sb += (long double)dlt * dlt; }
-    const double B_over_n = (double)(sb / (m - 1));
-    const double var_plus = (n - 1) / n * W + B_over_n;
-    rhat[p] = W > 0 ? std::sqrt(var_plus / W) : (double)NAN;
-    // whole-chain means: average of the two half means (equal lengths)
-    long double smc = 0;
-    for (size_t c = 0; c < C; ++c) smc += 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]);
-    const double gmc = (double)(smc / (double)C);
-    for (size_t c = 0; c < C; ++c) { const double dlt = 0.5 * (h[((size_t)0 * PR + p) * C + c] + h[((size_t)2 * PR + p) * C + c]) - gmc; sbc += (long double)dlt * dlt; }
-    const double var_chain_mean = (double)(sbc / ((double)C - 1));
-    ess[p] = var_chain_mean > 0 ? (double)C * var_plus / var_chain_mean : (double)NAN;
-  }
-  return AMWG_OK;
+  return amwg_pooled_diagnostics(dout.as<double>(), s->last_rows, s->P + s->D, s->C, rhat, ess, s->stream);
 }
 
 int amwg_info(amwg_sampler *s, double *pls, int32_t *ac, int32_t *it, int32_t *bc, int64_t *acc, int64_t *inb) {

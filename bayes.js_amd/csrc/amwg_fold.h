@@ -10,8 +10,8 @@ struct amwg_sampler;
 
 namespace amwg {
 
-// x is the k-th value (1-based) of its sequence; m its running mean, m2 the running sum of squares about the mean.  chain_halves_kernel (amwg_diag.hip),
-// group_chain_halves_kernel (amwg_group.hip) and fold_window_kernel (amwg_diag.hip) all step through this, in row order: with -ffp-contract=off every operation
+// x is the k-th value (1-based) of its sequence; m its running mean, m2 the running sum of squares about the mean.  chain_halves_kernel (which amwg_group.hip
+// launches too, through amwg_chain_halves) and fold_window_kernel (both amwg_diag.hip) step through this, in row order: with -ffp-contract=off every operation
 // rounds once, so a sequence gives the same bits whichever kernel walks it and however it is cut into windows.  The division stays a division.
 __device__ __forceinline__ void welford_add(double x, int64_t k, double &m, double &m2) {
   const double dlt = x - m;
@@ -58,4 +58,16 @@ int amwg_fold_halves(const double *acc, int64_t rows, int PR, int64_t C, double 
 int amwg_fold_moments(const double *acc, int64_t rows, int PR, int64_t C, int D, double *mean, double *sd, hipStream_t stream);
 // chain_halves_kernel on a stored array draws [rows][PR][C] -> halves [4][PR][C] (the selftest entry compares the fold with it)
 int amwg_chain_halves(const double *draws, int64_t rows, int PR, int64_t C, double *halves, hipStream_t stream);
+
+// ---- amwg_diag.hip: the summaries of stored draws and of halves over a DEVICE array, D datasets of C / D chains each (D = 1: pooled over all chains).  The
+// sampler's calls and the selftest entry (amwg_summaries_check) go through these; mean, sd, rhat, ess are HOST arrays, complete on return (`stream` has drained).
+// What split-R-hat / ESS refuse, in one place: AMWG_EINVAL "<call>: needs a sample() of >= 4 kept draws on >= 2 chains[ per dataset]" unless there is a sample
+// (`have`) of rows >= 4 on C / D >= 2 chains per dataset (D >= 1).  Host only: no device call.
+int amwg_diagnostics_refusal(const char *call, bool have, int64_t rows, int64_t C, int D, bool per_dataset);
+// dataset_moments_kernel on draws [rows][PR][C] -> mean, sd [D][PR]
+int amwg_moments_launch(const double *draws, int64_t rows, int PR, int64_t C, int D, double *mean, double *sd, hipStream_t stream);
+// dataset_diagnostics_kernel on halves [4][PR][C] (chain_halves_kernel's layout) of chains of `rows` kept draws -> rhat, ess [D][PR]
+int amwg_dataset_diagnostics_launch(const double *halves, int64_t rows, int PR, int64_t C, int D, double *rhat, double *ess, hipStream_t stream);
+// the pooled call's reduction: the halves come to the host and are summed there in long double over all C chains -> rhat, ess [PR]
+int amwg_pooled_diagnostics(const double *halves, int64_t rows, int PR, int64_t C, double *rhat, double *ess, hipStream_t stream);
 #pragma GCC visibility pop

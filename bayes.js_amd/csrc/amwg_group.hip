@@ -235,22 +235,7 @@ __global__ void __launch_bounds__(1024) draw_sums_kernel(const double *draws, in
   if (tid == 0) out[p] = red[0];
 }
 
-// per chain and recorded value: mean and (n-1) variance of each half of the chain's kept draws (the same kernel as in
-// amwg_diag.hip): out[((h*2 + stat) * PR + p) * C + c]
-__global__ void group_chain_halves_kernel(const double *draws, int64_t rows, int PR, int64_t C, double *out) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int p = blockIdx.y;
-  if (c >= C) return;
-  const int64_t half = rows / 2;
-  for (int h = 0; h < 2; ++h) {
-    const int64_t r0 = h * half, r1 = r0 + half;
-    double m = 0, m2 = 0;   // Welford
-    for (int64_t r = r0; r < r1; ++r) amwg::welford_add(draws[(r * PR + p) * C + c], r - r0 + 1, m, m2);
-    out[((size_t)(h * 2 + 0) * PR + p) * C + c] = m;
-    out[((size_t)(h * 2 + 1) * PR + p) * C + c] = half > 1 ? m2 / (double)(half - 1) : 0.0;
-  }
-}
-
+// (the halves per chain, hv[((h*2 + stat) * PR + p) * C + c], come from amwg_diag.hip's chain_halves_kernel: amwg_chain_halves, amwg_fold.h)
 // block p.  stage 0: out[p] = sum of half variances, out[PR + p] = sum of half means, out[2 PR + p] = sum of chain means
 //           stage 1: out[p] = sum (half mean - gm[p])^2, out[PR + p] = sum (chain mean - gm[PR + p])^2
 __global__ void __launch_bounds__(256) halves_sums_kernel(const double *hv, int PR, int64_t C, int stage, const double *gm, double *out) {
@@ -359,8 +344,8 @@ int amwg_group_diagnostics(amwg_sampler *const *shards, int32_t n, double *rhat,
     HIPG(hipSetDevice(s->device));
     HIPG(hipMalloc(reinterpret_cast<void **>(&halves[i]), 4 * (size_t)PR * C * 8));
     HIPG(hipMalloc(reinterpret_cast<void **>(&gmd[i]), 2 * (size_t)PR * 8));
-    hipLaunchKernelGGL(group_chain_halves_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)PR), dim3(256), 0, s->stream, s->last_draws, s->last_rows, PR, s->C, halves[i]);
-    HIPG(hipGetLastError());
+    rc = amwg_chain_halves(s->last_draws, s->last_rows, PR, s->C, halves[i], s->stream);
+    if (rc != AMWG_OK) return rc;
     hipLaunchKernelGGL(halves_sums_kernel, dim3(PR), dim3(256), 0, s->stream, (const double *)halves[i], PR, s->C, 0, (const double *)nullptr, g.buf[i]);
     HIPG(hipGetLastError());
   }

@@ -144,4 +144,31 @@ int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t P
   return AMWG_OK;
 }
 
+int amwg_summaries_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
+                         double *mean, double *sd, double *rhat_ds, double *ess_ds, double *rhat_pooled, double *ess_pooled) {
+  if (!draws || !mean || !sd || !rhat_ds || !ess_ds || !rhat_pooled || !ess_pooled) return amwg_fail(AMWG_EINVAL, "amwg_summaries_check: null argument");
+  if (rows < 1 || PR < 1 || PR > 65535 || C < 1 || D < 1 || D > 65535 || C % D != 0 || window_rows < 0)
+    return amwg_fail(AMWG_EINVAL, "amwg_summaries_check: bad shape (rows %lld, values %d, chains %lld, datasets %d -- dividing the chains --, window_rows %lld)", (long long)rows, PR, (long long)C, D, (long long)window_rows);
+  TRYB(amwg_diagnostics_refusal("amwg_summaries_check", true, rows, C, D, true));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "amwg_summaries_check: array too large");
+  TRYB(use_device(device));
+  const size_t row_elems = (size_t)PR * (size_t)C, bytes = (size_t)rows * row_elems * 8;
+  DevBuf dd, acc, hv;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hv.alloc(4 * row_elems * 8));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  if (window_rows > 0) {      // (the summarised path: window after window, as launch_steps folds them)
+    HIP_TRY(acc.alloc(kFoldStats * row_elems * 8));
+    HIP_TRY(hipMemsetAsync(acc.p, 0, kFoldStats * row_elems * 8, nullptr));
+    for (int64_t g0 = 0; g0 < rows; g0 += window_rows)
+      TRYB(amwg_fold_window(dd.as<double>() + (size_t)g0 * row_elems, g0, rows - g0 < window_rows ? rows - g0 : window_rows, rows / 2, PR, C, acc.as<double>(), nullptr));
+    TRYB(amwg_fold_halves(acc.as<double>(), rows, PR, C, hv.as<double>(), nullptr));
+  } else {
+    TRYB(amwg_chain_halves(dd.as<double>(), rows, PR, C, hv.as<double>(), nullptr));
+  }
+  TRYB(amwg_moments_launch(dd.as<double>(), rows, PR, C, D, mean, sd, nullptr));
+  TRYB(amwg_dataset_diagnostics_launch(hv.as<double>(), rows, PR, C, D, rhat_ds, ess_ds, nullptr));
+  return amwg_pooled_diagnostics(hv.as<double>(), rows, PR, C, rhat_pooled, ess_pooled, nullptr);
+}
+
 }  // extern "C"

@@ -356,7 +356,9 @@ int amwg_last_sample_moments(amwg_sampler *s, double *mean, double *sd);
 /* Convergence diagnostics over the draws of the LAST amwg_sample* call, computed on the device per recorded value
  * (what the reference's users do in R on the returned arrays, tests/test_mcmc_js.R): split-R-hat (every chain cut in
  * two halves; Gelman et al., BDA3 section 11.4) and the effective sample size from the variance of the chain means,
- * ess = chains * var_plus / Var(chain mean).  Needs >= 2 chains and >= 4 kept draws.  rhat[P], ess[P]. */
+ * ess = chains * var_plus / Var(chain mean).  Needs >= 2 chains and >= 4 kept draws.  rhat[P], ess[P].
+ * Degenerate columns: rhat is NaN when W = 0 (every half-chain constant) or when any used draw is not finite; ess is NaN when the chain means do not
+ * vary (Var(chain mean) = 0) or a used draw is not finite.  With an odd number of kept draws the last one is ignored (half = kept / 2, rounded down). */
 int amwg_last_sample_diagnostics(amwg_sampler *s, double *rhat, double *ess);
 
 /* Posterior quantiles over the draws of the LAST amwg_sample* call (all chains x kept draws pooled), per recorded value:

@@ -42,6 +42,16 @@ int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t ro
 int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
                     double *halves_folded, double *halves_direct, double *mean, double *sd);
 
+/* The summaries of stored draws on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each, through the launchers the sampler's calls use:
+ *   mean, sd             [D][PR]  dataset_moments_kernel (amwg_last_sample_moments / _dataset_moments on stored draws)
+ *   rhat_ds, ess_ds      [D][PR]  the halves of every chain + dataset_diagnostics_kernel (amwg_last_sample_dataset_diagnostics)
+ *   rhat_pooled, ess_pooled [PR]  the same halves + the host reduction of amwg_last_sample_diagnostics over all C chains
+ * window_rows = 0: the halves come from chain_halves_kernel (stored draws); window_rows > 0: from the fold of amwg_sample_summarize in windows of window_rows rows.
+ * Refused before a device is opened, with the product's words: a null pointer, a bad shape (non-positive sizes, C % D != 0, window_rows < 0), and what split-R-hat
+ * refuses ("needs a sample() of >= 4 kept draws on >= 2 chains per dataset": rows < 4 or C / D < 2). */
+int amwg_summaries_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
+                         double *mean, double *sd, double *rhat_ds, double *ess_ds, double *rhat_pooled, double *ess_pooled);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);

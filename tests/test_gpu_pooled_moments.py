@@ -12,42 +12,9 @@ import pytest
 
 import amwg_ctypes
 import model_spec
+from summary_reference import kernel_order_moments      # (tree_sum and strided_sums over 1 024 threads: the restated order lives there, shared)
 
 pytestmark = pytest.mark.gpu
-THREADS = 1024
-
-
-def tree_sum(partial):
-    red = partial.copy()
-    o = THREADS // 2
-    while o:
-        red[:o] = red[:o] + red[o:2 * o]
-        o //= 2
-    return red[0]
-
-
-def strided_sums(v, term):
-    """[1024]: thread t's running sum of term(v[i]) over i = t, t + 1024, ...; the padding of the last round is masked, not added"""
-    rounds = -(-v.size // THREADS)
-    x = np.zeros(rounds * THREADS)
-    x[:v.size] = v
-    have = (np.arange(rounds * THREADS) < v.size).reshape(rounds, THREADS)
-    acc = np.zeros(THREADS)
-    for r, row in enumerate(x.reshape(rounds, THREADS)):
-        acc = np.where(have[r], acc + term(row), acc)
-    return acc
-
-
-def kernel_order_moments(v):
-    n = v.size
-    m = tree_sum(strided_sums(v, lambda x: x)) / np.float64(n)
-
-    def square_about_the_mean(x):
-        dlt = x - m
-        return dlt * dlt
-    tot = tree_sum(strided_sums(v, square_about_the_mean))
-    return m, (np.sqrt(tot / np.float64(n - 1)) if n > 1 else np.float64(0.0))
-
 
 @pytest.mark.parametrize("chains,rows", [(1, 1), (64, 3), (192, 7)], ids=["n1_sd_is_0", "n192_idle_threads", "n1344_two_rounds"])
 def test_pooled_moments_follow_the_kernels_order_bit_for_bit(chains, rows):
