@@ -5,6 +5,7 @@ binding exists because the driver's bench/test harness is Python.  It carries no
 beyond marshalling: every computation happens in the HIP library, and loading fails loudly
 if the library is missing.
 """
+import bisect
 import ctypes as C
 import os
 
@@ -46,8 +47,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_sample_summarize", "amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_summaries_check", "amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -81,6 +82,9 @@ def lib():
         L.amwg_sample_summarize.argtypes = [vp, i64, i64, i64]
         L.amwg_sample_summarize_async.argtypes = [vp, i64, i64, i64]
         L.amwg_summary_info.argtypes = [vp, pi64, pi64, pi64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.amwg_last_sample_dataset_histogram.argtypes = [vp, pd, i32, pu64]
+        L.amwg_set_histogram.argtypes = [vp, pd, i32]
+        L.amwg_histogram_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_set_adapting.argtypes = [vp, i32]
         L.amwg_get_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_info.argtypes = [vp, pd, pi32, pi32, pi32, pi64, pi64]
@@ -165,6 +169,7 @@ def selftest_lib():
         L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
+        L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
         _selftest = L
     return _selftest
 
@@ -351,6 +356,35 @@ class Sampler:
         _check(lib().amwg_summary_info(self.h, C.byref(r), C.byref(w), C.byref(k), C.byref(wb), C.byref(ab)))
         return {"rows": r.value, "window_rows": w.value, "windows": k.value, "window_bytes": wb.value, "accumulator_bytes": ab.value}
 
+    def set_histogram(self, edges):
+        """Arms a histogram for every later summarize() (amwg_set_histogram): edges [bins + 1] for all recorded values, or [P + derived][bins + 1];
+        None disarms.  dataset_histogram() returns the counts after the call."""
+        if edges is None:
+            _check(lib().amwg_set_histogram(self.h, None, 0))
+            return
+        e = _edges_per_value(edges, self.PR)
+        _check(lib().amwg_set_histogram(self.h, _dp(e), e.shape[1] - 1))
+
+    def histogram_info(self):
+        """{"bins": the armed number of bins (0: none), "bytes": the device bytes of its edges and counts} (amwg_histogram_info)"""
+        b, n = C.c_int32(), C.c_size_t()
+        _check(lib().amwg_histogram_info(self.h, C.byref(b), C.byref(n)))
+        return {"bins": b.value, "bytes": n.value}
+
+    def dataset_histogram(self, edges=None):
+        """-> uint64 array [datasets][P + derived][bins + 3] (the bins, then under, over, nan) over the last sample call, counted on the device by the rule
+        np.searchsorted(edges, x, side="right") - 1 (amwg_last_sample_dataset_histogram).  After sample*(): under any `edges` ([bins + 1] or
+        [P + derived][bins + 1]).  After summarize(): edges=None, the counts under the edges of set_histogram()."""
+        if edges is None:
+            bins = self.histogram_info()["bins"]
+            out = np.zeros((self.D, self.PR, max(bins, 1) + 3), dtype=np.uint64)
+            _check(lib().amwg_last_sample_dataset_histogram(self.h, None, bins, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+            return out
+        e = _edges_per_value(edges, self.PR)
+        out = np.zeros((self.D, self.PR, e.shape[1] + 2), dtype=np.uint64)
+        _check(lib().amwg_last_sample_dataset_histogram(self.h, _dp(e), e.shape[1] - 1, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
     def sample_device(self, n, thin, dev_ptr, nbytes):
         _check(lib().amwg_sample_device(self.h, n, thin, C.c_void_p(dev_ptr), nbytes))
 
@@ -446,6 +480,61 @@ class Sampler:
         return {"lanes_per_chain": v[0].value, "block_threads": v[1].value, "grid_blocks": v[2].value,
                 "lds_bytes": v[3].value, "n_launches": v[4].value, "kernel_ms": ms.value, "kernel": (lib().amwg_kernel_name(self.h) or b"").decode(),
                 "summation_order": lib().amwg_summation_order(self.h), "datasets": lib().amwg_num_datasets(self.h)}
+
+
+def _edges_per_value(edges, PR):
+    """edges [bins + 1] (for every recorded value) or [PR][bins + 1] -> contiguous float64 [PR][bins + 1]"""
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim == 1:
+        e = np.broadcast_to(e, (PR, e.size))
+    if e.ndim != 2 or e.shape[0] != PR or e.shape[1] < 1:
+        raise AmwgError("edges must be [bins + 1] or [%d recorded values][bins + 1], got shape %s" % (PR, e.shape))
+    return np.ascontiguousarray(e)
+
+
+def histogram_check(draws, D, edges, window_rows=0, counts=None, device=0):
+    """libamwg_selftest.so: the kernel of Sampler.dataset_histogram / set_histogram on any array draws [rows][PR][C], D datasets of C / D columns each, under
+    edges [bins + 1] or [PR][bins + 1], in windows of window_rows rows (0: all at once); the kernel ADDS to `counts` (default: zeros)
+    -> uint64 array [D][PR][bins + 3]: the bins, then under, over, nan (amwg_histogram_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    e = _edges_per_value(edges, PR)
+    bins = e.shape[1] - 1
+    out = np.zeros((D, PR, bins + 3), dtype=np.uint64) if counts is None else np.array(counts, dtype=np.uint64).reshape(D, PR, bins + 3)
+    L = selftest_lib()
+    if L.amwg_histogram_check(_dp(dr), rows, PR, Cn, D, _dp(e), bins, window_rows, out.ctypes.data_as(C.POINTER(C.c_uint64)), device) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
+
+
+def interval_brackets(counts, edges, probs):
+    """For one cell of counts [bins + 3] (the bins, then under, over, nan) under edges [bins + 1]: per probability q the bracket [lo, hi] that contains the value
+    quantiles() returns for q over the counted draws (R's type 7: h = (n - 1) q, an interpolation between the order statistics of ranks floor(h) and
+    min(floor(h) + 1, n - 1)): lo = the left edge of the bin that holds the first rank (-inf in `under`, edges[bins] in `over`), hi = the right edge of the bin
+    that holds the second (+inf in `over`, edges[0] in `under`).  NaN, NaN when a NaN was counted, nothing was counted, or q is outside [0, 1].
+    Host arithmetic on integers; no device call.  -> array [len(probs)][2]"""
+    c = [int(v) for v in np.asarray(counts).reshape(-1)]
+    e = np.asarray(edges, dtype=np.float64).reshape(-1)
+    bins = e.size - 1
+    if bins < 1 or len(c) != bins + 3:
+        raise AmwgError("interval_brackets: counts [bins + 3] under edges [bins + 1], got %d counts and %d edges" % (len(c), e.size))
+    under, over, nan = c[bins], c[bins + 1], c[bins + 2]
+    n = sum(c[:bins]) + under + over
+    cum = [under]      # cum[k]: the values below edges[k]; rank r lies in `under` when r < cum[0], in bin i when cum[i] <= r < cum[i + 1], else in `over`
+    for v in c[:bins]:
+        cum.append(cum[-1] + v)
+    out = np.full((len(probs), 2), np.nan)
+    for k, q in enumerate(probs):
+        q = float(q)
+        if nan > 0 or n == 0 or not (0.0 <= q <= 1.0):
+            continue
+        h = float(n - 1) * q
+        r0 = int(np.floor(h))
+        r1 = min(r0 + 1, n - 1)
+        b0, b1 = bisect.bisect_right(cum, r0) - 1, bisect.bisect_right(cum, r1) - 1      # -1: under, bins: over, else the bin
+        out[k, 0] = -np.inf if b0 < 0 else e[b0]      # (e[bins] when the rank lies in `over`)
+        out[k, 1] = np.inf if b1 >= bins else e[b1 + 1]      # (e[0] when it lies in `under`)
+    return out
 
 
 def dataset_quantiles_check(draws, D, probs, device=0):

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "amwg_fold.h"
+#include "amwg_histogram.h"
 #include "amwg_host.h"
 #include "amwg_dataset.h"
 #include "amwg_kernel.h"
@@ -718,6 +719,7 @@ int amwg_destroy(amwg_sampler *s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void *p : s->dev_allocs) (void)hipFree(p);
   amwg_summary_forget(s);      // (amwg_fold.h: the accumulators of a summarising call were among dev_allocs)
+  amwg_histogram_forget(s);    // (amwg_histogram.h: the edges and counts of an armed histogram)
   if (s->d_draws) (void)hipFree(s->d_draws);
   if (s->user_module) (void)hipModuleUnload(s->user_module);
   for (hipEvent_t e : s->chunk_ev) (void)hipEventDestroy(e);

@@ -37,10 +37,12 @@ struct FoldSummary {
   size_t window_bytes = 0;
 };
 // a window for launch_steps' loop: the recorded rows go to rows [0, window_rows) of the draw buffer, and each time they are full (and at the end) they are folded into acc
+struct HistArm;      // (amwg_histogram.h)
 struct FoldWindow {
   int64_t window_rows = 0, total_rows = 0;
   double *acc = nullptr;
   int64_t windows = 0;      // out: folds enqueued
+  const HistArm *hist = nullptr;      // the histogram armed for the call (amwg_set_histogram): after each fold, the window's rows are counted into it too
 };
 // true when the last sample call of `s` was a summarising one (its draws were folded, not kept): last_rows > 0 without last_draws
 bool amwg_summarised(const amwg_sampler *s);

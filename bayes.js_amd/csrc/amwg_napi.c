@@ -755,6 +755,80 @@ static napi_value DatasetQuantiles(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* setHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins): amwg_set_histogram -- arms (null, 0: disarms) a histogram for later summarising calls */
+static napi_value SetHistogram(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t ne = 0;
+  const double *edges = (const double *)typed_data(env, a[1], napi_float64_array, &ne);
+  const int64_t bins = arg_i64(env, a[2]);
+  if (edges && (bins < 0 || bins > 4096 || ne != (size_t)amwg_num_recorded(s) * (size_t)(bins + 1))) {
+    napi_throw_type_error(env, NULL, "amwg_napi.setHistogram: edges must be a Float64Array [recorded values][bins + 1]");
+    return NULL;
+  }
+  int rc = amwg_set_histogram(s, edges, (int32_t)bins);
+  return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
+}
+
+/* datasetHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins) -> {datasets, bins, counts}: counts a Float64Array [datasets][recorded][bins + 3]
+ * (the bins, then under, over, nan) over the last sample call (amwg_last_sample_dataset_histogram); null edges: the counts of a summarising call under the armed
+ * edges.  A count of 2^53 or more is no Number: refused. */
+static napi_value DatasetHistogram(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t ne = 0;
+  const double *edges = (const double *)typed_data(env, a[1], napi_float64_array, &ne);
+  const int64_t bins = arg_i64(env, a[2]);
+  if (bins < 1 || bins > 4096 || (edges && ne != (size_t)amwg_num_recorded(s) * (size_t)(bins + 1))) {
+    napi_throw_type_error(env, NULL, "amwg_napi.datasetHistogram: edges must be a Float64Array [recorded values][bins + 1] (or null) and bins in 1 .. 4096");
+    return NULL;
+  }
+  const size_t n = (size_t)amwg_num_datasets(s) * (size_t)amwg_num_recorded(s) * (size_t)(bins + 3);
+  uint64_t *c = (uint64_t *)malloc(n * sizeof *c);
+  if (!c) { napi_throw_error(env, NULL, "amwg_napi.datasetHistogram: cannot allocate the counts"); return NULL; }
+  int rc = amwg_last_sample_dataset_histogram(s, edges, (int32_t)bins, c);
+  if (rc != AMWG_OK) { free(c); return throw_amwg(env, rc); }
+  double *q = NULL;
+  napi_value v = new_f64(env, n, &q);
+  if (!v) { free(c); return NULL; }
+  for (size_t i = 0; i < n; i++) {
+    if (c[i] >= ((uint64_t)1 << 53)) { free(c); napi_throw_range_error(env, NULL, "amwg_napi.datasetHistogram: a count of 2^53 or more does not fit a Number"); return NULL; }
+    q[i] = (double)c[i];
+  }
+  free(c);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "counts", v);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  napi_create_int32(env, (int32_t)bins, &t);
+  napi_set_named_property(env, o, "bins", t);
+  return o;
+}
+
+/* histogramInfo(handle) -> {bins, bytes}: the armed number of bins (0: none) and the device bytes of its edges and counts (amwg_histogram_info) */
+static napi_value HistogramInfo(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int32_t bins = 0;
+  size_t bytes = 0;
+  int rc = amwg_histogram_info(s, &bins, &bytes);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_create_int32(env, bins, &t);
+  napi_set_named_property(env, o, "bins", t);
+  napi_create_int64(env, (int64_t)bytes, &t);
+  napi_set_named_property(env, o, "bytes", t);
+  return o;
+}
+
 /* the shards of a multi-device sampler: JS array of handles -> C array (caller frees) */
 static amwg_sampler **unwrap_group(napi_env env, napi_value arr, uint32_t *n) {
   *n = 0;
@@ -958,7 +1032,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
       {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
-      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
+      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

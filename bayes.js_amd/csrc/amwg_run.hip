@@ -11,6 +11,7 @@
 
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
 #include "amwg_fold.h"
+#include "amwg_histogram.h"
 #include "amwg_host.h"
 #include "amwg_kernel.h"      // (StepArgs, and the kErr* bits the step kernels report)
 #include "amwg_dataset.h"     // (DatasetArgs: the second argument of a dataset sampler's kernel)
@@ -166,6 +167,8 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     if (win && row > 0 && (row == win->window_rows || done >= n)) {
       if (row > win->window_rows || folded + row > win->total_rows) return amwg_fail(AMWG_EINVAL, "internal: %lld rows in a window of %lld (%lld of %lld folded)", (long long)row, (long long)win->window_rows, (long long)folded, (long long)win->total_rows);
       TRYB(amwg_fold_window(d_draws, folded, row, win->total_rows / 2, s->P + s->D, s->C, win->acc, s->stream));
+      if (win->hist)      // (the same rows once more, on the same stream: the counts add up over the windows)
+        TRYB(amwg_histogram_launch("amwg_sample_summarize", d_draws, row, s->P + s->D, s->C, s->n_datasets, win->hist->d_edges, win->hist->bins, win->hist->uniform, win->hist->d_counts, s->stream));
       win->windows++;
       folded += row;
       row = 0;
@@ -351,6 +354,9 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   win.window_rows = W;
   win.total_rows = rows;
   win.acc = f.acc;
+  HistArm *arm = nullptr;
+  TRYB(amwg_histogram_begin(s, &arm));      // (amwg_set_histogram: its counts start afresh too)
+  win.hist = arm;
   TRYB(launch_steps(s, n, thin, s->d_draws, false, &win));
   f.rows = rows; f.window_rows = W; f.windows = win.windows; f.window_bytes = need;
   s->last_rows = rows;      // (rows > 0 without last_draws: the mark of a summary -- amwg_summarised)

@@ -3,6 +3,7 @@
 #include "../../include/amwg_selftest.h"
 #include "amwg_dataset_quantiles.h"
 #include "amwg_fold.h"
+#include "amwg_histogram.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
@@ -141,6 +142,30 @@ int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t P
   HIP_TRY(hipMemcpy(halves_direct, hd.p, 4 * row_elems * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(mean, mom.p, n_mom * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(sd, mom.as<double>() + n_mom, n_mom * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+int amwg_histogram_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *edges, int32_t bins, int64_t window_rows,
+                         uint64_t *counts, int32_t device) {
+  if (!draws || !edges || !counts) return amwg_fail(AMWG_EINVAL, "amwg_histogram_check: null argument");
+  if (window_rows < 0) return amwg_fail(AMWG_EINVAL, "amwg_histogram_check: bad shape (window_rows %lld)", (long long)window_rows);
+  TRYB(amwg_histogram_shape("amwg_histogram_check", rows, PR, C, D, bins));
+  TRYB(amwg_histogram_edges_check("amwg_histogram_check", edges, PR, bins));
+  TRYB(use_device(device));
+  const size_t row_elems = (size_t)PR * (size_t)C, bytes = (size_t)rows * row_elems * 8;
+  const size_t edge_bytes = (size_t)PR * (size_t)(bins + 1) * 8, count_bytes = (size_t)D * (size_t)PR * (size_t)(bins + 3) * 8;
+  DevBuf dd, de, dc;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(de.alloc(edge_bytes));
+  HIP_TRY(dc.alloc(count_bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(de.p, edges, edge_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dc.p, counts, count_bytes, hipMemcpyHostToDevice));
+  const int64_t w = window_rows > 0 ? window_rows : rows;
+  for (int64_t g0 = 0; g0 < rows; g0 += w)      // (window after window, as launch_steps counts them)
+    TRYB(amwg_histogram_launch("amwg_histogram_check", dd.as<double>() + (size_t)g0 * row_elems, rows - g0 < w ? rows - g0 : w, PR, C, D, de.as<double>(), bins, amwg_histogram_uniform(edges, PR, bins), dc.as<uint64_t>(), nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(counts, dc.p, count_bytes, hipMemcpyDeviceToHost));
   return AMWG_OK;
 }
 

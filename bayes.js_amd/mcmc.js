@@ -417,6 +417,16 @@ AmwgSampler.prototype.summarize = function (n_iterations, options) {
   const N = native(), w = options && options.window_rows !== undefined ? options.window_rows : 0;
   if (this._shards.length > 1 || (options && options.devices && options.devices.length > 1))
     throw 'AmwgSampler (MI355X): summarize() runs on one device: summaries over several devices (options.devices) are formed from the stored draws -- use sample_on_device()';
+  // options.histogram: edges ({name: [...]} per monitored or derived value, or one array for all) under which the draws are counted while they pass
+  // (amwg_set_histogram); dataset_histogram() / histogram() return the counts afterwards.  A call without it counts nothing.
+  if (options && options.histogram !== undefined && options.histogram !== null) {
+    const e = this._histogramEdges(options.histogram);
+    N.setHistogram(this._shards[0].handle, e.flat, e.bins);
+    this._hist_bins = e.bins;
+  } else if (this._hist_bins) {
+    N.setHistogram(this._shards[0].handle, null, 0);
+    this._hist_bins = 0;
+  }
   this._each((sh) => N.sampleSummarizeAsync(sh.handle, n_iterations, this.thinning_interval, w));
   this._each((sh) => N.sync(sh.handle));
   return Math.ceil(n_iterations / this.thinning_interval);
@@ -547,6 +557,77 @@ AmwgSampler.prototype.dataset_quantiles = function (probs) {
   }
   return out;
 };
+
+// edges as the caller gives them -- {name: [e0, ..., e_bins]} per parameter or derived quantity (every element of a vector parameter under the same edges), or one
+// array for all recorded values; all of one length -- -> {flat: Float64Array [recorded][bins + 1], bins}
+AmwgSampler.prototype._histogramEdges = function (edges) {
+  const PR = this.PR, one = Array.isArray(edges) || ArrayBuffer.isView(edges);
+  const of = (name) => {
+    const e = one ? edges : edges[name];
+    if (!e || !(e.length >= 2)) throw 'AmwgSampler (MI355X): histogram edges for ' + name + ' must be an array of at least two ascending numbers';
+    return e;
+  };
+  const rows = new Array(PR);
+  for (const L of this._layout) for (let k = 0; k < L.len; k++) rows[L.base + k] = of(L.name);
+  this.derived.forEach((name, q) => { rows[this.P + q] = of(name); });
+  const bins = rows[0].length - 1, flat = new Float64Array(PR * (bins + 1));
+  rows.forEach((e, p) => {
+    if (e.length !== bins + 1) throw 'AmwgSampler (MI355X): histogram edges must have the same length for every value (' + (bins + 1) + ' and ' + e.length + ')';
+    flat.set(e, p * (bins + 1));
+  });
+  return { flat, bins };
+};
+
+/** Histogram per dataset (options.datasets; an ordinary sampler is one dataset) over each dataset's chains x kept draws of the last sample call, counted on the
+ *  device: [{name: [[c_0, ..., c_{bins-1}, under, over, nan] per element]}, ...].  x is in bin i iff edges[i] <= x < edges[i+1] -- comparisons only.
+ *  After sample() / sample_on_device(): under any `edges` ({name: [...]} or one array for all values).  After summarize(n, {histogram: edges}): no argument, the
+ *  counts under those edges -- equal, count for count, to those of the stored run.  Counts are Numbers (a count of 2^53 or more is refused). */
+AmwgSampler.prototype.dataset_histogram = function (edges) {
+  const N = native(), out = [], PR = this.PR;
+  const given = edges !== undefined && edges !== null ? this._histogramEdges(edges) : null;
+  for (const sh of this._shards) {
+    const r = N.datasetHistogram(sh.handle, given ? given.flat : null, given ? given.bins : (this._hist_bins || 1)), w = r.bins + 3;
+    for (let d = 0; d < r.datasets; d++) {
+      const o = {}, row = (c) => Array.from(r.counts.subarray((d * PR + c) * w, (d * PR + c + 1) * w));
+      for (const L of this._layout) o[L.name] = Array.from({ length: L.len }, (_, e) => row(L.base + e));
+      this.derived.forEach((name, k) => { o[name] = [row(this.P + k)]; });
+      out.push(o);
+    }
+  }
+  return out;
+};
+
+/** Histogram over all chains x kept draws of the last sample call: {name: [[c_0, ..., c_{bins-1}, under, over, nan] per element]} -- dataset_histogram() of an
+ *  ordinary sampler on one device. */
+AmwgSampler.prototype.histogram = function (edges) {
+  this._refusePooled('histogram');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): histogram() runs on one device';
+  return this.dataset_histogram(edges)[0];
+};
+
+/** For one array of counts [c_0, ..., c_{bins-1}, under, over, nan] under edges [e_0, ..., e_bins]: per probability q the bracket [lo, hi] that contains the value
+ *  quantiles([q]) returns over the counted draws (type 7: h = (n - 1) q, an interpolation between the order statistics of ranks floor(h) and min(floor(h) + 1, n - 1)).
+ *  lo = the left edge of the bin that holds the first rank (-Infinity in `under`, e_bins in `over`), hi = the right edge of the bin that holds the second
+ *  (Infinity in `over`, e_0 in `under`).  [NaN, NaN] when a NaN was counted, nothing was counted, or q is outside [0, 1].  Host only: no device call. */
+function interval_brackets(counts, edges, probs) {
+  const bins = edges.length - 1;
+  if (bins < 1 || counts.length !== bins + 3) throw 'interval_brackets: counts [bins + 3] under edges [bins + 1]';
+  const under = counts[bins], over = counts[bins + 1], nan = counts[bins + 2];
+  const cum = new Array(bins + 1);      // cum[k]: the values below edges[k]; rank r lies in `under` when r < cum[0], in bin i when cum[i] <= r < cum[i + 1], else in `over`
+  cum[0] = under;
+  for (let i = 0; i < bins; i++) cum[i + 1] = cum[i] + counts[i];
+  const n = cum[bins] + over;
+  const where = (r) => {      // the last k with cum[k] <= r; -1: under, bins: over
+    let a = -1, b = bins;
+    while (a < b) { const m = Math.ceil((a + b) / 2); if (cum[m] <= r) a = m; else b = m - 1; }
+    return a;
+  };
+  return Array.from(probs, (q) => {
+    if (nan > 0 || n === 0 || !(q >= 0 && q <= 1)) return [NaN, NaN];
+    const h = (n - 1) * q, r0 = Math.floor(h), r1 = Math.min(r0 + 1, n - 1), b0 = where(r0), b1 = where(r1);
+    return [b0 < 0 ? -Infinity : edges[b0], b1 >= bins ? Infinity : edges[b1 + 1]];
+  });
+}
 
 /** Per-chain starting points: f(chainIndex) -> state object shaped like sampler.state of one chain ({name: number | nested array}).
  *  The reference starts from the completed `init` (mcmc.js:954-957); many chains want over-dispersed starts. */
@@ -766,5 +847,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { code_cache_stats, runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

@@ -328,6 +328,25 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
 int amwg_sample_summarize(amwg_sampler *s, int64_t n, int64_t thin, int64_t window_rows);
 int amwg_summary_info(const amwg_sampler *s, int64_t *rows, int64_t *window_rows, int64_t *windows, size_t *window_bytes, size_t *accumulator_bytes);
 
+/* POSTERIOR HISTOGRAMS over caller-given edges, counted on the device.  Per recorded value p (components, then derived quantities: PR = amwg_num_recorded) the caller
+ * gives edges[p][0 .. bins]: finite, strictly ascending, 1 <= bins <= 4096.  THE BIN RULE is comparisons with the edges and no arithmetic on the draws: x is in bin i
+ * iff edges[i] <= x < edges[i + 1]; x < edges[0] counts as UNDER, x >= edges[bins] as OVER (+inf is over, -inf under), a NaN as NAN; -0 equals +0 -- numpy's
+ * searchsorted(edges, x, side="right") - 1.  counts[dataset][p][bins + 3]: the bins, then under, over, nan; a dataset's counts are over its chains x kept draws, and an
+ * ordinary sampler is one dataset (as for amwg_last_sample_dataset_quantiles).  Counts are integers and do not depend on the order of the draws: the histogram of a
+ * summarising call EQUALS that of the stored run, count for count, whatever the window.
+ *   amwg_last_sample_dataset_histogram -- after amwg_sample*: the histogram of the kept draws under any valid edges.  After amwg_sample_summarize*: pass edges = NULL and
+ *     the armed number of bins, and receive the counts folded under the edges armed before the call; edges given afterwards, another number of bins, or a call for which
+ *     nothing was armed is AMWG_EINVAL with a message that names amwg_set_histogram.
+ *   amwg_set_histogram -- arms a histogram for every later amwg_sample_summarize[_async] of this sampler (the edges are copied; NULL, 0 disarms): the counts are zeroed
+ *     when a summarising call starts, and after each fold of a window the histogram kernel counts the same window on the same stream.  The edges stay fixed for the
+ *     whole of a call.  Moments, R-hat, ESS, the chains' state, n_launches and amwg_summary_info are those of the unarmed call.
+ *   amwg_histogram_info -- the armed number of bins (0: none) and the device bytes of its edges and counts (either pointer may be NULL).
+ * Refused with AMWG_EINVAL and the call's name, before any device call: null pointers, bins outside 1 .. 4096, an edge that is not finite, edges that are not strictly
+ * ascending, no sample call yet. */
+int amwg_last_sample_dataset_histogram(amwg_sampler *s, const double *edges, int32_t bins, uint64_t *counts);
+int amwg_set_histogram(amwg_sampler *s, const double *edges, int32_t bins);
+int amwg_histogram_info(const amwg_sampler *s, int32_t *bins, size_t *bytes);
+
 /* Replaces sampler.start_adaptation() / .stop_adaptation() (mcmc.js:1060-1073). */
 int amwg_set_adapting(amwg_sampler *s, int32_t flag);
 

@@ -52,6 +52,14 @@ int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t P
 int amwg_summaries_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,
                          double *mean, double *sd, double *rhat_ds, double *ess_ds, double *rhat_pooled, double *ess_pooled);
 
+/* The histogram kernel of amwg_last_sample_dataset_histogram / amwg_set_histogram on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each, under
+ * edges[PR][bins + 1] (host): the array is uploaded and the product's launcher runs over it in windows of window_rows rows (0 = all at once), as a summarising call
+ * runs it window after window.  counts[D][PR][bins + 3] (host) is IN and OUT: the kernel adds to what the caller passes.
+ * Refused before a device is opened, with the product's words: null pointers, a bad shape (non-positive sizes, C % D != 0, window_rows < 0), bins outside 1 .. 4096,
+ * edges that are not finite or not strictly ascending. */
+int amwg_histogram_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *edges, int32_t bins, int64_t window_rows,
+                         uint64_t *counts, int32_t device);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);
