@@ -47,8 +47,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -85,6 +85,9 @@ def lib():
         L.amwg_last_sample_dataset_histogram.argtypes = [vp, pd, i32, pu64]
         L.amwg_set_histogram.argtypes = [vp, pd, i32]
         L.amwg_histogram_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
+        L.amwg_last_sample_dataset_covariance.argtypes = [vp, pi32, i32, pd]
+        L.amwg_set_covariance.argtypes = [vp, pi32, i32]
+        L.amwg_covariance_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_set_adapting.argtypes = [vp, i32]
         L.amwg_get_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_info.argtypes = [vp, pd, pi32, pi32, pi32, pi64, pi64]
@@ -170,6 +173,7 @@ def selftest_lib():
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
+        L.amwg_covariance_check.argtypes = [pd, i64, i32, i64, i32, C.POINTER(i32), i32, i64, pd, i32]
         _selftest = L
     return _selftest
 
@@ -342,9 +346,16 @@ class Sampler:
         _check(lib().amwg_fetch_draws_slices(self.h, n, base, ln, ptrs, sizes))
         return outs
 
-    def summarize(self, n, thin=1, window_rows=0):
+    def summarize(self, n, thin=1, window_rows=0, covariance=None):
         """The steps of sample_async(n, thin) + sync(), the kept draws folded window by window into per-chain accumulators instead of stored
-        (amwg_sample_summarize): moments(), convergence() and their dataset_ forms then answer from those.  -> kept draws"""
+        (amwg_sample_summarize): moments(), convergence() and their dataset_ forms then answer from those.  -> kept draws
+        covariance: shorthand for set_covariance() before the call, which -- like set_histogram() -- arms this AND every later summarize() until it is disarmed:
+        True arms the covariance of every recorded value, a list of indices that of those values, False disarms; None (the default) leaves what is armed as it is.
+        (mcmc.js takes its options per call instead: a summarize() there without options.covariance disarms.)"""
+        if covariance is False:
+            self.set_covariance(None)
+        elif covariance is not None:
+            self.set_covariance(range(self.PR) if covariance is True else covariance)
         _check(lib().amwg_sample_summarize(self.h, n, thin, window_rows))
         self._pending = -(-n // thin)
         return self._pending
@@ -383,6 +394,39 @@ class Sampler:
         e = _edges_per_value(edges, self.PR)
         out = np.zeros((self.D, self.PR, e.shape[1] + 2), dtype=np.uint64)
         _check(lib().amwg_last_sample_dataset_histogram(self.h, _dp(e), e.shape[1] - 1, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
+    def _summarised(self):
+        """was the last sample call a summarising one?  The library knows (amwg_summary_info succeeds only then); a refusal here is the answer, not an error."""
+        return lib().amwg_summary_info(self.h, None, None, None, None, None) == 0
+
+    def set_covariance(self, values):
+        """Arms the covariance of the recorded values `values` (distinct indices; components, then derived quantities) for every later summarize()
+        (amwg_set_covariance); None disarms.  dataset_covariance() returns the matrices after the call."""
+        if values is None:
+            _check(lib().amwg_set_covariance(self.h, None, 0))
+            return
+        v = _value_list(values)
+        _check(lib().amwg_set_covariance(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size))
+
+    def covariance_info(self):
+        """{"n_values": the armed number of values (0: none), "bytes": the device bytes of its co-moments and list} (amwg_covariance_info)"""
+        k, n = C.c_int32(), C.c_size_t()
+        _check(lib().amwg_covariance_info(self.h, C.byref(k), C.byref(n)))
+        return {"n_values": k.value, "bytes": n.value}
+
+    def dataset_covariance(self, values=None):
+        """-> array [datasets][K][K]: per dataset the covariance matrix (n - 1 denominator over chains x kept draws) of the recorded values `values`, in
+        their order, formed on the device (amwg_last_sample_dataset_covariance).  After sample*(): any distinct `values` (None: every recorded value).
+        After summarize(): values=None, the matrix over the values of set_covariance().  correlation() turns it into correlations."""
+        if values is None and self._summarised():
+            K = self.covariance_info()["n_values"]
+            out = np.zeros((self.D, max(K, 1), max(K, 1)))
+            _check(lib().amwg_last_sample_dataset_covariance(self.h, None, max(K, 1), _dp(out)))
+            return out
+        v = _value_list(range(self.PR) if values is None else values)
+        out = np.zeros((self.D, v.size, v.size))
+        _check(lib().amwg_last_sample_dataset_covariance(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, _dp(out)))
         return out
 
     def sample_device(self, n, thin, dev_ptr, nbytes):
@@ -490,6 +534,44 @@ def _edges_per_value(edges, PR):
     if e.ndim != 2 or e.shape[0] != PR or e.shape[1] < 1:
         raise AmwgError("edges must be [bins + 1] or [%d recorded values][bins + 1], got shape %s" % (PR, e.shape))
     return np.ascontiguousarray(e)
+
+
+def _value_list(values):
+    v = np.ascontiguousarray(np.asarray(list(values), dtype=np.int64).reshape(-1))
+    if v.size and (v.min() < -2 ** 31 or v.max() >= 2 ** 31):
+        raise AmwgError("a list of recorded values holds an index beyond 32 bits")
+    return np.ascontiguousarray(v.astype(np.int32))
+
+
+def covariance_check(draws, D, values, window_rows=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_covariance / set_covariance on any array draws [rows][PR][C], D datasets of C / D columns each, over the
+    recorded values `values`; window_rows = 0: the stored path, > 0: folded in windows of that many rows through the fold + co-moment sequence of summarize()
+    -> array [D][K][K] (amwg_covariance_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    v = _value_list(values)
+    out = np.zeros((D, max(v.size, 1), max(v.size, 1)))
+    L = selftest_lib()
+    if L.amwg_covariance_check(_dp(dr), rows, PR, Cn, D, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, window_rows, _dp(out), device) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
+
+
+def correlation(cov):
+    """cov [..., K, K] -> correlations of the same shape: cov_ij / (sd_i sd_j) with sd = sqrt(cov_ii), clamped to [-1, 1]; the diagonal is 1; NaN where a
+    variance is 0 or not finite (and where the covariance is NaN).  Host arithmetic; no device call."""
+    c = np.asarray(cov, dtype=np.float64)
+    if c.ndim < 2 or c.shape[-1] != c.shape[-2]:
+        raise AmwgError("correlation: square matrices [..., K, K], got shape %s" % (c.shape,))
+    var = np.diagonal(c, axis1=-2, axis2=-1)
+    ok = np.isfinite(var) & (var > 0)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        sd = np.sqrt(np.where(ok, var, np.nan))
+        r = c / (sd[..., :, None] * sd[..., None, :])
+        r = np.where(np.isnan(r), np.nan, np.clip(r, -1.0, 1.0))
+    k = np.arange(c.shape[-1])
+    r[..., k, k] = np.where(ok, 1.0, np.nan)
+    return r
 
 
 def histogram_check(draws, D, edges, window_rows=0, counts=None, device=0):

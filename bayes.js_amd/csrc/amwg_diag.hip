@@ -31,15 +31,7 @@ __global__ void chain_halves_kernel(const double *draws, int64_t rows, int PR, i
 }
 
 // ---- summaries per dataset, one workgroup per (recorded value, dataset); dataset d owns the chains [d * cpd, (d + 1) * cpd).  An ordinary sampler is
-// one dataset of all its chains (cpd = C).
-__device__ inline double block_sum(double v, double *red) {      // sum over the workgroup (a power-of-two size), in every thread
-  const int tid = threadIdx.x, nt = blockDim.x;
-  __syncthreads();
-  red[tid] = v;
-  __syncthreads();
-  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
-  return red[0];
-}
+// one dataset of all its chains (cpd = C).  Their sums go through block_sum (amwg_fold.h).
 // mean and sd (n - 1 denominator) over the dataset's chains x kept draws, in a fixed order: thread t sums the values i = t, t + 1024, ... of the dataset's
 // rows laid end to end, a halving tree adds the 1024 partial sums; a second pass for the squares about the mean.  out [D][PR] each
 __global__ void __launch_bounds__(1024) dataset_moments_kernel(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, double *mean, double *sd) {

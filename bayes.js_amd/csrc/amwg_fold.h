@@ -19,6 +19,17 @@ __device__ __forceinline__ void welford_add(double x, int64_t k, double &m, doub
   m2 += dlt * (x - m);
 }
 
+// The sum of v over the workgroup (a power-of-two size), in every thread: a halving tree over red[blockDim.x] (LDS).  The per-dataset reductions of amwg_diag.hip
+// and amwg_covariance.hip share it, so that a sum over a dataset's chains has one order wherever it is formed.
+__device__ inline double block_sum(double v, double *red) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int o = nt / 2; o > 0; o >>= 1) { if (tid < o) red[tid] += red[tid + o]; __syncthreads(); }
+  return red[0];
+}
+
 // The accumulators of a summarising call, device, [kFoldStats][PR][C]: (m, M2) of the first half of a chain's kept draws, of the second half, of the whole chain.
 // half = rows / 2: rows [0, half) are the first half, [half, 2 half) the second; an odd last row enters the whole-chain pair only (chain_halves_kernel ignores it too).
 constexpr int kFoldStats = 6;
@@ -38,11 +49,13 @@ struct FoldSummary {
 };
 // a window for launch_steps' loop: the recorded rows go to rows [0, window_rows) of the draw buffer, and each time they are full (and at the end) they are folded into acc
 struct HistArm;      // (amwg_histogram.h)
+struct CovArm;       // (amwg_covariance.h)
 struct FoldWindow {
   int64_t window_rows = 0, total_rows = 0;
   double *acc = nullptr;
   int64_t windows = 0;      // out: folds enqueued
   const HistArm *hist = nullptr;      // the histogram armed for the call (amwg_set_histogram): after each fold, the window's rows are counted into it too
+  const CovArm *cov = nullptr;        // the covariance armed for the call (amwg_set_covariance): BEFORE each fold, the window's co-moments are added from the means it starts at
 };
 // true when the last sample call of `s` was a summarising one (its draws were folded, not kept): last_rows > 0 without last_draws
 bool amwg_summarised(const amwg_sampler *s);

@@ -829,6 +829,70 @@ static napi_value HistogramInfo(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* setCovariance(handle, Int32Array values | null): amwg_set_covariance -- arms (null: disarms) the covariance of those recorded values for later summarising calls */
+static napi_value SetCovariance(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t nv = 0;
+  const int32_t *values = (const int32_t *)typed_data(env, a[1], napi_int32_array, &nv);
+  if (values && (nv < 1 || nv > (size_t)amwg_num_recorded(s))) {
+    napi_throw_type_error(env, NULL, "amwg_napi.setCovariance: values must be an Int32Array of 1 .. recorded values indices (or null)");
+    return NULL;
+  }
+  int rc = amwg_set_covariance(s, values, values ? (int32_t)nv : 0);
+  return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
+}
+
+/* datasetCovariance(handle, Int32Array values | null, n_values) -> {datasets, n_values, cov}: cov a Float64Array [datasets][n_values][n_values] over the last sample
+ * call (amwg_last_sample_dataset_covariance); null values: the matrices of a summarising call over the armed values, n_values the armed number. */
+static napi_value DatasetCovariance(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t nv = 0;
+  const int32_t *values = (const int32_t *)typed_data(env, a[1], napi_int32_array, &nv);
+  const int64_t k = values ? (int64_t)nv : arg_i64(env, a[2]);
+  if (k < 1 || k > (int64_t)amwg_num_recorded(s)) {
+    napi_throw_type_error(env, NULL, "amwg_napi.datasetCovariance: values must be an Int32Array of 1 .. recorded values indices, or null with the armed number of values");
+    return NULL;
+  }
+  double *c = NULL;
+  napi_value v = new_f64(env, (size_t)amwg_num_datasets(s) * (size_t)k * (size_t)k, &c);
+  if (!v) return NULL;
+  int rc = amwg_last_sample_dataset_covariance(s, values, (int32_t)k, c);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "cov", v);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  napi_create_int32(env, (int32_t)k, &t);
+  napi_set_named_property(env, o, "n_values", t);
+  return o;
+}
+
+/* covarianceInfo(handle) -> {n_values, bytes}: the armed number of values (0: none) and the device bytes of its co-moments and list (amwg_covariance_info) */
+static napi_value CovarianceInfo(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int32_t k = 0;
+  size_t bytes = 0;
+  int rc = amwg_covariance_info(s, &k, &bytes);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_create_int32(env, k, &t);
+  napi_set_named_property(env, o, "n_values", t);
+  napi_create_int64(env, (int64_t)bytes, &t);
+  napi_set_named_property(env, o, "bytes", t);
+  return o;
+}
+
 /* the shards of a multi-device sampler: JS array of handles -> C array (caller frees) */
 static amwg_sampler **unwrap_group(napi_env env, napi_value arr, uint32_t *n) {
   *n = 0;
@@ -1032,7 +1096,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
       {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
-      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
+      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

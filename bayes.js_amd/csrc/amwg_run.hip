@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
+#include "amwg_covariance.h"
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
 #include "amwg_host.h"
@@ -166,6 +167,8 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
     done += m;
     if (win && row > 0 && (row == win->window_rows || done >= n)) {
       if (row > win->window_rows || folded + row > win->total_rows) return amwg_fail(AMWG_EINVAL, "internal: %lld rows in a window of %lld (%lld of %lld folded)", (long long)row, (long long)win->window_rows, (long long)folded, (long long)win->total_rows);
+      if (win->cov)      // (reads acc[4] as the fold of the window before left it: the running means its rows start from)
+        TRYB(amwg_comoment_window(d_draws, folded, row, s->P + s->D, s->C, win->cov->d_values, win->cov->n_values, win->acc, win->cov->d_co, s->stream));
       TRYB(amwg_fold_window(d_draws, folded, row, win->total_rows / 2, s->P + s->D, s->C, win->acc, s->stream));
       if (win->hist)      // (the same rows once more, on the same stream: the counts add up over the windows)
         TRYB(amwg_histogram_launch("amwg_sample_summarize", d_draws, row, s->P + s->D, s->C, s->n_datasets, win->hist->d_edges, win->hist->bins, win->hist->uniform, win->hist->d_counts, s->stream));
@@ -357,6 +360,9 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   HistArm *arm = nullptr;
   TRYB(amwg_histogram_begin(s, &arm));      // (amwg_set_histogram: its counts start afresh too)
   win.hist = arm;
+  CovArm *cov = nullptr;
+  TRYB(amwg_covariance_begin(s, &cov));      // (amwg_set_covariance: its co-moments start afresh too)
+  win.cov = cov;
   TRYB(launch_steps(s, n, thin, s->d_draws, false, &win));
   f.rows = rows; f.window_rows = W; f.windows = win.windows; f.window_bytes = need;
   s->last_rows = rows;      // (rows > 0 without last_draws: the mark of a summary -- amwg_summarised)

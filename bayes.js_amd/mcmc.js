@@ -344,6 +344,7 @@ AmwgSampler.prototype.step = function () { this.burn(1); return this.state; };
 AmwgSampler.prototype.sample = function (n_iterations) {
   const N = native(), thin = this.thinning_interval;
   const kept = Math.ceil(n_iterations / thin);
+  this._summarised = false;      // (the draws of this call are kept: dataset_covariance() reads them)
   this._each((sh) => N.sampleAsync(sh.handle, n_iterations, thin));
   // mcmc.js:1009-1013: by default every key of the state is recorded, parameters first, then derived quantities
   const monitored = this.monitored_params === null ? this.param_names.concat(this.derived) : this.monitored_params;
@@ -404,6 +405,7 @@ AmwgSampler.prototype._drawLayout = function (kept, L) {
  *  then summarise them on the device (65 536 chains x 5 000 draws are 5 GB -- more than a JS ArrayBuffer holds). */
 AmwgSampler.prototype.sample_on_device = function (n_iterations) {
   const N = native();
+  this._summarised = false;
   this._each((sh) => N.sampleAsync(sh.handle, n_iterations, this.thinning_interval));
   this._each((sh) => N.sync(sh.handle));
   return Math.ceil(n_iterations / this.thinning_interval);
@@ -427,6 +429,18 @@ AmwgSampler.prototype.summarize = function (n_iterations, options) {
     N.setHistogram(this._shards[0].handle, null, 0);
     this._hist_bins = 0;
   }
+  // options.covariance: true (every recorded value) or [names] -- the covariance of those values is folded while the draws pass (amwg_set_covariance);
+  // dataset_covariance() / covariance() without an argument answer afterwards.  Like options.histogram it holds for THIS call: a call without it folds none
+  // and disarms what an earlier call armed.  (Python's Sampler.set_covariance, like its set_histogram, arms every later call until it is disarmed.)
+  if (options && options.covariance) {
+    const sel = this._covarianceValues(options.covariance === true ? undefined : options.covariance);
+    N.setCovariance(this._shards[0].handle, sel.values);
+    this._cov_sel = sel;
+  } else if (this._cov_sel) {
+    N.setCovariance(this._shards[0].handle, null);
+    this._cov_sel = null;
+  }
+  this._summarised = Math.ceil(n_iterations / this.thinning_interval) > 0;      // (a call that keeps no row leaves nothing to summarise)
   this._each((sh) => N.sampleSummarizeAsync(sh.handle, n_iterations, this.thinning_interval, w));
   this._each((sh) => N.sync(sh.handle));
   return Math.ceil(n_iterations / this.thinning_interval);
@@ -604,6 +618,67 @@ AmwgSampler.prototype.histogram = function (edges) {
   if (this._shards.length > 1) throw 'AmwgSampler (MI355X): histogram() runs on one device';
   return this.dataset_histogram(edges)[0];
 };
+
+// names of parameters or derived quantities (default: every recorded value; a vector parameter contributes all its elements, labelled name[k] with k the row-major
+// index) -> {values: Int32Array of indices into the recorded values, labels}
+AmwgSampler.prototype._covarianceValues = function (names) {
+  const values = [], labels = [];
+  const all = this._layout.map((L) => L.name).concat(this.derived);
+  const list = names === undefined || names === null ? all : Array.from(names);
+  if (!list.length) throw 'AmwgSampler (MI355X): covariance needs at least one name';
+  for (const name of list) {
+    const L = this._layout.find((q) => q.name === name), q = this.derived.indexOf(name);
+    if (L) for (let k = 0; k < L.len; k++) { values.push(L.base + k); labels.push(L.scalar ? name : name + '[' + k + ']'); }
+    else if (q >= 0) { values.push(this.P + q); labels.push(name); }
+    else throw 'AmwgSampler (MI355X): covariance: ' + name + ' is neither a parameter nor a derived quantity of this sampler';
+  }
+  if (new Set(values).size !== values.length) throw 'AmwgSampler (MI355X): covariance: a name is listed twice';
+  return { values: Int32Array.from(values), labels };
+};
+
+/** Covariance and correlation matrices per dataset (options.datasets; an ordinary sampler is one dataset) over each dataset's chains x kept draws of the last
+ *  sample call, formed on the device: [{labels, cov, cor}, ...] with cov and cor arrays [K][K] in the order of `labels`.  `names`: parameters or derived
+ *  quantities (a vector parameter contributes all its elements, labelled name[k]); default: every recorded value.  After sample() / sample_on_device(): any names.
+ *  After summarize(n, {covariance: true | [names]}): no argument, the matrices folded while the draws passed -- equal, byte for byte, to those of the stored run.
+ *  One device: covariance over several devices is not formed. */
+AmwgSampler.prototype.dataset_covariance = function (names) {
+  const N = native(), out = [];
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): dataset_covariance() runs on one device';
+  const given = names !== undefined && names !== null ? this._covarianceValues(names) : null;
+  const sh = this._shards[0];
+  const summarised = !!this._summarised;      // was the last sample call a summarising one?  (summarize() sets it, sample() / sample_on_device() clear it)
+  // after summarize(): the folded matrix over the armed values (names given afterwards, or nothing armed: the library's refusal); else over any names
+  const sel = given || (summarised && this._cov_sel) || this._covarianceValues();
+  const r = summarised && !given ? N.datasetCovariance(sh.handle, null, this._cov_sel ? sel.values.length : 1) : N.datasetCovariance(sh.handle, sel.values, sel.values.length);
+  const K = r.n_values;
+  for (let d = 0; d < r.datasets; d++) {
+    const cov = Array.from({ length: K }, (_, i) => Array.from(r.cov.subarray((d * K + i) * K, (d * K + i + 1) * K)));
+    out.push({ labels: sel.labels.slice(), cov, cor: correlation(cov) });
+  }
+  return out;
+};
+
+/** Covariance and correlation over all chains x kept draws of the last sample call: {labels, cov, cor} -- dataset_covariance() of an ordinary sampler on one device. */
+AmwgSampler.prototype.covariance = function (names) {
+  this._refusePooled('covariance');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): covariance() runs on one device';
+  return this.dataset_covariance(names)[0];
+};
+
+/** cov [K][K] -> correlations [K][K]: cov_ij / (sd_i sd_j) with sd = sqrt(cov_ii), clamped to [-1, 1]; the diagonal is 1; NaN where a variance is 0 or not finite
+ *  (and where the covariance is NaN).  Host only: no device call. */
+function correlation(cov) {
+  const K = cov.length, sd = new Array(K);
+  for (let i = 0; i < K; i++) {
+    if (cov[i].length !== K) throw 'correlation: a square matrix [K][K]';
+    sd[i] = Number.isFinite(cov[i][i]) && cov[i][i] > 0 ? Math.sqrt(cov[i][i]) : NaN;
+  }
+  return Array.from({ length: K }, (_, i) => Array.from({ length: K }, (_, j) => {
+    if (i === j) return Number.isNaN(sd[i]) ? NaN : 1;
+    const r = cov[i][j] / (sd[i] * sd[j]);
+    return Number.isNaN(r) ? NaN : Math.min(1, Math.max(-1, r));
+  }));
+}
 
 /** For one array of counts [c_0, ..., c_{bins-1}, under, over, nan] under edges [e_0, ..., e_bins]: per probability q the bracket [lo, hi] that contains the value
  *  quantiles([q]) returns over the counted draws (type 7: h = (n - 1) q, an interpolation between the order statistics of ranks floor(h) and min(floor(h) + 1, n - 1)).
@@ -847,5 +922,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, correlation, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

@@ -37,10 +37,13 @@ sampler.burn(1000);
 sampler.sample(200);
 var moments = sampler.dataset_moments();
 var quant = sampler.dataset_quantiles([0.025, 0.975]);      // a 95 % credible interval per segment, selected on the device
+var cov = sampler.dataset_covariance(['b']);                // the coefficient covariance and correlation per segment, formed on the device
 [0, 1, 32, 63].forEach(function (d) {
   var q = quant[d].b[1];
   console.log('segment %d (true effect of x1 %s): mean(b[1]) = %s  sd = %s  95%% interval [%s, %s]', d, (0.2 + 0.02 * d).toFixed(2),
     moments[d].b.mean[1].toFixed(3), moments[d].b.sd[1].toFixed(3), q[0].toFixed(3), q[1].toFixed(3));
+  console.log('  correlation of %s:', cov[d].labels.join(', '));
+  cov[d].cor.forEach(function (row) { console.log('   ', row.map(function (v) { return v.toFixed(3); }).join('  ')); });
 });
 var launch = sampler.info().launch[0];
 console.log('kernel:', launch.kernel, ' lanes per chain:', launch.lanes_per_chain, ' summation order:', launch.summation_order, ' datasets per launch:', launch.datasets);

@@ -318,7 +318,9 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * accumulators: the halves are accumulated by the recurrence of the stored path in the same row order, so split-R-hat and ESS equal those of the stored run BIT FOR BIT
  * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
  * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_fetch_draws*,
- * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize.  A later amwg_sample* call replaces
+ * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
+ * amwg_last_sample_dataset_histogram and amwg_last_sample_dataset_covariance unless they were armed before the call (amwg_set_histogram, amwg_set_covariance) and
+ * are asked for what was folded while the draws passed (edges = NULL, values = NULL).  A later amwg_sample* call replaces
  * the summary, amwg_burn leaves it alone, and every summarising call starts its accumulators afresh.  n = 0 succeeds and leaves nothing to summarise.
  * amwg_launch_info's n_launches (step-kernel launches) and kernel_ms (which includes the folds) cover the whole call.
  * amwg_sample_summarize = the _async form + amwg_sync.  Refused before a device is opened: null sampler, n < 0, thin < 1, window_rows < 0.
@@ -346,6 +348,33 @@ int amwg_summary_info(const amwg_sampler *s, int64_t *rows, int64_t *window_rows
 int amwg_last_sample_dataset_histogram(amwg_sampler *s, const double *edges, int32_t bins, uint64_t *counts);
 int amwg_set_histogram(amwg_sampler *s, const double *edges, int32_t bins);
 int amwg_histogram_info(const amwg_sampler *s, int32_t *bins, size_t *bytes);
+
+/* POSTERIOR COVARIANCE over a caller-chosen subset of the recorded values, per dataset, on the device.  values[0 .. n_values) are DISTINCT indices into the recorded
+ * values (components, then derived quantities: PR = amwg_num_recorded); cov[dataset][n_values][n_values] is the full symmetric matrix in the order of `values`, with
+ * the n - 1 denominator over the dataset's n = kept draws x chains; an ordinary sampler is one dataset.  A pair is computed once and written to both places.
+ * THE ARITHMETIC is fixed (compiled with -ffp-contract=off, every operation rounds once).  Per chain c, in row order, for the k-th kept draw (1-based, over all kept
+ * draws): dx_i = x_i - m_i; m_i += dx_i / k -- the mean line of the fold's Welford update, so m_i is bit for bit the whole-chain mean the fold keeps --; then for every
+ * pair C_ij += dx_i * (x_j - m_j) with m_j already advanced to row k.  Of a pair, i is the value with the SMALLER index among the recorded values, wherever the two
+ * stand in `values`: permuting `values` permutes rows and columns, every byte.  Per (dataset, pair), over the dataset's cpd chains of `rows` kept draws each, in the
+ * order of the moments of a summarising call (256 threads, thread t takes chains t, t + 256, ...; a halving tree): gm_i = sum m_ic / cpd; within = sum C_ijc;
+ * between = sum (m_ic - gm_i)(m_jc - gm_j); cov_ij = (within + rows between) / (n - 1).  The diagonal is that call's own SS / (n - 1) from the whole-chain M2: after
+ * a summarising call sqrt(cov_ii) equals the sd of amwg_last_sample_dataset_moments as bytes.  The stored path runs the same kernels over the stored array from
+ * zeroed per-chain scratch, so the matrix of a summarising call EQUALS the stored run's byte for byte, whatever the window.  Non-finite draws give what IEEE gives: a
+ * NaN or infinity among a value's draws makes that value's row and column NaN in that dataset, and every other entry keeps its bytes.
+ *   amwg_last_sample_dataset_covariance -- after amwg_sample*: the matrices of the kept draws over any valid `values`.  After amwg_sample_summarize*: pass values = NULL
+ *     and the armed n_values, and receive the folded matrices; values given afterwards, another n_values, or a call for which nothing was armed is AMWG_EINVAL with a
+ *     message that names amwg_set_covariance.
+ *   amwg_set_covariance -- arms the covariance of `values` for every later amwg_sample_summarize[_async] of this sampler (the list is copied; NULL, 0 disarms): the
+ *     co-moments are zeroed when a summarising call starts, and before each fold of a window the co-moment kernel adds the same window on the same stream, starting
+ *     from the running means the fold has reached.  Moments, R-hat, ESS, the chains' state, n_launches and amwg_summary_info are those of the unarmed call.
+ *   amwg_covariance_info -- the armed n_values (0: none) and the device bytes it holds: n_values (n_values - 1) / 2 x chains doubles of co-moments plus the list of
+ *     values (either pointer may be NULL).
+ * There is no cap on n_values other than PR.  Refused with AMWG_EINVAL and the call's name, before any device call: null pointers, n_values < 1 or > PR, an index
+ * outside [0, PR), a repeated index, no sample call yet, kept draws x chains per dataset < 2, a byte count beyond size_t.  One device only: the amwg_group_* and
+ * amwg_comm_* calls have no covariance. */
+int amwg_last_sample_dataset_covariance(amwg_sampler *s, const int32_t *values, int32_t n_values, double *cov);
+int amwg_set_covariance(amwg_sampler *s, const int32_t *values, int32_t n_values);
+int amwg_covariance_info(const amwg_sampler *s, int32_t *n_values, size_t *bytes);
 
 /* Replaces sampler.start_adaptation() / .stop_adaptation() (mcmc.js:1060-1073). */
 int amwg_set_adapting(amwg_sampler *s, int32_t flag);

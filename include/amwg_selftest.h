@@ -60,6 +60,14 @@ int amwg_summaries_check(int32_t device, const double *draws, int64_t rows, int3
 int amwg_histogram_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *edges, int32_t bins, int64_t window_rows,
                          uint64_t *counts, int32_t device);
 
+/* The covariance kernels of amwg_last_sample_dataset_covariance / amwg_set_covariance on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each,
+ * over values[n_values]: the array is uploaded and the product's launchers run over it from zeroed per-chain scratch -- window_rows = 0: the stored path, the whole
+ * array as one window; window_rows > 0: window after window through the co-moment kernel and the fold, as a summarising call enqueues them.  cov[D][n_values][n_values]
+ * (host) in the order of `values`.  Refused before a device is opened, with the product's words: null pointers, a bad shape (non-positive sizes, C % D != 0,
+ * window_rows < 0), n_values outside 1 .. PR, an index outside [0, PR), a repeated index, rows x C / D < 2, a byte count beyond size_t. */
+int amwg_covariance_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const int32_t *values, int32_t n_values, int64_t window_rows,
+                          double *cov, int32_t device);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);
