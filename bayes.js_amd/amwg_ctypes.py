@@ -7,6 +7,7 @@ if the library is missing.
 """
 import bisect
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -47,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -88,6 +89,9 @@ def lib():
         L.amwg_last_sample_dataset_covariance.argtypes = [vp, pi32, i32, pd]
         L.amwg_set_covariance.argtypes = [vp, pi32, i32]
         L.amwg_covariance_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
+        L.amwg_last_sample_dataset_autocovariance.argtypes = [vp, pi32, i32, i32, pd, pd, pd]
+        L.amwg_set_autocovariance.argtypes = [vp, pi32, i32, i32]
+        L.amwg_autocovariance_info.argtypes = [vp, pi32, pi32, C.POINTER(C.c_size_t)]
         L.amwg_set_adapting.argtypes = [vp, i32]
         L.amwg_get_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_info.argtypes = [vp, pd, pi32, pi32, pi32, pi64, pi64]
@@ -174,6 +178,7 @@ def selftest_lib():
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
         L.amwg_covariance_check.argtypes = [pd, i64, i32, i64, i32, C.POINTER(i32), i32, i64, pd, i32]
+        L.amwg_autocovariance_check.argtypes = [pd, i64, i32, i64, i32, C.POINTER(i32), i32, i32, i64, pd, pd, pd, i32]
         _selftest = L
     return _selftest
 
@@ -321,6 +326,7 @@ class Sampler:
         kept = -(-n // thin)
         out = np.empty((kept, self.PR, self.C), dtype=np.float64)
         _check(lib().amwg_sample(self.h, n, thin, _dp(out), out.nbytes))
+        self._kept = kept
         return out
 
     def burn_async(self, n):
@@ -328,7 +334,7 @@ class Sampler:
 
     def sample_async(self, n, thin=1):
         _check(lib().amwg_sample_async(self.h, n, thin))
-        self._pending = -(-n // thin)
+        self._pending = self._kept = -(-n // thin)
 
     def fetch_draws(self):
         out = np.empty((self._pending, self.PR, self.C), dtype=np.float64)
@@ -357,7 +363,7 @@ class Sampler:
         elif covariance is not None:
             self.set_covariance(range(self.PR) if covariance is True else covariance)
         _check(lib().amwg_sample_summarize(self.h, n, thin, window_rows))
-        self._pending = -(-n // thin)
+        self._pending = self._kept = -(-n // thin)
         return self._pending
 
     def summary_info(self):
@@ -428,6 +434,39 @@ class Sampler:
         out = np.zeros((self.D, v.size, v.size))
         _check(lib().amwg_last_sample_dataset_covariance(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, _dp(out)))
         return out
+
+    def set_autocovariance(self, values, max_lag=0):
+        """Arms the autocovariance at lags 0 .. max_lag of the recorded values `values` (distinct indices) for every later summarize() (amwg_set_autocovariance);
+        None disarms.  A summarize() that would keep <= max_lag draws is then refused before it runs.  dataset_autocovariance() returns the result after the call."""
+        if values is None:
+            _check(lib().amwg_set_autocovariance(self.h, None, 0, 0))
+            return
+        v = _value_list(values)
+        _check(lib().amwg_set_autocovariance(self.h, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, max_lag))
+
+    def autocovariance_info(self):
+        """{"n_values": the armed number of values (0: none), "max_lag", "bytes": the device bytes of its lag sums, rows and list} (amwg_autocovariance_info)"""
+        k, lag, n = C.c_int32(), C.c_int32(), C.c_size_t()
+        _check(lib().amwg_autocovariance_info(self.h, C.byref(k), C.byref(lag), C.byref(n)))
+        return {"n_values": k.value, "max_lag": lag.value, "bytes": n.value}
+
+    def dataset_autocovariance(self, values=None, max_lag=None):
+        """-> (acov [datasets][K][max_lag + 1], mean [datasets][K], between [datasets][K]): per dataset and recorded value of `values`, in their order, the
+        autocovariance at lags 0 .. max_lag averaged over the dataset's chains (1 / n denominator per chain), the mean and the variance of the chain means
+        (n - 1 denominator; 0 for one chain), formed on the device (amwg_last_sample_dataset_autocovariance).  After sample*(): any distinct `values` (None: every
+        recorded value) and max_lag (None: min(100, kept draws - 1)).  After summarize(): both None, what set_autocovariance() armed.
+        autocorrelation_ess() turns one row of it into rho, tau and an effective sample size."""
+        if values is None and max_lag is None and self._summarised():
+            info = self.autocovariance_info()
+            K, lag = max(info["n_values"], 1), max(info["max_lag"], 1)
+            ptr = None
+        else:
+            v = _value_list(range(self.PR) if values is None else values)
+            K, lag = v.size, (min(100, getattr(self, "_kept", 0) - 1) if max_lag is None else int(max_lag))
+            ptr = v.ctypes.data_as(C.POINTER(C.c_int32))
+        acov, mean, between = np.zeros((self.D, K, max(lag, 0) + 1)), np.zeros((self.D, K)), np.zeros((self.D, K))
+        _check(lib().amwg_last_sample_dataset_autocovariance(self.h, ptr, K, lag, _dp(acov), _dp(mean), _dp(between)))
+        return acov, mean, between
 
     def sample_device(self, n, thin, dev_ptr, nbytes):
         _check(lib().amwg_sample_device(self.h, n, thin, C.c_void_p(dev_ptr), nbytes))
@@ -555,6 +594,52 @@ def covariance_check(draws, D, values, window_rows=0, device=0):
     if L.amwg_covariance_check(_dp(dr), rows, PR, Cn, D, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, window_rows, _dp(out), device) != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return out
+
+
+def autocovariance_check(draws, D, values, max_lag, window_rows=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_autocovariance / set_autocovariance on any array draws [rows][PR][C], D datasets of C / D columns each,
+    over the recorded values `values` at lags 0 .. max_lag; window_rows = 0: the stored path, > 0: in windows of that many rows through the lag-sum and carry
+    kernels as summarize() enqueues them -> (acov [D][K][max_lag + 1], mean [D][K], between [D][K]) (amwg_autocovariance_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    v = _value_list(values)
+    K = max(v.size, 1)
+    acov, mean, between = np.zeros((D, K, max(int(max_lag), 0) + 1)), np.zeros((D, K)), np.zeros((D, K))
+    L = selftest_lib()
+    if L.amwg_autocovariance_check(_dp(dr), rows, PR, Cn, D, v.ctypes.data_as(C.POINTER(C.c_int32)), v.size, max_lag, window_rows, _dp(acov), _dp(mean), _dp(between), device) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return acov, mean, between
+
+
+def autocorrelation_ess(acov, between, rows, chains):
+    """One (dataset, value) of dataset_autocovariance() -> {"rho", "tau", "ess", "truncated", "lags_used"}: the autocorrelation, the integrated autocorrelation
+    time and the effective sample size of `chains` chains of `rows` kept draws each, by Geyer's initial monotone sequence (BDA3 section 11.5; Stan's ess without rank
+    normalisation).  Host arithmetic; no device call.  acov [L + 1].
+        var_plus = acov_0 + (chains > 1 ? between : 0);  rho_l = 1 - (n / (n - 1)) (acov_0 - acov_l) / var_plus, rho_0 = 1 exactly;
+        P_k = rho_2k + rho_(2k+1), k = 0 .. floor((L + 1) / 2) - 1; the sum stops before the first P_k < 0 (truncated = True) and each kept P_k is replaced by
+        min(P_k, P_(k-1));  tau = -1 + 2 sum P_k;  ess = chains rows / tau;  lags_used = twice the number of pairs kept.
+    truncated = False: no negative pair was reached within max_lag -- the sum is still growing, `ess` is an UPPER bound, and the caller should ask for more lags.
+    var_plus = 0 or not finite: rho (except rho_0), tau and ess are NaN."""
+    g = np.asarray(acov, dtype=np.float64).reshape(-1)
+    n, M = float(rows), float(chains)
+    rho = np.full(g.size, np.nan)
+    rho[0] = 1.0
+    var_plus = g[0] + (float(between) if chains > 1 else 0.0)
+    if not (math.isfinite(var_plus) and var_plus != 0.0):
+        return {"rho": rho, "tau": math.nan, "ess": math.nan, "truncated": False, "lags_used": 0}
+    for l in range(1, g.size):
+        rho[l] = 1.0 - (n / (n - 1.0)) * (g[0] - g[l]) / var_plus
+    total, prev, used, truncated = 0.0, math.inf, 0, False
+    for k in range(g.size // 2):
+        p = rho[2 * k] + rho[2 * k + 1]
+        if not p >= 0.0:      # (a NaN stops the sum too)
+            truncated = True
+            break
+        prev = min(p, prev)
+        total += prev
+        used += 1
+    tau = -1.0 + 2.0 * total
+    return {"rho": rho, "tau": tau, "ess": float(np.float64(M * n) / np.float64(tau)) if tau != 0.0 else math.inf, "truncated": truncated, "lags_used": 2 * used}
 
 
 def correlation(cov):

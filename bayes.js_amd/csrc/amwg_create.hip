@@ -8,6 +8,7 @@
 #include <limits>
 #include <type_traits>
 
+#include "amwg_autocov.h"
 #include "amwg_covariance.h"
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
@@ -722,6 +723,7 @@ int amwg_destroy(amwg_sampler *s) {
   amwg_summary_forget(s);      // (amwg_fold.h: the accumulators of a summarising call were among dev_allocs)
   amwg_histogram_forget(s);    // (amwg_histogram.h: the edges and counts of an armed histogram)
   amwg_covariance_forget(s);   // (amwg_covariance.h: the co-moments and values of an armed covariance)
+  amwg_autocov_forget(s);      // (amwg_autocov.h: the lag sums, rows and values of an armed autocovariance)
   if (s->d_draws) (void)hipFree(s->d_draws);
   if (s->user_module) (void)hipModuleUnload(s->user_module);
   for (hipEvent_t e : s->chunk_ev) (void)hipEventDestroy(e);

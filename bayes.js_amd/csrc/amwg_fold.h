@@ -50,12 +50,14 @@ struct FoldSummary {
 // a window for launch_steps' loop: the recorded rows go to rows [0, window_rows) of the draw buffer, and each time they are full (and at the end) they are folded into acc
 struct HistArm;      // (amwg_histogram.h)
 struct CovArm;       // (amwg_covariance.h)
+struct AutocovArm;   // (amwg_autocov.h)
 struct FoldWindow {
   int64_t window_rows = 0, total_rows = 0;
   double *acc = nullptr;
   int64_t windows = 0;      // out: folds enqueued
   const HistArm *hist = nullptr;      // the histogram armed for the call (amwg_set_histogram): after each fold, the window's rows are counted into it too
   const CovArm *cov = nullptr;        // the covariance armed for the call (amwg_set_covariance): BEFORE each fold, the window's co-moments are added from the means it starts at
+  const AutocovArm *acf = nullptr;    // the autocovariance armed for the call (amwg_set_autocovariance): after the fold and the histogram, the window's lag sums, then its carry
 };
 // true when the last sample call of `s` was a summarising one (its draws were folded, not kept): last_rows > 0 without last_draws
 bool amwg_summarised(const amwg_sampler *s);

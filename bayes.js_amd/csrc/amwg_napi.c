@@ -893,6 +893,80 @@ static napi_value CovarianceInfo(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* setAutocovariance(handle, Int32Array values | null, max_lag): amwg_set_autocovariance -- arms (null: disarms) the autocovariance of those recorded values at lags
+ * 0 .. max_lag for later summarising calls */
+static napi_value SetAutocovariance(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  if (!get_args(env, info, 3, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t nv = 0;
+  const int32_t *values = (const int32_t *)typed_data(env, a[1], napi_int32_array, &nv);
+  const int64_t lag = values ? arg_i64(env, a[2]) : 0;
+  if (values && (nv < 1 || nv > (size_t)amwg_num_recorded(s) || lag < INT32_MIN || lag > INT32_MAX)) {
+    napi_throw_type_error(env, NULL, "amwg_napi.setAutocovariance: values must be an Int32Array of 1 .. recorded values indices (or null), max_lag a 32-bit integer");
+    return NULL;
+  }
+  int rc = amwg_set_autocovariance(s, values, values ? (int32_t)nv : 0, (int32_t)lag);
+  return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
+}
+
+/* datasetAutocovariance(handle, Int32Array values | null, n_values, max_lag) -> {datasets, n_values, max_lag, acov, mean, between}: Float64Arrays
+ * acov [datasets][n_values][max_lag + 1], mean and between [datasets][n_values] over the last sample call (amwg_last_sample_dataset_autocovariance); null values:
+ * what a summarising call folded for the armed values, n_values and max_lag the armed ones. */
+static napi_value DatasetAutocovariance(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t nv = 0;
+  const int32_t *values = (const int32_t *)typed_data(env, a[1], napi_int32_array, &nv);
+  const int64_t k = values ? (int64_t)nv : arg_i64(env, a[2]), lag = arg_i64(env, a[3]);
+  if (k < 1 || k > (int64_t)amwg_num_recorded(s) || lag < 1 || lag > 1024) {
+    napi_throw_type_error(env, NULL, "amwg_napi.datasetAutocovariance: values must be an Int32Array of 1 .. recorded values indices, or null with the armed number of values; max_lag 1 .. 1024");
+    return NULL;
+  }
+  const size_t dk = (size_t)amwg_num_datasets(s) * (size_t)k;
+  double *c = NULL, *m = NULL, *b = NULL;
+  napi_value vc = new_f64(env, dk * (size_t)(lag + 1), &c), vm = new_f64(env, dk, &m), vb = new_f64(env, dk, &b);
+  if (!vc || !vm || !vb) return NULL;
+  int rc = amwg_last_sample_dataset_autocovariance(s, values, (int32_t)k, (int32_t)lag, c, m, b);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "acov", vc);
+  napi_set_named_property(env, o, "mean", vm);
+  napi_set_named_property(env, o, "between", vb);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  napi_create_int32(env, (int32_t)k, &t);
+  napi_set_named_property(env, o, "n_values", t);
+  napi_create_int32(env, (int32_t)lag, &t);
+  napi_set_named_property(env, o, "max_lag", t);
+  return o;
+}
+
+/* autocovarianceInfo(handle) -> {n_values, max_lag, bytes}: what is armed (0: nothing) and the device bytes it holds (amwg_autocovariance_info) */
+static napi_value AutocovarianceInfo(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int32_t k = 0, lag = 0;
+  size_t bytes = 0;
+  int rc = amwg_autocovariance_info(s, &k, &lag, &bytes);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_create_int32(env, k, &t);
+  napi_set_named_property(env, o, "n_values", t);
+  napi_create_int32(env, lag, &t);
+  napi_set_named_property(env, o, "max_lag", t);
+  napi_create_int64(env, (int64_t)bytes, &t);
+  napi_set_named_property(env, o, "bytes", t);
+  return o;
+}
+
 /* the shards of a multi-device sampler: JS array of handles -> C array (caller frees) */
 static amwg_sampler **unwrap_group(napi_env env, napi_value arr, uint32_t *n) {
   *n = 0;
@@ -1096,7 +1170,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
       {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
-      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
+      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

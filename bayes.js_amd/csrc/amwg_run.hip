@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "../../include/amwg_selftest.h"      // (amwg_audit_fetch: the audit build)
+#include "amwg_autocov.h"
 #include "amwg_covariance.h"
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
@@ -172,6 +173,8 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
       TRYB(amwg_fold_window(d_draws, folded, row, win->total_rows / 2, s->P + s->D, s->C, win->acc, s->stream));
       if (win->hist)      // (the same rows once more, on the same stream: the counts add up over the windows)
         TRYB(amwg_histogram_launch("amwg_sample_summarize", d_draws, row, s->P + s->D, s->C, s->n_datasets, win->hist->d_edges, win->hist->bins, win->hist->uniform, win->hist->d_counts, s->stream));
+      if (win->acf)       // (the lag sums read the ring as the windows before left it; the carry kernel behind them, on the same stream, moves it on)
+        TRYB(amwg_autocov_window(d_draws, folded, row, s->P + s->D, s->C, win->acf->d_values, win->acf->n_values, win->acf->max_lag, win->acf->d_state, s->stream));
       win->windows++;
       folded += row;
       row = 0;
@@ -341,6 +344,8 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   if (W < 1) W = 1;
   const size_t need = (size_t)W * row_bytes, acc_bytes = (size_t)kFoldStats * row_bytes;
   HIP_TRY(hipSetDevice(s->device));
+  AutocovArm *acf = nullptr;
+  TRYB(amwg_autocov_begin(s, rows, &acf));      // (amwg_set_autocovariance: refuses a call of too few kept rows before anything is touched; its state starts afresh too)
   if (need > s->d_draws_cap) {
     if (s->d_draws) { (void)hipFree(s->d_draws); s->d_draws = nullptr; s->d_draws_cap = 0; }
     HIP_TRY(hipMalloc(reinterpret_cast<void **>(&s->d_draws), need));
@@ -363,6 +368,7 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   CovArm *cov = nullptr;
   TRYB(amwg_covariance_begin(s, &cov));      // (amwg_set_covariance: its co-moments start afresh too)
   win.cov = cov;
+  win.acf = acf;
   TRYB(launch_steps(s, n, thin, s->d_draws, false, &win));
   f.rows = rows; f.window_rows = W; f.windows = win.windows; f.window_bytes = need;
   s->last_rows = rows;      // (rows > 0 without last_draws: the mark of a summary -- amwg_summarised)

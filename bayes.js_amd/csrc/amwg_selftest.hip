@@ -2,6 +2,7 @@
 // libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
 #include "../../include/amwg_selftest.h"
 #include "amwg_dataset_quantiles.h"
+#include "amwg_autocov.h"
 #include "amwg_covariance.h"
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
@@ -183,6 +184,21 @@ int amwg_covariance_check(const double *draws, int64_t rows, int32_t PR, int64_t
   HIP_TRY(dd.alloc(bytes));
   HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
   return amwg_covariance_of_array(call, dd.as<double>(), rows, PR, C, D, values, n_values, window_rows, cov, nullptr);
+}
+
+int amwg_autocovariance_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const int32_t *values, int32_t n_values, int32_t max_lag,
+                              int64_t window_rows, double *acov, double *mean, double *between, int32_t device) {
+  const char *call = "amwg_autocovariance_check";
+  if (!draws || !values || !acov || !mean || !between) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (window_rows < 0) return amwg_fail(AMWG_EINVAL, "%s: bad shape (window_rows %lld)", call, (long long)window_rows);
+  TRYB(amwg_autocov_shape(call, rows, PR, C, D, n_values, max_lag));
+  TRYB(amwg_covariance_values_check(call, values, n_values, PR));
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  return amwg_autocov_of_array(call, dd.as<double>(), rows, PR, C, D, values, n_values, max_lag, window_rows, acov, mean, between, nullptr);
 }
 
 int amwg_summaries_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,

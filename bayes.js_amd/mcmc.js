@@ -345,6 +345,7 @@ AmwgSampler.prototype.sample = function (n_iterations) {
   const N = native(), thin = this.thinning_interval;
   const kept = Math.ceil(n_iterations / thin);
   this._summarised = false;      // (the draws of this call are kept: dataset_covariance() reads them)
+  this._kept = kept;
   this._each((sh) => N.sampleAsync(sh.handle, n_iterations, thin));
   // mcmc.js:1009-1013: by default every key of the state is recorded, parameters first, then derived quantities
   const monitored = this.monitored_params === null ? this.param_names.concat(this.derived) : this.monitored_params;
@@ -406,6 +407,7 @@ AmwgSampler.prototype._drawLayout = function (kept, L) {
 AmwgSampler.prototype.sample_on_device = function (n_iterations) {
   const N = native();
   this._summarised = false;
+  this._kept = Math.ceil(n_iterations / this.thinning_interval);
   this._each((sh) => N.sampleAsync(sh.handle, n_iterations, this.thinning_interval));
   this._each((sh) => N.sync(sh.handle));
   return Math.ceil(n_iterations / this.thinning_interval);
@@ -440,7 +442,21 @@ AmwgSampler.prototype.summarize = function (n_iterations, options) {
     N.setCovariance(this._shards[0].handle, null);
     this._cov_sel = null;
   }
+  // options.autocorrelation: {max_lag, names?} -- the lagged sums of those values (default: every recorded value) at lags 0 .. max_lag (default: min(100,
+  // kept - 1)) are folded while the draws pass (amwg_set_autocovariance); dataset_autocorrelation() / autocorrelation() without arguments answer afterwards.
+  // Like options.covariance it holds for THIS call.
+  if (options && options.autocorrelation) {
+    const o = options.autocorrelation === true ? {} : options.autocorrelation;
+    const sel = this._covarianceValues(o.names);
+    const lag = o.max_lag !== undefined ? o.max_lag : Math.min(100, Math.ceil(n_iterations / this.thinning_interval) - 1);
+    N.setAutocovariance(this._shards[0].handle, sel.values, lag);
+    this._acf_sel = { values: sel.values, labels: sel.labels, max_lag: lag };
+  } else if (this._acf_sel) {
+    N.setAutocovariance(this._shards[0].handle, null, 0);
+    this._acf_sel = null;
+  }
   this._summarised = Math.ceil(n_iterations / this.thinning_interval) > 0;      // (a call that keeps no row leaves nothing to summarise)
+  this._kept = Math.ceil(n_iterations / this.thinning_interval);
   this._each((sh) => N.sampleSummarizeAsync(sh.handle, n_iterations, this.thinning_interval, w));
   this._each((sh) => N.sync(sh.handle));
   return Math.ceil(n_iterations / this.thinning_interval);
@@ -664,6 +680,71 @@ AmwgSampler.prototype.covariance = function (names) {
   if (this._shards.length > 1) throw 'AmwgSampler (MI355X): covariance() runs on one device';
   return this.dataset_covariance(names)[0];
 };
+
+/** Autocorrelation along the chains per dataset (options.datasets; an ordinary sampler is one dataset) of the last sample call:
+ *  [{labels, acov, rho, tau, ess, truncated}, ...] with, per label, acov and rho arrays [max_lag + 1] (the autocovariance averaged over the dataset's chains, formed
+ *  on the device, and the autocorrelation), tau the integrated autocorrelation time, ess = chains x kept draws / tau and truncated (autocorrelation_ess()).  This
+ *  ESS looks ALONG the chains, so it answers for one chain too.  `names`: as for dataset_covariance(); options.max_lag: default min(100, kept draws - 1).  After
+ *  summarize(n, {autocorrelation: {max_lag, names}}): no arguments, what was folded while the draws passed -- byte for byte the stored run's.  truncated = false
+ *  means no negative pair of autocorrelations was reached within max_lag: ess is then an UPPER bound -- ask for more lags.  One device. */
+AmwgSampler.prototype.dataset_autocorrelation = function (names, options) {
+  const N = native(), out = [];
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): dataset_autocorrelation() runs on one device';
+  const named = names !== undefined && names !== null, lagged = options && options.max_lag !== undefined;
+  const sh = this._shards[0], kept = this._kept || 0;
+  let sel, r;
+  if (this._summarised && !named && !lagged) {      // what was folded (nothing armed: the library's refusal)
+    sel = this._acf_sel || { values: Int32Array.from([0]), labels: [], max_lag: 1 };
+    r = N.datasetAutocovariance(sh.handle, null, sel.values.length, sel.max_lag);
+  } else {
+    sel = this._covarianceValues(named ? names : undefined);
+    r = N.datasetAutocovariance(sh.handle, sel.values, sel.values.length, lagged ? options.max_lag : Math.max(1, Math.min(100, kept - 1)));
+  }
+  const K = r.n_values, L1 = r.max_lag + 1, cpd = this.chains / r.datasets;
+  for (let d = 0; d < r.datasets; d++) {
+    const o = { labels: sel.labels.slice(), acov: [], rho: [], tau: [], ess: [], truncated: [] };
+    for (let k = 0; k < K; k++) {
+      const acov = Array.from(r.acov.subarray((d * K + k) * L1, (d * K + k + 1) * L1));
+      const e = autocorrelation_ess(acov, r.between[d * K + k], kept, cpd);
+      o.acov.push(acov); o.rho.push(e.rho); o.tau.push(e.tau); o.ess.push(e.ess); o.truncated.push(e.truncated);
+    }
+    out.push(o);
+  }
+  return out;
+};
+
+/** Autocorrelation, tau and ESS over all chains of the last sample call: {labels, acov, rho, tau, ess, truncated} -- dataset_autocorrelation() of an ordinary
+ *  sampler on one device. */
+AmwgSampler.prototype.autocorrelation = function (names, options) {
+  this._refusePooled('autocorrelation');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): autocorrelation() runs on one device';
+  return this.dataset_autocorrelation(names, options)[0];
+};
+
+/** acov [L + 1] (one value of one dataset: the autocovariance at lags 0 .. L averaged over the chains), the between-chain variance of the chain means, the kept
+ *  draws per chain n and the chains M -> {rho, tau, ess, truncated, lags_used} by Geyer's initial monotone sequence (BDA3 section 11.5; Stan's ess without rank
+ *  normalisation): var_plus = acov_0 + (M > 1 ? between : 0); rho_l = 1 - (n / (n - 1)) (acov_0 - acov_l) / var_plus, rho_0 = 1; P_k = rho_2k + rho_(2k+1); the sum
+ *  stops before the first P_k < 0 (truncated = true), each kept P_k is replaced by min(P_k, P_(k-1)); tau = -1 + 2 sum P_k; ess = M n / tau.  truncated = false: no
+ *  negative pair within the lags given -- ess is an UPPER bound and the caller should ask for more lags.  var_plus 0 or not finite: rho (but rho_0), tau, ess NaN.
+ *  Host only: no device call.  The same arithmetic as amwg_ctypes.autocorrelation_ess. */
+function autocorrelation_ess(acov, between, rows, chains) {
+  const g = Array.from(acov), n = rows, M = chains;
+  const rho = g.map(() => NaN);
+  rho[0] = 1;
+  const var_plus = g[0] + (M > 1 ? between : 0);
+  if (!Number.isFinite(var_plus) || var_plus === 0) return { rho, tau: NaN, ess: NaN, truncated: false, lags_used: 0 };
+  for (let l = 1; l < g.length; l++) rho[l] = 1 - (n / (n - 1)) * (g[0] - g[l]) / var_plus;
+  let total = 0, prev = Infinity, used = 0, truncated = false;
+  for (let k = 0; k < Math.floor(g.length / 2); k++) {
+    const p = rho[2 * k] + rho[2 * k + 1];
+    if (!(p >= 0)) { truncated = true; break; }      // (a NaN stops the sum too)
+    prev = Math.min(p, prev);
+    total += prev;
+    used++;
+  }
+  const tau = -1 + 2 * total;
+  return { rho, tau, ess: M * n / tau, truncated, lags_used: 2 * used };
+}
 
 /** cov [K][K] -> correlations [K][K]: cov_ij / (sd_i sd_j) with sd = sqrt(cov_ii), clamped to [-1, 1]; the diagonal is 1; NaN where a variance is 0 or not finite
  *  (and where the covariance is NaN).  Host only: no device call. */
@@ -922,5 +1003,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, correlation, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

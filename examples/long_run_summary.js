@@ -35,13 +35,16 @@ for (const name of ['mu', 'sigma']) {
 }
 // the long run counts its draws under those edges while they pass: the 95 % interval of the stored run's quantiles() lies inside the brackets printed below
 // ... and folds the co-moment of mu and sigma beside the fold of each window: a correlation for a run that kept no draw
-var kept = sampler.summarize(200000, { histogram: edges, covariance: true });
-var m = sampler.moments(), c = sampler.convergence(), h = sampler.histogram(), cv = sampler.covariance();
+// ... and the lagged sums of each chain at lags 0 .. 100: the integrated autocorrelation time tau and an ESS that looks along the chains, beside the between-chain one
+var kept = sampler.summarize(200000, { histogram: edges, covariance: true, autocorrelation: { max_lag: 100 } });
+var m = sampler.moments(), c = sampler.convergence(), h = sampler.histogram(), cv = sampler.covariance(), ac = sampler.autocorrelation();
 console.log('kept draws per chain:', kept);
 for (const name of ['mu', 'sigma']) {
   const b = mcmc.interval_brackets(h[name][0], edges[name], [0.025, 0.975]);
-  console.log('%s: mean %s  sd %s  R-hat %s  ESS %s  2.5 %% in [%s, %s]  97.5 %% in [%s, %s]', name, m[name].mean[0].toFixed(3), m[name].sd[0].toFixed(3), c[name].rhat[0].toFixed(5),
-              c[name].ess[0].toFixed(0), b[0][0].toFixed(3), b[0][1].toFixed(3), b[1][0].toFixed(3), b[1][1].toFixed(3));
+  const k = ac.labels.indexOf(name);
+  console.log('%s: mean %s  sd %s  R-hat %s  ESS %s  tau %s  autocorrelation ESS %s%s  2.5 %% in [%s, %s]  97.5 %% in [%s, %s]', name, m[name].mean[0].toFixed(3), m[name].sd[0].toFixed(3),
+              c[name].rhat[0].toFixed(5), c[name].ess[0].toFixed(0), ac.tau[k].toFixed(2), ac.ess[k].toFixed(0), ac.truncated[k] ? '' : ' (an upper bound: ask for more lags)',
+              b[0][0].toFixed(3), b[0][1].toFixed(3), b[1][0].toFixed(3), b[1][1].toFixed(3));
 }
 console.log('cor(%s, %s) = %s  (cov %s)', cv.labels[0], cv.labels[1], cv.cor[0][1].toFixed(4), cv.cov[0][1].toExponential(3));
 console.log('held on the device:', JSON.stringify(sampler.summary_info()));

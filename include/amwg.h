@@ -319,8 +319,9 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
  * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_fetch_draws*,
  * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
- * amwg_last_sample_dataset_histogram and amwg_last_sample_dataset_covariance unless they were armed before the call (amwg_set_histogram, amwg_set_covariance) and
- * are asked for what was folded while the draws passed (edges = NULL, values = NULL).  A later amwg_sample* call replaces
+ * amwg_last_sample_dataset_histogram, amwg_last_sample_dataset_covariance and amwg_last_sample_dataset_autocovariance unless they were armed before the call
+ * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL).  An
+ * armed autocovariance whose max_lag is not below the kept draws makes the summarising call itself AMWG_EINVAL, before its first launch.  A later amwg_sample* call replaces
  * the summary, amwg_burn leaves it alone, and every summarising call starts its accumulators afresh.  n = 0 succeeds and leaves nothing to summarise.
  * amwg_launch_info's n_launches (step-kernel launches) and kernel_ms (which includes the folds) cover the whole call.
  * amwg_sample_summarize = the _async form + amwg_sync.  Refused before a device is opened: null sampler, n < 0, thin < 1, window_rows < 0.
@@ -375,6 +376,38 @@ int amwg_histogram_info(const amwg_sampler *s, int32_t *bins, size_t *bytes);
 int amwg_last_sample_dataset_covariance(amwg_sampler *s, const int32_t *values, int32_t n_values, double *cov);
 int amwg_set_covariance(amwg_sampler *s, const int32_t *values, int32_t n_values);
 int amwg_covariance_info(const amwg_sampler *s, int32_t *n_values, size_t *bytes);
+
+/* AUTOCOVARIANCE ALONG THE CHAINS at lags 0 .. max_lag over a caller-chosen subset of the recorded values, per dataset, on the device: what an autocorrelation, an
+ * integrated autocorrelation time and an effective sample size that needs no second chain are formed from (the host function autocorrelation_ess of the front ends
+ * does that: Geyer's initial monotone sequence, BDA3 section 11.5, without rank normalisation).  values[0 .. n_values) are DISTINCT indices into the recorded values;
+ * acov[dataset][n_values][max_lag + 1], mean[dataset][n_values] and between[dataset][n_values] are in the order of `values`; an ordinary sampler is one dataset,
+ * and one chain per dataset is allowed.
+ * THE ARITHMETIC is fixed (compiled with -ffp-contract=off, every operation rounds once).  Per chain c and value, x_0 .. x_(n-1) its kept draws in row order, n = kept
+ * draws: the pilot a = x_0 and y_t = x_t - a; in row order Y += y_t and, for every lag l = 0 .. min(t, L), S_l += y_t * y_(t-l), each S_l one running sum in
+ * ascending t.  At the end ybar = Y / n; H_0 = T_0 = 0, H_(l+1) = H_l + y_l, T_(l+1) = T_l + y_(n-1-l) (the sums of the first and of the last l deviations);
+ *   gamma_l = ((S_l - ybar * ((Y - H_l) + (Y - T_l))) + (double)(n - l) * (ybar * ybar)) / (double)n
+ * -- in exact arithmetic (1 / n) sum_(t >= l) (x_t - xbar)(x_(t-l) - xbar), the estimator an FFT-based ACF computes; centring on the pilot removes a large offset --
+ * and the chain mean m_c = a + ybar.  Per (dataset, value), over the dataset's cpd chains in the order of the moments of a summarising call (256 threads, thread t
+ * takes chains t, t + 256, ...; a halving tree): acov_l = (sum_c gamma_lc) / cpd; gm = (sum_c m_c) / cpd, returned as mean; between = sum_c (m_c - gm)^2 / (cpd - 1),
+ * 0.0 when cpd = 1.  A NaN or an infinity among a value's draws in a dataset -- and sums that overflow: whatever leaves acov_0 not finite -- makes that (dataset,
+ * value)'s acov, mean and between NaN; every other output keeps its bytes.  The stored path runs the kernels of the folded path over the stored array from a zeroed
+ * state, so the result of a summarising call EQUALS the stored run's byte for byte, whatever the window.
+ *   amwg_last_sample_dataset_autocovariance -- after amwg_sample*: over any valid `values` and max_lag.  After amwg_sample_summarize*: pass values = NULL with the
+ *     armed n_values and max_lag and receive what was folded; values given afterwards, another n_values or max_lag, or a call for which nothing was armed is
+ *     AMWG_EINVAL with a message that names amwg_set_autocovariance.
+ *   amwg_set_autocovariance -- arms `values` and max_lag for every later amwg_sample_summarize[_async] of this sampler (the list is copied; NULL, 0, 0 disarms): the
+ *     state is zeroed when a summarising call starts; after the fold (and the histogram) of each window a kernel adds the window's lagged sums on the same stream,
+ *     reading draws older than the window from a ring of the last max_lag kept rows, and a second kernel then moves the ring on.  A summarising call that would keep
+ *     <= max_lag draws is itself refused (AMWG_EINVAL) before its first launch, the chains' state untouched.  Moments, R-hat, ESS, the chains' state, n_launches and
+ *     amwg_summary_info are those of the unarmed call.
+ *   amwg_autocovariance_info -- the armed n_values (0: none) and max_lag and the device bytes held: (3 max_lag + 2) x n_values x chains doubles (the lagged sums,
+ *     the sum of deviations, the ring and the first max_lag rows) plus the list of values (any pointer may be NULL).
+ * max_lag is at most 1024, a chosen cap: the state grows with it.  Refused with AMWG_EINVAL and the call's name, before any device call: null pointers, n_values < 1 or
+ * > PR, an index outside [0, PR), a repeated index, max_lag outside 1 .. 1024, no sample call yet, max_lag >= kept draws, a byte count beyond size_t.  One device
+ * only: the amwg_group_* and amwg_comm_* calls have no autocovariance. */
+int amwg_last_sample_dataset_autocovariance(amwg_sampler *s, const int32_t *values, int32_t n_values, int32_t max_lag, double *acov, double *mean, double *between);
+int amwg_set_autocovariance(amwg_sampler *s, const int32_t *values, int32_t n_values, int32_t max_lag);
+int amwg_autocovariance_info(const amwg_sampler *s, int32_t *n_values, int32_t *max_lag, size_t *bytes);
 
 /* Replaces sampler.start_adaptation() / .stop_adaptation() (mcmc.js:1060-1073). */
 int amwg_set_adapting(amwg_sampler *s, int32_t flag);

@@ -68,6 +68,15 @@ int amwg_histogram_check(const double *draws, int64_t rows, int32_t PR, int64_t 
 int amwg_covariance_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const int32_t *values, int32_t n_values, int64_t window_rows,
                           double *cov, int32_t device);
 
+/* The autocovariance kernels of amwg_last_sample_dataset_autocovariance / amwg_set_autocovariance on a caller's array draws[rows][PR][C] (host), D datasets of C / D
+ * chains each, over values[n_values] at lags 0 .. max_lag: the array is uploaded and the product's launchers run over it from a zeroed state -- window_rows = 0: the
+ * stored path, the whole array as one window; window_rows > 0: window after window through the lag-sum and the carry kernel, as a summarising call enqueues them.
+ * acov[D][n_values][max_lag + 1], mean and between [D][n_values] (host) in the order of `values`.  Refused before a device is opened, with the product's words: null
+ * pointers, a bad shape (non-positive sizes, C % D != 0, window_rows < 0), n_values outside 1 .. PR, an index outside [0, PR), a repeated index, max_lag outside
+ * 1 .. 1024, max_lag >= rows, a byte count beyond size_t. */
+int amwg_autocovariance_check(const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const int32_t *values, int32_t n_values, int32_t max_lag,
+                              int64_t window_rows, double *acov, double *mean, double *between, int32_t device);
+
 /* The host machinery behind sample()'s copy-out (csrc/amwg_run.hip Prefaulter: huge pages, MADV_POPULATE_WRITE, helper threads that touch the destination ahead of
  * the device-to-host copies) on a caller's buffer, cut into n_chunks chunks, with `threads` helpers (0 = the calling thread alone).  Changes no byte.  No GPU. */
 int amwg_prefault_selftest(char *buf, size_t bytes, int32_t n_chunks, int32_t threads);
