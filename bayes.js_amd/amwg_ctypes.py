@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -73,6 +73,7 @@ def lib():
         L.amwg_last_sample_dataset_moments.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_diagnostics.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_quantiles.argtypes = [vp, pd, i32, pd]
+        L.amwg_last_sample_dataset_hpd.argtypes = [vp, pd, i32, pd]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -174,6 +175,8 @@ def selftest_lib():
         L.amwg_ld_device.argtypes = [i32, i64, pd, pd]
         L.amwg_prefault_selftest.argtypes = [C.c_void_p, C.c_size_t, i32, i32]
         L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
+        L.amwg_hpd_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
+        L.amwg_hpd_limits.argtypes = [i32, i64, C.POINTER(i64), C.POINTER(i64)]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
@@ -531,6 +534,21 @@ class Sampler:
         _check(lib().amwg_last_sample_dataset_quantiles(self.h, _dp(pr), pr.size, _dp(out)))
         return out
 
+    def dataset_hpd(self, probs):
+        """-> array [datasets][P + derived][len(probs)][2]: the highest-density interval (lower, upper) per dataset, value and probability, by the rule of
+        include/amwg.h -- the shortest interval spanning floor(p N) + 1 sorted draws -- on the device (amwg_last_sample_dataset_hpd)"""
+        pr = np.ascontiguousarray(probs, dtype=np.float64)
+        out = np.empty((self.D, self.PR, pr.size, 2))
+        _check(lib().amwg_last_sample_dataset_hpd(self.h, _dp(pr), pr.size, _dp(out)))
+        return out
+
+    def hpd(self, probs):
+        """-> array [P + derived][len(probs)][2]: dataset_hpd() of an ordinary sampler; a dataset sampler refuses the pooled question"""
+        if self.D > 1:
+            raise AmwgError("amwg error -1: hpd: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_hpd "
+                            "(dataset_hpd)" % self.D)      # (the words of amwg_refuse_pooled; the library has no pooled call to ask)
+        return self.dataset_hpd(probs)[0]
+
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)
         assert st.shape == (self.P, self.C)
@@ -715,6 +733,29 @@ def dataset_quantiles_check(draws, D, probs, device=0):
     if L.amwg_dataset_quantiles_check(device, _dp(dr), rows, PR, Cn, D, _dp(pr), pr.size, _dp(out)) != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return out
+
+
+def hpd_check(draws, D, probs, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_hpd on any array draws [rows][PR][C], D datasets of C / D columns each
+    -> array [D][PR][len(probs)][2] (amwg_hpd_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    pr = np.ascontiguousarray(probs, dtype=np.float64)
+    rows, PR, Cn = dr.shape
+    out = np.empty((D, PR, pr.size, 2))
+    L = selftest_lib()
+    if L.amwg_hpd_check(device, _dp(dr), rows, PR, Cn, D, _dp(pr), pr.size, _dp(out)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
+
+
+def hpd_limits(scratch_bytes=0, device=0, lds=True):
+    """libamwg_selftest.so: sets the scratch budget of later hpd_check calls (0: the default) -> (keys one workgroup sorts in LDS on `device`, or None with
+    lds=False, which opens no device; the budget in force before) (amwg_hpd_limits)"""
+    L = selftest_lib()
+    keys, before = C.c_int64(0), C.c_int64(0)
+    if L.amwg_hpd_limits(device, scratch_bytes, C.byref(keys) if lds else None, C.byref(before)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return (keys.value if lds else None), before.value
 
 
 def fold_check(draws, D, window_rows, device=0):

@@ -755,6 +755,28 @@ static napi_value DatasetQuantiles(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* datasetHpd(handle, Float64Array probs) -> {datasets, hpd}: hpd a Float64Array [datasets][recorded][n_probs][2] (lower, upper) over the last sample() */
+static napi_value DatasetHpd(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t np = 0;
+  const double *probs = (const double *)typed_data(env, a[1], napi_float64_array, &np);
+  if (!probs || np < 1) { napi_throw_type_error(env, NULL, "amwg_napi.datasetHpd: probs must be a non-empty Float64Array"); return NULL; }
+  double *q = NULL;
+  napi_value v = new_f64(env, (size_t)amwg_num_datasets(s) * (size_t)amwg_num_recorded(s) * np * 2, &q);
+  if (!v) return NULL;
+  int rc = amwg_last_sample_dataset_hpd(s, probs, (int32_t)np, q);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "hpd", v);
+  napi_create_int32(env, amwg_num_datasets(s), &t);
+  napi_set_named_property(env, o, "datasets", t);
+  return o;
+}
+
 /* setHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins): amwg_set_histogram -- arms (null, 0: disarms) a histogram for later summarising calls */
 static napi_value SetHistogram(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -1169,7 +1191,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

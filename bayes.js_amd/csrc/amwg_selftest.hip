@@ -6,6 +6,7 @@
 #include "amwg_covariance.h"
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
+#include "amwg_hpd.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
@@ -117,6 +118,26 @@ int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t ro
   HIP_TRY(dd.alloc(bytes));
   HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
   return amwg_dataset_quantiles_launch("amwg_dataset_quantiles_check", dd.as<double>(), rows, PR, C, D, probs, n_probs, out, nullptr);
+}
+
+int amwg_hpd_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *probs, int32_t n_probs, double *out) {
+  if (!draws || !probs || !out) return amwg_fail(AMWG_EINVAL, "amwg_hpd_check: null argument");
+  TRYB(amwg_hpd_shape("amwg_hpd_check", rows, PR, C, D, n_probs));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "amwg_hpd_check: array too large");
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  return amwg_hpd_launch("amwg_hpd_check", dd.as<double>(), rows, PR, C, D, probs, n_probs, out, nullptr);
+}
+
+int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, int64_t *scratch_before) {
+  if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "amwg_hpd_limits: bad argument (scratch_bytes %lld)", (long long)scratch_bytes);
+  if (lds_keys) { TRYB(use_device(device)); TRYB(amwg_hpd_lds_keys(lds_keys)); }
+  const size_t before = amwg_hpd_set_budget((size_t)scratch_bytes);
+  if (scratch_before) *scratch_before = (int64_t)before;
+  return AMWG_OK;
 }
 
 int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,

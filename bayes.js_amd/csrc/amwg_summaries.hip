@@ -12,6 +12,7 @@
 #include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_sampler.h"
+#include "amwg_select.h"
 
 namespace {
 
@@ -80,28 +81,7 @@ constexpr int kSelProbs = 24;               // probabilities per launch: <= 48 r
 constexpr int kSelRanks = 2 * kSelProbs;
 constexpr int kSelLoads = 4;                // elements a thread has in flight
 
-__device__ inline uint64_t select_key(double v) {      // order of the doubles = order of the keys (-0 before +0)
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  return (b >> 63) ? ~b : b ^ 0x8000000000000000ull;
-}
-__device__ inline double select_value(uint64_t k) {
-  return __longlong_as_double((long long)((k >> 63) ? k ^ 0x8000000000000000ull : ~k));
-}
-
-// hist[slot] += 1 for every lane with `active`.  The draws of one posterior agree in sign, exponent and leading mantissa bits, so in the early passes all 64
-// lanes name the same bin: the first lane still waiting broadcasts its slot, the lanes that agree are counted by a ballot and ONE lane adds the count; repeat
-// while lanes wait.  The loop's trip count is the number of distinct slots in the wavefront.
-__device__ inline void wave_count(uint32_t *hist, bool active, uint32_t slot) {
-  const int lane = threadIdx.x & 63;
-  uint64_t todo = __ballot(active);
-  while (todo) {
-    const int leader = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)slot, leader);
-    const uint64_t same = __ballot(active && slot == ls);
-    if (lane == leader) atomicAdd(&hist[ls], (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
-}
+// (select_key, select_value, wave_count and select_scan: amwg_select.h, shared with the thresholds of amwg_hpd.hip)
 
 // out[d][p][k0 + k] for k < kc <= kSelProbs; dynamic LDS: 2 kc histograms of 256 u32
 __global__ void __launch_bounds__(kSelThreads) dataset_select_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd,
@@ -184,14 +164,7 @@ __global__ void __launch_bounds__(kSelThreads) dataset_select_kernel(const doubl
     }
     __syncthreads();
     // exclusive scan of each group's bins, a wavefront per group, four bins per lane
-    for (int g = wave; g < G; g += kSelThreads / 64) {
-      uint32_t *hb = hist + g * 256 + lane * 4;
-      const uint32_t c0 = hb[0], c1 = hb[1], c2 = hb[2], c3 = hb[3], s = c0 + c1 + c2 + c3;
-      uint32_t incl = s;
-      for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-      const uint32_t excl = incl - s;
-      hb[0] = excl; hb[1] = excl + c0; hb[2] = excl + c0 + c1; hb[3] = excl + c0 + c1 + c2;
-    }
+    for (int g = wave; g < G; g += kSelThreads / 64) select_scan(hist + g * 256, lane);
     __syncthreads();
     // each rank takes the bin that holds it: the last bin whose exclusive count is <= the rank's position inside its group
     uint64_t new_prefix = 0;

@@ -588,6 +588,31 @@ AmwgSampler.prototype.dataset_quantiles = function (probs) {
   return out;
 };
 
+/** Highest-density intervals per dataset (options.datasets; an ordinary sampler: one dataset): [{name: [[[lo, hi] per prob] per element]}, ...], shaped like
+ *  dataset_quantiles() with a pair where it has a number.  The rule of include/amwg.h -- the shortest interval spanning floor(p N) + 1 of the dataset's N sorted
+ *  draws, the first of equal widths -- on the device: two order statistics by radix select, the two tails sorted, nothing else moved.  A dataset lives wholly on
+ *  one shard: no collective. */
+AmwgSampler.prototype.dataset_hpd = function (probs) {
+  const N = native(), pr = Float64Array.from(probs), out = [], PR = this.PR;
+  for (const sh of this._shards) {
+    const r = N.datasetHpd(sh.handle, pr);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = {}, row = (c) => Array.from({ length: pr.length }, (_, k) => { const at = ((d * PR + c) * pr.length + k) * 2; return [r.hpd[at], r.hpd[at + 1]]; });
+      for (const L of this._layout) o[L.name] = Array.from({ length: L.len }, (_, e) => row(L.base + e));
+      this.derived.forEach((name, k) => { o[name] = [row(this.P + k)]; });
+      out.push(o);
+    }
+  }
+  return out;
+};
+/** hpd(probs) over all chains x kept draws of the last sample(): {name: [[[lo, hi] per prob] per element]}, shaped like quantiles().  One device: the tails of
+ *  a posterior spread over several devices would have to be merged, which is out of scope -- dataset_hpd() works there, a dataset being on one shard. */
+AmwgSampler.prototype.hpd = function (probs) {
+  this._refusePooled('hpd');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): hpd() over several devices (options.devices) is out of scope: the multi-device HPD is not built; hpd() runs on one device';
+  return this.dataset_hpd(probs)[0];
+};
+
 // edges as the caller gives them -- {name: [e0, ..., e_bins]} per parameter or derived quantity (every element of a vector parameter under the same edges), or one
 // array for all recorded values; all of one length -- -> {flat: Float64Array [recorded][bins + 1], bins}
 AmwgSampler.prototype._histogramEdges = function (edges) {

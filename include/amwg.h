@@ -205,6 +205,25 @@ int amwg_last_sample_dataset_diagnostics(amwg_sampler *s, double *rhat, double *
  * kernel runs once per 24 probabilities).  Works on an ordinary sampler too (D = 1: the pooled call's result).  AMWG_EINVAL: a null argument or n_probs < 1
  * (before any device call), no sample() yet, more than 2^31 - 1 values per dataset and component, more than 65535 datasets. */
 int amwg_last_sample_dataset_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out);
+/* HIGHEST-DENSITY INTERVALS per dataset: out[D][P + derived][n_probs][2], (lower, upper) per probability.  amwg_last_sample_dataset_quantiles at (0.025, 0.975)
+ * is the equal-tailed interval; for a skewed posterior the shortest interval of the same content is the one to report.
+ * THE RULE applies per dataset d, recorded value v (the P parameters plus the derived quantities) and probability p.  The N = rows * (C / D) draws of (d, v) in the
+ * last stored sample() are ordered by the key order of the doubles: the order of the doubles, with -0 before +0.  Write the sorted draws as x_(0) <= ... <= x_(N-1).
+ *   g = floor(p * (double)N), one IEEE fp64 multiply then floor, clamped to [1, N - 1].  Set k = N - g.
+ *   w_i = x_(i+g) - x_(i) in fp64, for i = 0 ... k - 1.
+ *   i* is the smallest i whose w_i is minimal, with widths compared as doubles.
+ *   The result is (x_(i*), x_(i*+g)): the shortest interval spanning g + 1 sorted draws (the Kruschke / ArviZ rule).  Its bytes are those of two draws.
+ *   A p that is NaN or outside the open interval (0, 1) gives (NaN, NaN) for that probability (as amwg_last_sample_dataset_quantiles does with a bad q).
+ *   A NaN or +-inf anywhere among the N draws of (d, v) gives (NaN, NaN) for every probability of that (d, v), and nowhere else (the autocovariance's convention).
+ * (0.29 * 100 floors to 28, not 29: the rule is what the fp64 product says.)
+ * The draws do not leave the device and no slice is gathered or sorted whole: per probability a radix select finds t_lo = x_(k-1) and t_hi = x_(g) where the draws
+ * lie, the k draws up to t_lo and the k draws from t_hi go into scratch, the two tails are sorted (in LDS where a tail fits, else by global passes) and the k
+ * widths are scanned for the first smallest.  Scratch is 2 x k keys per (d, v), rounded up to a power of two, allocated per call on the sampler's device and freed
+ * before the call returns; the (d, v) go in batches under a budget of 256 MiB, and a single (d, v) whose two tails exceed the budget runs alone.  Any p in
+ * (0, 1) is served; AS p -> 0 THE TAILS APPROACH THE WHOLE SLICE, twice over: the call is meant for the probabilities people report (0.5 .. 0.99).
+ * Works on an ordinary sampler too (D = 1).  AMWG_EINVAL: a null argument or n_probs < 1 (before any device call), no sample() yet, after a summarising call,
+ * fewer than 2 values per dataset and value, and the shape limits of amwg_last_sample_dataset_quantiles.  A failed scratch allocation is AMWG_EHIP. */
+int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n_probs, double *out);   /* out[D][P + derived][n_probs][2] */
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,
@@ -317,7 +336,7 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * Afterwards amwg_last_sample_moments, amwg_last_sample_diagnostics, amwg_last_sample_dataset_moments and amwg_last_sample_dataset_diagnostics answer from the
  * accumulators: the halves are accumulated by the recurrence of the stored path in the same row order, so split-R-hat and ESS equal those of the stored run BIT FOR BIT
  * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
- * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_fetch_draws*,
+ * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_fetch_draws*,
  * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
  * amwg_last_sample_dataset_histogram, amwg_last_sample_dataset_covariance and amwg_last_sample_dataset_autocovariance unless they were armed before the call
  * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL).  An

@@ -35,6 +35,14 @@ int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_
 int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D,
                                  const double *probs, int32_t n_probs, double *out);
 
+/* the kernels of amwg_last_sample_dataset_hpd on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each: out[D][PR][n_probs][2] (host),
+ * through the launcher the sampler uses.  The arguments are checked before a device is opened. */
+int amwg_hpd_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const double *probs, int32_t n_probs, double *out);
+/* the two sizes at which that launcher changes route, so that tests can stand on them: lds_keys (NULL: not asked, and no device is opened) = the keys one
+ * workgroup sorts in LDS on `device`, a power of two; the scratch budget of later calls in this process is set to scratch_bytes (0: the default of csrc/amwg_hpd.h)
+ * and the one in force before goes to scratch_before (may be NULL). */
+int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, int64_t *scratch_before);
+
 /* The fold of amwg_sample_summarize on a caller's array draws[rows][PR][C] (host): the array is folded in windows of window_rows rows through the kernels and the
  * launcher the sampler uses (halves_folded, 4 * PR * C doubles in chain_halves_kernel's layout [half][mean | variance][PR][C]), chain_halves_kernel runs on the whole
  * array (halves_direct, the same size), and the moments of D datasets of C / D chains each come from the folded whole-chain pairs (mean, sd: [D][PR]).
