@@ -353,6 +353,11 @@ struct CoopStream {
       return mine;
     }
   }
+  // one lane per chain: the next two uniforms -- next(); next() -- with the refill at one call site (amwg_philox.h stream_next_pair)
+  __device__ __forceinline__ void next_pair(double &a, double &b) {
+    static_assert(L == 1, "the pair draw is the one-lane stream's");
+    stream_next_pair(*this, a, b);
+  }
 };
 
 // A condition every lane of the chain decides alike.  For a chain on a whole wave (G >= 64) saying so -- through the ballot, which is a scalar -- turns
@@ -397,8 +402,10 @@ __device__ __forceinline__ double rnorm_js(Rng &rng, double mean, double sd) {  
   double u, v, q;
   bool again;
   do {
-    u = rng.next();
-    v = 1.7156 * (rng.next() - 0.5);
+    double r;
+    if constexpr (GU == 1) rng.next_pair(u, r);      // (the lanes are chains at either parity of their streams: one refill site in this loop, not one per draw)
+    else { u = rng.next(); r = rng.next(); }
+    v = 1.7156 * (r - 0.5);
     const double x = u - 0.449871;
     const double y = __builtin_fabs(v) + 0.386595;
     q = x * x + y * (0.19600 * y - 0.25472 * x);

@@ -160,6 +160,12 @@ struct NormalModel {
   //                    rounds them (u S2), 1 / den correctly rounded and one product (2 u Q), n c and two additions (3 u mag)
   // i.e. |difference| <= (1.125 n + 16) u mag; eps = (2 n + 64) u (|prior| + n |c| + 2 Q) 1.25 leaves a factor of two.  A non-finite value anywhere
   // makes eps non-finite, which the stepper reads as "evaluate the expression".
+  // ANY ORDER of the n additions is covered (docs/CERTIFIED.md): the terms are non-negative, so every partial sum is at most S2 and each of the n roundings of
+  // `s = fma(t, t, s)` -- the first one, onto zero, included -- adds at most u S2 (1 + n u) whatever tree the additions form: n u S2 on this side instead of
+  // (n / 8 + 3) u S2, (n + 6) u mag in all.  With the (n + 2) u mag of the term-by-term side that is (2 n + 8) u mag against eps >= (2.5 n + 80) u mag.  The
+  // wavefront's pass (amwg_pass.h norm_sq_pass_wave) uses it: n / 64 additions per lane in row order, six butterfly steps, then up to 63 leftover terms in sequence
+  // -- at most n / 64 + 69 roundings on any term's way into the sum, which is within the n / 8 + 3 above (and so keeps the factor of two) from n = 613 on; for shorter
+  // data the any-order figure applies and the margin is 1.25 at the least.
   static constexpr bool kCertified = true;
   static constexpr int kCertifiedLanes = 1;
   struct Approx { double value, eps; };

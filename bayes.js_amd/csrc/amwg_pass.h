@@ -358,9 +358,10 @@ AMWG_HD double norm_sq_pass_uniform(const double *x_global, double mean, int n_o
 // DPP: 63 exchange-and-add steps) leaves chain c's total in lane c.  Same count of fp64 operations, no load on the critical path.  The order of the
 // additions is whatever this schedule gives: the value is used with its rounding bound only (NormalModel::log_post_approx).
 // THE ROW PLAN of the wavefront's pass (norm_sq_pass_wave below; a row = 64 consecutive observations, one per lane).  n_obs observations are `blocks` full blocks of B
-// full rows, then ONE remainder of `full` (0 .. B-1) full rows and, when n_obs is no multiple of 64, a partly filled last row (`masked`).  The remainder's rows sit in
-// one register set of B slots: the parts p = B/2, B/4, .., 1 that make up `full` (its binary digits) take, in that order, the rows pass_part_row .. + p - 1 of the
-// remainder into the slots pass_part_slot .. + p - 1; slot B - 1 belongs to no part and holds the partly filled row.
+// full rows, then ONE remainder of `full` (0 .. B-1) full rows.  The remainder's rows sit in one register set of B slots: the parts p = B/2, B/4, .., 1 that make up
+// `full` (its binary digits) take, in that order, the rows pass_part_row .. + p - 1 of the remainder into the slots pass_part_slot .. + p - 1 (slot B - 1 is never
+// taken).  `masked` = 1 when n_obs is no multiple of 64: the n_obs % 64 LEFTOVER observations behind the last full row.  They are no row of the pass (until round 8
+// they were a masked one: a whole row's instructions for a quarter of a row at n = 10^4): each chain adds them itself, after the butterfly.
 struct PassRows { int blocks, full, masked; };
 AMWG_HD PassRows pass_rows(int n_obs, int B) { const int rows = n_obs / 64; return PassRows{rows / B, rows % B, (n_obs % 64) != 0 ? 1 : 0}; }
 AMWG_HD constexpr int pass_part_slot(int B, int p) { return B - 2 * p; }
@@ -462,9 +463,8 @@ __device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, 
       const int nb = k + 1 < pr.blocks ? k + 1 : k;
       rows_s(PassBlock<0>{}, PassBlock<B>{}, [&](int b0, int b1) { read_rows(nb, b0, b1); });
     }
-    if (pr.full > 0 || pr.masked) {
+    if (pr.full > 0) {
       const int rbase = pr.blocks * B * 64 + lane;
-      const bool has = pr.masked && rbase + pr.full * 64 < n_obs;
       // every row of the remainder is requested before its first part starts: part p (B/2, B/4, .., 1: the binary digits of pr.full) into the slots pass_part_slot
       auto read_part = [&](auto pt) {
         constexpr int P = decltype(pt)::value;
@@ -478,7 +478,6 @@ __device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, 
       if constexpr (B >= 8) read_part(PassBlock<4>{});
       if constexpr (B >= 4) read_part(PassBlock<2>{});
       if constexpr (B >= 2) read_part(PassBlock<1>{});
-      if (pr.masked) xv[B - 1] = x[has ? rbase + pr.full * 64 : 0];
       auto part = [&](auto pt) {
         constexpr int P = decltype(pt)::value;
         if (pr.full & P) rows_s(PassBlock<pass_part_slot(B, P)>{}, pt, [](int, int) {});
@@ -488,18 +487,6 @@ __device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, 
       if constexpr (B >= 8) part(PassBlock<4>{});
       if constexpr (B >= 4) part(PassBlock<2>{});
       if constexpr (B >= 2) part(PassBlock<1>{});
-      if (pr.masked) {      // the partly filled last row: the only selects of the pass
-        const double xm = xv[B - 1];
-#pragma unroll
-        for (int g = 0; g < 64; g += 8) {
-          amwg_v16i nxt = cur;
-          if (g + 8 < 64) nxt = fetch(g + 8);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { const double t = has ? xm - mean_in(cur, j) : 0.0; a[g + j] = __builtin_fma(t, t, a[g + j]); }
-          if (g + 8 < 64) landed(nxt);
-          cur = nxt;
-        }
-      }
     }
     smem_done = true;
   }
@@ -526,27 +513,20 @@ __device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, 
   };
   int base = 0;
   for (; base + 64 * B <= n_obs; base += 64 * B) block(PassBlock<B>{}, base);
-  // the rest in blocks of half the length each (round 5 walked it 64 observations at a time: a quarter of a block's arithmetic for all of its broadcasts), the last round masked
+  // the rest in blocks of half the length each (round 5 walked it 64 observations at a time: a quarter of a block's arithmetic for all of its broadcasts); the leftover observations follow the butterfly
   if constexpr (B >= 32) { if (base + 64 * 16 <= n_obs) { block(PassBlock<16>{}, base); base += 64 * 16; } }
   if constexpr (B >= 16) { if (base + 64 * 8 <= n_obs) { block(PassBlock<8>{}, base); base += 64 * 8; } }
   if constexpr (B >= 8) { if (base + 64 * 4 <= n_obs) { block(PassBlock<4>{}, base); base += 64 * 4; } }
   if constexpr (B >= 4) { if (base + 64 * 2 <= n_obs) { block(PassBlock<2>{}, base); base += 64 * 2; } }
   if constexpr (B >= 2) { if (base + 64 <= n_obs) { block(PassBlock<1>{}, base); base += 64; } }
   for (; base + 64 <= n_obs; base += 64) block(PassBlock<1>{}, base);
-  if (base < n_obs) {
-    const int i = base + lane;
-    const bool has = i < n_obs;
-    const double xv = x[has ? i : base];
-#pragma unroll
-    for (int g = 0; g < 64; g += 8) {
-      double m[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) m[j] = mean_of(g + j);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { const double t = has ? xv - m[j] : 0.0; a[g + j] = __builtin_fma(t, t, a[g + j]); }
-    }
-  }
   }      // (!smem_done)
+  // THE LEFTOVER OBSERVATIONS (n_obs % 64 of them, behind the last full row) are not a row of the pass: against 64 means they would cost what a full row costs,
+  // with most lanes idle.  They are added where a lane is a chain again, after the butterfly.  ONE read, requested here so that it travels under the butterfly: lane l
+  // takes leftover l (from the tile or the array, whichever the pass reads), and afterwards observation k -- wave-uniform -- is read out of lane k into scalar registers.
+  const int rem = __builtin_amdgcn_readfirstlane(n_obs & 63);
+  double xl = 0.0;
+  if (rem != 0) xl = x[n_obs - rem + (lane < rem ? lane : 0)];
   // transposing butterfly: after the step with offset o a lane holds the chains that agree with it in that bit, a[j] <- kept + received
   auto swap_add = [&](double A, double Bv, int off) {      // A: what the lanes with the bit CLEAR keep, Bv: what the lanes with the bit SET keep
     const uint32_t al = (uint32_t)f64_bits(A), ah = (uint32_t)(f64_bits(A) >> 32), bl = (uint32_t)f64_bits(Bv), bh = (uint32_t)(f64_bits(Bv) >> 32);
@@ -582,7 +562,32 @@ __device__ __forceinline__ double norm_sq_pass_wave(XP x, double mu, int n_obs, 
     const double send = up ? a[0] : a[1], keep = up ? a[1] : a[0];
     a[0] = keep + xor_partner<1>(send);
   }
-  return a[0];
+  // lane c holds S2_c over the full rows; now the leftover terms (up to 63 more additions: the bound of NormalModel::log_post_approx holds for any order).  Eight at a
+  // time while eight are left -- the reads out of the lanes and the subtractions of a group are independent of each other, its fma run as two chains of four --, then
+  // one by one
+  double s = a[0];
+  if (rem != 0) {
+    const int xl_lo = (int)(uint32_t)f64_bits(xl), xl_hi = (int)(uint32_t)(f64_bits(xl) >> 32);
+    auto leftover = [&](int k) { return bits_f64(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(xl_hi, k) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readlane(xl_lo, k)); };
+    int k = 0;
+    for (; k + 8 <= rem; k += 8) {
+      double t[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t[j] = leftover(k + j) - mu;
+      AMWG_STAGE_FENCE();
+      double e = t[1] * t[1];
+      s = __builtin_fma(t[0], t[0], s);
+#pragma unroll
+      for (int j = 2; j < 8; j += 2) { e = __builtin_fma(t[j + 1], t[j + 1], e); s = __builtin_fma(t[j], t[j], s); }
+      s = s + e;
+    }
+#pragma unroll 1
+    for (; k < rem; ++k) {
+      const double t = leftover(k) - mu;
+      s = __builtin_fma(t, t, s);
+    }
+  }
+  return s;
 #else
   (void)x; (void)mu; (void)n_obs;
   return 0.0;

@@ -74,4 +74,20 @@ struct ChainStream {
   }
 };
 
+// The next TWO uniforms of a stream that holds one block at a time as the two uniforms it yields (u0, u1), `pos` of them consumed (0, 1, or 2 = the next
+// draw refills), b0 the block's number, fill() = "compute block b0" -- the one-lane CoopStream of amwg_kernel.h.  The values and the position afterwards
+// are those of two single draws; what differs is that the refill stands at ONE place whatever the position:
+//     pos 0: u0, u1             pos 1: u1, refill, u0             pos 2: refill, u0, u1
+// (the lanes of a wavefront are chains at different positions: with a refill inside each of two single draws the wavefront runs the block function twice,
+// each time for part of its lanes)
+template <class S>
+AMWG_HD void stream_next_pair(S &s, double &a, double &b) {
+  const uint32_t p = s.pos;
+  const double held = s.u1;      // (pos 1: the first of the pair, taken before the refill overwrites it)
+  if (p != 0u) { s.b0 += 1; s.fill(); }
+  a = p == 1u ? held : s.u0;
+  b = p == 1u ? s.u0 : s.u1;
+  s.pos = p == 1u ? 1u : 2u;
+}
+
 }  // namespace amwg
