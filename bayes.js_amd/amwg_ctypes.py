@@ -49,7 +49,7 @@ class UserModel(C.Structure):
 
 
 EXPORTS = ["amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval"]      # include/amwg_selftest.h: libamwg_selftest.so only
+SELFTEST_EXPORTS = ["amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -159,6 +159,7 @@ def selftest_lib():
         L.amwg_last_error.restype = C.c_char_p
         L.amwg_device_eval.argtypes = [i32, i32, i64, pd, pd, pd, pd]
         L.amwg_two_valued_sum_check.argtypes = [i32, pd, i32, i64, pd, pd, pd, pd, pd]
+        L.amwg_stream_check.argtypes = [i32, i32, C.c_uint64, C.c_uint64, i64, C.POINTER(C.c_uint64), i64, C.POINTER(C.c_uint8), i64, pd, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.amwg_pow.restype = dbl
         L.amwg_pow.argtypes = [dbl, dbl]
         L.amwg_math1.restype = dbl
@@ -884,6 +885,32 @@ def fp64_peak(device=0):
     v = C.c_double()
     _check(lib().amwg_fp64_peak(device, C.byref(v)))
     return v.value
+
+
+STREAM_CHAIN, STREAM_PAIRS, STREAM_WINDOW, STREAM_WINDOW_AT = 0, 100, 200, 201      # amwg_stream_check's kinds beside CoopStream<G>::next, whose kind is G
+
+
+def stream_check(kind, seed, chain0, consumed0, n_draws, calls=None, device=0):
+    """libamwg_selftest.so: the product's uniform-stream classes on the device, chain i with id chain0 + i from position consumed0[i] (amwg_stream_check).
+    kind: STREAM_CHAIN, a lane count G of CoopStream<G> (1 .. 64), STREAM_PAIRS (CoopStream<1> under calls: 0 = next(), 1 = next_pair()), STREAM_WINDOW,
+    STREAM_WINDOW_AT -> dict of draws [chains][n_draws], consumed [chains]; for STREAM_WINDOW_AT also ahead [chains][128] (at() after ensure_b()), window
+    [chains][256] (at() after a shift() and the next ensure_b()) and flags [chains][3][4]: EA, OA, EB, OB after ensure_b(), shift(), ensure_b()."""
+    c0 = np.ascontiguousarray(consumed0, dtype=np.uint64)
+    n = c0.size
+    width = n_draws + (384 if kind == STREAM_WINDOW_AT else 0)
+    out = np.empty((n, width))
+    cons = np.empty(n, dtype=np.uint64)
+    flags = np.empty((n, 3, 4), dtype=np.uint64) if kind == STREAM_WINDOW_AT else None
+    cl = np.ascontiguousarray(calls, dtype=np.uint8) if calls is not None else None
+    pu64 = C.POINTER(C.c_uint64)
+    L = selftest_lib()
+    if L.amwg_stream_check(device, kind, seed, chain0, n, c0.ctypes.data_as(pu64), n_draws, cl.ctypes.data_as(C.POINTER(C.c_uint8)) if cl is not None else None,
+                           cl.size if cl is not None else 0, _dp(out), cons.ctypes.data_as(pu64), flags.ctypes.data_as(pu64) if flags is not None else None) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    res = {"draws": out[:, :n_draws], "consumed": cons}
+    if flags is not None:
+        res.update(ahead=out[:, n_draws:n_draws + 128], window=out[:, n_draws + 128:], flags=flags)
+    return res
 
 
 def device_eval(op, a, b=None, c=None, device=0):

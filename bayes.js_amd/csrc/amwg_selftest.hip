@@ -27,6 +27,87 @@ __global__ void two_valued_check_kernel(const uint32_t *tab, int N, int64_t m, c
   out_seq[j] = acc;
 }
 
+// tests only (amwg_stream_check): the product's stream classes, drawn from one by one.  Chain c has id chain0 + c and starts at consumed0[c]; the lanes past the
+// last chain of a wavefront shadow chain n_chains - 1, as the step kernels' dead lanes do, so that every cross-lane read has its 64 lanes.
+__global__ void stream_chain_kernel(uint64_t seed, uint64_t chain0, int64_t n_chains, const uint64_t *consumed0, int64_t n_draws, double *out, uint64_t *consumed_out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_chains) return;
+  ChainStream s;
+  s.init(seed, chain0 + (uint64_t)c, consumed0[c]);
+  for (int64_t i = 0; i < n_draws; ++i) out[c * n_draws + i] = s.next();
+  consumed_out[c] = s.n;
+}
+
+template <int G>
+__global__ void stream_coop_kernel(uint64_t seed, uint64_t chain0, int64_t n_chains, const uint64_t *consumed0, int64_t n_draws, double *out, uint64_t *consumed_out) {
+  constexpr int L = CoopStream<G>::L;
+  const int tid = (int)threadIdx.x;      // (64-thread workgroups: one wavefront)
+  int64_t c = (int64_t)blockIdx.x * (64 / L) + tid / L;
+  const bool writer = c < n_chains && (tid & (L - 1)) == 0;
+  if (c >= n_chains) c = n_chains - 1;
+  CoopStream<G> s;
+  s.init(seed, chain0 + (uint64_t)c, consumed0[c], tid);
+  for (int64_t i = 0; i < n_draws; ++i) {
+    const double u = s.next();
+    if (writer) out[c * n_draws + i] = u;
+  }
+  if (writer) consumed_out[c] = s.consumed();
+}
+
+// the one-lane stream under a caller's sequence of next() and next_pair() calls (the same sequence for every chain; their starting parities differ)
+__global__ void stream_pair_kernel(uint64_t seed, uint64_t chain0, int64_t n_chains, const uint64_t *consumed0, int64_t n_draws, const uint8_t *calls, int64_t n_calls,
+                                   double *out, uint64_t *consumed_out) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_chains) return;
+  CoopStream<1> s;
+  s.init(seed, chain0 + (uint64_t)c, consumed0[c], (int)threadIdx.x);
+  double *o = out + c * n_draws;
+  int64_t k = 0;
+  for (int64_t j = 0; j < n_calls; ++j) {
+    if (calls[j]) {
+      if (k + 2 > n_draws) break;      // (the host has checked that the calls add up to n_draws)
+      double a, b;
+      s.next_pair(a, b);
+      o[k++] = a;
+      o[k++] = b;
+    } else {
+      if (k + 1 > n_draws) break;
+      o[k++] = s.next();
+    }
+  }
+  consumed_out[c] = s.consumed();
+}
+
+// a chain per wavefront on the window stream; with_at: what a sweep does after its draws -- position(), ensure_b(), per-lane reads of the 128 uniforms ahead --, the
+// flag words at each stage, and the whole window after a shift() and the next ensure_b()
+__global__ void stream_window_kernel(uint64_t seed, uint64_t chain0, const uint64_t *consumed0, int64_t n_draws, int with_at, int64_t width, double *out,
+                                     uint64_t *consumed_out, uint64_t *flags) {
+  __shared__ double window[256];
+  const int64_t c = (int64_t)blockIdx.x;
+  const int lane = (int)threadIdx.x;
+  WindowStream s;
+  s.init(seed, chain0 + (uint64_t)c, consumed0[c], lane, window);
+  __syncthreads();
+  double *o = out + c * width;
+  for (int64_t i = 0; i < n_draws; ++i) {
+    const double u = s.next();
+    if (lane == 0) o[i] = u;
+  }
+  if (lane == 0) consumed_out[c] = s.consumed();
+  if (!with_at) return;
+  uint64_t *f = flags + c * 12;
+  const uint32_t p = s.position();
+  s.ensure_b();
+  if (lane == 0) { f[0] = s.EA; f[1] = s.OA; f[2] = s.EB; f[3] = s.OB; }
+  o[n_draws + lane] = s.at(p + (uint32_t)lane);
+  o[n_draws + 64 + lane] = s.at(p + 64u + (uint32_t)lane);
+  s.shift();
+  if (lane == 0) { f[4] = s.EA; f[5] = s.OA; f[6] = s.EB; f[7] = s.OB; }
+  s.ensure_b();
+  if (lane == 0) { f[8] = s.EA; f[9] = s.OA; f[10] = s.EB; f[11] = s.OB; }
+  for (int k = 0; k < 4; ++k) o[n_draws + 128 + 64 * k + lane] = s.at((uint32_t)(64 * k + lane));
+}
+
 extern "C" {
 double amwg_pow(double x, double y) { return pow_v8(x, y); }
 double amwg_log1p(double x) { return log1p_v8(x); }
@@ -76,6 +157,57 @@ int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out_fast_forward, d[3].p, (size_t)m * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_term_by_term, d[4].p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+int amwg_stream_check(int32_t device, int32_t kind, uint64_t seed, uint64_t chain0, int64_t n_chains, const uint64_t *consumed0, int64_t n_draws,
+                      const uint8_t *calls, int64_t n_calls, double *out, uint64_t *consumed_out, uint64_t *flags) {
+  const bool coop = kind == 1 || kind == 2 || kind == 4 || kind == 8 || kind == 16 || kind == 32 || kind == 64;
+  if (!(kind == 0 || coop || kind == 100 || kind == 200 || kind == 201)) return amwg_fail(AMWG_EINVAL, "amwg_stream_check: unknown kind %d", kind);
+  if (!consumed0 || !out || !consumed_out || (kind == 201) != (flags != nullptr) || (kind == 100) != (calls != nullptr))
+    return amwg_fail(AMWG_EINVAL, "amwg_stream_check: null argument, or flags / calls given to a kind that has none");
+  const int64_t kMax = (int64_t)1 << 28;
+  if (n_chains < 1 || n_draws < 0 || n_chains > kMax || n_draws > kMax || n_calls < 0 || n_calls > kMax) return amwg_fail(AMWG_EINVAL, "amwg_stream_check: bad shape");
+  const int64_t width = n_draws + (kind == 201 ? 384 : 0);
+  if (width > kMax / n_chains) return amwg_fail(AMWG_EINVAL, "amwg_stream_check: bad shape");
+  if (kind == 100) {
+    int64_t total = 0;
+    for (int64_t j = 0; j < n_calls; ++j) total += calls[j] ? 2 : 1;
+    if (total != n_draws) return amwg_fail(AMWG_EINVAL, "amwg_stream_check: the calls draw %lld uniforms, not n_draws = %lld", (long long)total, (long long)n_draws);
+  }
+  TRYB(use_device(device));
+  DevBuf dc0, dout, dcons, dflags, dcalls;
+  const size_t C = (size_t)n_chains;
+  HIP_TRY(dc0.alloc(C * 8));
+  HIP_TRY(dout.alloc(C * (size_t)width * 8));
+  HIP_TRY(dcons.alloc(C * 8));
+  HIP_TRY(hipMemcpy(dc0.p, consumed0, C * 8, hipMemcpyHostToDevice));
+  if (flags) HIP_TRY(dflags.alloc(C * 12 * 8));
+  if (calls) {
+    HIP_TRY(dcalls.alloc((size_t)n_calls));
+    if (n_calls) HIP_TRY(hipMemcpy(dcalls.p, calls, (size_t)n_calls, hipMemcpyHostToDevice));
+  }
+  const uint64_t *c0 = dc0.as<uint64_t>();
+  double *o = dout.as<double>();
+  uint64_t *co = dcons.as<uint64_t>();
+  const dim3 wave(64);
+  auto per_wave = [&](int chains_per_wave) { return dim3((unsigned)((n_chains + chains_per_wave - 1) / chains_per_wave)); };
+  switch (kind) {
+    case 0: hipLaunchKernelGGL(stream_chain_kernel, per_wave(64), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 1: hipLaunchKernelGGL(stream_coop_kernel<1>, per_wave(64), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 2: hipLaunchKernelGGL(stream_coop_kernel<2>, per_wave(32), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 4: hipLaunchKernelGGL(stream_coop_kernel<4>, per_wave(16), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 8: hipLaunchKernelGGL(stream_coop_kernel<8>, per_wave(8), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 16: hipLaunchKernelGGL(stream_coop_kernel<16>, per_wave(4), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 32: hipLaunchKernelGGL(stream_coop_kernel<32>, per_wave(2), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 64: hipLaunchKernelGGL(stream_coop_kernel<64>, per_wave(1), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, o, co); break;
+    case 100: hipLaunchKernelGGL(stream_pair_kernel, per_wave(64), wave, 0, 0, seed, chain0, n_chains, c0, n_draws, dcalls.as<uint8_t>(), n_calls, o, co); break;
+    default: hipLaunchKernelGGL(stream_window_kernel, per_wave(1), wave, 0, 0, seed, chain0, c0, n_draws, (int)(kind == 201), width, o, co, dflags.as<uint64_t>()); break;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout.p, C * (size_t)width * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(consumed_out, dcons.p, C * 8, hipMemcpyDeviceToHost));
+  if (flags) HIP_TRY(hipMemcpy(flags, dflags.p, C * 12 * 8, hipMemcpyDeviceToHost));
   return AMWG_OK;
 }
 

@@ -175,6 +175,13 @@ function nest(flat, offset, dim) {          // row-major flat values -> nested a
 // the state object they share with the caller, {state, fixed: [{name, dim, len, flat}]}
 const SHARED = Symbol('amwg.shared_state');
 
+// The id of a shard's first chain: options.chain_offset (a Number or a BigInt, validated by the constructor) + the shard's offset among the chains, without mixing
+// the two types: a Number while the sum is exact in one, a BigInt above (the addon takes either).
+function shard_chain_offset(chain_offset, offset) {
+  if (typeof chain_offset !== 'bigint' && Number.isSafeInteger(chain_offset + offset)) return chain_offset + offset;
+  return BigInt(chain_offset) + BigInt(offset);
+}
+
 function AmwgSampler(params, log_post, data, options) {
   options = options || {};
   const opt = (k, d) => (options.hasOwnProperty(k) && options[k] !== undefined && options[k] !== null) ? options[k] : d;
@@ -258,6 +265,12 @@ function AmwgSampler(params, log_post, data, options) {
   // silently become another key)
   if (!(typeof this.seed === 'bigint' ? (this.seed >= 0n && this.seed < 18446744073709551616n) : (Number.isSafeInteger(this.seed) && this.seed >= 0)))
     throw 'AmwgSampler (MI355X): options.seed must be a non-negative integer (number up to 2^53 - 1, or BigInt below 2^64), got ' + String(this.seed);
+  // the id of the first chain is an unsigned 64-bit integer like the key (the Philox counter's words c2, c3): the same two forms, and the last chain's id below 2^64
+  this.chain_offset = opt('chain_offset', 0);
+  if (!(typeof this.chain_offset === 'bigint' ? (this.chain_offset >= 0n && this.chain_offset < 18446744073709551616n) : (Number.isSafeInteger(this.chain_offset) && this.chain_offset >= 0)))
+    throw 'AmwgSampler (MI355X): options.chain_offset must be a non-negative integer (number up to 2^53 - 1, or BigInt below 2^64), got ' + String(this.chain_offset);
+  if (BigInt(this.chain_offset) + BigInt(this.chains) > 18446744073709551616n)
+    throw 'AmwgSampler (MI355X): options.chain_offset + options.chains must not exceed 2^64, got ' + String(this.chain_offset) + ' + ' + this.chains;
   const devices = opt('devices', [opt('device', 0)]);
   // the model: a built-in family, or the closure translated to HIP (compiled by the addon with hiprtc)
   let desc = null, user = null;
@@ -307,7 +320,7 @@ function AmwgSampler(params, log_post, data, options) {
                                                     : Object.assign({}, user, { arrays: userSets[firstDataset] }));
     const create = user ? (userSets && nUnits > 1 ? N.createUserDatasets : N.createUser) : (dsDescs ? (unequal ? N.createDatasetsRagged : N.createDatasets) : N.create);
     const handle = create(userHere || (dsDescs ? slice : desc), descs, Float64Array.from(init), compOpts, {
-      chains: count, seed: this.seed, chain_offset: opt('chain_offset', 0) + offset, device: devices[r],
+      chains: count, seed: this.seed, chain_offset: shard_chain_offset(this.chain_offset, offset), device: devices[r],
       lanes_per_chain: lanes, block_threads: opt('block_threads', 0),
       steps_per_launch: opt('steps_per_launch', 0), exact_division: opt('exact_division', 0), group_local: opt('group_local', 0) ? 1 : 0, full_evaluation: Number(opt('full_evaluation', 0)) | 0, test_bound_shift: Number(opt('test_bound_shift', 0)) | 0,
       sufficient_statistics: opt('sufficient_statistics', 0) ? 1 : 0 });
@@ -1028,5 +1041,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

@@ -30,6 +30,21 @@ int amwg_ld_device(int32_t device, int64_t n, const double *records, double *out
 int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_t m, const double *acc0, const double *l1, const double *l0,
                               double *out_fast_forward, double *out_term_by_term);
 
+/* The product's own uniform-stream classes (csrc/amwg_philox.h ChainStream, csrc/amwg_kernel.h CoopStream<G>, csrc/amwg_window.h WindowStream) driven one by one
+ * on the device: chain i < n_chains has id chain0 + i under `seed` and starts with consumed0[i] uniforms consumed (host array), so that the chains sharing a
+ * wavefront stand at different positions and parities.  kind:
+ *     0                          ChainStream::next, a chain per thread
+ *     1, 2, 4, 8, 16, 32, 64     CoopStream<kind>::next, `kind` lanes per chain and 64 / kind chains per wavefront (64: the readlane path)
+ *     100                        CoopStream<1> under calls[n_calls] (host bytes; 0: next(), 1: next_pair()), which must add up to n_draws uniforms
+ *     200                        WindowStream::next, a chain per wavefront
+ *     201                        the same, then position() = p, ensure_b(), at(p + i) for i < 128, shift(), ensure_b(), at(q) for q < 256
+ * out[n_chains][width] (host): the n_draws uniforms in the order drawn; width = n_draws, for kind 201 n_draws + 128 + 256 (the two runs of at()).
+ * consumed_out[n_chains]: consumed() after the n_draws draws.  flags[n_chains][12] (kind 201 only, else NULL): EA, OA, EB, OB after the first ensure_b(), after
+ * shift(), and after the second ensure_b().  calls is NULL unless kind is 100.
+ * Refused before a device is opened: null pointers, an unknown kind, n_chains < 1, n_draws < 0, sizes beyond 2^28 doubles, calls that do not add up. */
+int amwg_stream_check(int32_t device, int32_t kind, uint64_t seed, uint64_t chain0, int64_t n_chains, const uint64_t *consumed0, int64_t n_draws,
+                      const uint8_t *calls, int64_t n_calls, double *out, uint64_t *consumed_out, uint64_t *flags);
+
 /* the kernel of amwg_last_sample_dataset_quantiles on a caller's array draws[rows][PR][C] (host), D datasets of C / D chains each: out[D][PR][n_probs] (host).
  * The arguments are checked before a device is opened. */
 int amwg_dataset_quantiles_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D,

@@ -11,6 +11,7 @@ const path = require('path');
 const h = require('./ref_harness.js');
 const OUT = path.join(__dirname, '..', 'tests', 'golden');
 const SEED = 20260925, DSEED = 20260925;
+const KEY64 = 8765432109876543, CHAINS64 = [0, 4294967295, 4294967296, 4294967301];
 
 const CASES = [
   // BASELINE.json configs[0]: README.md:20 data, burn 1000 + 5000 draws
@@ -55,6 +56,16 @@ const CASES = [
     seed: SEED, chains: [0, 1], schedule: [{ op: 'burn', n: 150 }, { op: 'sample', n: 150, keep: 50 }] },
   { name: 'cfg5_full', model: 'pois_glm', N: 50000, data_seed: DSEED,
     seed: SEED, chains: [0, 65535], schedule: [{ op: 'burn', n: 150 }, { op: 'sample', n: 150, keep: 10 }] },
+  // every family under a key and chain ids that need their high words: a seed between 2^32 and 2^53 (what an unseeded run draws, mcmc.js of the port),
+  // chain ids on either side of 2^32 -- philox.js' k1 and c3 are non-zero here, as in no case above
+  { name: 'normal_key64', model: 'normal', N: 100, data_seed: DSEED + 6, store_data: true,
+    seed: KEY64, chains: CHAINS64, schedule: [{ op: 'burn', n: 100 }, { op: 'sample', n: 60 }] },
+  { name: 'beta_bern_key64', model: 'beta_bern', N: 300, data_seed: DSEED + 6, store_data: true,
+    seed: KEY64, chains: CHAINS64, schedule: [{ op: 'burn', n: 100 }, { op: 'sample', n: 60 }] },
+  { name: 'hier_key64', model: 'hier_normal', N: 300, G: 5, data_seed: DSEED + 6, store_data: true,
+    seed: KEY64, chains: CHAINS64, schedule: [{ op: 'burn', n: 100 }, { op: 'sample', n: 60, keep: 20 }] },
+  { name: 'glm_key64', model: 'pois_glm', N: 200, data_seed: DSEED + 6, store_data: true,
+    seed: KEY64, chains: CHAINS64, schedule: [{ op: 'burn', n: 100 }, { op: 'sample', n: 60, keep: 20 }] },
 ];
 
 function checksum(data) { // order-sensitive sum so the Python twin of synth.js can be checked at full N

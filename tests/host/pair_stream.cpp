@@ -42,7 +42,19 @@ static bool same(double a, double b) { return memcmp(&a, &b, 8) == 0; }
 
 int main(int argc, char **argv) {
   const long n_uniforms = argc > 1 ? atol(argv[1]) : 10000;
-  const uint64_t seed = 0x9E3779B97F4A7C15ull, chain = (1ull << 32) + 12345u, base = 0xFFFFFFFEull;      // (the block number crosses 2^32 / 2 early: both counter words move)
+  // (the block number crosses 2^31 early.  argv[2], [3], [4]: another first uniform, seed and chain id -- tests/test_pair_stream.py starts on either side of the
+  // carry of the block number into its high word, uniform 2^33, under several keys; argv[5] (a uniform's index): prints ChainStream's value there, for a check
+  // against the numpy twin)
+  const uint64_t base = argc > 2 ? strtoull(argv[2], nullptr, 0) : 0xFFFFFFFEull;
+  const uint64_t seed = argc > 3 ? strtoull(argv[3], nullptr, 0) : 0x9E3779B97F4A7C15ull, chain = argc > 4 ? strtoull(argv[4], nullptr, 0) : (1ull << 32) + 12345u;
+  if (argc > 5) {
+    ChainStream at;
+    at.init(seed, chain, strtoull(argv[5], nullptr, 0));
+    const double u = at.next();
+    uint64_t bits;
+    memcpy(&bits, &u, 8);
+    printf("uniform=%016llx\n", (unsigned long long)bits);
+  }
   long bad = 0, patterns = 0, draws = 0;
   auto fail = [&](const char *what, int start, int len, unsigned bits, uint64_t at) {
     if (bad++ < 10) printf("FAIL start=%d pattern(len=%d,bits=%u) at uniform %llu: %s\n", start, len, bits, (unsigned long long)at, what);

@@ -154,6 +154,32 @@ if (reordered !== null) {
 // the Philox key must be an unsigned integer: anything else would silently become another key
 for (const bad of [-1, 1.5, NaN, Infinity, 2 ** 53, -5n, 2n ** 64n])
   assert.throws(() => new mcmc.AmwgSampler(params, readme_normal, data10, { seed: bad }), (e) => typeof e === 'string' && /options\.seed must be a non-negative integer/.test(e));
+// ... and so must the id of the first chain (the counter's words c2, c3): a negative one became 0 and a fraction was cut off in the addon, a BigInt threw a TypeError
+for (const bad of [-1, 1.5, NaN, Infinity, 2 ** 53, -5n, 2n ** 64n])
+  assert.throws(() => new mcmc.AmwgSampler(params, readme_normal, data10, { seed: 1, chain_offset: bad }), (e) => typeof e === 'string' && /options\.chain_offset must be a non-negative integer/.test(e));
+assert.throws(() => new mcmc.AmwgSampler(params, readme_normal, data10, { seed: 1, chains: 4, chain_offset: 2n ** 64n - 3n }), (e) => typeof e === 'string' && /options\.chain_offset \+ options\.chains must not exceed 2\^64/.test(e));
+// the first chain of every shard: Number + Number while that is exact, BigInt above, never a mixture
+assert.strictEqual(mcmc.shard_chain_offset(0, 0), 0);
+assert.strictEqual(mcmc.shard_chain_offset(4294967293, 8), 4294967301);
+assert.strictEqual(mcmc.shard_chain_offset(2 ** 53 - 1, 0), 2 ** 53 - 1);
+assert.strictEqual(mcmc.shard_chain_offset(2 ** 53 - 1, 2), 2n ** 53n + 1n);
+assert.strictEqual(mcmc.shard_chain_offset(2n ** 63n + 5n, 0), 2n ** 63n + 5n);
+assert.strictEqual(mcmc.shard_chain_offset(2n ** 63n + 5n, 32), 2n ** 63n + 37n);
+assert.strictEqual(mcmc.shard_chain_offset(2n ** 64n - 64n, 63), 2n ** 64n - 1n);
+// a BigInt offset on two shards (both on device 0) is accepted: the constructor gets as far as opening the device (without one: AMWG_EHIP, not a TypeError), and
+// with one the second shard starts 32 chains on
+{
+  let two = null;
+  try {
+    two = new mcmc.AmwgSampler(params, readme_normal, data10, { seed: 2n ** 64n - 1n, chains: 64, chain_offset: 2n ** 63n + 5n, devices: [0, 0] });
+  } catch (e) {
+    assert.ok(e instanceof Error && e.code === 'AMWG_EHIP', String(e));
+  }
+  if (two !== null) {
+    assert.deepStrictEqual(two._shards.map((sh) => [sh.offset, sh.count]), [[0, 32], [32, 32]]);
+    two.close();
+  }
+}
 assert.throws(() => new mcmc.AmwgSampler({ mu: { type: 'binary' }, sigma: {} }, readme_normal, data10), (e) => typeof e === 'string' && /has no binary parameters/.test(e));
 assert.throws(() => new mcmc.AmwgSampler({ mu: { type: 'complex', init: 1 }, sigma: {} }, readme_normal, data10), (e) => e === "AmwgStepper can't handle parameter mu with type complex");
 

@@ -216,4 +216,36 @@ checkAgainstGolden('glm_small', (g, rec) => new mcmc.AmwgSampler(
   assert.deepStrictEqual(a.acc, c.acc);
   for (const nm of ['theta', 'mu', 'sigma']) assert.deepStrictEqual(Array.from(a.smp[nm]), Array.from(c.smp[nm]));      // same decisions => same draws
 }
+// ---- 8. keys and chain ids that need their high words (tests/golden/*_key64.json: a Number seed between 2^32 and 2^53, chain ids on either side of 2^32)
+{
+  const bern = function (state, data) { var lp = 0; lp += ld.beta(state.theta, 2, 2); var n = data.x.length; for (var i = 0; i < n; i++) { lp += ld.bern(data.x[i], state.theta); } return lp; };
+  const opts = (g, rec) => ({ seed: g.case.seed, chain_offset: rec.chain, lanes_per_chain: 1 });
+  checkAgainstGolden('normal_key64', (g, rec) => new mcmc.AmwgSampler({ mu: { type: 'real' }, sigma: { type: 'real', lower: 0 } }, models.normal(), g.data.x, opts(g, rec)), ['mu', 'sigma']);
+  checkAgainstGolden('beta_bern_key64', (g, rec) => new mcmc.AmwgSampler({ theta: { type: 'real', lower: 0, upper: 1 } }, bern, { x: g.data.x }, opts(g, rec)), ['theta']);
+  checkAgainstGolden('hier_key64', (g, rec) => new mcmc.AmwgSampler(
+    { theta: { type: 'real', dim: [g.data.G] }, mu: { type: 'real' }, sigma: { type: 'real', lower: 0, init: 1 } },
+    models.hier_normal(), { y: g.data.y, g: g.data.g, G: g.data.G }, opts(g, rec)), ['theta', 'mu', 'sigma']);
+  checkAgainstGolden('glm_key64', (g, rec) => new mcmc.AmwgSampler(
+    { beta: { type: 'real', dim: [8], init: 0 }, cp: { type: 'int', lower: 0, upper: g.data.y.length - 1 } },
+    models.pois_glm(), { X: g.data.X, y: g.data.y }, opts(g, rec)), ['beta', 'cp']);
+  // one sampler from chain id 2^32 - 1 on: its local chains 0, 1 and 6 are the golden's chains 4294967295, 4294967296 and 4294967301
+  const g = golden('normal_key64');
+  assert.strictEqual(g.case.seed, 8765432109876543);
+  const s = new mcmc.AmwgSampler({ mu: { type: 'real' }, sigma: { type: 'real', lower: 0 } }, models.normal(), g.data.x, { seed: g.case.seed, chain_offset: 4294967295, chains: 7, lanes_per_chain: 1 });
+  s.burn(100);
+  const smp = s.sample(60);
+  for (const rec of g.chains.filter((r) => r.chain >= 4294967295)) {
+    const c = rec.chain - 4294967295;
+    rec.samples[0].draws.forEach((row, t) => assert.deepStrictEqual([smp.mu[t * 7 + c], smp.sigma[t * 7 + c]], row, 'chain ' + rec.chain + ' draw ' + t));
+    assert.strictEqual(s.diagnostics()[0].uniforms[c], rec.uniforms);
+  }
+  s.close();
+  // a BigInt key with every bit set, chain ids that carry into the high word at local chain 3: the pytest wrapper (tests/test_js_frontend.py) compares this line with
+  // the same sampler made through the C ABI from Python, and with the oracle
+  const b = new mcmc.AmwgSampler({ mu: { type: 'real' }, sigma: { type: 'real', lower: 0 } }, models.normal(), g.data.x, { seed: 2n ** 64n - 1n, chain_offset: 2 ** 32 - 3, chains: 8, lanes_per_chain: 1 });
+  b.burn(30);
+  const first = b.sample(5);
+  console.log('key64 ' + JSON.stringify({ uniforms: Array.from(b.diagnostics()[0].uniforms), mu: Array.from(first.mu), sigma: Array.from(first.sigma) }));
+  b.close();
+}
 console.log('gpu frontend ok');

@@ -55,6 +55,66 @@ def test_host_uniform_stream_matches_twin():
     assert L.amwg_uniform(7, (1 << 32) + 5, 3) == u[3]
 
 
+def _stream_grid():
+    """(seed, chain, index): each of k1 (seed >> 32), c3 (chain >> 32) and b_hi (index >> 33) non-zero alone and together, indices of either parity, and the indices
+    around the carry of the block number into its high word that tests/stream_reference.py lists"""
+    import stream_reference as R
+    seeds, chains = [20260925] + R.SEEDS + [8765432109876543], [3, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 5, 2 ** 63 + 5, 2 ** 64 - 1]
+    indices = [0, 1, 2, 129] + [2 * (2 ** 32 - k) + p for k in R.CARRY_K for p in (0, 1)] + [2 ** 33, 2 ** 33 + 1, 2 ** 52 - 1, 2 ** 53 - 2, 2 ** 62 - 3, 2 ** 64 - 1]
+    return [(s, c, i) for s in seeds for c in chains for i in indices]
+
+
+def _bits(v):
+    return np.float64(v).tobytes()[::-1].hex()
+
+
+def _oracle_on(grid):
+    import oracle_lib
+    O = oracle_lib.lib()
+    return [_bits(O.orc_uniform(s, c, i)) for s, c, i in grid]
+
+
+def test_three_host_streams_agree_on_every_word_of_counter_and_key():
+    """The product's host function amwg_uniform, the oracle's orc_uniform and the numpy twin synth.uniforms, pairwise, as bits."""
+    import stream_reference as R
+    grid = _stream_grid()
+    assert any(s >> 32 and not c >> 32 and not i >> 33 for s, c, i in grid) and any(c >> 32 and not s >> 32 and not i >> 33 for s, c, i in grid)
+    assert any(i >> 33 and not s >> 32 and not c >> 32 for s, c, i in grid) and any(s >> 32 and c >> 32 and i >> 33 for s, c, i in grid)
+    L = amwg_ctypes.lib()
+    product = [_bits(L.amwg_uniform(s, c, i)) for s, c, i in grid]
+    oracle = _oracle_on(grid)
+    twin = [_bits(R.uniforms(s, c, i, 1)[0]) for s, c, i in grid]
+    assert product == oracle
+    assert twin == oracle
+    assert twin == product
+    assert len(set(oracle)) == len(grid)      # (no word is ignored by all three alike: every entry of the grid gives another uniform)
+
+
+@pytest.mark.skipif(__import__("shutil").which("node") is None, reason="node is not installed")
+def test_philox_js_agrees_with_the_oracle_on_every_word_of_counter_and_key(tmp_path):
+    """oracle/philox.js seeds the unmodified reference for every golden: against orc_uniform (which the test above ties to the other two) on the same grid, seeds
+    and chain ids as BigInt above 2^53 and as Number below.  philox.js keeps its position in a Number: the indices below 2^53."""
+    import json
+    import subprocess
+    grid = [g for g in _stream_grid() if g[2] < 2 ** 53 - 1]
+    assert any(i >> 33 for _, _, i in grid) and any(s > 2 ** 53 for s, _, _ in grid) and any(2 ** 32 <= s < 2 ** 53 for s, _, _ in grid)
+    f = tmp_path / "grid.json"
+    f.write_text(json.dumps([[str(v) for v in g] for g in grid]))
+    p = subprocess.run(["node", os.path.join(ROOT, "tests", "js", "philox_cli.js"), str(f)], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.split() == _oracle_on(grid)
+
+
+def test_stream_check_refuses_bad_arguments_before_a_device_is_opened():
+    """include/amwg_selftest.h amwg_stream_check: an unknown kind, calls that are missing, that do not add up to n_draws, or that are given to a kind that takes none, no
+    chains -- refused with the entry point's own message, on a device number that does not exist"""
+    for kw in (dict(kind=3), dict(kind=amwg_ctypes.STREAM_PAIRS), dict(kind=amwg_ctypes.STREAM_PAIRS, calls=[1, 1], n_draws=5), dict(kind=1, calls=[0]), dict(consumed0=[])):
+        a = dict(kind=1, seed=1, chain0=0, consumed0=[0], n_draws=4, device=10 ** 6)
+        a.update(kw)
+        with pytest.raises(amwg_ctypes.AmwgError, match="amwg_stream_check"):
+            amwg_ctypes.stream_check(**a)
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="GPU present")
 def test_no_cpu_fallback_without_gpu():
     data = synth.normal(100, 1)

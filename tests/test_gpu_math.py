@@ -137,6 +137,16 @@ def test_device_philox_stream():
     assert got.tobytes() == synth.uniforms(20260925, 12345, n).tobytes()
 
 
+def test_device_philox_stream_with_high_words_in_seed_chain_and_index():
+    """the same op with all six words of the counter and the key in use (its arguments travel as doubles: values below 2^53): seed 2^52 + 1, chain 2^32 + 5, from index
+    2^33 + 1 -- an odd start, block numbers past 2^32.  tests/test_gpu_stream_words.py drives the other stream classes, beyond 2^53."""
+    import stream_reference
+    n = 4096
+    seed, chain, start = 2 ** 52 + 1, 2 ** 32 + 5, 2 ** 33 + 1
+    got = A.device_eval(8, np.full(n, float(seed)), np.full(n, float(chain)), float(start) + np.arange(n, dtype=np.float64))
+    assert got.tobytes() == stream_reference.uniforms(seed, chain, start, n).tobytes()
+
+
 def test_device_ld_functions_and_pow_equal_the_reference_goldens():
     """Every scalar ld.* / helper and Math.pow evaluated ON THE DEVICE against the reference's recorded outputs."""
     import ctypes as C

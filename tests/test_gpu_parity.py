@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN_CASES = ["cfg1_heights", "normal_n1000", "cfg2_full", "normal_opts", "beta_bern_n2000", "cfg3_full", "hier_small",
                 "cfg4_full", "glm_small", "cfg5_full", "normal_hyper", "beta_bern_hyper", "beta_bern_hyper2", "hier_hyper", "glm_hyper",
-         "cfg4_theta_bounded", "cfg4_theta_int"]      # (configs[3] with a bounded / an integer theta: updates that draw no accept uniform, rounded proposals)
+         "cfg4_theta_bounded", "cfg4_theta_int",      # (configs[3] with a bounded / an integer theta: updates that draw no accept uniform, rounded proposals)
+         "normal_key64", "beta_bern_key64", "hier_key64", "glm_key64"]      # (a seed above 2^32 and chain ids on either side of 2^32: k1 and c3 of the device's Philox key are non-zero)
 
 
 @pytest.fixture(scope="module")

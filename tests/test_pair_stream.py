@@ -14,3 +14,12 @@ def test_pair_draws_are_two_single_draws_from_every_position_in_every_pattern(tm
                            os.path.join(ROOT, "tests", "host", "pair_stream.cpp"), "-o", exe])
     p = subprocess.run([exe, "10000"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and "patterns=%d " % (3 * 126) in p.stdout and "failures=0" in p.stdout, p.stdout[-2000:]
+    # the same comparison under keys with every word in use, from first uniforms on either side of the carry of the block number into its high word (uniform
+    # 2^33) -- runs that begin before it and cross it, begin on it, begin after it.  Both sides are host builds of the product's code: the value ChainStream gives
+    # at the carry is pinned to the numpy twin as well.
+    import synth
+    for seed, chain in ((0x9E3779B97F4A7C15, 2 ** 32 - 3 + 5), (2 ** 64 - 1, 2 ** 63 + 5), (2 ** 32, 2 ** 32)):
+        for base in (2 ** 33 - 40, 2 ** 33 - 2, 2 ** 33, 2 ** 33 + 4):
+            p = subprocess.run([exe, "96", str(base), str(seed), str(chain), str(2 ** 33 + 1)], capture_output=True, text=True, timeout=120)
+            assert p.returncode == 0 and "patterns=%d " % (3 * 126) in p.stdout and "failures=0" in p.stdout, (hex(seed), hex(chain), base, p.stdout[-2000:])
+            assert "uniform=%016x\n" % int(synth.uniforms(seed, chain, 2, 2 ** 33)[1:].view("<u8")[0]) in p.stdout, (hex(seed), hex(chain), p.stdout[-300:])
