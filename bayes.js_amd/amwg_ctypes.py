@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_waic_check", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -74,6 +74,7 @@ def lib():
         L.amwg_last_sample_dataset_diagnostics.argtypes = [vp, pd, pd]
         L.amwg_last_sample_dataset_quantiles.argtypes = [vp, pd, i32, pd]
         L.amwg_last_sample_dataset_hpd.argtypes = [vp, pd, i32, pd]
+        L.amwg_last_sample_dataset_waic.argtypes = [vp, pd, pi32, pd]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -178,6 +179,7 @@ def selftest_lib():
         L.amwg_dataset_quantiles_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_hpd_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_hpd_limits.argtypes = [i32, i64, C.POINTER(i64), C.POINTER(i64)]
+        L.amwg_waic_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
@@ -550,6 +552,29 @@ class Sampler:
                             "(dataset_hpd)" % self.D)      # (the words of amwg_refuse_pooled; the library has no pooled call to ask)
         return self.dataset_hpd(probs)[0]
 
+    def dataset_waic(self, pointwise=False):
+        """-> dict(summary [datasets][4] = elpd_waic, se, p_waic, lppd; high [datasets] = observations with p_i > 0.4; with pointwise=True also
+        pointwise [datasets][n_max][2] = lppd_i, p_i, NaN beyond a dataset's n_obs): WAIC per dataset by the rule of include/amwg.h, the families' pointwise
+        terms over the stored draws on the device (amwg_last_sample_dataset_waic)"""
+        summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
+        pw = np.empty((self.D, max(self.dataset_n_obs()), 2)) if pointwise else None
+        _check(lib().amwg_last_sample_dataset_waic(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
+        out = {"summary": summary, "high": high}
+        if pointwise:
+            out["pointwise"] = pw
+        return out
+
+    def waic(self, pointwise=False):
+        """-> dict(elpd_waic, se, p_waic, lppd, high[, pointwise [n_obs][2]]): dataset_waic() of an ordinary sampler; a dataset sampler refuses the pooled question"""
+        if self.D > 1:
+            raise AmwgError("amwg error -1: waic: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_waic "
+                            "(dataset_waic)" % self.D)      # (the words of amwg_refuse_pooled; the library has no pooled call to ask)
+        r = self.dataset_waic(pointwise)
+        out = dict(zip(("elpd_waic", "se", "p_waic", "lppd"), r["summary"][0].tolist()), high=int(r["high"][0]))
+        if pointwise:
+            out["pointwise"] = r["pointwise"][0]
+        return out
+
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)
         assert st.shape == (self.P, self.C)
@@ -746,6 +771,73 @@ def hpd_check(draws, D, probs, device=0):
     L = selftest_lib()
     if L.amwg_hpd_check(device, _dp(dr), rows, PR, Cn, D, _dp(pr), pr.size, _dp(out)) != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
+
+
+def waic_totals(pointwise, n_obs):
+    """The finish of amwg_last_sample_dataset_waic restated (include/amwg.h): pointwise [n_max][2] = lppd_i, p_i of ONE dataset with n_obs observations
+    -> (summary [4] = elpd_waic, se, p_waic, lppd; high).  Running sums from 0.0 in index order, one IEEE operation each: the bytes of the library's."""
+    pw = np.asarray(pointwise, dtype=np.float64)
+    n = int(n_obs)
+    lppd = p = elpd = np.float64(0.0)
+    high = 0
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            lppd = lppd + pw[i, 0]
+            p = p + pw[i, 1]
+            elpd = elpd + (pw[i, 0] - pw[i, 1])
+            high += 1 if pw[i, 1] > 0.4 else 0
+        centre = elpd / np.float64(n)
+        ss = np.float64(0.0)
+        for i in range(n):
+            e = (pw[i, 0] - pw[i, 1]) - centre
+            ss = ss + e * e
+        se = np.float64(np.nan) if n == 1 else np.sqrt(np.float64(n) * ss / np.float64(n - 1))
+    return np.array([elpd, se, p, lppd]), high
+
+
+def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_waic on any array draws [rows][PR][C] and the data of `specs`, one dict(model, n_obs, data{x[,y,g]}[, G, K])
+    per dataset (one family; ragged sizes allowed), C / len(specs) columns each -> dict(summary [D][4], high [D][, pointwise [D][n_max][2]][, loglik [D][S][n_max],
+    the terms themselves in draw order s = row * (C / D) + chain]) (amwg_waic_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: waic_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    D = len(specs)
+    keep = []
+    mds = (ModelDesc * max(1, D))()
+    for k, q in enumerate(specs):
+        d = q["data"]
+        mds[k].model, mds[k].n_obs = MODEL_ID[q["model"]], int(q["n_obs"])
+        x = np.ascontiguousarray(d["x"], dtype=np.float64)
+        keep.append(x)
+        mds[k].x = _dp(x)
+        if "y" in d:
+            y = np.ascontiguousarray(d["y"], dtype=np.float64)
+            keep.append(y)
+            mds[k].y = _dp(y)
+        if "g" in d:
+            g = np.ascontiguousarray(d["g"], dtype=np.int32)
+            keep.append(g)
+            mds[k].g = g.ctypes.data_as(C.POINTER(C.c_int32))
+        mds[k].G, mds[k].K = int(q.get("G", 0)), int(q.get("K", 0))
+    n_max = max([int(q["n_obs"]) for q in specs] + [1])
+    S = rows * (Cn // D) if D and Cn % D == 0 else 0
+    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    pw = np.empty((max(1, D), n_max, 2)) if pointwise else None
+    ll = np.empty((max(1, D), S, n_max)) if loglik and S * n_max * max(1, D) <= (1 << 24) else None
+    if loglik and ll is None:
+        ll = np.empty(1)      # (refused by the library before it is written: more than 2^24 doubles)
+    L = selftest_lib()
+    if L.amwg_waic_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
+                         _dp(pw) if pointwise else None, _dp(ll) if loglik else None) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    out = {"summary": summary, "high": high}
+    if pointwise:
+        out["pointwise"] = pw
+    if loglik:
+        out["loglik"] = ll
     return out
 
 

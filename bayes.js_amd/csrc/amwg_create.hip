@@ -398,6 +398,21 @@ static int upload_bernoulli_data(amwg_sampler *s, const amwg_model_desc *models,
   TRYB(upload_datasets(s, D, [&](int k) { return xw[k].size(); }, [&](int k) { return xw[k].data(); }, consts, &DatasetConsts::off_xw, &dxw));
   s->d.xb = dxb;
   s->d.xw = dxw;
+  // which observations are neither 0 nor 1 (xb holds 0 there): no step kernel asks -- has_invalid settles their sum --, the pointwise terms of
+  // amwg_last_sample_dataset_waic do.  Bytes laid out like xb (the same lengths, so off_xb serves both), behind arr[1]; absent while every value is valid
+  bool any_invalid = false;
+  for (int k = 0; k < D; ++k) any_invalid = any_invalid || consts[k].has_invalid;
+  if (any_invalid) {
+    std::vector<std::vector<uint8_t>> bad((size_t)D);
+    for (int k = 0; k < D; ++k) {
+      bad[k].assign((size_t)models[k].n_obs, 0);
+      for (int i = 0; i < models[k].n_obs; ++i) bad[k][i] = !(models[k].x[i] == 1 || models[k].x[i] == 0);
+    }
+    std::vector<DatasetConsts> same(consts);      // (the offsets come out as off_xb's)
+    uint8_t *dbad = nullptr;
+    TRYB(upload_datasets(s, D, [&](int k) { return bad[k].size(); }, [&](int k) { return bad[k].data(); }, same, &DatasetConsts::off_xb, &dbad));
+    s->d.arr[1] = dbad;
+  }
   return AMWG_OK;
 }
 // Poisson family: the design matrix column-major [7][n_d] (a dataset's column stride is its own size), the counts, log(y_i!), and what the bounds of the certified

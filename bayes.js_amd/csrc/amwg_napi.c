@@ -777,6 +777,40 @@ static napi_value DatasetHpd(napi_env env, napi_callback_info info) {
   return o;
 }
 
+/* datasetWaic(handle, bool pointwise) -> {datasets, n_max, n_obs: Int32Array [datasets], summary: Float64Array [datasets][4] (elpd_waic, se, p_waic, lppd),
+ * high: Int32Array [datasets][, pointwise: Float64Array [datasets][n_max][2] (lppd_i, p_i; NaN beyond a dataset's n_obs)]} over the last sample() */
+static napi_value DatasetWaic(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  bool want = false;
+  napi_get_value_bool(env, a[1], &want);
+  const size_t D = (size_t)amwg_num_datasets(s);
+  int32_t *n_obs = NULL, *high = NULL;
+  double *summary = NULL, *pw = NULL;
+  napi_value vn = new_i32(env, D, &n_obs), vh = new_i32(env, D, &high), vs = new_f64(env, D * 4, &summary), vp = NULL;
+  if (!vn || !vh || !vs) return NULL;
+  int rc = amwg_dataset_n_obs(s, n_obs);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  int32_t n_max = 0;
+  for (size_t d = 0; d < D; ++d) n_max = n_obs[d] > n_max ? n_obs[d] : n_max;
+  if (want) { vp = new_f64(env, D * (size_t)n_max * 2, &pw); if (!vp) return NULL; }
+  rc = amwg_last_sample_dataset_waic(s, summary, high, want ? pw : NULL);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "summary", vs);
+  napi_set_named_property(env, o, "high", vh);
+  napi_set_named_property(env, o, "n_obs", vn);
+  if (want) napi_set_named_property(env, o, "pointwise", vp);
+  napi_create_int32(env, (int32_t)D, &t);
+  napi_set_named_property(env, o, "datasets", t);
+  napi_create_int32(env, n_max, &t);
+  napi_set_named_property(env, o, "n_max", t);
+  return o;
+}
+
 /* setHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins): amwg_set_histogram -- arms (null, 0: disarms) a histogram for later summarising calls */
 static napi_value SetHistogram(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -1191,7 +1225,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

@@ -7,6 +7,7 @@
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
 #include "amwg_hpd.h"
+#include "amwg_waic.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
@@ -270,6 +271,96 @@ int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, in
   const size_t before = amwg_hpd_set_budget((size_t)scratch_bytes);
   if (scratch_before) *scratch_before = (int64_t)before;
   return AMWG_OK;
+}
+
+}  // extern "C"
+// one array of every dataset, the copies back to back on 256-byte boundaries as amwg_create.hip lays them (upload_datasets); off[d] in elements
+template <class T, class Len, class Fill>
+static int waic_pack(int D, Len len, Fill fill, std::vector<int64_t> &off, DevBuf &dev) {
+  constexpr size_t align = 256 / sizeof(T);
+  size_t total = 0;
+  off.assign((size_t)D, 0);
+  for (int d = 0; d < D; ++d) { off[(size_t)d] = (int64_t)total; total += (len(d) + align - 1) / align * align; }
+  std::vector<T> packed(total ? total : 1, T(0));
+  for (int d = 0; d < D; ++d) fill(d, packed.data() + off[(size_t)d]);
+  HIP_TRY(dev.alloc(packed.size() * sizeof(T)));
+  HIP_TRY(hipMemcpy(dev.p, packed.data(), packed.size() * sizeof(T), hipMemcpyHostToDevice));
+  return AMWG_OK;
+}
+extern "C" {
+
+int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
+                    int32_t *high, double *pointwise, double *loglik) {
+  static const char *call = "amwg_waic_check";
+  if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
+  TRYB(amwg_waic_shape(call, rows, PR, C, D));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
+  const int model = models[0].model;
+  if (model < AMWG_MODEL_NORMAL || model > AMWG_MODEL_POIS_GLM) return amwg_fail(AMWG_EINVAL, "%s: unknown model %d", call, model);
+  if (model == AMWG_MODEL_HIER_NORMAL && D != 1) return amwg_fail(AMWG_EINVAL, "%s: the hierarchical family runs on one dataset", call);
+  int64_t n_max = 0;
+  for (int d = 0; d < D; ++d) {
+    const amwg_model_desc &m = models[d];
+    if (m.model != model) return amwg_fail(AMWG_EINVAL, "%s: dataset %d is of model %d, dataset 0 of %d", call, d, m.model, model);
+    if (m.n_obs < 1 || !m.x) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: n_obs %d (at least 1) or a null x", call, d, m.n_obs);
+    if (model == AMWG_MODEL_POIS_GLM && (!m.y || m.K != 7)) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: the Poisson family needs y and K = 7", call, d);
+    if (model == AMWG_MODEL_HIER_NORMAL) {
+      if (!m.g || m.G < 1 || m.G > 255) return amwg_fail(AMWG_EINVAL, "%s: the hierarchical family needs g and 1 <= G <= 255", call);
+      for (int i = 0; i < m.n_obs; ++i) if (m.g[i] < 0 || m.g[i] >= m.G) return amwg_fail(AMWG_EINVAL, "%s: g[%d] = %d outside 0..%d", call, i, m.g[i], m.G - 1);
+    }
+    n_max = m.n_obs > n_max ? m.n_obs : n_max;
+  }
+  const int need = model == AMWG_MODEL_NORMAL ? 2 : model == AMWG_MODEL_BETA_BERN ? 1 : model == AMWG_MODEL_HIER_NORMAL ? models[0].G + 2 : 9;
+  if (PR < need) return amwg_fail(AMWG_EINVAL, "%s: the family reads %d components of a draw, the draws hold %d", call, need, PR);
+  if (loglik && (double)D * (double)rows * (double)(C / D) * (double)n_max > 16777216.0) return amwg_fail(AMWG_EINVAL, "%s: loglik of more than 2^24 doubles", call);
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd, dx, dy, dlf, dxb, dbad;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  std::vector<WaicDataset> sets((size_t)D);
+  std::vector<int64_t> off;
+  WaicModel wm{};
+  wm.model = model; wm.G = models[0].G; wm.exact_division = 0;
+  wm.neg_half_log_2pi = -0.5 * log_v8(2 * kPi);
+  for (int d = 0; d < D; ++d) sets[(size_t)d] = WaicDataset{models[d].n_obs, 1, 0, 0, 0, 0};
+  if (model == AMWG_MODEL_NORMAL || model == AMWG_MODEL_HIER_NORMAL) {
+    TRYB((waic_pack<double>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, double *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = models[d].x[i]; }, off, dx)));
+    for (int d = 0; d < D; ++d) {
+      sets[(size_t)d].off_x = off[(size_t)d];
+      bool mid = true;
+      for (int i = 0; i < models[d].n_obs; ++i) mid = mid && (models[d].x[i] == 0.0 || mid_range(std::fabs(models[d].x[i])));
+      sets[(size_t)d].data_mid_range = mid ? 1 : 0;
+    }
+    wm.x = dx.as<double>();
+    if (model == AMWG_MODEL_HIER_NORMAL) {
+      TRYB((waic_pack<uint8_t>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, uint8_t *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = (uint8_t)models[d].g[i]; }, off, dxb)));
+      wm.xb = dxb.as<uint8_t>();
+    }
+  } else if (model == AMWG_MODEL_BETA_BERN) {
+    TRYB((waic_pack<uint8_t>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, uint8_t *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = models[d].x[i] == 1 ? 1 : 0; }, off, dxb)));
+    for (int d = 0; d < D; ++d) sets[(size_t)d].off_xb = off[(size_t)d];
+    wm.xb = dxb.as<uint8_t>();
+    bool any = false;
+    for (int d = 0; d < D; ++d) for (int i = 0; i < models[d].n_obs; ++i) any = any || !(models[d].x[i] == 1 || models[d].x[i] == 0);
+    if (any) {
+      TRYB((waic_pack<uint8_t>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, uint8_t *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = !(models[d].x[i] == 1 || models[d].x[i] == 0); }, off, dbad)));
+      wm.invalid = dbad.as<uint8_t>();
+    }
+  } else {      // the Poisson family: X column-major [7][n_d], the counts, lfactorial of the counts (+inf for a negative one) -- amwg_create.hip upload_poisson_data
+    TRYB((waic_pack<double>(D, [&](int d) { return (size_t)models[d].n_obs * 7; }, [&](int d, double *dst) { const int N = models[d].n_obs; for (int i = 0; i < N; ++i) for (int k = 0; k < 7; ++k) dst[(size_t)k * N + i] = models[d].x[(size_t)i * 7 + k]; }, off, dx)));
+    for (int d = 0; d < D; ++d) sets[(size_t)d].off_x = off[(size_t)d];
+    TRYB((waic_pack<double>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, double *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = models[d].y[i]; }, off, dy)));
+    for (int d = 0; d < D; ++d) sets[(size_t)d].off_y = off[(size_t)d];
+    TRYB((waic_pack<double>(D, [&](int d) { return (size_t)models[d].n_obs; }, [&](int d, double *dst) { for (int i = 0; i < models[d].n_obs; ++i) dst[i] = models[d].y[i] < 0 ? (double)INFINITY : lfactorial_js(models[d].y[i]); }, off, dlf)));
+    for (int d = 0; d < D; ++d) sets[(size_t)d].off_lfact = off[(size_t)d];
+    wm.x = dx.as<double>(); wm.y = dy.as<double>(); wm.lfact = dlf.as<double>();
+  }
+  const size_t before = amwg_waic_set_budget((size_t)scratch_bytes);
+  const int rc = amwg_waic_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, loglik, nullptr);
+  amwg_waic_set_budget(before);
+  return rc;
 }
 
 int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,

@@ -626,6 +626,45 @@ AmwgSampler.prototype.hpd = function (probs) {
   return this.dataset_hpd(probs)[0];
 };
 
+/** WAIC per dataset (options.datasets; an ordinary sampler: one dataset): [{elpd_waic, se, p_waic, lppd, waic (= -2 elpd_waic), high_variance (observations with
+ *  p_i > 0.4: WAIC is unreliable there)[, pointwise: [[lppd_i, p_i] per observation]]}, ...].  The rule of include/amwg.h: the family's own pointwise terms over the
+ *  dataset's chains x kept draws on the device, lppd_i by log-sum-exp and p_i the variance of the terms; the totals in index order.  Built-in families only.  A
+ *  dataset lives wholly on one shard: no collective. */
+AmwgSampler.prototype.dataset_waic = function (opts) {
+  const N = native(), want = !!(opts && opts.pointwise), out = [];
+  for (const sh of this._shards) {
+    const r = N.datasetWaic(sh.handle, want);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = { elpd_waic: r.summary[d * 4], se: r.summary[d * 4 + 1], p_waic: r.summary[d * 4 + 2], lppd: r.summary[d * 4 + 3], waic: -2 * r.summary[d * 4], high_variance: r.high[d] };
+      if (want) o.pointwise = Array.from({ length: r.n_obs[d] }, (_, i) => [r.pointwise[(d * r.n_max + i) * 2], r.pointwise[(d * r.n_max + i) * 2 + 1]]);
+      out.push(o);
+    }
+  }
+  return out;
+};
+/** waic(opts) of an ordinary sampler: dataset_waic(opts)[0].  One device: a posterior spread over several devices would need its partial sums merged, which is
+ *  out of scope -- dataset_waic() works there, a dataset being on one shard. */
+AmwgSampler.prototype.waic = function (opts) {
+  this._refusePooled('waic');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): waic() over several devices (options.devices) is out of scope: the multi-device WAIC is not built; waic() runs on one device';
+  return this.dataset_waic(opts)[0];
+};
+/** Two fits of the SAME observations compared: a, b results of waic({pointwise: true}) / dataset_waic({pointwise: true})[d] -> {elpd_diff, se_diff}, elpd_diff the sum
+ *  over the observations of elpd_i(a) - elpd_i(b) in index order (positive: a predicts better), se_diff = sqrt(n var_i) of those differences with denominator n - 1
+ *  (Vehtari, Gelman & Gabry 2017, eq. 24).  Pure JavaScript. */
+function compare_waic(a, b) {
+  if (!a || !b || !Array.isArray(a.pointwise) || !Array.isArray(b.pointwise)) throw 'compare_waic: both results need pointwise (ask for {pointwise: true})';
+  const n = a.pointwise.length;
+  if (n !== b.pointwise.length) throw 'compare_waic: the results hold ' + n + ' and ' + b.pointwise.length + ' observations: not the same data';
+  const diff = new Float64Array(n);
+  let elpd_diff = 0;
+  for (let i = 0; i < n; i++) { diff[i] = (a.pointwise[i][0] - a.pointwise[i][1]) - (b.pointwise[i][0] - b.pointwise[i][1]); elpd_diff += diff[i]; }
+  const mean = elpd_diff / n;
+  let ss = 0;
+  for (let i = 0; i < n; i++) ss += (diff[i] - mean) * (diff[i] - mean);
+  return { elpd_diff, se_diff: Math.sqrt(n * ss / (n - 1)) };
+}
+
 // edges as the caller gives them -- {name: [e0, ..., e_bins]} per parameter or derived quantity (every element of a vector parameter under the same edges), or one
 // array for all recorded values; all of one length -- -> {flat: Float64Array [recorded][bins + 1], bins}
 AmwgSampler.prototype._histogramEdges = function (edges) {
@@ -1041,5 +1080,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, compare_waic, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

@@ -224,6 +224,42 @@ int amwg_last_sample_dataset_quantiles(amwg_sampler *s, const double *probs, int
  * Works on an ordinary sampler too (D = 1).  AMWG_EINVAL: a null argument or n_probs < 1 (before any device call), no sample() yet, after a summarising call,
  * fewer than 2 values per dataset and value, and the shape limits of amwg_last_sample_dataset_quantiles.  A failed scratch allocation is AMWG_EHIP. */
 int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n_probs, double *out);   /* out[D][P + derived][n_probs][2] */
+/* WAIC per dataset (Watanabe; Vehtari, Gelman & Gabry 2017): how well the model predicts each dataset, from the stored draws, on the device.
+ *   summary[D][4] = elpd_waic, se, p_waic, lppd;  high[D] (or NULL) = the number of observations with p_i > 0.4, the usual warning that WAIC is unreliable there;
+ *   pointwise (NULL, or [D][n_max][2] = lppd_i, p_i; NaN beyond n_d), n_max the largest value amwg_dataset_n_obs reports.
+ * THE RULE applies per dataset d with n_d observations; the S = rows * (C / D) draws of d in the last stored sample() are numbered s = row * (C / D) + chain.
+ *   l_si is the double the reference's expression adds for observation i under draw s, the family's own term, BIT FOR BIT:
+ *     AMWG_MODEL_NORMAL       ld_norm(x_i, mu, sigma)
+ *     AMWG_MODEL_BETA_BERN    ld_bern(x_i, theta)              (-inf for an x_i that is neither 0 nor 1)
+ *     AMWG_MODEL_HIER_NORMAL  ld_norm(y_i, theta[g_i], sigma)
+ *     AMWG_MODEL_POIS_GLM     log(lambda) * y_i - lambda - lfactorial(y_i), lambda = exp(eta), eta = X[i][0] * beta[0] + ... + X[i][6] * beta[6] by products and
+ *                             additions in that order (no fused operation), + beta[7] from i >= cp on; exp and log are V8's, lfactorial(y_i) the stored one
+ *     (the quotient of ld_norm is IEEE's; where the step kernels form it by the reciprocal of csrc/amwg_div.h, which reproduces it, so does this call.)  Priors are
+ *     not part of l.
+ *   lppd_i = m_i + log(sum_s exp(l_si - m_i)) - log S, with m_i = max_s l_si.
+ *   p_i    = sum_s (l_si - mean_i)^2 / (S - 1).
+ *   These two ACCUMULATIONS ARE NOT FIXED TO THE BIT; they are deterministic (no floating-point atomics: a fixed split of the draws, merged in a fixed order: (m, sum)
+ *   by rescaling, (count, mean, M2) by Chan's formula), and a dataset's result bytes depend only on its own draws, its own data and (rows, C / D) -- not on D, the other
+ *   datasets or the scratch budget.  The exponential is exp_v8 (V8's: fdlibm's, below 1 ulp); the logarithm log_v8.  With u = 2^-53 and E = 8 (S + 16) u:
+ *     |lppd_i - exact| <= E + 4 u |exact|,     |p_i - exact| <= E sqrt(V (V + mean_i^2)) + (E max_s |l_si|)^2, V the exact p_i
+ *   (a sum of S non-negative terms of relative error 2 u is within (S + 3) u in any order; the variance term is Chan, Golub & LeVeque's bound for updating and
+ *   two-pass schemes; the factor 8 covers any merge tree).  tests/README.waic.md has the derivation and the largest ratio observed.
+ *   NON-FINITE VALUES: if any l_si of (d, i) is NaN or +-inf, lppd_i and p_i are NaN for that (d, i) only; the totals of d are then NaN, and no other dataset's are
+ *   (the convention of the autocovariance and of the HPD).  Terms whose squared distance from their mean overflows (beyond 1e154) count as non-finite.
+ *   THE FINISH runs on the host inside the library from the pointwise pairs, in index order, so its bytes are a function of the pointwise bytes:
+ *     elpd_i = lppd_i - p_i;  lppd, p_waic and elpd_waic are running sums from 0.0 over i = 0 ... n_d - 1;
+ *     se = sqrt(n_d * sum_i (elpd_i - elpd_waic / n_d)^2 / (n_d - 1)), the sum again from 0.0 in index order; NaN for n_d = 1;  high[d] counts p_i > 0.4.
+ * Works on ordinary samplers (D = 1), dataset samplers and ragged dataset samplers; the hierarchical family on an ordinary sampler (amwg_create_datasets refuses it).
+ * The Bernoulli family's pairs take two values per dataset (x_i = 1, x_i = 0): those two are computed, not n_d.
+ * AMWG_EINVAL with a message that names the call: a null s or summary (before any device call); no sample() yet; after a summarising call (the message names
+ * amwg_sample_summarize); fewer than 2 draws per dataset; a translated closure (amwg_create_user*): "the pointwise terms of a closure are not known to the library;
+ * built-in families only"; a group_local sampler (its observations lie as a lane-major tile).  Scratch -- the partials of the split, 32 bytes per observation and
+ * run of draws -- is allocated per call on the sampler's device and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset
+ * beyond it runs alone).  A failed allocation is AMWG_EHIP.
+ * OUT OF SCOPE: WAIC after amwg_sample_summarize (per-observation accumulators could be folded; not built), PSIS-LOO, a public pointwise log-likelihood matrix,
+ * translated closures, a pooled WAIC across devices (no amwg_group_* / amwg_comm_* twin). */
+int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary /* [D][4]: elpd_waic, se, p_waic, lppd */, int32_t *high /* [D] or NULL */,
+                                  double *pointwise /* NULL or [D][n_max][2]: lppd_i, p_i; NaN beyond n_d */);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,
@@ -336,7 +372,7 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * Afterwards amwg_last_sample_moments, amwg_last_sample_diagnostics, amwg_last_sample_dataset_moments and amwg_last_sample_dataset_diagnostics answer from the
  * accumulators: the halves are accumulated by the recurrence of the stored path in the same row order, so split-R-hat and ESS equal those of the stored run BIT FOR BIT
  * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
- * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_fetch_draws*,
+ * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_last_sample_dataset_waic, amwg_fetch_draws*,
  * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
  * amwg_last_sample_dataset_histogram, amwg_last_sample_dataset_covariance and amwg_last_sample_dataset_autocovariance unless they were armed before the call
  * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL).  An

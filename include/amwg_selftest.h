@@ -58,6 +58,14 @@ int amwg_hpd_check(int32_t device, const double *draws, int64_t rows, int32_t PR
  * and the one in force before goes to scratch_before (may be NULL). */
 int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, int64_t *scratch_before);
 
+/* the kernels of amwg_last_sample_dataset_waic on a caller's draws[rows][PR][C] (host) and the data of D model descriptions of one family (ragged sizes allowed; the
+ * hyper-parameters are not read: priors are not part of the terms), through the launcher the sampler uses: summary[D][4], high[D] (or NULL), pointwise (NULL, or
+ * [D][n_max][2]) as that call returns them.  loglik (NULL, or [D][S][n_max], S = rows * (C / D), NaN beyond n_d): the terms l_si themselves from the same device
+ * functions, in draw order s = row * (C / D) + chain -- for small shapes, more than 2^24 doubles are refused.  scratch_bytes: the scratch budget of this call
+ * (0: the default of csrc/amwg_waic.h).  The arguments are checked before a device is opened. */
+int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
+                    int32_t *high, double *pointwise, double *loglik);
+
 /* The fold of amwg_sample_summarize on a caller's array draws[rows][PR][C] (host): the array is folded in windows of window_rows rows through the kernels and the
  * launcher the sampler uses (halves_folded, 4 * PR * C doubles in chain_halves_kernel's layout [half][mean | variance][PR][C]), chain_halves_kernel runs on the whole
  * array (halves_direct, the same size), and the moments of D datasets of C / D chains each come from the folded whole-chain pairs (mean, sd: [D][PR]).
