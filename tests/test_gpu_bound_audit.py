@@ -2,7 +2,9 @@
 evaluates the reference's expression E beside the cheap value A in every update of the certified kernels and records max |A - E| / eps, max |dA - dE| / eta and
 the verdicts that contradict exp(dE) > u (mcmc.js:527-528).  tools/bound_audit.py --quick: the small and adversarial cases of every family -- n in {1, 2, 17, 63,
 65}, data at 1e8, sigma at 1e-6 / 1e6, rows with one observation, group counts that are not powers of two, Poisson predictors at the 690 cut-off, counts of 1e6.
-Every ratio must stay below 0.5 (the derivations leave a factor of two) and not one verdict may be wrong.  The full-size run is profiles/r06_bound_audit.json."""
+Every ratio must stay below 0.5 (the derivations leave a factor of two) and not one verdict may be wrong.  The full-size run is profiles/r06_bound_audit.json.
+Every case here runs in one geometry (whole wavefronts, the planner's workgroup, one burn): tests/test_gpu_value_audit.py holds the same bars in every kernel class and
+form, per dataset of the families' dataset kernels, and under adversarial uniforms, where it also shows that the detector behind `wrong_verdicts == 0` fires."""
 import json
 import os
 import subprocess

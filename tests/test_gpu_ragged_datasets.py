@@ -47,10 +47,17 @@ def ragged_specs(model, sizes, tweak=None):
 NORMAL_ONE_LANE = (1, 2, 63, 64, 65, 1023, 1024, 1025, 1100)
 
 
-@pytest.mark.parametrize("block,cpd", [(64, 64), (256, 256)])
+NORMAL_ONE_LANE_512 = (1, 513, 1025)
+
+
+@pytest.mark.parametrize("block,cpd", [(64, 64), (256, 256), (512, 512)])
 def test_normal_certified_pass_one_lane(block, cpd):
     """Below a wavefront, either side of one row of 64, either side of one block of 16 rows, block + row + masked tail; an LDS tile of each dataset's own size
-    in front of the stepper state; one-wavefront and 256-thread workgroups."""
+    in front of the stepper state; one-wavefront and 256-thread workgroups.  (512, 512): the 512-thread class, blocks of 8 rows -- below a wavefront, a block and a
+    single observation, two blocks and one (the byte-parity companion of the class tests/test_gpu_value_audit.py audits per dataset)."""
+    if block == 512:
+        against_twins("n1_512", ragged_specs("normal", NORMAL_ONE_LANE_512), cpd, 1, block, kernel="amwg_step_kernel_cert_ds<NormalModel,1,512>")
+        return
     against_twins("n1", ragged_specs("normal", NORMAL_ONE_LANE), cpd, 1, block, kernel="amwg_step_kernel_cert_ds<NormalModel,1,256>")
 
 

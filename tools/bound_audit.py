@@ -21,6 +21,10 @@ verdict goes wrong or a chain differs from the expression-in-every-update run.
     python tools/bound_audit.py --quick                                        # the small cases only (what tests/test_gpu_bound_audit.py asserts)
     python tools/bound_audit.py --only logit                                   # the certified logistic tail's cases alone (tests/test_gpu_logit_tail.py)
     python tools/bound_audit.py --only dstail                                  # the certified tails of closures on MANY datasets (tests/test_gpu_user_dataset_tails.py)
+
+run_case is also what tests/test_gpu_value_audit.py drives, one case after the other in a child process: beside the keys the lists above use, a case may name
+block (block_threads), chain_offset, steps_per_launch, ragged, schedule ("geometry": the mixed schedule of tests/test_gpu_geometry.py instead of one burn) and a
+start state per chain ([P][C]); the result carries launch_info() as `launch` and, for a case with `datasets`, a row per dataset (dataset_rows).
 """
 import argparse
 import ctypes as C
@@ -228,23 +232,64 @@ def dstail_cases():
     return out
 
 
+def geometry_schedule(s, steps, bump=None):
+    """the mixed schedule of tests/test_gpu_geometry.py _schedule: sample with thin, burn, adaptation off and on, a state overwritten from the host (chains c = 1 mod 3
+    but the last, param 0; or the chains `bump` names), burn, sample -- launches that record and launches that do not, the pair (lpA, epsA) carried between them, a
+    cached log_post thrown away"""
+    s.sample(steps // 4, 3)
+    s.burn(steps // 2)
+    s.set_adapting(False)
+    s.sample(steps // 8, 1)
+    s.set_adapting(True)
+    st = s.state()
+    st[0, np.arange(1, s.C - 1, 3) if bump is None else np.asarray(bump, dtype=np.int64)] += 0.25
+    s.set_state(st)
+    s.burn(steps // 8)
+    s.sample(steps // 8 + 4, 2)
+
+
+def dataset_rows(per, datasets):
+    """the per-chain rows of amwg_audit_fetch reduced per dataset: dataset d = chains [d cpd, (d + 1) cpd).  A NaN among a dataset's ratios stays a NaN."""
+    cpd = per.shape[1] // datasets
+    return [dict(dataset=d, audited_decisions=int(per[2, d * cpd:(d + 1) * cpd].sum()), wrong_verdicts=int(per[3, d * cpd:(d + 1) * cpd].sum()),
+                 max_value_ratio=float(np.max(per[0, d * cpd:(d + 1) * cpd])), max_difference_ratio=float(np.max(per[1, d * cpd:(d + 1) * cpd])))
+            for d in range(datasets)]
+
+
 def run_case(c, shift=0, full_evaluation=0):
+    """Runs one case on the audit library.  Keys of a case: name, spec (one, or a list: a dataset sampler), chains, steps, lanes, seed, state (None, [P]: every chain
+    starts there, or [P][C]: a start per chain) and optionally suff (sufficient_statistics), datasets (their number: the result then carries a row per dataset),
+    block (block_threads), chain_offset, steps_per_launch, ragged (the list through amwg_create_datasets_ragged), schedule ("geometry": geometry_schedule over
+    `steps`; the default is one burn(steps)) and bump (the chains that schedule overwrites; default: 1 mod 3 but the last)."""
     s = A.Sampler(c["spec"], chains=c["chains"], seed=c["seed"], lanes_per_chain=c["lanes"], test_bound_shift=shift, full_evaluation=full_evaluation,
-                  sufficient_statistics=(c.get("suff", 0) if full_evaluation == 0 else 0))
+                  sufficient_statistics=(c.get("suff", 0) if full_evaluation == 0 else 0), block_threads=c.get("block", 0), chain_offset=c.get("chain_offset", 0),
+                  steps_per_launch=c.get("steps_per_launch", 0), ragged=bool(c.get("ragged", False)))
     try:
-        kernel = s.launch_info()["kernel"]
-        if c["state"] is not None:
-            st = np.repeat(np.asarray(c["state"], dtype=np.float64)[:, None], c["chains"], axis=1)
+        li = s.launch_info()
+        kernel = li["kernel"]
+        if c.get("state") is not None:
+            st = np.asarray(c["state"], dtype=np.float64)
+            if st.ndim == 1:
+                st = np.repeat(st[:, None], c["chains"], axis=1)
             s.set_state(st)
         t0 = time.time()
-        s.burn(c["steps"])
+        if c.get("schedule", "burn") == "geometry":
+            geometry_schedule(s, c["steps"], c.get("bump"))
+        elif c.get("schedule", "burn") == "burn":
+            s.burn(c["steps"])
+        else:
+            raise ValueError("schedule %r: 'burn' or 'geometry'" % c["schedule"])
         per, hist = (audit_fetch(s) if full_evaluation == 0 else (np.zeros((4, c["chains"])), np.zeros((2, 64), dtype=np.uint64)))
         wall = time.time() - t0
         info = s.info()
         final = (s.state().tobytes(), info["accepts"].tobytes(), s.diag()["uniforms"].tobytes())
     finally:
         s.close()
-    return dict(kernel=kernel, per=per, hist=hist, wall=wall, final=final, accepts=int(info["accepts"].sum()), inbounds=int(info["inbounds"].sum()))
+    out = dict(kernel=kernel, per=per, hist=hist, wall=wall, final=final, accepts=int(info["accepts"].sum()), inbounds=int(info["inbounds"].sum()),
+               launch={k: li[k] for k in ("kernel", "block_threads", "grid_blocks", "summation_order", "lanes_per_chain", "datasets")})
+    if c.get("datasets"):
+        out["datasets"] = dataset_rows(per, c["datasets"])
+    return out
 
 
 def main():
@@ -272,10 +317,7 @@ def main():
                  audited_decisions=int(per[2].sum()), wrong_verdicts=int(per[3].sum()), max_value_ratio=mv, max_difference_ratio=md,
                  value_ratio_hist=hist_summary(r["hist"][0]), difference_ratio_hist=hist_summary(r["hist"][1]), seconds=round(r["wall"], 2))
         if c.get("datasets"):      # the worst ratios of every dataset's own chains
-            cpd = c["chains"] // c["datasets"]
-            e["datasets"] = [dict(dataset=d, audited_decisions=int(per[2, d * cpd:(d + 1) * cpd].sum()), wrong_verdicts=int(per[3, d * cpd:(d + 1) * cpd].sum()),
-                                  max_value_ratio=float(np.max(per[0, d * cpd:(d + 1) * cpd])), max_difference_ratio=float(np.max(per[1, d * cpd:(d + 1) * cpd])))
-                             for d in range(c["datasets"])]
+            e["datasets"] = r["datasets"]
         rec["cases"].append(e)
         if "_cert" in r["kernel"]:
             worst_v, worst_d, wrong = max(worst_v, mv if mv == mv else INF), max(worst_d, md if md == md else INF), wrong + e["wrong_verdicts"]
