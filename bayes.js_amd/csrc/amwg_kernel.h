@@ -582,12 +582,63 @@ __device__ __forceinline__ double lane_value(double v, int src) {
 // of at most 65 535 steps); a launch that breaks one -- a future geometry or launch change -- must not look like a successful no-op: the
 // kernel leaves a bit in ChainArrays::error, which the host reads after every call (finish_timing) and reports as AMWG_EHIP.
 // kErrNoKernelBody: a kernel of a translated closure's code object (amwg_user_kernels.h) launched at a geometry the closure has no body for.
-constexpr int kErrReplicasNeedOneWave = 1, kErrLaunchTooLong = 2, kErrMirrorOutOfSync = 4, kErrSweepNeedsOrderInRegisters = 8, kErrNoKernelBody = 16;
+// kErrLeanShape: the lean one-lane body of the Normal family (amwg_normal1.h) launched for anything but two scalar named parameters of real / int type, cpb == 0.
+constexpr int kErrReplicasNeedOneWave = 1, kErrLaunchTooLong = 2, kErrMirrorOutOfSync = 4, kErrSweepNeedsOrderInRegisters = 8, kErrNoKernelBody = 16, kErrLeanShape = 32;
 __device__ __forceinline__ void device_error(const StepArgs &a, int code) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (threadIdx.x == 0) (void)atomicOr(a.ch.error, code);
 #endif
 }
+// Roberts-Rosenthal adaptation at a batch boundary (mcmc.js:539-549), the arithmetic alone: the batch count and the log proposal scale that the batch leaves.
+// (step_body's adapt_component and the lean one-lane body of the Normal family, amwg_normal1.h, both go through here: the same operations in the same order)
+struct AdaptedScale { int32_t batch_count; double prop_log_scale; };
+__device__ __forceinline__ AdaptedScale adapt_scale(const CompConst &k, int32_t batch_count, double prop_log_scale, int32_t acceptance_count) {
+  const int32_t bc = batch_count + 1;
+  const double adj = __builtin_fmin(k.max_adaptation, k.initial_adaptation / __builtin_sqrt((double)bc));
+  double pls = prop_log_scale;
+  if ((double)acceptance_count / k.batch_size > k.target_accept_rate) pls += adj; else pls -= adj;
+  return AdaptedScale{bc, pls};
+}
+
+// BOUND AUDIT (-DAMWG_AUDIT; step_body has the account of it): the pieces that every certified stepper's audit is made of.  `writer`: this lane counts into the histograms.
+__device__ __forceinline__ void audit_count_bin([[maybe_unused]] const ChainArrays &ch, [[maybe_unused]] bool writer, [[maybe_unused]] int which, [[maybe_unused]] double ratio) {
+#if defined(AMWG_AUDIT)
+  if (writer) {
+    int b = 0;
+    if (ratio > 0.0) { b = (int)((f64_bits(ratio) >> 52) & 0x7ffu) - 1023 + 40; b = b < 1 ? 1 : (b > 63 ? 63 : b); }      // (bin 0: the two values agree exactly)
+    if (!(ratio == ratio)) b = 63;
+    (void)atomicAdd(ch.audit_hist + which * 64 + b, 1ull);
+  }
+#endif
+}
+// (--shrink's adversarial uniforms: u just outside the sliver of the certified test, where a bound that is too small by more than the placement's 1.5 gives a wrong verdict)
+__device__ __forceinline__ double audit_place_u(double ex, double eta, double u, int parity) {
+  if (!(eta < 0x1p-8) || !(ex > 0x1p-900) || !(ex < kInf)) return u;
+  const double below = ex * (1.0 - 1.5 * eta), above = ex * (1.0 + 1.5 * eta);
+  const double v = ((parity & 1) && above < 1.0) ? above : below;
+  return (v > 0.0 && v < 1.0) ? v : u;
+}
+// a cheap value against the expression's: -> the ratio |A - E| / eps, or a negative number when the pair is not audited
+__device__ __forceinline__ double audit_ratio(double A, double eps, double E) {
+  if (eps == eps && eps < kInf && eps > 0.0 && E == E && __builtin_fabs(E) < kInf) return __builtin_fabs(A - E) / eps;
+  return -1.0;
+}
+__device__ __forceinline__ void audit_max(double &m, double r) { m = (r > m || !(r == r)) ? r : m; }
+// the verdict of a certified test against the expression's own test exp_v8(dE) > u: counted, and counted as wrong when the two contradict each other
+__device__ __forceinline__ void audit_verdict(uint32_t &n, uint32_t &bad, double dE, int verdict, double u) {
+  const bool exact_acc = exp_v8(dE) > u;
+  ++n;
+  if ((verdict > 0 && !exact_acc) || (verdict < 0 && exact_acc)) ++bad;
+}
+// the four per-chain figures, merged into ChainArrays::audit when the launch ends
+__device__ __forceinline__ void audit_store(double *au, int64_t C, int64_t cl, double max_v, double max_d, uint32_t n, uint32_t bad) {
+  const double v0 = au[cl], d0 = au[C + cl];
+  au[cl] = (max_v > v0 || !(max_v == max_v)) ? max_v : v0;
+  au[C + cl] = (max_d > d0 || !(max_d == max_d)) ? max_d : d0;
+  au[2 * C + cl] += (double)n;
+  au[3 * C + cl] += (double)bad;
+}
+
 // a model that mirrors the state in registers (kTracksState) says whether the mirror still equals the LDS copy (Model::mirror_ok)
 template <class M, class = void> struct MirrorCheckOf { static constexpr bool value = false; };
 template <class M> struct MirrorCheckOf<M, void_of<decltype(M::kMirrorCheck)>> { static constexpr bool value = M::kMirrorCheck; };
@@ -714,39 +765,16 @@ __device__ __forceinline__ void step_body(const StepArgs &a, unsigned char *smem
 #endif
   [[maybe_unused]] double audE = 0.0, aud_max_v = 0.0, aud_max_d = 0.0;      // E of the current state; the two maxima
   [[maybe_unused]] uint32_t aud_n = 0u, aud_bad = 0u;
-  [[maybe_unused]] auto audit_bin = [&](int which, double ratio) {
-#if defined(AMWG_AUDIT)
-    if (writer) {
-      int b = 0;
-      if (ratio > 0.0) { b = (int)((f64_bits(ratio) >> 52) & 0x7ffu) - 1023 + 40; b = b < 1 ? 1 : (b > 63 ? 63 : b); }      // (bin 0: the two values agree exactly)
-      if (!(ratio == ratio)) b = 63;
-      (void)atomicAdd(cold_args()->ch.audit_hist + which * 64 + b, 1ull);
-    }
-#endif
-  };
-  // (--shrink's adversarial uniforms: u just outside the sliver of the certified test, where a bound that is too small by more than the placement's 1.5 gives a wrong verdict)
-  [[maybe_unused]] auto audit_adversarial_u = [&](double ex, double eta, double u, int parity) -> double {
-    if (!(eta < 0x1p-8) || !(ex > 0x1p-900) || !(ex < kInf)) return u;
-    const double below = ex * (1.0 - 1.5 * eta), above = ex * (1.0 + 1.5 * eta);
-    const double v = ((parity & 1) && above < 1.0) ? above : below;
-    return (v > 0.0 && v < 1.0) ? v : u;
-  };
+  [[maybe_unused]] auto audit_bin = [&](int which, double ratio) { audit_count_bin(cold_args()->ch, writer, which, ratio); };
+  [[maybe_unused]] auto audit_adversarial_u = [&](double ex, double eta, double u, int parity) -> double { return audit_place_u(ex, eta, u, parity); };
   [[maybe_unused]] auto audit_value = [&](double A, double eps, double E) {      // a cheap value against the expression's
-    if (eps == eps && eps < kInf && eps > 0.0 && E == E && __builtin_fabs(E) < kInf) {
-      const double r = __builtin_fabs(A - E) / eps;
-      aud_max_v = (r > aud_max_v || !(r == r)) ? r : aud_max_v;
-      audit_bin(0, r);
-    }
+    const double r = audit_ratio(A, eps, E);
+    if (!(r < 0.0)) { audit_max(aud_max_v, r); audit_bin(0, r); }
   };
   [[maybe_unused]] auto audit_difference = [&](double dA, double eta0, double dE, int verdict, double u) {      // ... a difference, and the verdict drawn from it
-    if (eta0 == eta0 && eta0 < kInf && eta0 > 0.0 && dE == dE && __builtin_fabs(dE) < kInf) {
-      const double r = __builtin_fabs(dA - dE) / eta0;
-      aud_max_d = (r > aud_max_d || !(r == r)) ? r : aud_max_d;
-      audit_bin(1, r);
-    }
-    const bool exact_acc = exp_v8(dE) > u;
-    ++aud_n;
-    if ((verdict > 0 && !exact_acc) || (verdict < 0 && exact_acc)) ++aud_bad;
+    const double r = audit_ratio(dA, eta0, dE);
+    if (!(r < 0.0)) { audit_max(aud_max_d, r); audit_bin(1, r); }
+    audit_verdict(aud_n, aud_bad, dE, verdict, u);
   };
   // PHASE CLOCK (-DAMWG_X_PHASES, a development build: tools/phase_clock.py): shader-clock cycles per phase of the step loop, summed over the launch's wavefronts into
   // ChainArrays::audit_hist[64 ..] -- where a latency-bound stepper spends its time, which counters of issued instructions cannot say
@@ -840,10 +868,9 @@ __device__ __forceinline__ void step_body(const StepArgs &a, unsigned char *smem
       const int64_t gi = (int64_t)comp * C + cl;
       int32_t *const g_bc = kMulti ? nullptr : cold_args()->ch.batch_count;
       double *const g_pls = kMulti ? nullptr : cold_args()->ch.prop_log_scale;
-      const int32_t bc = (kMulti ? BCme[comp] : g_bc[gi]) + 1;
-      const double adj = __builtin_fmin(k.max_adaptation, k.initial_adaptation / __builtin_sqrt((double)bc));
-      double pls = kMulti ? LOGPLSme[comp] : g_pls[gi];
-      if ((double)cnt.x / k.batch_size > k.target_accept_rate) pls += adj; else pls -= adj;
+      const AdaptedScale ad = adapt_scale(k, kMulti ? BCme[comp] : g_bc[gi], kMulti ? LOGPLSme[comp] : g_pls[gi], cnt.x);
+      const int32_t bc = ad.batch_count;
+      const double pls = ad.prop_log_scale;
       cnt = make_int2(0, 0);
       SDme[comp] = exp_v8_cold(pls);
       if constexpr (kMulti) { BCme[comp] = bc; LOGPLSme[comp] = pls; }
@@ -1522,14 +1549,7 @@ __device__ __forceinline__ void step_body(const StepArgs &a, unsigned char *smem
   }
 #endif
   if constexpr (kAudit) {
-    if (writer) {
-      double *const au = cold_args()->ch.audit;
-      const double v0 = au[cl], d0 = au[C + cl];
-      au[cl] = (aud_max_v > v0 || !(aud_max_v == aud_max_v)) ? aud_max_v : v0;
-      au[C + cl] = (aud_max_d > d0 || !(aud_max_d == aud_max_d)) ? aud_max_d : d0;
-      au[2 * C + cl] += (double)aud_n;
-      au[3 * C + cl] += (double)aud_bad;
-    }
+    if (writer) audit_store(cold_args()->ch.audit, C, cl, aud_max_v, aud_max_d, aud_n, aud_bad);
   }
   if (writer) {
     const cold_args_ptr ca = cold_args();
@@ -1573,10 +1593,16 @@ __global__ void __launch_bounds__(BT, MinWavesOf<Model>::value) amwg_sweep_kerne
 }
 // the kernels that DECIDE FROM CERTIFIED VALUES (step_body: kCert -- options.full_evaluation = 0 for a model and lane count that has them): the ordinary one
 // (the Normal family at one lane per chain, the Poisson family at 16) and the sweep kernel (the hierarchical family)
+// (a family with a stepper of its own at one lane per chain -- Model::kLeanOneLane, Model::lean_one_lane<BT>: the Normal family, amwg_normal1.h -- runs that one
+// under this kernel's name: the generic step_body is not instantiated for it, and none of its registers stay in the kernel.  The dataset twin, the kernel that
+// evaluates the expression in every update and the translated closures keep step_body.)
+template <class M, class = void> struct LeanOneLaneOf { static constexpr bool value = false; };
+template <class M> struct LeanOneLaneOf<M, void_of<decltype(M::kLeanOneLane)>> { static constexpr bool value = M::kLeanOneLane; };
 template <class Model, int G, int BT>
 __global__ void __launch_bounds__(BT, MinWavesOf<Model>::value) amwg_step_kernel_cert(const StepArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  step_body<Model, G, BT, false, false, true>(a, smem);
+  if constexpr (G == 1 && LeanOneLaneOf<Model>::value) Model::template lean_one_lane<BT>(a, smem);
+  else step_body<Model, G, BT, false, false, true>(a, smem);
 }
 template <class Model, int BT>
 __global__ void __launch_bounds__(BT, MinWavesOf<Model>::value) amwg_sweep_kernel_cert(const StepArgs a) {

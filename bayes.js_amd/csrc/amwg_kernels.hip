@@ -15,6 +15,7 @@
 #include "amwg_host.h"
 #include "amwg_kernel.h"
 #include "amwg_models.h"
+#include "amwg_normal1.h"
 
 using namespace amwg;
 

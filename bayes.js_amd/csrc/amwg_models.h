@@ -169,7 +169,10 @@ struct NormalModel {
   static constexpr bool kCertified = true;
   static constexpr int kCertifiedLanes = 1;
   struct Approx { double value, eps; };
-  template <int G, int BT>
+  // WB: rows per block of the wavefront's pass.  Any WB gives the same bits: a lane adds a chain's rows in increasing row order whatever the block length, and the
+  // bound above -- a lane's at most ceil(n / 64) terms, six butterfly levels, the leftovers -- does not depend on it.  The lean one-lane body (amwg_normal1.h) names
+  // its own (kLeanWaveBlock: 32 rows fit there and were measured, 16 are in); step_body's instantiations (the dataset twin) take the default.
+  template <int G, int BT, int WB = (BT <= 256 ? kWaveBlock : 8)>
   __device__ __forceinline__ static Approx log_post_approx(Cache &kc, const StateView &S, const ModelConsts &mc, const DataRef &d, const unsigned char *smem, int sub) {
     static_assert(G == 1, "the certified pass of the Normal family is the one-lane one");
     load<G>(kc, S, mc, d, smem, sub);
@@ -189,7 +192,7 @@ struct NormalModel {
     // (the tile's address space is the pass's at compile time -- ds_read from the tile; the array in global memory, or no wave scratch, through the generic
     // instantiation --: one wave-uniform branch here)
     if constexpr (BT <= 512) {
-      constexpr int B = BT <= 256 ? kWaveBlock : 8;
+      constexpr int B = WB;
       double *scr = wave_scratch_of(d);
       const bool tile = lds_bytes_of(d, 1, 0) != 0;
       if (tile && scr != nullptr) S2 = norm_sq_pass_wave<B, true>((amwg_lds_f64_ptr)smem, kc.mu, d.n_obs, scr);
@@ -201,6 +204,11 @@ struct NormalModel {
     const double mag = __builtin_fabs(P) + __builtin_fabs(nc) + 2.0 * Q;
     return Approx{(P + nc) - Q, (2.0 * n + 64.0) * 0x1p-53 * mag * 1.25};
   }
+  // THE STEPPER OF ITS OWN at one lane per chain (amwg_normal1.h; amwg_kernel.h amwg_step_kernel_cert runs it instead of step_body): two scalar components, the
+  // chain's state, scales and counters in registers
+  static constexpr bool kLeanOneLane = true;
+  template <int BT>
+  __device__ __forceinline__ static void lean_one_lane(const StepArgs &a, unsigned char *smem);
 };
 
 // ---------------------------------------------------------------------------------------------

@@ -196,12 +196,13 @@ int finish_timing(amwg_sampler *s) {
     HIP_TRY(hipMemcpy(&bits, s->ch.error, sizeof bits, hipMemcpyDeviceToHost));
     if (bits) {
       HIP_TRY(hipMemset(s->ch.error, 0, sizeof bits));
-      return amwg_fail(AMWG_EHIP, "the step kernel reported an internal error (bits %d:%s%s%s%s%s): the chains' state is not to be trusted", bits,
+      return amwg_fail(AMWG_EHIP, "the step kernel reported an internal error (bits %d:%s%s%s%s%s%s): the chains' state is not to be trusted", bits,
                        (bits & kErrReplicasNeedOneWave) ? " replicated chains in a workgroup of more than one wavefront" : "",
                        (bits & kErrLaunchTooLong) ? " more than 65535 steps in one launch" : "",
                        (bits & kErrMirrorOutOfSync) ? " the register mirror of the state is out of sync with the state" : "",
                        (bits & kErrSweepNeedsOrderInRegisters) ? " the sweep kernel was launched for a parameter vector of more than 64 entries" : "",
-                       (bits & kErrNoKernelBody) ? " the launched kernel has no body for this closure at this geometry" : "");
+                       (bits & kErrNoKernelBody) ? " the launched kernel has no body for this closure at this geometry" : "",
+                       (bits & kErrLeanShape) ? " the Normal family's one-lane stepper was launched for something other than two scalar parameters of real or int type" : "");
     }
   }
   return AMWG_OK;
