@@ -338,6 +338,18 @@ const BENCH = {
   // other densities and a mean / sd that are EXPRESSIONS of the state)
   bench_normal_50k: { params: CASES.readme_normal.params, data: () => synth.normal(50000, 20260926).x, log_post: CASES.readme_normal.log_post },
   bench_normal_n65: { params: CASES.readme_normal.params, data: () => synth.normal(65, 20260927).x, log_post: CASES.readme_normal.log_post },
+  // (tests/test_gpu_value_edges.py case a: bench_normal's closure with the priors widened to 1e80 as literals and one observation at 1e70 -- outside the range
+  // of the fast quotient, its square finite)
+  edge_normal_one_out: { params: CASES.readme_normal.params, data: () => { var x = synth.normal(200, 31).x; x[5] = 1e70; return x; },
+    log_post: function(state, data) {
+      var log_post = 0;
+      log_post += ld.norm(state.mu, 0, 1e80);
+      log_post += ld.unif(state.sigma, 0, 1e80);
+      for(var i = 0; i < data.length; i++) {
+        log_post += ld.norm(data[i], state.mu, state.sigma);
+      }
+      return log_post;
+    } },
   bench_normal_expr: { params: () => ({ a: { type: 'real' }, b: { type: 'real' }, tau: { type: 'real', lower: 0, init: 1 } }),
     data: () => ({ x: synth.normal(3000, 20260928).x }),
     log_post: function(state, data) {
