@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_waic_check", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -75,6 +75,7 @@ def lib():
         L.amwg_last_sample_dataset_quantiles.argtypes = [vp, pd, i32, pd]
         L.amwg_last_sample_dataset_hpd.argtypes = [vp, pd, i32, pd]
         L.amwg_last_sample_dataset_waic.argtypes = [vp, pd, pi32, pd]
+        L.amwg_last_sample_dataset_loo.argtypes = [vp, pd, pi32, pd]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -180,6 +181,8 @@ def selftest_lib():
         L.amwg_hpd_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_hpd_limits.argtypes = [i32, i64, C.POINTER(i64), C.POINTER(i64)]
         L.amwg_waic_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
+        L.amwg_loo_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
+        L.amwg_loo_stats.argtypes = [i32, C.POINTER(i32), pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
         L.amwg_histogram_check.argtypes = [pd, i64, i32, i64, i32, pd, i32, i64, C.POINTER(C.c_uint64), i32]
@@ -575,6 +578,29 @@ class Sampler:
             out["pointwise"] = r["pointwise"][0]
         return out
 
+    def dataset_loo(self, pointwise=False):
+        """-> dict(summary [datasets][4] = elpd_loo, se, p_loo, lppd; high [datasets] = observations with khat_i > 0.7; with pointwise=True also
+        pointwise [datasets][n_max][3] = elpd_loo_i, lppd_i, khat_i, NaN beyond a dataset's n_obs): PSIS-LOO per dataset by the rule of include/amwg.h, the
+        families' pointwise terms over the stored draws on the device (amwg_last_sample_dataset_loo)"""
+        summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
+        pw = np.empty((self.D, max(self.dataset_n_obs()), 3)) if pointwise else None
+        _check(lib().amwg_last_sample_dataset_loo(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
+        out = {"summary": summary, "high": high}
+        if pointwise:
+            out["pointwise"] = pw
+        return out
+
+    def loo(self, pointwise=False):
+        """-> dict(elpd_loo, se, p_loo, lppd, high[, pointwise [n_obs][3]]): dataset_loo() of an ordinary sampler; a dataset sampler refuses the pooled question"""
+        if self.D > 1:
+            raise AmwgError("amwg error -1: loo: this sampler runs %d datasets, a posterior each: pooled summaries are refused -- use amwg_last_sample_dataset_loo "
+                            "(dataset_loo)" % self.D)      # (the words of amwg_refuse_pooled; the library has no pooled call to ask)
+        r = self.dataset_loo(pointwise)
+        out = dict(zip(("elpd_loo", "se", "p_loo", "lppd"), r["summary"][0].tolist()), high=int(r["high"][0]))
+        if pointwise:
+            out["pointwise"] = r["pointwise"][0]
+        return out
+
     def set_state(self, state):
         st = np.ascontiguousarray(state, dtype=np.float64)
         assert st.shape == (self.P, self.C)
@@ -796,14 +822,8 @@ def waic_totals(pointwise, n_obs):
     return np.array([elpd, se, p, lppd]), high
 
 
-def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
-    """libamwg_selftest.so: the kernels of Sampler.dataset_waic on any array draws [rows][PR][C] and the data of `specs`, one dict(model, n_obs, data{x[,y,g]}[, G, K])
-    per dataset (one family; ragged sizes allowed), C / len(specs) columns each -> dict(summary [D][4], high [D][, pointwise [D][n_max][2]][, loglik [D][S][n_max],
-    the terms themselves in draw order s = row * (C / D) + chain]) (amwg_waic_check)"""
-    dr = np.ascontiguousarray(draws, dtype=np.float64)
-    if dr.ndim != 3:
-        raise AmwgError("amwg error: waic_check: draws must be [rows][PR][C]")
-    rows, PR, Cn = dr.shape
+def _model_descs(specs):
+    """specs -> (the ModelDesc array of the check calls, the arrays it points into: keep them alive over the call)"""
     D = len(specs)
     keep = []
     mds = (ModelDesc * max(1, D))()
@@ -822,6 +842,19 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
             keep.append(g)
             mds[k].g = g.ctypes.data_as(C.POINTER(C.c_int32))
         mds[k].G, mds[k].K = int(q.get("G", 0)), int(q.get("K", 0))
+    return mds, keep
+
+
+def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_waic on any array draws [rows][PR][C] and the data of `specs`, one dict(model, n_obs, data{x[,y,g]}[, G, K])
+    per dataset (one family; ragged sizes allowed), C / len(specs) columns each -> dict(summary [D][4], high [D][, pointwise [D][n_max][2]][, loglik [D][S][n_max],
+    the terms themselves in draw order s = row * (C / D) + chain]) (amwg_waic_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: waic_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    D = len(specs)
+    mds, keep = _model_descs(specs)
     n_max = max([int(q["n_obs"]) for q in specs] + [1])
     S = rows * (Cn // D) if D and Cn % D == 0 else 0
     summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
@@ -839,6 +872,74 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
     if loglik:
         out["loglik"] = ll
     return out
+
+
+def loo_tail_len(S):
+    """M = min(S // 5, the smallest m3 with m3^2 >= 9 S), in integers: the tail length of amwg_last_sample_dataset_loo (include/amwg.h)"""
+    import math
+    S = int(S)
+    m3 = math.isqrt(9 * S)
+    if m3 * m3 < 9 * S:
+        m3 += 1
+    return min(S // 5, m3)
+
+
+def loo_totals(pointwise, n_obs):
+    """The finish of amwg_last_sample_dataset_loo restated (include/amwg.h): pointwise [n_max][3] = elpd_loo_i, lppd_i, khat_i of ONE dataset with n_obs
+    observations -> (summary [4] = elpd_loo, se, p_loo, lppd; high).  Running sums from 0.0 in index order, one IEEE operation each: the bytes of the library's."""
+    pw = np.asarray(pointwise, dtype=np.float64)
+    n = int(n_obs)
+    elpd = lppd = np.float64(0.0)
+    high = 0
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            elpd = elpd + pw[i, 0]
+            lppd = lppd + pw[i, 1]
+            high += 1 if pw[i, 2] > 0.7 else 0
+        centre = elpd / np.float64(n)
+        ss = np.float64(0.0)
+        for i in range(n):
+            e = pw[i, 0] - centre
+            ss = ss + e * e
+        se = np.float64(np.nan) if n == 1 else np.sqrt(np.float64(n) * ss / np.float64(n - 1))
+        return np.array([elpd, se, lppd - elpd, lppd]), high
+
+
+def loo_check(draws, specs, pointwise=True, tails=False, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_loo on any array draws [rows][PR][C] and the data of `specs` (as waic_check takes them) ->
+    dict(summary [D][4], high [D][, pointwise [D][n_max][3]][, tails [D][n_max][M + 1], the sorted smallest terms the fit read]) (amwg_loo_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: loo_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    D = len(specs)
+    mds, keep = _model_descs(specs)
+    n_max = max([int(q["n_obs"]) for q in specs] + [1])
+    S = rows * (Cn // D) if D and Cn % D == 0 else 0
+    M = loo_tail_len(S)
+    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    pw = np.empty((max(1, D), n_max, 3)) if pointwise else None
+    tl = np.empty((max(1, D), n_max, M + 1)) if tails and (M + 1) * n_max * max(1, D) <= (1 << 24) else None
+    if tails and tl is None:
+        tl = np.empty(1)      # (refused by the library before it is written: more than 2^24 doubles)
+    L = selftest_lib()
+    if L.amwg_loo_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
+                        _dp(pw) if pointwise else None, _dp(tl) if tails else None) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    out = {"summary": summary, "high": high}
+    if pointwise:
+        out["pointwise"] = pw
+    if tails:
+        out["tails"] = tl
+    return out
+
+
+def loo_stats(timing=False):
+    """libamwg_selftest.so: (select passes over the terms, [ms of the lppd pass, the select, the compaction, the sort and fit] or None unless timing was on) of this
+    process's last LOO call; then switches the phase timing of later calls on or off (amwg_loo_stats)"""
+    passes, ms = C.c_int32(0), np.zeros(4)
+    selftest_lib().amwg_loo_stats(1 if timing else 0, C.byref(passes), _dp(ms))
+    return int(passes.value), (None if ms[0] < 0 else ms.tolist())
 
 
 def hpd_limits(scratch_bytes=0, device=0, lds=True):

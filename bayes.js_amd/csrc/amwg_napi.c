@@ -777,9 +777,9 @@ static napi_value DatasetHpd(napi_env env, napi_callback_info info) {
   return o;
 }
 
-/* datasetWaic(handle, bool pointwise) -> {datasets, n_max, n_obs: Int32Array [datasets], summary: Float64Array [datasets][4] (elpd_waic, se, p_waic, lppd),
- * high: Int32Array [datasets][, pointwise: Float64Array [datasets][n_max][2] (lppd_i, p_i; NaN beyond a dataset's n_obs)]} over the last sample() */
-static napi_value DatasetWaic(napi_env env, napi_callback_info info) {
+/* what DatasetWaic and DatasetLoo share: `width` doubles per observation in pointwise */
+typedef int (*pointwise_call)(amwg_sampler *, double *, int32_t *, double *);
+static napi_value dataset_pointwise(napi_env env, napi_callback_info info, pointwise_call call, size_t width) {
   napi_value a[2];
   if (!get_args(env, info, 2, a)) return NULL;
   amwg_sampler *s = unwrap(env, a[0]);
@@ -795,8 +795,8 @@ static napi_value DatasetWaic(napi_env env, napi_callback_info info) {
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   int32_t n_max = 0;
   for (size_t d = 0; d < D; ++d) n_max = n_obs[d] > n_max ? n_obs[d] : n_max;
-  if (want) { vp = new_f64(env, D * (size_t)n_max * 2, &pw); if (!vp) return NULL; }
-  rc = amwg_last_sample_dataset_waic(s, summary, high, want ? pw : NULL);
+  if (want) { vp = new_f64(env, D * (size_t)n_max * width, &pw); if (!vp) return NULL; }
+  rc = call(s, summary, high, want ? pw : NULL);
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   napi_value o, t;
   NAPI_OK(napi_create_object(env, &o));
@@ -810,6 +810,12 @@ static napi_value DatasetWaic(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, o, "n_max", t);
   return o;
 }
+/* datasetWaic(handle, bool pointwise) -> {datasets, n_max, n_obs: Int32Array [datasets], summary: Float64Array [datasets][4] (elpd_waic, se, p_waic, lppd),
+ * high: Int32Array [datasets][, pointwise: Float64Array [datasets][n_max][2] (lppd_i, p_i; NaN beyond a dataset's n_obs)]} over the last sample() */
+static napi_value DatasetWaic(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_waic, 2); }
+/* datasetLoo(handle, bool pointwise) -> the same object over amwg_last_sample_dataset_loo: summary [datasets][4] (elpd_loo, se, p_loo, lppd), high (observations with
+ * khat_i > 0.7), pointwise [datasets][n_max][3] (elpd_loo_i, lppd_i, khat_i) */
+static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo, 3); }
 
 /* setHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins): amwg_set_histogram -- arms (null, 0: disarms) a histogram for later summarising calls */
 static napi_value SetHistogram(napi_env env, napi_callback_info info) {
@@ -1225,7 +1231,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

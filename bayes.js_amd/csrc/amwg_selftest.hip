@@ -7,6 +7,7 @@
 #include "amwg_fold.h"
 #include "amwg_histogram.h"
 #include "amwg_hpd.h"
+#include "amwg_loo.h"
 #include "amwg_waic.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
@@ -287,14 +288,14 @@ static int waic_pack(int D, Len len, Fill fill, std::vector<int64_t> &off, DevBu
   HIP_TRY(hipMemcpy(dev.p, packed.data(), packed.size() * sizeof(T), hipMemcpyHostToDevice));
   return AMWG_OK;
 }
-extern "C" {
-
-int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
-                    int32_t *high, double *pointwise, double *loglik) {
-  static const char *call = "amwg_waic_check";
+// amwg_waic_check and amwg_loo_check: the arguments checked, the draws and the family's data on the device as the sampler lays them, then the launcher of either
+// (extra: WAIC's loglik, or LOO's tails)
+static int pointwise_check(const char *call, bool loo, int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models,
+                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra) {
+  double *loglik = loo ? nullptr : extra;
   if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
   if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
-  TRYB(amwg_waic_shape(call, rows, PR, C, D));
+  TRYB(loo ? amwg_loo_shape(call, rows, PR, C, D) : amwg_waic_shape(call, rows, PR, C, D));
   if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
   const int model = models[0].model;
   if (model < AMWG_MODEL_NORMAL || model > AMWG_MODEL_POIS_GLM) return amwg_fail(AMWG_EINVAL, "%s: unknown model %d", call, model);
@@ -314,6 +315,7 @@ int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t P
   const int need = model == AMWG_MODEL_NORMAL ? 2 : model == AMWG_MODEL_BETA_BERN ? 1 : model == AMWG_MODEL_HIER_NORMAL ? models[0].G + 2 : 9;
   if (PR < need) return amwg_fail(AMWG_EINVAL, "%s: the family reads %d components of a draw, the draws hold %d", call, need, PR);
   if (loglik && (double)D * (double)rows * (double)(C / D) * (double)n_max > 16777216.0) return amwg_fail(AMWG_EINVAL, "%s: loglik of more than 2^24 doubles", call);
+  if (loo && extra && (double)D * (double)(loo_tail_len(rows * (C / D)) + 1) * (double)n_max > 16777216.0) return amwg_fail(AMWG_EINVAL, "%s: tails of more than 2^24 doubles", call);
   TRYB(use_device(device));
   const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
   DevBuf dd, dx, dy, dlf, dxb, dbad;
@@ -357,10 +359,35 @@ int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t P
     for (int d = 0; d < D; ++d) sets[(size_t)d].off_lfact = off[(size_t)d];
     wm.x = dx.as<double>(); wm.y = dy.as<double>(); wm.lfact = dlf.as<double>();
   }
+  if (loo) {
+    const size_t before = amwg_loo_set_budget((size_t)scratch_bytes);
+    const int rc = amwg_loo_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, nullptr);
+    amwg_loo_set_budget(before);
+    return rc;
+  }
   const size_t before = amwg_waic_set_budget((size_t)scratch_bytes);
   const int rc = amwg_waic_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, loglik, nullptr);
   amwg_waic_set_budget(before);
   return rc;
+}
+extern "C" {
+
+int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
+                    int32_t *high, double *pointwise, double *loglik) {
+  return pointwise_check("amwg_waic_check", false, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, loglik);
+}
+
+int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
+                   int32_t *high, double *pointwise, double *tails) {
+  return pointwise_check("amwg_loo_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, tails);
+}
+
+int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms) {
+  const LooStats st = amwg_loo_last_stats();
+  if (passes) *passes = st.passes;
+  if (ms) { ms[0] = st.timed ? st.ms_lppd : -1.0; ms[1] = st.timed ? st.ms_select : -1.0; ms[2] = st.timed ? st.ms_compact : -1.0; ms[3] = st.timed ? st.ms_fit : -1.0; }
+  amwg_loo_set_timing(timing);
+  return AMWG_OK;
 }
 
 int amwg_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, int64_t window_rows,

@@ -23,6 +23,9 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
+
+struct amwg_sampler;
 
 constexpr size_t kWaicScratchBytes = (size_t)256 << 20;      // the default scratch budget of a call: 256 MiB, as amwg_hpd.h
 
@@ -48,6 +51,8 @@ int amwg_waic_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
 // library only).  Returns after `stream` has drained.
 int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
                      int32_t *high, double *pointwise, double *loglik, hipStream_t stream);
+// sets [D] and model of a sampler's own data, as the launchers take them; the sampler's device is current (one copy from it when D > 1)
+int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicModel &model);
 // the finish of include/amwg.h over one dataset's pairs pw[n][2]: summary[4], *high (may be nullptr)
 void amwg_waic_totals(const double *pw, int64_t n, double *summary, int32_t *high);
 // the scratch budget of later calls in bytes (0: kWaicScratchBytes); returns the budget in force before.  For the test library: the product never calls it.

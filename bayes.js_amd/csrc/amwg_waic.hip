@@ -1,7 +1,7 @@
 // amwg_waic.hip -- WAIC per dataset on the device from the stored draws (amwg_last_sample_dataset_waic; part of libamwg.so).  include/amwg.h states the rule,
 // amwg_waic.h the route: a thread owns an observation and walks the draws, the draw-invariant values come from LDS as broadcasts, the draws are split over
-// wavefronts and workgroups by a function of (S, n) alone, and the partials are merged in a fixed order.  The terms are the reference's, bit for bit (amwg_ld.h,
-// amwg_div.h, exp_log_v8); the accumulations are bounded, not pinned.  The exponential of the log-sum-exp is exp_v8 (fdlibm's, below 1 ulp).
+// wavefronts and workgroups by a function of (S, n) alone, and the partials are merged in a fixed order.  The terms are the reference's, bit for bit (amwg_terms.h,
+// shared with amwg_loo.hip: amwg_ld.h, amwg_div.h, exp_log_v8); the accumulations are bounded, not pinned.  The exponential of the log-sum-exp is exp_v8 (fdlibm's, below 1 ulp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,39 +14,14 @@
 #include "amwg_host.h"
 #include "amwg_ld.h"
 #include "amwg_sampler.h"
+#include "amwg_terms.h"
 #include "amwg_waic.h"
 
 using namespace amwg;
 
 namespace {
 
-constexpr int kThreads = 256;      // a workgroup: four wavefronts
-constexpr int kTile = 64;          // observations per workgroup, a lane each
-constexpr int kWaves = kThreads / 64;
-constexpr int kStage = 256;        // draws staged in LDS at a time, a thread each
-constexpr int64_t kTargetBlocks = 2048;      // workgroups per dataset the split aims at (256 CUs x 8)
-constexpr int64_t kMinRun = 256;             // draws per split at least: one staged run
-
 struct Part { double m, sum, mean, M2; };      // max term and sum exp(l - m); mean and sum (l - mean)^2.  The count is a function of the indices.
-
-// the number of contiguous runs a dataset's S draws are cut into, from S and its n alone
-__host__ __device__ inline int64_t waic_splits(int64_t S, int64_t n) {
-  const int64_t tiles = (n + kTile - 1) / kTile;
-  int64_t want = tiles > 0 ? kTargetBlocks / tiles : 1;
-  want = want < 1 ? 1 : want;
-  int64_t by_len = S / kMinRun;
-  by_len = by_len < 1 ? 1 : by_len;
-  return want < by_len ? want : by_len;
-}
-__host__ __device__ inline int64_t split_begin(int64_t S, int64_t splits, int64_t k) { return S / splits * k + (S % splits) * k / splits; }
-
-// exp_v8 with its rare arguments out of line (0, beyond -708, the sliver at ln2 / 2): the loop's code holds the common path only
-__device__ __forceinline__ double waic_exp(double a) {
-  if (__builtin_expect(exp_is_rare(a), 0)) return exp_v8_cold(a);
-  const ExpParts e = exp_parts(a, ExpLogLiterals{});
-  return set_hi_word(e.y, hi_word(e.y) + (e.k << 20));
-}
-
 __device__ __forceinline__ void merge_parts(Part &a, double &na, const Part &b, double nb) {
   if (nb == 0.0) return;
   if (na == 0.0) { a = b; na = nb; return; }
@@ -57,108 +32,6 @@ __device__ __forceinline__ void merge_parts(Part &a, double &na, const Part &b, 
   a.mean = a.mean + delta * (nb / nt);
   a.M2 = a.M2 + b.M2 + delta * delta * (na * nb / nt);
   na = nt;
-}
-
-// ---- the families: what an evaluation needs of a draw (staged in LDS), what it needs of an observation (registers), and the term
-template <int MODEL> struct Family;
-
-template <> struct Family<AMWG_MODEL_NORMAL> {
-  struct Draw { double mu, c, den, yhi, ylo; int32_t fast, pad; };
-  struct Obs { double x; };
-  __device__ static int64_t n_eff(const WaicDataset &ds) { return ds.n_obs; }
-  __device__ static Draw make_draw(const double *at, int64_t C, const WaicModel &M, const WaicDataset &ds) {      // at: component 0 of the draw
-    Draw w;
-    w.mu = at[0];
-    const double sigma = at[C];
-    w.c = norm_c(M.neg_half_log_2pi, sigma);
-    w.den = norm_den(sigma);
-    const Reciprocal y = make_reciprocal(w.den);
-    w.yhi = y.hi; w.ylo = y.lo;
-    w.fast = !M.exact_division && ds.data_mid_range && mid_range(w.den) && (w.mu == 0 || mid_range(__builtin_fabs(w.mu)));      // NormalModel::begin's condition
-    w.pad = 0;
-    return w;
-  }
-  __device__ static void set_base(Draw &, int64_t) {}
-  __device__ static Obs load_obs(const WaicModel &M, const WaicDataset &ds, int64_t i) { return Obs{M.x[ds.off_x + i]}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *, int64_t) {
-    const double t = o.x - w.mu;
-    const double tt = t * t;
-    return w.c - (w.fast ? div_by_invariant(tt, w.den, Reciprocal{w.yhi, w.ylo}) : tt / w.den);
-  }
-};
-
-template <> struct Family<AMWG_MODEL_HIER_NORMAL> {      // theta[0 .. G - 1], mu, sigma.  The group's mean is read where the draws lie; IEEE division throughout
-  struct Draw { double c, den; int64_t base; };
-  struct Obs { double x; int64_t g_off; };
-  __device__ static int64_t n_eff(const WaicDataset &ds) { return ds.n_obs; }
-  __device__ static Draw make_draw(const double *at, int64_t C, const WaicModel &M, const WaicDataset &) {
-    Draw w;
-    const double sigma = at[(int64_t)(M.G + 1) * C];
-    w.c = norm_c(M.neg_half_log_2pi, sigma);
-    w.den = norm_den(sigma);
-    w.base = 0;
-    return w;
-  }
-  __device__ static void set_base(Draw &w, int64_t base) { w.base = base; }      // where the draw's component 0 lies
-  __device__ static Obs load_obs(const WaicModel &M, const WaicDataset &ds, int64_t i) { return Obs{M.x[ds.off_x + i], (int64_t)M.xb[ds.off_xb + i]}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *draws, int64_t C) {
-    const double t = o.x - draws[w.base + o.g_off * C];
-    return w.c - (t * t) / w.den;
-  }
-};
-
-template <> struct Family<AMWG_MODEL_BETA_BERN> {      // two observations: x = 1 and x = 0
-  struct Draw { double l1, l0; };
-  struct Obs { int one; };
-  __device__ static int64_t n_eff(const WaicDataset &ds) { return ds.n_obs > 0 ? 2 : 0; }
-  __device__ static Draw make_draw(const double *at, int64_t, const WaicModel &, const WaicDataset &) {
-    const double th = at[0];
-    return Draw{log_v8(th), log_v8(1 - th)};      // BetaBernModel::begin: ld.bern(1, th), ld.bern(0, th)
-  }
-  __device__ static void set_base(Draw &, int64_t) {}
-  __device__ static Obs load_obs(const WaicModel &, const WaicDataset &, int64_t i) { return Obs{i == 0}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *, int64_t) { return o.one ? w.l1 : w.l0; }
-};
-
-template <> struct Family<AMWG_MODEL_POIS_GLM> {      // beta[0 .. 7], cp
-  struct Draw { double b[8]; int32_t icp, pad; };
-  struct Obs { double v[9]; };
-  __device__ static int64_t n_eff(const WaicDataset &ds) { return ds.n_obs; }
-  __device__ static Draw make_draw(const double *at, int64_t C, const WaicModel &, const WaicDataset &) {
-    Draw w;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) w.b[k] = at[(int64_t)k * C];
-    const double cp = at[8 * C];
-    w.icp = !(cp < 536870912.0) ? 536870912 : (cp <= 0.0 ? 0 : (int)__builtin_ceil(cp));      // PoisGlmModel::begin: i >= cp as an integer comparison
-    w.pad = 0;
-    return w;
-  }
-  __device__ static void set_base(Draw &, int64_t) {}
-  __device__ static Obs load_obs(const WaicModel &M, const WaicDataset &ds, int64_t i) {
-    Obs o;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) o.v[k] = M.x[ds.off_x + (int64_t)k * ds.n_obs + i];
-    o.v[7] = M.y[ds.off_y + i];
-    o.v[8] = M.lfact[ds.off_lfact + i];
-    return o;
-  }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t i, const double *, int64_t) {      // PoisGlmModel::eta_of, term_of
-    double eta = o.v[0] * w.b[0];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) eta += o.v[k] * w.b[k];
-    if (i >= (int64_t)w.icp) eta += w.b[7];
-    double lam;
-    const double lg = exp_log_v8(eta, lam, ExpLogLiterals{});
-    return lg * o.v[7] - lam - o.v[8];
-  }
-};
-
-template <class F>
-__device__ __forceinline__ typename F::Draw draw_at(const double *draws, int PR, int64_t C, int64_t cpd, int d, int64_t s, const WaicModel &M, const WaicDataset &ds) {
-  const int64_t row = s / cpd, base = row * PR * C + (int64_t)d * cpd + (s - row * cpd);
-  typename F::Draw w = F::make_draw(draws + base, C, M, ds);
-  F::set_base(w, base);
-  return w;
 }
 
 // parts[part_off[z] + split * n + i], z = the dataset's place in the batch
@@ -426,6 +299,24 @@ int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR
   return AMWG_OK;
 }
 
+// the sampler's datasets and family as the launchers take them (shared with amwg_last_sample_dataset_loo); the sampler's device is current
+int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicModel &m) {
+  const int D = s->n_datasets;
+  sets.assign((size_t)D, WaicDataset{});
+  if (D == 1) {
+    sets[0] = WaicDataset{s->ds_n_obs.empty() ? s->d.n_obs : s->ds_n_obs[0], s->mc.data_mid_range, 0, 0, 0, 0};
+  } else {
+    std::vector<DatasetConsts> consts((size_t)D);
+    HIP_TRY(hipMemcpy(consts.data(), s->d_ds_consts, (size_t)D * sizeof(DatasetConsts), hipMemcpyDeviceToHost));
+    for (int d = 0; d < D; ++d) sets[(size_t)d] = WaicDataset{consts[(size_t)d].n_obs, consts[(size_t)d].data_mid_range, consts[(size_t)d].off_x, consts[(size_t)d].off_y, consts[(size_t)d].off_lfact, consts[(size_t)d].off_xb};
+  }
+  m.model = s->model; m.G = s->d.G; m.exact_division = s->mc.exact_division;
+  m.neg_half_log_2pi = s->mc.neg_half_log_2pi;
+  m.x = s->d.x; m.y = s->d.y; m.lfact = s->d.lfact; m.xb = s->d.xb;
+  m.invalid = s->model == AMWG_MODEL_BETA_BERN ? static_cast<const uint8_t *>(s->d.arr[1]) : nullptr;      // (amwg_create.hip upload_bernoulli_data)
+  return AMWG_OK;
+}
+
 extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
   static const char *call = "amwg_last_sample_dataset_waic";
   if (!s || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
@@ -436,18 +327,8 @@ extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, i
   TRYB(amwg_waic_shape(call, s->last_rows, PR, s->C, D));
   if (s->mc.group_local) return amwg_fail(AMWG_EINVAL, "%s: a group_local sampler keeps its observations as a lane-major tile; the pointwise terms need them in index order", call);
   HIP_TRY(hipSetDevice(s->device));
-  std::vector<WaicDataset> sets((size_t)D);
-  if (D == 1) {
-    sets[0] = WaicDataset{s->ds_n_obs.empty() ? s->d.n_obs : s->ds_n_obs[0], s->mc.data_mid_range, 0, 0, 0, 0};
-  } else {
-    std::vector<DatasetConsts> consts((size_t)D);
-    HIP_TRY(hipMemcpy(consts.data(), s->d_ds_consts, (size_t)D * sizeof(DatasetConsts), hipMemcpyDeviceToHost));
-    for (int d = 0; d < D; ++d) sets[(size_t)d] = WaicDataset{consts[(size_t)d].n_obs, consts[(size_t)d].data_mid_range, consts[(size_t)d].off_x, consts[(size_t)d].off_y, consts[(size_t)d].off_lfact, consts[(size_t)d].off_xb};
-  }
+  std::vector<WaicDataset> sets;
   WaicModel m{};
-  m.model = s->model; m.G = s->d.G; m.exact_division = s->mc.exact_division;
-  m.neg_half_log_2pi = s->mc.neg_half_log_2pi;
-  m.x = s->d.x; m.y = s->d.y; m.lfact = s->d.lfact; m.xb = s->d.xb;
-  m.invalid = s->model == AMWG_MODEL_BETA_BERN ? static_cast<const uint8_t *>(s->d.arr[1]) : nullptr;      // (amwg_create.hip upload_bernoulli_data)
+  TRYB(amwg_waic_describe(s, sets, m));
   return amwg_waic_launch(call, s->last_draws, s->last_rows, PR, s->C, D, m, sets.data(), summary, high, pointwise, nullptr, s->stream);
 }

@@ -665,6 +665,43 @@ function compare_waic(a, b) {
   return { elpd_diff, se_diff: Math.sqrt(n * ss / (n - 1)) };
 }
 
+/** PSIS-LOO per dataset (options.datasets; an ordinary sampler: one dataset): [{elpd_loo, se, p_loo, lppd, looic (= -2 elpd_loo), high_k (observations with
+ *  khat_i > 0.7: the estimate is unreliable there)[, pointwise: [[elpd_loo_i, lppd_i, khat_i] per observation]]}, ...].  The rule of include/amwg.h: per observation
+ *  the smallest terms over the dataset's chains x kept draws selected, sorted and fitted by a generalised Pareto on the device, the importance weights smoothed;
+ *  the totals in index order.  What to use where dataset_waic() reports high_variance.  Built-in families only.  A dataset lives wholly on one shard: no collective. */
+AmwgSampler.prototype.dataset_loo = function (opts) {
+  const N = native(), want = !!(opts && opts.pointwise), out = [];
+  for (const sh of this._shards) {
+    const r = N.datasetLoo(sh.handle, want);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = { elpd_loo: r.summary[d * 4], se: r.summary[d * 4 + 1], p_loo: r.summary[d * 4 + 2], lppd: r.summary[d * 4 + 3], looic: -2 * r.summary[d * 4], high_k: r.high[d] };
+      if (want) o.pointwise = Array.from({ length: r.n_obs[d] }, (_, i) => [0, 1, 2].map((k) => r.pointwise[(d * r.n_max + i) * 3 + k]));
+      out.push(o);
+    }
+  }
+  return out;
+};
+/** loo(opts) of an ordinary sampler: dataset_loo(opts)[0].  One device, as waic(). */
+AmwgSampler.prototype.loo = function (opts) {
+  this._refusePooled('loo');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): loo() over several devices (options.devices) is out of scope: the multi-device LOO is not built; loo() runs on one device';
+  return this.dataset_loo(opts)[0];
+};
+/** Two fits of the SAME observations compared by PSIS-LOO: a, b results of loo({pointwise: true}) / dataset_loo({pointwise: true})[d] -> {elpd_diff, se_diff} over the
+ *  pointwise elpd_loo_i, as compare_waic.  Pure JavaScript. */
+function compare_loo(a, b) {
+  if (!a || !b || !Array.isArray(a.pointwise) || !Array.isArray(b.pointwise)) throw 'compare_loo: both results need pointwise (ask for {pointwise: true})';
+  const n = a.pointwise.length;
+  if (n !== b.pointwise.length) throw 'compare_loo: the results hold ' + n + ' and ' + b.pointwise.length + ' observations: not the same data';
+  const diff = new Float64Array(n);
+  let elpd_diff = 0;
+  for (let i = 0; i < n; i++) { diff[i] = a.pointwise[i][0] - b.pointwise[i][0]; elpd_diff += diff[i]; }
+  const mean = elpd_diff / n;
+  let ss = 0;
+  for (let i = 0; i < n; i++) ss += (diff[i] - mean) * (diff[i] - mean);
+  return { elpd_diff, se_diff: Math.sqrt(n * ss / (n - 1)) };
+}
+
 // edges as the caller gives them -- {name: [e0, ..., e_bins]} per parameter or derived quantity (every element of a vector parameter under the same edges), or one
 // array for all recorded values; all of one length -- -> {flat: Float64Array [recorded][bins + 1], bins}
 AmwgSampler.prototype._histogramEdges = function (edges) {
@@ -1080,5 +1117,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, compare_waic, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, compare_waic, compare_loo, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

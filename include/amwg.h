@@ -256,10 +256,49 @@ int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n
  * built-in families only"; a group_local sampler (its observations lie as a lane-major tile).  Scratch -- the partials of the split, 32 bytes per observation and
  * run of draws -- is allocated per call on the sampler's device and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset
  * beyond it runs alone).  A failed allocation is AMWG_EHIP.
- * OUT OF SCOPE: WAIC after amwg_sample_summarize (per-observation accumulators could be folded; not built), PSIS-LOO, a public pointwise log-likelihood matrix,
+ * OUT OF SCOPE: WAIC after amwg_sample_summarize (per-observation accumulators could be folded; not built), a public pointwise log-likelihood matrix,
  * translated closures, a pooled WAIC across devices (no amwg_group_* / amwg_comm_* twin). */
 int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary /* [D][4]: elpd_waic, se, p_waic, lppd */, int32_t *high /* [D] or NULL */,
                                   double *pointwise /* NULL or [D][n_max][2]: lppd_i, p_i; NaN beyond n_d */);
+/* PSIS-LOO per dataset (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024): leave-one-out predictive accuracy by Pareto-smoothed importance
+ * sampling from the stored draws, on the device -- what to use where WAIC's high[d] is not zero.
+ *   summary[D][4] = elpd_loo, se, p_loo, lppd;  high[D] (or NULL) = the number of observations with khat_i > 0.7, where the estimate is unreliable;
+ *   pointwise (NULL, or [D][n_max][3] = elpd_loo_i, lppd_i, khat_i; NaN beyond n_d).
+ * THE RULE applies per dataset d and observation i; S and the terms l_s = l_si are those of amwg_last_sample_dataset_waic, the same doubles.
+ *   Sorted ascending by the key order of doubles (-0 before +0): a_0 <= ... <= a_{S-1}; a small term is a large importance ratio.
+ *   TAIL LENGTH M = min(floor(S / 5), m3), m3 the smallest integer with m3^2 >= 9 S (integer arithmetic).
+ *   lppd_i is WAIC's, the same bytes.
+ *   RAW ROUTE, if M < 5: khat_i = +inf, elpd_loo_i = a_0 + log S - log sum_t exp(a_0 - a_t).
+ *   SMOOTHED ROUTE otherwise: ec = exp_v8(a_0 - a_M); THE EXCESSES ARE PINNED TO THE BIT: x_r = exp_v8(a_0 - a_{M-r}) - ec for r = 1 ... M, ascending.
+ *   FIT (Zhang & Stephens 2009, as the loo package's gpdfit): mm = 30 + floor(sqrt(M)); x* = x_{floor(M / 4 + 0.5)};
+ *     theta_j = 1 / x_M + (1 - sqrt(mm / (j - 0.5))) / (3 x*) for j = 1 ... mm;  k_j = mean_r log1p(-theta_j x_r);  L_j = M (log(-theta_j / k_j) - k_j - 1);
+ *     w_j = 1 / sum_i exp(L_i - L_j);  theta^ = sum_j theta_j w_j;  k' = mean_r log1p(-theta^ x_r);  sigma = -k' / theta^;  khat_i = (M k' + 5) / (M + 10).
+ *     If x* <= 0, or x_M <= 0, or khat is not finite: the raw route, khat_i = +inf (the loo package's behaviour for a degenerate tail).
+ *   SMOOTHING: p_r = (r - 0.5) / M;  q_r = sigma expm1(-khat log1p(-p_r)) / khat, and -sigma log1p(-p_r) when khat == 0;  lw~_r = min(log(q_r + ec), 0), paired by
+ *     rank with the raw lw_r = a_0 - a_{M-r}.
+ *   elpd_loo_i = a_0 + log((S - M) + sum_r exp(lw~_r - lw_r)) - log(B + sum_r exp(lw~_r)), with B = sum_{t >= M} exp(a_0 - a_t).
+ *   Only the sorted multiset of the M + 1 smallest terms and B enter: no draw indices, and ties at the cutoff cannot change the result.
+ *   exp, log, log1p and expm1 are V8's (exp_v8, log_v8, log1p_v8, expm1_v8).  THE ACCUMULATIONS ARE NOT PINNED TO THE BIT; they are deterministic: no floating-point
+ *   atomics (the only atomics count and place terms: integers), a split of the draws that is a function of (S, n_d) alone merged in a fixed order, a fixed order of
+ *   every sum over the tail; a dataset's result bytes depend only on its own draws, its own data and (rows, C / D) -- not on D, the other datasets or the scratch budget.
+ *   With u = 2^-53, E = 8 (S + 16) u and E_k = M (M + mm) u (1 + |khat|):
+ *     |khat_i - exact| <= E_k,     |elpd_loo_i - exact| <= E (1 + |exact|) + 4 ln(2 M) E_k
+ *   (measured, not proven: tests/README.loo.md has the measurement and the largest ratios observed).
+ *   NON-FINITE VALUES: if any l_s of (d, i) is NaN or +-inf, elpd_loo_i, lppd_i and khat_i are NaN for that (d, i) only; the totals of d are then NaN, and no other
+ *   dataset's are.  Where WAIC's lppd_i is NaN for terms beyond 1e154 (its rule), so is the triple.
+ *   THE FINISH runs on the host inside the library from the pointwise triples, in index order, running sums from 0.0:
+ *     elpd_loo = sum_i elpd_loo_i;  lppd = sum_i lppd_i;  p_loo = lppd - elpd_loo;
+ *     se = sqrt(n_d * sum_i (elpd_loo_i - elpd_loo / n_d)^2 / (n_d - 1)); NaN for n_d = 1;  high[d] counts khat_i > 0.7, +inf included.
+ * The samplers served are WAIC's; the Bernoulli family's two values (x_i = 1, x_i = 0) are computed and expanded, as there.
+ * AMWG_EINVAL with a message that names the call: a null s or summary (before any device call); no sample() yet; after a summarising call (the message names
+ * amwg_sample_summarize); fewer than 2 draws per dataset; a translated closure: "the pointwise terms of a closure are not known to the library; built-in families
+ * only"; a group_local sampler; and, from the shape alone, M + 1 > 8192 (about 7.4e6 draws per dataset): one workgroup sorts and fits a tail in LDS, 8192 doubles (64 KB) of it at most.
+ * Scratch -- per observation the tail (M + 1 padded to a power of two, at least 64 doubles), 512 bytes of counters, a double per run of draws -- is allocated per call
+ * and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset beyond it runs alone).  A failed allocation is AMWG_EHIP.
+ * OUT OF SCOPE: LOO after amwg_sample_summarize, moment matching or exact refits for observations of high khat, a relative-efficiency (r_eff) correction of the tail
+ * length, translated closures, a pooled LOO across devices, tails beyond the LDS cap. */
+int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary /* [D][4]: elpd_loo, se, p_loo, lppd */, int32_t *high /* [D] or NULL: observations with khat_i > 0.7 */,
+                                 double *pointwise /* NULL or [D][n_max][3]: elpd_loo_i, lppd_i, khat_i; NaN beyond n_d */);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,
@@ -372,7 +411,7 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * Afterwards amwg_last_sample_moments, amwg_last_sample_diagnostics, amwg_last_sample_dataset_moments and amwg_last_sample_dataset_diagnostics answer from the
  * accumulators: the halves are accumulated by the recurrence of the stored path in the same row order, so split-R-hat and ESS equal those of the stored run BIT FOR BIT
  * (same refusals: < 4 kept draws, < 2 chains); mean and sd come from the whole-chain pairs (mean = sum m_c / chains, SS = sum M2_c + kept * sum (m_c - mean)^2) and
- * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_last_sample_dataset_waic, amwg_fetch_draws*,
+ * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_last_sample_dataset_waic, amwg_last_sample_dataset_loo, amwg_fetch_draws*,
  * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
  * amwg_last_sample_dataset_histogram, amwg_last_sample_dataset_covariance and amwg_last_sample_dataset_autocovariance unless they were armed before the call
  * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL).  An

@@ -65,6 +65,14 @@ int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, in
  * (0: the default of csrc/amwg_waic.h).  The arguments are checked before a device is opened. */
 int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                     int32_t *high, double *pointwise, double *loglik);
+/* the kernels of amwg_last_sample_dataset_loo likewise: summary[D][4], high[D] (or NULL), pointwise (NULL, or [D][n_max][3]) as that call returns them.  tails (NULL,
+ * or [D][n_max][M + 1], M the tail length of S = rows * (C / D)): the M + 1 smallest terms of each observation, sorted, as the fit read them; NaN beyond n_d and for an
+ * observation with a non-finite term -- more than 2^24 doubles are refused.  scratch_bytes: the scratch budget of this call (0: the default of csrc/amwg_loo.h). */
+int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
+                   int32_t *high, double *pointwise, double *tails);
+/* what the last LOO call of this process did, for the measurement: *passes = the select passes over the terms; ms[4] = milliseconds of the lppd pass, the select,
+ * the compaction, the sort and fit (-1 unless timing was on).  Then timing of later calls is switched on (1) or off (0).  Either pointer may be NULL. */
+int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms);
 
 /* The fold of amwg_sample_summarize on a caller's array draws[rows][PR][C] (host): the array is folded in windows of window_rows rows through the kernels and the
  * launcher the sampler uses (halves_folded, 4 * PR * C doubles in chain_halves_kernel's layout [half][mean | variance][PR][C]), chain_halves_kernel runs on the whole
