@@ -12,6 +12,7 @@
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
 #include "amwg_kernel.h"
+#include "amwg_kval.h"
 #include "amwg_models.h"
 
 using namespace amwg;
@@ -27,6 +28,32 @@ __global__ void two_valued_check_kernel(const uint32_t *tab, int N, int64_t m, c
   double acc = acc0[j];
   for (int i = 0; i < N; ++i) acc = acc + (((tab[i >> 5] >> (i & 31)) & 1u) ? l1[j] : l0[j]);
   out_seq[j] = acc;
+}
+
+// tests only: thread j sums the same sequence of value indices from acc0[j] with the K addends c[j][0 .. K - 1], once with k_valued_sum<K> on the caller's
+// tables and once term by term; 64-thread workgroups, so that every wavefront holds 64 different cases (the divergence csrc/amwg_kval.h is shaped for)
+template <int K>
+__global__ void k_valued_check_kernel(const uint32_t *tab, const uint8_t *idx, int N, int64_t m, const double *acc0, const double *c, double *out_ff, double *out_seq) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  double cs[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) cs[k] = c[j * K + k];
+  const KValData B{tab, idx, N};
+  out_ff[j] = k_valued_sum<K>(acc0[j], cs, B);
+  double acc = acc0[j];
+  for (int i = 0; i < N; ++i) {
+    const int v = (int)idx[i];
+    double a = cs[0];
+#pragma unroll
+    for (int q = 1; q < K; ++q) a = v == q ? cs[q] : a;
+    acc = acc + a;
+  }
+  out_seq[j] = acc;
+}
+template <int K>
+static void k_valued_check_launch(const uint32_t *tab, const uint8_t *idx, int N, int64_t m, const double *acc0, const double *c, double *out_ff, double *out_seq) {
+  hipLaunchKernelGGL(k_valued_check_kernel<K>, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, 0, tab, idx, N, m, acc0, c, out_ff, out_seq);
 }
 
 // tests only (amwg_stream_check): the product's stream classes, drawn from one by one.  Chain c has id chain0 + c and starts at consumed0[c]; the lanes past the
@@ -159,6 +186,45 @@ int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out_fast_forward, d[3].p, (size_t)m * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_term_by_term, d[4].p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  return AMWG_OK;
+}
+
+int amwg_k_valued_sum_check(int32_t device, int32_t K, const uint8_t *idx, int32_t n, const uint32_t *tab, int64_t m, const double *acc0, const double *c,
+                            double *out_fast_forward, double *out_term_by_term) {
+  const char *call = "amwg_k_valued_sum_check";
+  if (!idx || !tab || !acc0 || !c || !out_fast_forward || !out_term_by_term || n < 0 || m < 0 || m > ((int64_t)1 << 24)) return amwg_fail(AMWG_EINVAL, "%s: bad argument", call);
+  if (!(K == 1 || K == 2 || K == 3 || K == 5 || K == 8 || K == 13 || K == 16)) return amwg_fail(AMWG_EINVAL, "%s: K = %d is not instantiated (1, 2, 3, 5, 8, 13, 16)", call, K);
+  for (int i = 0; i < n; ++i) if ((int)idx[i] >= K) return amwg_fail(AMWG_EINVAL, "%s: idx[%d] = %d outside 0..%d", call, i, (int)idx[i], K - 1);
+  if (m == 0) return AMWG_OK;
+  TRYB(use_device(device));
+  const size_t tab_bytes = 2 * (size_t)K * k_valued_words(n) * 4, lanes = (size_t)m;
+  DevBuf dtab, didx, dacc, dc, dff, dseq;
+  HIP_TRY(dtab.alloc(tab_bytes));
+  HIP_TRY(didx.alloc(n ? (size_t)n : 1));      // (n = 0: a byte nobody reads, not a zero-sized buffer)
+  HIP_TRY(dacc.alloc(lanes * 8));
+  HIP_TRY(dc.alloc(lanes * (size_t)K * 8));
+  HIP_TRY(dff.alloc(lanes * 8));
+  HIP_TRY(dseq.alloc(lanes * 8));
+  HIP_TRY(hipMemcpy(dtab.p, tab, tab_bytes, hipMemcpyHostToDevice));
+  if (n) HIP_TRY(hipMemcpy(didx.p, idx, (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dacc.p, acc0, lanes * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dc.p, c, lanes * (size_t)K * 8, hipMemcpyHostToDevice));
+  const uint32_t *t = dtab.as<uint32_t>();
+  const uint8_t *ix = didx.as<uint8_t>();
+  const double *a0 = dacc.as<double>(), *cc = dc.as<double>();
+  double *ff = dff.as<double>(), *seq = dseq.as<double>();
+  switch (K) {
+    case 1: k_valued_check_launch<1>(t, ix, n, m, a0, cc, ff, seq); break;
+    case 2: k_valued_check_launch<2>(t, ix, n, m, a0, cc, ff, seq); break;
+    case 3: k_valued_check_launch<3>(t, ix, n, m, a0, cc, ff, seq); break;
+    case 5: k_valued_check_launch<5>(t, ix, n, m, a0, cc, ff, seq); break;
+    case 8: k_valued_check_launch<8>(t, ix, n, m, a0, cc, ff, seq); break;
+    case 13: k_valued_check_launch<13>(t, ix, n, m, a0, cc, ff, seq); break;
+    default: k_valued_check_launch<16>(t, ix, n, m, a0, cc, ff, seq); break;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out_fast_forward, dff.p, lanes * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_term_by_term, dseq.p, lanes * 8, hipMemcpyDeviceToHost));
   return AMWG_OK;
 }
 

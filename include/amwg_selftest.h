@@ -29,6 +29,13 @@ int amwg_ld_device(int32_t device, int64_t n, const double *records, double *out
  * l1[j] (x_i = 1) and l0[j] (x_i = 0); j < m. */
 int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_t m, const double *acc0, const double *l1, const double *l0,
                               double *out_fast_forward, double *out_term_by_term);
+/* The same for the K-valued sequential sum of csrc/amwg_kval.h, K in {1, 2, 3, 5, 8, 13, 16}: idx[n] (host bytes) is the value index of every observation, shared
+ * by all lanes; tab the 2 K k_valued_words(n) table words AS THE CALLER BUILT THEM (per block of 32 observations pre[K] then mask[K]; they are not rebuilt here, so
+ * that a translator's tables can be put to the test); lane j < m starts from acc0[j] with the addends c[j * K + k].  Lane j is thread j of 64-thread workgroups:
+ * every wavefront holds 64 different cases.  out_fast_forward[j] = k_valued_sum<K>, out_term_by_term[j] = acc = acc + c[idx[i]], both on the device.
+ * Refused before any device call: null pointers, n < 0, m < 0 or above 2^24, any other K, idx[i] >= K.  n = 0 and m = 0 are legal (m = 0 opens no device). */
+int amwg_k_valued_sum_check(int32_t device, int32_t K, const uint8_t *idx, int32_t n, const uint32_t *tab, int64_t m, const double *acc0, const double *c,
+                            double *out_fast_forward, double *out_term_by_term);
 
 /* The product's own uniform-stream classes (csrc/amwg_philox.h ChainStream, csrc/amwg_kernel.h CoopStream<G>, csrc/amwg_window.h WindowStream) driven one by one
  * on the device: chain i < n_chains has id chain0 + i under `seed` and starts with consumed0[i] uniforms consumed (host array), so that the chains sharing a

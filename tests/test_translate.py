@@ -155,9 +155,13 @@ def test_two_valued_sum_host_fuzz(tmp_path):
 
 def test_k_valued_sum_host_fuzz(tmp_path):
     """csrc/amwg_kval.h compiled for the host (K = 1, 2, 3, 5, 8, 16 distinct addends): ~100 000 random / adversarial (data, acc0, addends)
-    cases -- trailing-zero significands (ties in reachable binades: summed term by term there), exact multiples of one another, either sign
-    of acc0, non-finite and positive addends -- against the plain fp64 loop, bit for bit."""
+    cases -- trailing-zero significands (ties in reachable binades: a binade with ONE tying addend is walked 32 observations at a time on the
+    occurrence masks, one with several is summed term by term), exact multiples of one another, either sign of acc0, starts far above every
+    addend, non-finite and positive addends -- against the plain fp64 loop, bit for bit.  The harness says what it reached (its own census
+    along the plain sum, by the header's definitions): every class of binade visit is met, in the numbers its generator supports (a
+    condition on the inputs; at 20 000 cases per K the generator gives about three times each bound)."""
     import os
+    import re
     import subprocess
     exe = str(tmp_path / "kval_fuzz")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -165,6 +169,9 @@ def test_k_valued_sum_host_fuzz(tmp_path):
                            os.path.join(root, "tests", "host", "kval_fuzz.cpp"), "-o", exe])
     p = subprocess.run([exe, "20000"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "mismatches=0" in p.stdout, p.stdout[-2000:]
+    visits = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", [ln for ln in p.stdout.splitlines() if ln.startswith("visits:")][0])}
+    least = {"tie_free": 100000, "one_tie_walked": 10000, "one_tie_walked_left": 7000, "one_tie_short": 5000, "several_ties": 1500, "stalled": 200, "partial_zero": 70}
+    assert set(visits) == set(least) and all(visits[k] >= least[k] for k in least), visits
 
 
 def test_constant_rate_count_loops_are_fast_forwarded_with_one_lane():

@@ -68,6 +68,23 @@ def translated(name):
             json.load(open(os.path.join(d, name + ".meta.json"))))
 
 
+_with_options = {}
+
+
+def translated_with(name, options):
+    """-> (source, arrays, meta) of one closure translated under extra translator options (a dict, handed to tests/js/translate_cli.js as $AMWG_TRANSLATE_OPTS;
+    e.g. {"no_fast_forward": True}: the term-by-term twin), in a directory of its own: the cached default translation of workdir() is not overwritten."""
+    key = (name, json.dumps(options, sort_keys=True))
+    if key not in _with_options:
+        d = tempfile.mkdtemp(prefix="amwg_user_opts_")
+        p = subprocess.run([NODE, os.path.join(ROOT, "tests", "js", "translate_cli.js"), d, name], cwd=ROOT, capture_output=True, text=True, timeout=300,
+                           env=dict(os.environ, AMWG_TRANSLATE_OPTS=key[1]))
+        assert p.returncode == 0, p.stdout + "\n" + p.stderr
+        _with_options[key] = (open(os.path.join(d, name + ".hip")).read(), read_arrays(os.path.join(d, name + ".arrays.bin")),
+                              json.load(open(os.path.join(d, name + ".meta.json"))))
+    return _with_options[key]
+
+
 def user_spec_part(source, arrays, meta):
     """The `user` entry of an amwg_ctypes.Sampler spec."""
     return {"source": source, "arrays": arrays, "array_types": meta["array_types"], "n_derived": len(meta["derived"]),
