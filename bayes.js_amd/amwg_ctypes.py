@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -123,6 +123,10 @@ def lib():
                                        C.POINTER(Options), C.POINTER(vp)]
         L.amwg_create_user_datasets.argtypes = [C.POINTER(UserModel), i32, C.POINTER(ParamDesc), i32, pd, C.POINTER(CompOpt), C.POINTER(Options), C.POINTER(vp)]
         L.amwg_compile_user_datasets.argtypes = L.amwg_compile_user.argtypes
+        L.amwg_compile_pointwise.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_size_t)]
+        L.amwg_set_pointwise.argtypes = [vp, C.c_char_p]
+        L.amwg_pointwise_n_obs.argtypes = [vp]
+        L.amwg_pointwise_n_obs.restype = i64
         L.amwg_num_recorded.argtypes = [vp]
         L.amwg_set_state.argtypes = [vp, pd, C.c_size_t]
         L.amwg_fp64_peak.argtypes = [i32, pd]
@@ -183,6 +187,8 @@ def selftest_lib():
         L.amwg_hpd_limits.argtypes = [i32, i64, C.POINTER(i64), C.POINTER(i64)]
         L.amwg_waic_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_loo_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
+        L.amwg_user_waic_check.argtypes = [i32, C.POINTER(UserModel), i32, i32, C.c_char_p, pd, i64, i32, i64, i64, pd, C.POINTER(i32), pd, pd]
+        L.amwg_user_loo_check.argtypes = L.amwg_user_waic_check.argtypes
         L.amwg_loo_stats.argtypes = [i32, C.POINTER(i32), pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
@@ -320,6 +326,17 @@ class Sampler:
         self.C = chains
         self.n_params = n
         self.D = L.amwg_num_datasets(h)      # datasets (1 unless made from a list of specs)
+        # options.pointwise: the closure's pointwise text (translate.js), stored on the sampler; compiled at the first waic() / loo()
+        terms = spec.get("pointwise") if user is None else user.get("pointwise", spec.get("pointwise"))
+        if terms is not None:
+            if user is None:
+                self.close()
+                raise AmwgError("amwg error -1: pointwise: a built-in family needs no flag -- its pointwise terms are known to the library")
+            try:
+                _check(L.amwg_set_pointwise(h, terms.encode() if isinstance(terms, str) else terms))
+            except AmwgError:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -522,6 +539,13 @@ class Sampler:
         _check(lib().amwg_dataset_n_obs(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out.tolist()
 
+    def pointwise_n_obs(self):
+        """-> the observations per dataset of a closure whose pointwise text is set (amwg_pointwise_n_obs); 0 otherwise"""
+        return int(lib().amwg_pointwise_n_obs(self.h))
+
+    def _n_max(self):
+        return max(self.dataset_n_obs() + [self.pointwise_n_obs()])
+
     def dataset_moments(self):
         """-> mean, sd, arrays [datasets][P + derived]: moments() per dataset (amwg_last_sample_dataset_moments)"""
         m, s = np.empty((self.D, self.PR)), np.empty((self.D, self.PR))
@@ -561,7 +585,7 @@ class Sampler:
         pointwise [datasets][n_max][2] = lppd_i, p_i, NaN beyond a dataset's n_obs): WAIC per dataset by the rule of include/amwg.h, the families' pointwise
         terms over the stored draws on the device (amwg_last_sample_dataset_waic)"""
         summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
-        pw = np.empty((self.D, max(self.dataset_n_obs()), 2)) if pointwise else None
+        pw = np.empty((self.D, self._n_max(), 2)) if pointwise else None
         _check(lib().amwg_last_sample_dataset_waic(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
         out = {"summary": summary, "high": high}
         if pointwise:
@@ -584,7 +608,7 @@ class Sampler:
         pointwise [datasets][n_max][3] = elpd_loo_i, lppd_i, khat_i, NaN beyond a dataset's n_obs): PSIS-LOO per dataset by the rule of include/amwg.h, the
         families' pointwise terms over the stored draws on the device (amwg_last_sample_dataset_loo)"""
         summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
-        pw = np.empty((self.D, max(self.dataset_n_obs()), 3)) if pointwise else None
+        pw = np.empty((self.D, self._n_max(), 3)) if pointwise else None
         _check(lib().amwg_last_sample_dataset_loo(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
         out = {"summary": summary, "high": high}
         if pointwise:
@@ -873,6 +897,67 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
     if loglik:
         out["loglik"] = ll
     return out
+
+
+def _user_models(users):
+    """users: one dict(source, arrays[, array_types, ...]) per dataset -> (the UserModel array of the check calls, what it points into)"""
+    keep = []
+    ums = (UserModel * max(1, len(users)))()
+    for k, user in enumerate(users):
+        src = user["source"].encode() if isinstance(user["source"], str) else user["source"]
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in user["arrays"]]
+        ptrs = (C.POINTER(C.c_double) * max(1, len(arrs)))(*[_dp(a) for a in arrs])
+        lens = (C.c_int64 * max(1, len(arrs)))(*[a.size for a in arrs])
+        types = (C.c_int32 * max(1, len(arrs)))(*[int(t) for t in user.get("array_types", [0] * len(arrs))])
+        keep.extend([src, arrs, ptrs, lens, types])
+        ums[k].source, ums[k].n_arrays, ums[k].arrays, ums[k].array_len, ums[k].array_type = src, len(arrs), ptrs, lens, types
+    return ums, keep
+
+
+def _user_check(loo, draws, users, terms, P, n_obs, pointwise, extra, scratch_bytes, device):
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: user_%s_check: draws must be [rows][PR][C]" % ("loo" if loo else "waic"))
+    rows, PR, Cn = dr.shape
+    D = len(users)
+    ums, keep = _user_models(users)
+    n_max = max(1, int(n_obs))
+    S = rows * (Cn // D) if D and Cn % D == 0 else 0
+    width = (loo_tail_len(S) + 1) if loo else S
+    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    pw = np.empty((max(1, D), n_max, 3 if loo else 2)) if pointwise else None
+    ex = None
+    if extra:
+        ex = (np.empty((max(1, D), n_max, width)) if loo else np.empty((max(1, D), S, n_max))) if width * n_max * max(1, D) <= (1 << 24) else np.empty(1)
+    L = selftest_lib()
+    call = L.amwg_user_loo_check if loo else L.amwg_user_waic_check
+    if call(device, ums, D, int(P), terms.encode() if isinstance(terms, str) else terms, _dp(dr), rows, PR, Cn, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
+            _dp(pw) if pointwise else None, _dp(ex) if extra else None) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    out = {"summary": summary, "high": high}
+    if pointwise:
+        out["pointwise"] = pw
+    if extra:
+        out["tails" if loo else "loglik"] = ex
+    return out
+
+
+def user_waic_check(draws, users, terms, P, n_obs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: waic_check for a translated closure -- users: one dict(source, arrays[, array_types]) per dataset (one source), terms: the pointwise
+    text of translate.js (options.pointwise), P the components of the state, n_obs its kTermN -> what waic_check returns (amwg_user_waic_check)"""
+    return _user_check(False, draws, users, terms, P, n_obs, pointwise, loglik, scratch_bytes, device)
+
+
+def user_loo_check(draws, users, terms, P, n_obs, pointwise=True, tails=False, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: loo_check for a translated closure, as user_waic_check (amwg_user_loo_check)"""
+    return _user_check(True, draws, users, terms, P, n_obs, pointwise, tails, scratch_bytes, device)
+
+
+def compile_pointwise(source, terms, arch="gfx950"):
+    """-> bytes of the code object: hiprtc compilation of a closure's pointwise program without a device (amwg_compile_pointwise)"""
+    n = C.c_size_t(0)
+    _check(lib().amwg_compile_pointwise(source.encode() if isinstance(source, str) else source, terms.encode() if isinstance(terms, str) else terms, arch.encode(), C.byref(n)))
+    return int(n.value)
 
 
 def loo_tail_len(S):

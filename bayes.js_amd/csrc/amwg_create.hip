@@ -523,7 +523,7 @@ static int upload_user_array(amwg_sampler *s, const amwg_user_model *models, int
 
 // every array the closure reads, row-major, in the storage type the translator chose.  D > 1: of every dataset, and the device table [D][row_stride] of their
 // places (amwg_user_dataset.h); the sampler's own DataRef then holds dataset 0's, as an ordinary sampler's would.
-static int upload_user_arrays(amwg_sampler *s, const amwg_user_model *models, int D) {
+int upload_user_arrays(amwg_sampler *s, const amwg_user_model *models, int D) {
   const amwg_user_model *m = &models[0];
   s->d.n_obs = 0;
   const int row_stride = m->n_arrays > kInlineUserArrays ? m->n_arrays : kInlineUserArrays;
@@ -726,6 +726,8 @@ static int create_user(const char *entry, const amwg_user_model *models, int D, 
   TRYB(upload_user_arrays(s, models, D));
   TRYB(alloc_chain_state(s, params, n_params, init, comp_opts));
   TRYB(plan_and_prepare(s, prop, clk, [&]() { return load_user_kernel(s, m->source, prop.gcnArchName); }));
+  s->user_source = m->source;      // (amwg_set_pointwise: the program of the pointwise terms begins with it)
+  s->user_arch = prop.gcnArchName;
   *out = guard.release();
   return AMWG_OK;
 }
@@ -741,6 +743,7 @@ int amwg_destroy(amwg_sampler *s) {
   amwg_autocov_forget(s);      // (amwg_autocov.h: the lag sums, rows and values of an armed autocovariance)
   if (s->d_draws) (void)hipFree(s->d_draws);
   if (s->user_module) (void)hipModuleUnload(s->user_module);
+  if (s->pw_module) (void)hipModuleUnload(s->pw_module);
   for (hipEvent_t e : s->chunk_ev) (void)hipEventDestroy(e);
   if (s->copy_stream) (void)hipStreamDestroy(s->copy_stream);
   if (s->ev0) (void)hipEventDestroy(s->ev0);

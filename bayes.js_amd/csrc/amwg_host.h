@@ -73,7 +73,10 @@ int autotune_geometry(amwg_sampler *s, int n_cus, size_t max_lds, const std::fun
 struct SourceTraits { long row_n, row_groups; bool row_sweep, row_cert; int cert_tail_n, pois_tail_n, logit_tail_n; bool tail_per_dataset; };
 SourceTraits source_traits(const char *src);
 int load_user_kernel(amwg_sampler *s, const char *source, const char *arch);
+int load_pointwise(amwg_sampler *s, const char *arch);      // the code object of amwg_set_pointwise's text on the sampler's device (once)
 
+// ---- amwg_create.hip: every array a closure reads on the sampler's device, in its storage type, and the table of a dataset sampler (also the check library's)
+int upload_user_arrays(amwg_sampler *s, const amwg_user_model *models, int D);
 // ---- amwg_create.hip (the tables of two_valued_sum), amwg_run.hip
 std::vector<uint32_t> two_valued_tables(const uint8_t *xb, int N);
 int use_device(int device);      // hipSetDevice for the helper entry points that take a device number; AMWG_EHIP where there is none

@@ -57,6 +57,9 @@ int amwg_loo_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
 // terms; NaN beyond n_d and for an observation with a non-finite term; the test library only).  Returns after `stream` has drained.
 int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
                     int32_t *high, double *pointwise, double *tails, hipStream_t stream);
+// amwg_loo_launch over any PointwiseLaunch (amwg_waic.h): the built-in families' kernels, or a closure's.  A closure: sets[d].n_obs = kTermN for every d.
+int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
+                 int32_t *high, double *pointwise, double *tails, hipStream_t stream);
 // the finish of include/amwg.h over one dataset's triples pw[n][3]: summary[4], *high (may be nullptr)
 void amwg_loo_totals(const double *pw, int64_t n, double *summary, int32_t *high);
 // the scratch budget of later calls in bytes (0: kLooScratchBytes); returns the budget in force before.  For the test library: the product never calls it.

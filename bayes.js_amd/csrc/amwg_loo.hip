@@ -21,20 +21,8 @@ using namespace amwg;
 
 namespace {
 
-constexpr int kDigitBits = 7, kBins = 1 << kDigitBits;      // 128 x 64 counters of 4 bytes: 32 KB of LDS beside the staged draws
-constexpr int kPasses = (64 + kDigitBits - 1) / kDigitBits;      // 10: nine digits of 7 bits and the last bit
 constexpr int kMaxTheta = 128;                                    // 30 + floor(sqrt(M)) <= 120 for M < kLooTailCap
 constexpr int kFitExtra = 2 * kMaxTheta + 16;                     // doubles of LDS of the fit beside the tail: L_j, w_j, the wavefronts' partial sums
-constexpr uint64_t kMaxKey = ~(uint64_t)0;
-
-struct LooState {
-  uint64_t prefix, thr, minkey;      // the digits chosen so far (low bits 0); the threshold key once done; the smallest key
-  uint32_t lo, in, done, inclusive, bad, cursor;      // keys below the bin, keys in it; 1: take keys <= thr, 0: keys < thr and copies of thr; a non-finite term; tail slots taken
-};
-
-__host__ __device__ inline int pass_shift(int pass) { const int s = 64 - kDigitBits * (pass + 1); return s < 0 ? 0 : s; }
-__host__ __device__ inline int pass_bins(int pass) { return 64 - kDigitBits * pass >= kDigitBits ? kBins : 1 << (64 - kDigitBits * pass); }
-
 __global__ void __launch_bounds__(kThreads) loo_init_kernel(LooState *state, int64_t count) {
   const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (k < count) state[k] = LooState{0, 0, kMaxKey, 0, 0, 0, 0, 0, 0};
@@ -45,57 +33,14 @@ __global__ void __launch_bounds__(kThreads) loo_fill_nan_kernel(double *out, int
   if (k < count) out[k] = __builtin_nan("");
 }
 
-// one digit of the select: hist[(obs_off[z] + i) * kBins + bin] += the terms of (d, i) whose key agrees with the prefix, by the bin of this pass's digit
+// one digit of the select (amwg_pointwise.h).  The atomics of the two kernels that walk the terms are there now, and as before every one is on an integer:
+// atomicAdd(&cnt[...], 1u) on the LDS counters, atomicAdd(&h[...], c) on the global ones, atomicMin((unsigned long long *)&state[o_at].minkey, ...) and
+// atomicOr(&state[o_at].bad, 1u) on the state's integer fields, atomicAdd(&state[o_at].cursor, 1u) for the tail slots
 template <int MODEL>
 __global__ void __launch_bounds__(kThreads) loo_hist_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicModel M,
                                                             const WaicDataset *__restrict__ sets, const int64_t *__restrict__ obs_off, LooState *__restrict__ state,
                                                             uint32_t *__restrict__ hist, int pass) {
-  typedef Family<MODEL> F;
-  __shared__ typename F::Draw stage[kStage];
-  __shared__ uint32_t cnt[kBins * kTile];      // [bin][lane]: a wavefront's 64 lanes fall into 64 different banks whatever their bins
-  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const WaicDataset ds = sets[d];
-  const int64_t n = F::n_eff(ds), S = rows * cpd, splits = waic_splits(S, n);
-  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
-  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
-  const int64_t i = (int64_t)blockIdx.x * kTile + lane;
-  const bool active = i < n;
-  const int64_t o_at = obs_off[blockIdx.z] + (active ? i : n - 1);
-  const LooState st = state[o_at];
-  const bool counting = active && !st.done;
-  if (!__syncthreads_or(counting ? 1 : 0)) return;      // every observation of the tile is done
-  for (int k = tid; k < kBins * kTile; k += kThreads) cnt[k] = 0;
-  const typename F::Obs o = F::load_obs(M, ds, active ? i : n - 1);
-  const int shift = pass_shift(pass), shift_prev = 64 - kDigitBits * pass;
-  const uint32_t mask = (uint32_t)pass_bins(pass) - 1u;
-  uint64_t kmin = kMaxKey;
-  bool bad = false;
-  for (int64_t s0 = s_begin; s0 < s_end; s0 += kStage) {
-    const int L = (int)(s_end - s0 < kStage ? s_end - s0 : kStage);
-    __syncthreads();
-    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, M, ds);
-    __syncthreads();
-    for (int j = wave; j < L; j += kWaves) {
-      const double l = F::term(o, stage[j], i, draws, C);
-      const uint64_t key = select_key(l);
-      if (pass == 0) {
-        kmin = key < kmin ? key : kmin;
-        bad = bad || !(__builtin_fabs(l) < kInf);
-      }
-      const bool match = pass == 0 || ((key ^ st.prefix) >> shift_prev) == 0;
-      if (counting && match) atomicAdd(&cnt[(((uint32_t)(key >> shift)) & mask) * kTile + lane], 1u);
-    }
-  }
-  __syncthreads();
-  uint32_t *h = hist + obs_off[blockIdx.z] * kBins;
-  for (int k = tid; k < kBins * kTile; k += kThreads) {
-    const uint32_t c = cnt[k];
-    if (c) atomicAdd(&h[((int64_t)blockIdx.x * kTile + (k & (kTile - 1))) * kBins + (k >> 6)], c);      // (a lane that counted is an observation below n)
-  }
-  if (pass == 0 && active) {
-    atomicMin((unsigned long long *)&state[o_at].minkey, (unsigned long long)kmin);
-    if (bad) atomicOr(&state[o_at].bad, 1u);
-  }
+  loo_hist_body<Family<MODEL>>(draws, rows, PR, C, cpd, d0, M, sets, obs_off, state, hist, pass);
 }
 
 // after a pass: the bin that holds rank M, per observation; *pending counts the observations that need another pass
@@ -132,53 +77,12 @@ __global__ void __launch_bounds__(kThreads) loo_pick_kernel(int d0, const WaicDa
   state[o_at] = st;
 }
 
-// the terms at or below the threshold into the tail, the others into the split's partial of B = sum exp(a_0 - l): parts[part_off[z] + split * n + i]
+// the terms at or below the threshold into the tail, the others into the split's partial of B (amwg_pointwise.h)
 template <int MODEL>
 __global__ void __launch_bounds__(kThreads) loo_compact_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicModel M,
                                                                const WaicDataset *__restrict__ sets, const int64_t *__restrict__ obs_off, const int64_t *__restrict__ part_off,
                                                                LooState *__restrict__ state, double *__restrict__ tail, uint32_t cap, double *__restrict__ parts) {
-  typedef Family<MODEL> F;
-  __shared__ typename F::Draw stage[kStage];
-  __shared__ double wave_b[kWaves - 1][kTile];
-  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const WaicDataset ds = sets[d];
-  const int64_t n = F::n_eff(ds), S = rows * cpd, splits = waic_splits(S, n);
-  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
-  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
-  const int64_t i = (int64_t)blockIdx.x * kTile + lane;
-  const bool active = i < n;
-  const int64_t o_at = obs_off[blockIdx.z] + (active ? i : n - 1);
-  const LooState st = state[o_at];
-  const double a0 = select_value(st.minkey);
-  const typename F::Obs o = F::load_obs(M, ds, active ? i : n - 1);
-  double *my_tail = tail + o_at * cap;
-  double b = 0.0;
-  for (int64_t s0 = s_begin; s0 < s_end; s0 += kStage) {
-    const int L = (int)(s_end - s0 < kStage ? s_end - s0 : kStage);
-    __syncthreads();
-    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, M, ds);
-    __syncthreads();
-    for (int j = wave; j < L; j += kWaves) {
-      const double l = F::term(o, stage[j], i, draws, C);
-      const uint64_t key = select_key(l);
-      const bool take = st.inclusive ? key <= st.thr : key < st.thr;
-      if (take) {
-        if (active) {
-          const uint32_t at = atomicAdd(&state[o_at].cursor, 1u);
-          if (at < cap) my_tail[at] = l;      // (the counts of the select say at < cap; the comparison keeps a wrong count inside the buffer)
-        }
-      } else if (key > st.thr) {
-        b += waic_exp(a0 - l);
-      }
-    }
-  }
-  __syncthreads();
-  if (wave > 0) wave_b[wave - 1][lane] = b;
-  __syncthreads();
-  if (wave != 0 || !active) return;
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) b += wave_b[w - 1][lane];
-  parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + i] = b;
+  loo_compact_body<Family<MODEL>>(draws, rows, PR, C, cpd, d0, M, sets, obs_off, part_off, state, tail, cap, parts);
 }
 
 // the sum of v over the workgroup's threads (one wavefront, or four), the same double in every thread: a butterfly over the lanes, then the wavefronts in the
@@ -199,12 +103,10 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // One workgroup per observation -- 256 threads, or one wavefront for a tail of at most kFitSmall slots (fit_threads) --: the tail sorted in LDS, the fit, the smoothed sum.  out[(d * out_stride + i) * 2 + (0 | 1)] = elpd_loo_i | khat_i; the sorted
 // tail's first M + 1 go to tails_out[(d * out_stride + i) * (M + 1) + t] when asked for.  Dynamic LDS: (cap + kFitExtra) * 8 bytes.
-template <int MODEL>
-__global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t cpd, int d0, const WaicDataset *__restrict__ sets, const int64_t *__restrict__ obs_off,
+__global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t cpd, int d0, const WaicDataset *__restrict__ sets, int bern, const int64_t *__restrict__ obs_off,
                                                            const int64_t *__restrict__ part_off, const LooState *__restrict__ state, double *__restrict__ tail, uint32_t cap,
                                                            const double *__restrict__ parts, uint32_t Mlen, int mm, double *__restrict__ out, int64_t out_stride,
                                                            double *__restrict__ tails_out) {
-  typedef Family<MODEL> F;
   extern __shared__ uint64_t lds[];
   uint64_t *keys = lds;
   double *X = reinterpret_cast<double *>(lds);      // the excesses take the place of the keys: x_r at X[M - r]
@@ -213,7 +115,7 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
   const uint32_t T = blockDim.x;
   const int waves = (int)(T >> 6);
   const WaicDataset ds = sets[d];
-  const int64_t n = F::n_eff(ds), S = rows * cpd, splits = waic_splits(S, n), i = blockIdx.x;
+  const int64_t n = bern ? (ds.n_obs > 0 ? 2 : 0) : ds.n_obs, S = rows * cpd, splits = waic_splits(S, n), i = blockIdx.x;
   if (i >= n) return;      // (uniform over the workgroup)
   const int64_t o_at = obs_off[blockIdx.y] + i;
   const LooState st = state[o_at];
@@ -348,16 +250,15 @@ inline uint32_t loo_cap(int64_t M) {
 }
 inline int loo_thetas(int64_t M) { return 30 + (int)(loo_isqrt_up(M + 1) - 1); }      // 30 + floor(sqrt(M)): the largest r with r * r <= M is isqrt_up(M + 1) - 1
 
-template <int MODEL>
-int run_family(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, const WaicDataset *d_sets,
-               int64_t n_max, double *d_pw, double *d_tails, LooStats &stats, hipStream_t stream) {
-  const bool bern = MODEL == AMWG_MODEL_BETA_BERN;
+int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, const WaicDataset *d_sets,
+                int64_t n_max, double *d_pw, double *d_tails, LooStats &stats, hipStream_t stream) {
+  const bool bern = K.bern;
   const int64_t cpd = C / D, S = rows * cpd, M = loo_tail_len(S);
   const uint32_t cap = loo_cap(M);
   const int mm = loo_thetas(M);
   const size_t fit_lds = ((size_t)cap + kFitExtra) * 8;
   if (fit_lds > 65536) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(loo_fit_kernel<MODEL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fit_lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(loo_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)fit_lds);
     if (e != hipSuccess) return amwg_fail(AMWG_EHIP, "%s: a tail of %lld terms needs %zu bytes of LDS in one workgroup: %s", call, (long long)(M + 1), fit_lds, hipGetErrorString(e));
   }
   DevBuf two, two_tails, offs, state, hist, tail, parts, pending;
@@ -419,9 +320,7 @@ int run_family(const char *call, const double *draws, int64_t rows, int PR, int6
           int waiting = 0;
           HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)obs * kBins * 4, stream));
           HIP_TRY(hipMemsetAsync(pending.p, 0, sizeof(int), stream));
-          hipLaunchKernelGGL(loo_hist_kernel<MODEL>, walk, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, d_sets, obs_off + d0, state.as<LooState>(),
-                             hist.as<uint32_t>(), pass);
-          HIP_TRY(hipGetLastError());
+          HIP_TRY(K.loo_hist(walk, stream, draws, rows, PR, C, cpd, d0, d_sets, obs_off + d0, state.as<LooState>(), hist.as<uint32_t>(), pass));
           hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern ? 1 : 0, obs_off + d0, state.as<LooState>(), hist.as<uint32_t>(), pass,
                              (uint32_t)M, cap, pending.as<int>());
           HIP_TRY(hipGetLastError());
@@ -435,14 +334,12 @@ int run_family(const char *call, const double *draws, int64_t rows, int PR, int6
       }
       {
         Phase ph(stream, stats.timed != 0);
-        hipLaunchKernelGGL(loo_compact_kernel<MODEL>, walk, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, d_sets, obs_off + d0, part_off + d0,
-                           state.as<LooState>(), tail.as<double>(), cap, parts.as<double>());
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(K.loo_compact(walk, stream, draws, rows, PR, C, cpd, d0, d_sets, obs_off + d0, part_off + d0, state.as<LooState>(), tail.as<double>(), cap, parts.as<double>()));
         ph.end(stats.ms_compact);
       }
       {
         Phase ph(stream, stats.timed != 0);
-        hipLaunchKernelGGL(loo_fit_kernel<MODEL>, dim3((unsigned)n_most, (unsigned)(d1 - d0)), dim3(fit_threads(cap)), fit_lds, stream, rows, cpd, d0, d_sets, obs_off + d0,
+        hipLaunchKernelGGL(loo_fit_kernel, dim3((unsigned)n_most, (unsigned)(d1 - d0)), dim3(fit_threads(cap)), fit_lds, stream, rows, cpd, d0, d_sets, bern ? 1 : 0, obs_off + d0,
                            part_off + d0, state.as<LooState>(), tail.as<double>(), cap, parts.as<double>(), (uint32_t)M, mm, out, out_stride, tails_out);
         HIP_TRY(hipGetLastError());
         ph.end(stats.ms_fit);
@@ -452,18 +349,42 @@ int run_family(const char *call, const double *draws, int64_t rows, int PR, int6
   }
   if (bern) {
     const dim3 grid((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)D);
-    hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, model, d_sets, two.as<double>(), d_pw, n_max, (int64_t)2);
+    hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, *K.family, d_sets, two.as<double>(), d_pw, n_max, (int64_t)2);
     HIP_TRY(hipGetLastError());
     if (d_tails) {
-      hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, model, d_sets, two_tails.as<double>(), d_tails, n_max, M + 1);
+      hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, *K.family, d_sets, two_tails.as<double>(), d_tails, n_max, M + 1);
       HIP_TRY(hipGetLastError());
     }
   }
   HIP_TRY(hipStreamSynchronize(stream));      // (the scratch is freed on return)
+  (void)call;
   return AMWG_OK;
 }
 
+template <int MODEL>
+void family_kernels(PointwiseLaunch &K, const WaicModel &model) {
+  K.loo_hist = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off, void *state,
+                       uint32_t *hist, int pass) {
+    hipLaunchKernelGGL(loo_hist_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, sets, obs_off, static_cast<LooState *>(state), hist, pass);
+    return hipGetLastError();
+  };
+  K.loo_compact = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off,
+                          const int64_t *part_off, void *state, double *tail, uint32_t cap, double *parts) {
+    hipLaunchKernelGGL(loo_compact_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, sets, obs_off, part_off, static_cast<LooState *>(state), tail, cap, parts);
+    return hipGetLastError();
+  };
+}
+
 }  // namespace
+
+void amwg_loo_family_kernels(PointwiseLaunch &K, const WaicModel &model) {
+  switch (model.model) {
+    case AMWG_MODEL_NORMAL: family_kernels<AMWG_MODEL_NORMAL>(K, model); break;
+    case AMWG_MODEL_BETA_BERN: family_kernels<AMWG_MODEL_BETA_BERN>(K, model); break;
+    case AMWG_MODEL_HIER_NORMAL: family_kernels<AMWG_MODEL_HIER_NORMAL>(K, model); break;
+    default: family_kernels<AMWG_MODEL_POIS_GLM>(K, model); break;
+  }
+}
 
 size_t amwg_loo_set_budget(size_t bytes) {
   const size_t before = g_budget;
@@ -505,6 +426,14 @@ void amwg_loo_totals(const double *pw, int64_t n, double *summary, int32_t *high
 
 int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
                     int32_t *high, double *pointwise, double *tails, hipStream_t stream) {
+  PointwiseLaunch K;
+  amwg_waic_family_kernels(K, model);
+  amwg_loo_family_kernels(K, model);
+  return amwg_loo_run(call, draws, rows, PR, C, D, K, sets, summary, high, pointwise, tails, stream);
+}
+
+int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
+                 int32_t *high, double *pointwise, double *tails, hipStream_t stream) {
   if (!draws || !sets || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
   TRYB(amwg_loo_shape(call, rows, PR, C, D));
   int64_t n_max = 0;
@@ -516,7 +445,8 @@ int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR,
   std::vector<double> wsum((size_t)D * 4), wpw(pairs * 2), got(pairs * 2);
   {
     Phase ph(stream, stats.timed != 0);
-    TRYB(amwg_waic_launch(call, draws, rows, PR, C, D, model, sets, wsum.data(), nullptr, wpw.data(), nullptr, stream));
+    if (K.family) TRYB(amwg_waic_launch(call, draws, rows, PR, C, D, *K.family, sets, wsum.data(), nullptr, wpw.data(), nullptr, stream));
+    else TRYB(amwg_waic_run(call, draws, rows, PR, C, D, K, sets, wsum.data(), nullptr, wpw.data(), nullptr, stream));
     ph.end(stats.ms_lppd);
   }
   const size_t pw_count = (size_t)D * (size_t)n_max * 2, tl_count = tails ? (size_t)D * (size_t)n_max * (size_t)(M + 1) : 0;
@@ -537,12 +467,7 @@ int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR,
   }
   double *dt = tails ? d_tl.as<double>() : nullptr;
   const WaicDataset *ds = d_sets.as<WaicDataset>();
-  switch (model.model) {
-    case AMWG_MODEL_NORMAL: TRYB(run_family<AMWG_MODEL_NORMAL>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream)); break;
-    case AMWG_MODEL_BETA_BERN: TRYB(run_family<AMWG_MODEL_BETA_BERN>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream)); break;
-    case AMWG_MODEL_HIER_NORMAL: TRYB(run_family<AMWG_MODEL_HIER_NORMAL>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream)); break;
-    default: TRYB(run_family<AMWG_MODEL_POIS_GLM>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream)); break;
-  }
+  TRYB(run_kernels(call, draws, rows, PR, C, D, K, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream));
   {
     std::lock_guard<std::mutex> hold(g_stats_lock);
     g_stats = stats;
@@ -566,7 +491,7 @@ int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR,
 extern "C" int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
   static const char *call = "amwg_last_sample_dataset_loo";
   if (!s || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
-  if (s->user) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
+  if (s->user && s->pw_terms.empty()) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
   TRYB(amwg_refuse_summarised(s, call));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "%s: no sample() call yet", call);
   const int D = s->n_datasets, PR = s->P + s->D;
@@ -574,6 +499,13 @@ extern "C" int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary, in
   if (s->mc.group_local) return amwg_fail(AMWG_EINVAL, "%s: a group_local sampler keeps its observations as a lane-major tile; the pointwise terms need them in index order", call);
   HIP_TRY(hipSetDevice(s->device));
   std::vector<WaicDataset> sets;
+  if (s->user) {
+    UserPointwise u;
+    TRYB(amwg_pointwise_describe_user(s, sets, u));
+    PointwiseLaunch K;
+    amwg_pointwise_user_kernels(K, u);
+    return amwg_loo_run(call, s->last_draws, s->last_rows, PR, s->C, D, K, sets.data(), summary, high, pointwise, nullptr, s->stream);
+  }
   WaicModel m{};
   TRYB(amwg_waic_describe(s, sets, m));
   return amwg_loo_launch(call, s->last_draws, s->last_rows, PR, s->C, D, m, sets.data(), summary, high, pointwise, nullptr, s->stream);

@@ -452,6 +452,23 @@ static napi_value Destroy(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* setPointwise(handle, terms_source): the pointwise text of a translated closure (translate.js, options.pointwise) stored on its sampler (amwg_set_pointwise) */
+static napi_value SetPointwise(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  size_t slen = 0;
+  if (napi_get_value_string_utf8(env, a[1], NULL, 0, &slen) != napi_ok) { napi_throw_type_error(env, NULL, "amwg_napi.setPointwise: the text must be a string"); return NULL; }
+  char *src = (char *)malloc(slen + 1);
+  if (!src) { napi_throw_error(env, NULL, "amwg_napi.setPointwise: out of memory"); return NULL; }
+  napi_get_value_string_utf8(env, a[1], src, slen + 1, &slen);
+  const int rc = amwg_set_pointwise(s, src);
+  free(src);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  return NULL;
+}
+
 static int64_t arg_i64(napi_env env, napi_value v) {
   double d = 0;
   napi_get_value_double(env, v, &d);
@@ -793,6 +810,8 @@ static napi_value dataset_pointwise(napi_env env, napi_callback_info info, point
   if (!vn || !vh || !vs) return NULL;
   int rc = amwg_dataset_n_obs(s, n_obs);
   if (rc != AMWG_OK) return throw_amwg(env, rc);
+  const int64_t closure_n = amwg_pointwise_n_obs(s);      /* (a closure whose pointwise text is set: kTermN observations per dataset) */
+  if (closure_n > 0) for (size_t d = 0; d < D; ++d) n_obs[d] = (int32_t)closure_n;
   int32_t n_max = 0;
   for (size_t d = 0; d < D; ++d) n_max = n_obs[d] > n_max ? n_obs[d] : n_max;
   if (want) { vp = new_f64(env, D * (size_t)n_max * width, &pw); if (!vp) return NULL; }
@@ -1231,7 +1250,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

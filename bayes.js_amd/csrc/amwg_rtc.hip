@@ -18,7 +18,7 @@
 extern "C" {
 extern const char amwg_hdr_stdint[], amwg_hdr_types[], amwg_hdr_math[], amwg_hdr_div[], amwg_hdr_ld[], amwg_hdr_philox[],
     amwg_hdr_kernel[], amwg_hdr_user[], amwg_hdr_twoval[], amwg_hdr_kval[], amwg_hdr_trig[], amwg_hdr_pass[], amwg_hdr_rows[], amwg_hdr_window[], amwg_hdr_gtail[],
-    amwg_hdr_user_kernels[], amwg_hdr_user_dataset[];
+    amwg_hdr_user_kernels[], amwg_hdr_user_dataset[], amwg_hdr_select[], amwg_hdr_pointwise[], amwg_hdr_pointwise_types[];
 }
 
 // ---- hiprtc: a translated closure + its step kernels (amwg_user_kernels.h) -> code object for one (lanes, workgroup) geometry
@@ -113,13 +113,15 @@ static void dump_code_object(const std::vector<char> &code) {      // developmen
 
 // use_cache = false: compile even if the on-disk cache has the object (the caller found the cached one unloadable)
 // datasets: with the dataset twins (amwg_user_dataset.h) compiled in -- one more compile option, hence one more part of the cache key
-static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool datasets, bool use_cache = true) {
+// pointwise = true: prog_src is a closure's pointwise program (pointwise_program) -- the same options and cache, three more headers (amwg_select.h, amwg_pointwise.h, amwg_pointwise_types.h)
+static int compile_program(const std::string &prog_src, const char *arch, std::vector<char> *code, bool datasets, bool use_cache, bool pointwise) {
   static const char *names[] = {"amwg_stdint.h", "amwg_types.h", "amwg_math.h", "amwg_div.h", "amwg_ld.h", "amwg_philox.h", "amwg_kernel.h", "amwg_user.h",
-                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_gtail.h", "amwg_user_kernels.h", "amwg_user_dataset.h"};
+                                "amwg_twoval.h", "amwg_kval.h", "amwg_trig.h", "amwg_pass.h", "amwg_rows.h", "amwg_window.h", "amwg_gtail.h", "amwg_user_kernels.h", "amwg_user_dataset.h",
+                                "amwg_select.h", "amwg_pointwise.h", "amwg_pointwise_types.h"};
   const char *texts[] = {amwg_hdr_stdint, amwg_hdr_types, amwg_hdr_math, amwg_hdr_div, amwg_hdr_ld, amwg_hdr_philox, amwg_hdr_kernel, amwg_hdr_user,
-                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_gtail, amwg_hdr_user_kernels, amwg_hdr_user_dataset};
-  constexpr int kHeaders = (int)(sizeof(texts) / sizeof(texts[0]));
-  const std::string prog_src = user_program(source, lanes, block);
+                         amwg_hdr_twoval, amwg_hdr_kval, amwg_hdr_trig, amwg_hdr_pass, amwg_hdr_rows, amwg_hdr_window, amwg_hdr_gtail, amwg_hdr_user_kernels, amwg_hdr_user_dataset,
+                         amwg_hdr_select, amwg_hdr_pointwise, amwg_hdr_pointwise_types};
+  const int kHeaders = (int)(sizeof(texts) / sizeof(texts[0])) - (pointwise ? 0 : 3);      // (a step-kernel program sees, and is keyed by, the headers it always had)
 #if defined(AMWG_AUDIT)      // (libamwg_audit.so: the certified kernels of translated closures record |A - E| / eps as the built-in families' do)
   const char *const kOpts[] = {"-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-value", "-DAMWG_AUDIT=1"};
 #elif defined(AMWG_X_PHASES)      // (the phase-clock development build: translated closures are clocked too)
@@ -137,7 +139,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
     std::vector<std::string> parts = {prog_src, arch, "hiprtc " + std::to_string(rt_major) + "." + std::to_string(rt_minor)};
     for (const char *o : kOpts) parts.push_back(o);
     if (datasets) parts.push_back(kDatasetsOpt);
-    for (const char *t : texts) parts.push_back(t);
+    for (int h = 0; h < kHeaders; ++h) parts.push_back(texts[h]);
     key = hash_key(parts);
     char name[64];
     snprintf(name, sizeof name, "/%016llx%016llx.hsaco", (unsigned long long)key.h1, (unsigned long long)key.h2);
@@ -161,7 +163,7 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
     std::string log(n ? n : 1, '\0');
     if (n) hiprtcGetProgramLog(prog, &log[0]);
     hiprtcDestroyProgram(&prog);
-    g_err = "the translated log_post did not compile (hiprtc): " + log;
+    g_err = std::string(pointwise ? "the pointwise terms of the translated log_post did not compile (hiprtc): " : "the translated log_post did not compile (hiprtc): ") + log;
     return AMWG_EINVAL;
   }
   size_t cs = 0;
@@ -172,6 +174,18 @@ static int compile_user(const char *source, int lanes, int block, const char *ar
   if (!file.empty()) cache_write(dir, file, key, *code);
   dump_code_object(*code);
   return AMWG_OK;
+}
+
+static int compile_user(const char *source, int lanes, int block, const char *arch, std::vector<char> *code, bool datasets, bool use_cache = true) {
+  return compile_program(user_program(source, lanes, block), arch, code, datasets, use_cache, false);
+}
+
+// ---- hiprtc: a translated closure + its pointwise terms (translate.js pointwisePlan: struct UserTerms) + the kernels of amwg_pointwise.h -> one code object
+static std::string pointwise_program(const char *source, const char *terms) {
+  return std::string("#include \"amwg_kernel.h\"\n#include \"amwg_user.h\"\n") + source + "\n" + terms + "\n#define AMWG_POINTWISE_USER 1\n#include \"amwg_pointwise.h\"\n";
+}
+static int compile_pointwise(const char *source, const char *terms, const char *arch, std::vector<char> *code, bool use_cache = true) {
+  return compile_program(pointwise_program(source, terms), arch, code, false, use_cache, true);
 }
 
 // What the generated source of a translated closure (translate.js) states about itself, read off its markers: the row plan (kRowN, kRowGroups, kRowSweep,
@@ -223,7 +237,42 @@ int load_user_kernel(amwg_sampler *s, const char *source, const char *arch) {
   return AMWG_OK;
 }
 
+// ---- the pointwise code object of a sampler (amwg_set_pointwise): compiled at the first WAIC / LOO call, loaded on the sampler's device, kept until destroy
+int load_pointwise(amwg_sampler *s, const char *arch) {
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);      // (taken first: two calls on one sampler must not both find no module)
+  if (s->pw_module) return AMWG_OK;
+  std::vector<char> code;
+  TRYB(compile_pointwise(s->user_source.c_str(), s->pw_terms.c_str(), arch, &code));
+  static const char *const kEntries[4] = {"amwg_pw_waic_partial", "amwg_pw_waic_loglik", "amwg_pw_loo_hist", "amwg_pw_loo_compact"};
+  auto load = [&]() {
+    hipError_t e = hipModuleLoadData(&s->pw_module, code.data());
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipModuleGetFunction(&s->pw_fn[k], s->pw_module, kEntries[k]);
+    return e;
+  };
+  hipError_t e = load();
+  if (e != hipSuccess) {      // (as load_user_kernel: an object the loader refuses is compiled afresh, once)
+    (void)hipGetLastError();
+    if (s->pw_module) { (void)hipModuleUnload(s->pw_module); s->pw_module = nullptr; }
+    TRYB(compile_pointwise(s->user_source.c_str(), s->pw_terms.c_str(), arch, &code, false));
+    e = load();
+    if (e != hipSuccess) {
+      if (s->pw_module) { (void)hipModuleUnload(s->pw_module); s->pw_module = nullptr; }
+      return amwg_fail(AMWG_EHIP, "loading the compiled pointwise terms failed: %s", hipGetErrorString(e));
+    }
+  }
+  return AMWG_OK;
+}
+
 extern "C" {
+
+int amwg_compile_pointwise(const char *source, const char *terms_source, const char *arch, size_t *code_bytes) {
+  if (!source || !terms_source || !arch) return amwg_fail(AMWG_EINVAL, "amwg_compile_pointwise: null argument");
+  std::vector<char> code;
+  int rc = compile_pointwise(source, terms_source, arch, &code);
+  if (rc == AMWG_OK && code_bytes) *code_bytes = code.size();
+  return rc;
+}
 
 int amwg_code_cache_stats(int64_t *hits, int64_t *misses, char *dir, size_t dir_capacity) {
   if (hits) *hits = g_cache_hits;

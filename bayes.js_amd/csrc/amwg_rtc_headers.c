@@ -21,3 +21,6 @@ AMWG_TEXT(amwg_hdr_window, "amwg_window.h");
 AMWG_TEXT(amwg_hdr_gtail, "amwg_gtail.h");
 AMWG_TEXT(amwg_hdr_user_kernels, "amwg_user_kernels.h");
 AMWG_TEXT(amwg_hdr_user_dataset, "amwg_user_dataset.h");
+AMWG_TEXT(amwg_hdr_select, "amwg_select.h");
+AMWG_TEXT(amwg_hdr_pointwise, "amwg_pointwise.h");
+AMWG_TEXT(amwg_hdr_pointwise_types, "amwg_pointwise_types.h");

@@ -77,6 +77,12 @@ struct amwg_sampler {
   double user_work_one_lane = 0;   // the same with one lane per chain when that enables a fast-forwarded sum (0 = n/a)
   hipFunction_t user_fn = nullptr;
   hipModule_t user_module = nullptr;
+  // ... its pointwise terms (amwg_set_pointwise; amwg_pointwise.h): the closure's source and the terms text as given, the architecture of the device, and the code
+  // object of the four kernels that evaluate them, compiled and loaded at the first call that needs it (amwg_rtc.hip load_pointwise)
+  std::string user_source, user_arch, pw_terms;
+  int pw_n_obs = 0, pw_state_n = 0;      // kTermN, kStateN of the terms text
+  hipModule_t pw_module = nullptr;
+  hipFunction_t pw_fn[4] = {nullptr, nullptr, nullptr, nullptr};      // the entries of amwg_pointwise.h, in its order
   // last call
   int n_launches = 0;
   double kernel_ms = 0.0;

@@ -2,9 +2,11 @@
 // quantiles (dataset_select_kernel, amwg_summaries.hip) and the thresholds of the highest-density interval (hpd_threshold_kernel, amwg_hpd.hip).  Device code
 // only; internal to those two translation units, and not a source of the step kernels (tools/build_id.py).
 #pragma once
+#if !defined(__HIPCC_RTC__)      // (hiprtc -- amwg_pointwise.h for a translated closure -- has the runtime's names built in)
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#endif
 
 __device__ inline uint64_t select_key(double v) {      // order of the doubles = order of the keys (-0 before +0)
   const uint64_t b = (uint64_t)__double_as_longlong(v);

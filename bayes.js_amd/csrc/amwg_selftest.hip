@@ -1,5 +1,7 @@
 // amwg_selftest.hip -- the test-only entry points of include/amwg_selftest.h: the building blocks one by one, for the test suite.  Linked into
 // libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
+#include <cstring>
+
 #include "../../include/amwg_selftest.h"
 #include "amwg_dataset_quantiles.h"
 #include "amwg_autocov.h"
@@ -446,6 +448,58 @@ int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t P
 int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                    int32_t *high, double *pointwise, double *tails) {
   return pointwise_check("amwg_loo_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, tails);
+}
+
+// amwg_user_waic_check and amwg_user_loo_check: a closure's source and pointwise text, its arrays per dataset as amwg_create_user_datasets takes them, on a handle
+// that holds nothing but those (no chains, no step kernel): the arrays uploaded as a sampler's, the code object compiled and loaded as its first WAIC / LOO call does
+static int user_pointwise_check(const char *call, bool loo, int32_t device, const amwg_user_model *models, int32_t D, int32_t P, const char *terms, const double *draws, int64_t rows,
+                                int32_t PR, int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra) {
+  if (!models || !terms || !draws || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
+  TRYB(loo ? amwg_loo_shape(call, rows, PR, C, D) : amwg_waic_shape(call, rows, PR, C, D));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
+  if (P < 1 || PR < P) return amwg_fail(AMWG_EINVAL, "%s: the closure reads %d components of a draw, the draws hold %d", call, P, PR);
+  for (int d = 0; d < D; ++d) {
+    if (!models[d].source || strcmp(models[d].source, models[0].source) != 0 || models[d].n_arrays != models[0].n_arrays) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: another source or n_arrays than dataset 0's", call, d);
+    for (int j = 0; j < models[d].n_arrays; ++j) if (models[d].array_len[j] != models[0].array_len[j]) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: array %d of another length than dataset 0's", call, d, j);
+  }
+  TRYB(use_device(device));
+  struct Handle { amwg_sampler *s = new amwg_sampler(); ~Handle() { amwg_destroy(s); } } h;
+  amwg_sampler *s = h.s;
+  s->device = device; s->user = true; s->P = P; s->n_datasets = D; s->C = C;
+  hipDeviceProp_t prop;
+  HIP_TRY(hipGetDeviceProperties(&prop, device));
+  s->user_source = models[0].source;
+  s->user_arch = prop.gcnArchName;
+  TRYB(upload_user_arrays(s, models, D));
+  TRYB(amwg_set_pointwise(s, terms));
+  const int64_t S = rows * (C / D), n = s->pw_n_obs;
+  if (!loo && extra && (double)D * (double)S * (double)n > 16777216.0) return amwg_fail(AMWG_EINVAL, "%s: loglik of more than 2^24 doubles", call);
+  if (loo && extra && (double)D * (double)(loo_tail_len(S) + 1) * (double)n > 16777216.0) return amwg_fail(AMWG_EINVAL, "%s: tails of more than 2^24 doubles", call);
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  std::vector<WaicDataset> sets;
+  UserPointwise u;
+  TRYB(amwg_pointwise_describe_user(s, sets, u));
+  PointwiseLaunch K;
+  amwg_pointwise_user_kernels(K, u);
+  const size_t before = loo ? amwg_loo_set_budget((size_t)scratch_bytes) : amwg_waic_set_budget((size_t)scratch_bytes);
+  const int rc = loo ? amwg_loo_run(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, nullptr)
+                     : amwg_waic_run(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, nullptr);
+  if (loo) amwg_loo_set_budget(before); else amwg_waic_set_budget(before);
+  return rc;
+}
+
+int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR, int64_t C,
+                         int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik) {
+  return user_pointwise_check("amwg_user_waic_check", false, device, models, n_datasets, P, terms_source, draws, rows, PR, C, scratch_bytes, summary, high, pointwise, loglik);
+}
+
+int amwg_user_loo_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR, int64_t C,
+                        int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails) {
+  return user_pointwise_check("amwg_user_loo_check", true, device, models, n_datasets, P, terms_source, draws, rows, PR, C, scratch_bytes, summary, high, pointwise, tails);
 }
 
 int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms) {

@@ -1,5 +1,5 @@
-// amwg_terms.h -- the pointwise terms l_si of the four built-in families over stored draws, and the split of a dataset's draws over workgroups: what the WAIC
-// (amwg_waic.hip) and the PSIS-LOO (amwg_loo.hip) kernels share, so that both see the same doubles.  Device code; internal to those two translation units, and
+// amwg_terms.h -- the pointwise terms l_si of the four built-in families over stored draws: what the WAIC (amwg_waic.hip) and the PSIS-LOO (amwg_loo.hip) kernels
+// share, so that both see the same doubles.  The kernels that evaluate them, and the split of a dataset's draws over workgroups, are amwg_pointwise.h's.  Device code; internal to those two translation units, and
 // not a source of the step kernels (tools/build_id.py).  The terms are the reference's, bit for bit (amwg_ld.h, amwg_div.h, exp_log_v8).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,34 +8,10 @@
 
 #include "amwg_div.h"
 #include "amwg_ld.h"
+#include "amwg_pointwise.h"
 #include "amwg_waic.h"
 
 namespace amwg {
-
-constexpr int kThreads = 256;      // a workgroup: four wavefronts
-constexpr int kTile = 64;          // observations per workgroup, a lane each
-constexpr int kWaves = kThreads / 64;
-constexpr int kStage = 256;        // draws staged in LDS at a time, a thread each
-constexpr int64_t kTargetBlocks = 2048;      // workgroups per dataset the split aims at (256 CUs x 8)
-constexpr int64_t kMinRun = 256;             // draws per split at least: one staged run
-
-// the number of contiguous runs a dataset's S draws are cut into, from S and its n alone
-__host__ __device__ inline int64_t waic_splits(int64_t S, int64_t n) {
-  const int64_t tiles = (n + kTile - 1) / kTile;
-  int64_t want = tiles > 0 ? kTargetBlocks / tiles : 1;
-  want = want < 1 ? 1 : want;
-  int64_t by_len = S / kMinRun;
-  by_len = by_len < 1 ? 1 : by_len;
-  return want < by_len ? want : by_len;
-}
-__host__ __device__ inline int64_t split_begin(int64_t S, int64_t splits, int64_t k) { return S / splits * k + (S % splits) * k / splits; }
-
-// exp_v8 with its rare arguments out of line (0, beyond -708, the sliver at ln2 / 2): the loop's code holds the common path only
-__device__ __forceinline__ double waic_exp(double a) {
-  if (__builtin_expect(exp_is_rare(a), 0)) return exp_v8_cold(a);
-  const ExpParts e = exp_parts(a, ExpLogLiterals{});
-  return set_hi_word(e.y, hi_word(e.y) + (e.k << 20));
-}
 
 // ---- the families: what an evaluation needs of a draw (staged in LDS), what it needs of an observation (registers), and the term
 template <int MODEL> struct Family;
@@ -58,7 +34,7 @@ template <> struct Family<AMWG_MODEL_NORMAL> {
   }
   __device__ static void set_base(Draw &, int64_t) {}
   __device__ static Obs load_obs(const WaicModel &M, const WaicDataset &ds, int64_t i) { return Obs{M.x[ds.off_x + i]}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *, int64_t) {
+  __device__ __forceinline__ static double term(const WaicModel &, const Obs &o, const Draw &w, int64_t, const double *, int64_t) {
     const double t = o.x - w.mu;
     const double tt = t * t;
     return w.c - (w.fast ? div_by_invariant(tt, w.den, Reciprocal{w.yhi, w.ylo}) : tt / w.den);
@@ -79,7 +55,7 @@ template <> struct Family<AMWG_MODEL_HIER_NORMAL> {      // theta[0 .. G - 1], m
   }
   __device__ static void set_base(Draw &w, int64_t base) { w.base = base; }      // where the draw's component 0 lies
   __device__ static Obs load_obs(const WaicModel &M, const WaicDataset &ds, int64_t i) { return Obs{M.x[ds.off_x + i], (int64_t)M.xb[ds.off_xb + i]}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *draws, int64_t C) {
+  __device__ __forceinline__ static double term(const WaicModel &, const Obs &o, const Draw &w, int64_t, const double *draws, int64_t C) {
     const double t = o.x - draws[w.base + o.g_off * C];
     return w.c - (t * t) / w.den;
   }
@@ -95,7 +71,7 @@ template <> struct Family<AMWG_MODEL_BETA_BERN> {      // two observations: x = 
   }
   __device__ static void set_base(Draw &, int64_t) {}
   __device__ static Obs load_obs(const WaicModel &, const WaicDataset &, int64_t i) { return Obs{i == 0}; }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t, const double *, int64_t) { return o.one ? w.l1 : w.l0; }
+  __device__ __forceinline__ static double term(const WaicModel &, const Obs &o, const Draw &w, int64_t, const double *, int64_t) { return o.one ? w.l1 : w.l0; }
 };
 
 template <> struct Family<AMWG_MODEL_POIS_GLM> {      // beta[0 .. 7], cp
@@ -120,7 +96,7 @@ template <> struct Family<AMWG_MODEL_POIS_GLM> {      // beta[0 .. 7], cp
     o.v[8] = M.lfact[ds.off_lfact + i];
     return o;
   }
-  __device__ __forceinline__ static double term(const Obs &o, const Draw &w, int64_t i, const double *, int64_t) {      // PoisGlmModel::eta_of, term_of
+  __device__ __forceinline__ static double term(const WaicModel &, const Obs &o, const Draw &w, int64_t i, const double *, int64_t) {      // PoisGlmModel::eta_of, term_of
     double eta = o.v[0] * w.b[0];
 #pragma unroll
     for (int k = 1; k < 7; ++k) eta += o.v[k] * w.b[k];
@@ -130,13 +106,5 @@ template <> struct Family<AMWG_MODEL_POIS_GLM> {      // beta[0 .. 7], cp
     return lg * o.v[7] - lam - o.v[8];
   }
 };
-
-template <class F>
-__device__ __forceinline__ typename F::Draw draw_at(const double *draws, int PR, int64_t C, int64_t cpd, int d, int64_t s, const WaicModel &M, const WaicDataset &ds) {
-  const int64_t row = s / cpd, base = row * PR * C + (int64_t)d * cpd + (s - row * cpd);
-  typename F::Draw w = F::make_draw(draws + base, C, M, ds);
-  F::set_base(w, base);
-  return w;
-}
 
 }  // namespace amwg

@@ -23,17 +23,15 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <vector>
+
+#include "amwg_pointwise_types.h"      // WaicDataset, UserTermsArg
 
 struct amwg_sampler;
 
 constexpr size_t kWaicScratchBytes = (size_t)256 << 20;      // the default scratch budget of a call: 256 MiB, as amwg_hpd.h
 
-// one dataset's size and the places of its copies inside the family's arrays (DatasetConsts, amwg_dataset.h: what the step kernels read)
-struct WaicDataset {
-  int32_t n_obs, data_mid_range;
-  int64_t off_x, off_y, off_lfact, off_xb;
-};
 // the family and its arrays on the device, in the sampler's own layout (DataRef, amwg_types.h)
 struct WaicModel {
   int32_t model, G, exact_division, reserved;      // AMWG_MODEL_*; the hierarchical family's groups; amwg_options::exact_division
@@ -43,7 +41,30 @@ struct WaicModel {
   const uint8_t *invalid;                          // BETA_BERN: 1 where x_i is neither 0 nor 1, laid out like xb; nullptr: no such observation anywhere
 };
 
+// HOW A CALL LAUNCHES THE KERNELS THAT EVALUATE THE MODEL (amwg_pointwise.h): the instantiations for a built-in family (amwg_waic_family_kernels,
+// amwg_loo_family_kernels), or the entries of a closure's code object (amwg_pointwise_user_kernels).  Everything else of a call is the same code for both.
+struct PointwiseLaunch {
+  bool bern = false;                     // the family of two observations per dataset (its pairs are picked by x_i afterwards)
+  const WaicModel *family = nullptr;     // the built-in family's model (nullptr: a closure)
+  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, void *)> waic_partial;
+  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, const WaicDataset *, double *, int64_t)> waic_loglik;
+  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, void *, uint32_t *, int)> loo_hist;
+  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, const int64_t *, void *, double *, uint32_t, double *)> loo_compact;
+};
+// the pointwise code object of a translated closure, loaded on the sampler's device (amwg_rtc.hip load_pointwise), and its model argument
+struct UserPointwise {
+  hipFunction_t waic_partial = nullptr, waic_loglik = nullptr, loo_hist = nullptr, loo_compact = nullptr;
+  amwg::UserTermsArg arg{};
+  int32_t n_obs = 0, state_n = 0;      // kTermN, kStateN of the terms text
+};
+
 #pragma GCC visibility push(hidden)
+void amwg_waic_family_kernels(PointwiseLaunch &K, const WaicModel &model);      // (keeps &model: the launch must not outlive it)
+void amwg_loo_family_kernels(PointwiseLaunch &K, const WaicModel &model);
+void amwg_pointwise_user_kernels(PointwiseLaunch &K, const UserPointwise &u);
+// amwg_waic_launch behind its family checks: the same call over any PointwiseLaunch.  A closure: sets[d].n_obs = kTermN for every d.
+int amwg_waic_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
+                  int32_t *high, double *pointwise, double *loglik, hipStream_t stream);
 // AMWG_EINVAL "<call>: ..." unless the shape can be served: amwg_dataset_quantiles_shape's limits and at least 2 draws per dataset.  Host only.
 int amwg_waic_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
 // draws [rows][PR][C] on the current device, D datasets of C / D columns each; sets [D] on the host.  Host outputs: summary [D][4] (elpd_waic, se, p_waic, lppd),
@@ -53,6 +74,8 @@ int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR
                      int32_t *high, double *pointwise, double *loglik, hipStream_t stream);
 // sets [D] and model of a sampler's own data, as the launchers take them; the sampler's device is current (one copy from it when D > 1)
 int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicModel &model);
+// the same for a closure sampler whose pointwise text is set: compiles and loads the code object on first use; every dataset has kTermN observations
+int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, UserPointwise &u);
 // the finish of include/amwg.h over one dataset's pairs pw[n][2]: summary[4], *high (may be nullptr)
 void amwg_waic_totals(const double *pw, int64_t n, double *summary, int32_t *high);
 // the scratch budget of later calls in bytes (0: kWaicScratchBytes); returns the budget in force before.  For the test library: the product never calls it.

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "amwg_dataset.h"
@@ -21,91 +23,20 @@ using namespace amwg;
 
 namespace {
 
-struct Part { double m, sum, mean, M2; };      // max term and sum exp(l - m); mean and sum (l - mean)^2.  The count is a function of the indices.
-__device__ __forceinline__ void merge_parts(Part &a, double &na, const Part &b, double nb) {
-  if (nb == 0.0) return;
-  if (na == 0.0) { a = b; na = nb; return; }
-  const double M = b.m > a.m ? b.m : a.m;
-  a.sum = a.sum * exp_v8_cold(a.m - M) + b.sum * exp_v8_cold(b.m - M);
-  a.m = M;
-  const double nt = na + nb, delta = b.mean - a.mean;
-  a.mean = a.mean + delta * (nb / nt);
-  a.M2 = a.M2 + b.M2 + delta * delta * (na * nb / nt);
-  na = nt;
-}
-
-// parts[part_off[z] + split * n + i], z = the dataset's place in the batch
+// parts[part_off[z] + split * n + i], z = the dataset's place in the batch (amwg_pointwise.h)
 template <int MODEL>
 __global__ void __launch_bounds__(kThreads) waic_partial_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicModel M,
                                                                 const WaicDataset *__restrict__ sets, const int64_t *__restrict__ part_off, Part *__restrict__ parts) {
-  typedef Family<MODEL> F;
-  __shared__ typename F::Draw stage[kStage];
-  __shared__ Part wave_part[kWaves - 1][kTile];
-  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const WaicDataset ds = sets[d];
-  const int64_t n = F::n_eff(ds), S = rows * cpd, splits = waic_splits(S, n);
-  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
-  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
-  const int64_t i = (int64_t)blockIdx.x * kTile + lane;
-  const bool active = i < n;
-  const typename F::Obs o = F::load_obs(M, ds, active ? i : n - 1);
-  Part a{-kInf, 0.0, 0.0, 0.0};
-  double cnt = 0.0;
-  for (int64_t s0 = s_begin; s0 < s_end; s0 += kStage) {
-    const int L = (int)(s_end - s0 < kStage ? s_end - s0 : kStage);
-    __syncthreads();
-    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, M, ds);
-    __syncthreads();
-    if (wave >= L) continue;      // (uniform over the wavefront; the barriers above are reached by all: L does not depend on the wavefront)
-    const double K = cnt == 0.0 ? F::term(o, stage[wave], i, draws, C) : a.mean;
-    double s1 = 0.0, s2 = 0.0;
-    int nb = 0;
-    for (int j = wave; j < L; j += kWaves) {
-      const double l = F::term(o, stage[j], i, draws, C);
-      const double dm = l - a.m;
-      const double e = waic_exp(-__builtin_fabs(dm));
-      const bool up = dm > 0.0;
-      a.sum = up ? __builtin_fma(a.sum, e, 1.0) : a.sum + e;
-      a.m = up ? l : a.m;
-      const double dk = l - K;
-      s1 += dk;
-      s2 = __builtin_fma(dk, dk, s2);
-      ++nb;
-    }
-    const double nbd = (double)nb, q = s1 / nbd;
-    double M2b = s2 - s1 * q;
-    M2b = M2b < 0.0 ? 0.0 : M2b;      // (a NaN stays a NaN)
-    const double mean_b = K + q;
-    if (cnt == 0.0) { a.mean = mean_b; a.M2 = M2b; cnt = nbd; }
-    else {
-      const double nt = cnt + nbd, delta = mean_b - a.mean;
-      a.mean = a.mean + delta * (nbd / nt);
-      a.M2 = a.M2 + M2b + delta * delta * (cnt * nbd / nt);
-      cnt = nt;
-    }
-  }
-  __syncthreads();
-  if (wave > 0) wave_part[wave - 1][lane] = a;
-  __syncthreads();
-  if (wave != 0 || !active) return;
-  // the draws of the split went round the four wavefronts: wavefront w took those with (s - s0) % 4 == w of every staged run
-  const int64_t len = s_end - s_begin, full = len / kStage, rest = len % kStage;
-#pragma unroll
-  for (int w = 1; w < kWaves; ++w) {
-    const double nw = (double)(full * (kStage / kWaves) + (rest > w ? (rest - w + kWaves - 1) / kWaves : 0));
-    merge_parts(a, cnt, wave_part[w - 1][lane], nw);
-  }
-  parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + i] = a;
+  waic_partial_body<Family<MODEL>>(draws, rows, PR, C, cpd, d0, M, sets, part_off, parts);
 }
 
 // out[(d * out_stride + i) * 2 + (0 | 1)] = lppd_i | p_i for i < n: the splits merged in ascending order
-template <int MODEL>
-__global__ void __launch_bounds__(kThreads) waic_merge_kernel(int64_t rows, int64_t cpd, int d0, const WaicDataset *__restrict__ sets, const int64_t *__restrict__ part_off,
+// (model-free: bern = the family of two observations per dataset; stage = the staged run length of the partial kernel is no part of it)
+__global__ void __launch_bounds__(kThreads) waic_merge_kernel(int64_t rows, int64_t cpd, int d0, const WaicDataset *__restrict__ sets, int bern, const int64_t *__restrict__ part_off,
                                                               const Part *__restrict__ parts, double *__restrict__ out, int64_t out_stride) {
-  typedef Family<MODEL> F;
   const int d = d0 + (int)blockIdx.y;
   const WaicDataset ds = sets[d];
-  const int64_t n = F::n_eff(ds), S = rows * cpd, splits = waic_splits(S, n);
+  const int64_t n = bern ? (ds.n_obs > 0 ? 2 : 0) : ds.n_obs, S = rows * cpd, splits = waic_splits(S, n);
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   const Part *p = parts + part_off[blockIdx.y] + i;
@@ -137,32 +68,18 @@ __global__ void __launch_bounds__(kThreads) waic_bern_expand_kernel(const WaicMo
   out[(d * n_max + i) * 2 + 1] = invalid ? __builtin_nan("") : two[(d * 2 + k) * 2 + 1];
 }
 
-// the terms themselves, out[(d * S + s) * n_max + i]: the test library's view of what the partial kernel accumulates (the same device functions)
+// the terms themselves, out[(d * S + s) * n_max + i]: the test library's view of what the partial kernel accumulates (amwg_pointwise.h)
 template <int MODEL>
 __global__ void __launch_bounds__(kThreads) waic_loglik_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, const WaicModel M,
                                                                const WaicDataset *__restrict__ sets, double *__restrict__ out, int64_t n_max) {
-  typedef Family<MODEL> F;
-  const int d = blockIdx.z;
-  const WaicDataset ds = sets[d];
-  const int64_t S = rows * cpd, s = blockIdx.y, i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= ds.n_obs) return;
-  const typename F::Draw w = draw_at<F>(draws, PR, C, cpd, d, s, M, ds);
-  double l;
-  if constexpr (MODEL == AMWG_MODEL_BETA_BERN) {
-    const bool invalid = M.invalid && M.invalid[ds.off_xb + i];
-    l = invalid ? -kInf : F::term(F::load_obs(M, ds, M.xb[ds.off_xb + i] ? 0 : 1), w, i, draws, C);
-  } else {
-    l = F::term(F::load_obs(M, ds, i), w, i, draws, C);
-  }
-  out[((int64_t)d * S + s) * n_max + i] = l;
+  waic_loglik_body<Family<MODEL>, WaicModel, MODEL == AMWG_MODEL_BETA_BERN>(draws, rows, PR, C, cpd, M, sets, out, n_max);
 }
 
 size_t g_budget = kWaicScratchBytes;
 
-template <int MODEL>
-int run_family(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, const WaicDataset *d_sets,
-               int64_t n_max, double *d_pw, double *d_loglik, hipStream_t stream) {
-  const bool bern = MODEL == AMWG_MODEL_BETA_BERN;
+int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, const WaicDataset *d_sets,
+                int64_t n_max, double *d_pw, double *d_loglik, hipStream_t stream) {
+  const bool bern = K.bern;
   const int64_t cpd = C / D, S = rows * cpd;
   DevBuf two, off, parts;
   if (bern) HIP_TRY(two.alloc((size_t)D * 4 * 8));
@@ -195,27 +112,35 @@ int run_family(const char *call, const double *draws, int64_t rows, int PR, int6
       tiles = t > tiles ? t : tiles; splits = sp > splits ? sp : splits; n_most = n > n_most ? n : n_most;
     }
     if (tiles > 0) {
-      hipLaunchKernelGGL(waic_partial_kernel<MODEL>, dim3((unsigned)tiles, (unsigned)splits, (unsigned)(d1 - d0)), dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model,
-                         d_sets, off.as<int64_t>() + d0, parts.as<Part>());
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(waic_merge_kernel<MODEL>, dim3((unsigned)((n_most + kThreads - 1) / kThreads), (unsigned)(d1 - d0)), dim3(kThreads), 0, stream, rows, cpd, d0, d_sets,
+      HIP_TRY(K.waic_partial(dim3((unsigned)tiles, (unsigned)splits, (unsigned)(d1 - d0)), stream, draws, rows, PR, C, cpd, d0, d_sets, off.as<int64_t>() + d0, parts.as<Part>()));
+      hipLaunchKernelGGL(waic_merge_kernel, dim3((unsigned)((n_most + kThreads - 1) / kThreads), (unsigned)(d1 - d0)), dim3(kThreads), 0, stream, rows, cpd, d0, d_sets, bern ? 1 : 0,
                          off.as<int64_t>() + d0, parts.as<Part>(), out, out_stride);
       HIP_TRY(hipGetLastError());
     }
     d0 = d1;
   }
   if (bern) {
-    hipLaunchKernelGGL(waic_bern_expand_kernel, dim3((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)D), dim3(kThreads), 0, stream, model, d_sets, two.as<double>(), d_pw, n_max);
+    hipLaunchKernelGGL(waic_bern_expand_kernel, dim3((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)D), dim3(kThreads), 0, stream, *K.family, d_sets, two.as<double>(), d_pw, n_max);
     HIP_TRY(hipGetLastError());
   }
   if (d_loglik) {
-    hipLaunchKernelGGL(waic_loglik_kernel<MODEL>, dim3((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)S, (unsigned)D), dim3(kThreads), 0, stream, draws, rows, PR, C, cpd,
-                       model, d_sets, d_loglik, n_max);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(K.waic_loglik(dim3((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)S, (unsigned)D), stream, draws, rows, PR, C, cpd, d_sets, d_loglik, n_max));
   }
   HIP_TRY(hipStreamSynchronize(stream));      // (the scratch is freed on return)
   (void)call;
   return AMWG_OK;
+}
+
+template <int MODEL>
+void family_kernels(PointwiseLaunch &K, const WaicModel &model) {
+  K.waic_partial = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *part_off, void *parts) {
+    hipLaunchKernelGGL(waic_partial_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, sets, part_off, static_cast<Part *>(parts));
+    return hipGetLastError();
+  };
+  K.waic_loglik = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, const WaicDataset *sets, double *out, int64_t n_max) {
+    hipLaunchKernelGGL(waic_loglik_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, model, sets, out, n_max);
+    return hipGetLastError();
+  };
 }
 
 }  // namespace
@@ -251,6 +176,47 @@ void amwg_waic_totals(const double *pw, int64_t n, double *summary, int32_t *hig
   if (high) *high = h;
 }
 
+void amwg_waic_family_kernels(PointwiseLaunch &K, const WaicModel &model) {
+  K.bern = model.model == AMWG_MODEL_BETA_BERN;
+  K.family = &model;
+  switch (model.model) {
+    case AMWG_MODEL_NORMAL: family_kernels<AMWG_MODEL_NORMAL>(K, model); break;
+    case AMWG_MODEL_BETA_BERN: family_kernels<AMWG_MODEL_BETA_BERN>(K, model); break;
+    case AMWG_MODEL_HIER_NORMAL: family_kernels<AMWG_MODEL_HIER_NORMAL>(K, model); break;
+    default: family_kernels<AMWG_MODEL_POIS_GLM>(K, model); break;
+  }
+}
+
+// a closure's code object (amwg_rtc.hip load_pointwise): the four entries of amwg_pointwise.h, launched with the closure's model argument
+void amwg_pointwise_user_kernels(PointwiseLaunch &K, const UserPointwise &u) {
+  K.bern = false;
+  K.family = nullptr;
+  const UserPointwise U = u;
+  auto go = [](hipFunction_t fn, dim3 grid, hipStream_t stream, void **args) { return hipModuleLaunchKernel(fn, grid.x, grid.y, grid.z, kThreads, 1, 1, 0, stream, args, nullptr); };
+  K.waic_partial = [U, go](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *part_off, void *parts) {
+    UserTermsArg M = U.arg;
+    void *args[] = {&draws, &rows, &PR, &C, &cpd, &d0, &M, &sets, &part_off, &parts};
+    return go(U.waic_partial, grid, stream, args);
+  };
+  K.waic_loglik = [U, go](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, const WaicDataset *sets, double *out, int64_t n_max) {
+    UserTermsArg M = U.arg;
+    void *args[] = {&draws, &rows, &PR, &C, &cpd, &M, &sets, &out, &n_max};
+    return go(U.waic_loglik, grid, stream, args);
+  };
+  K.loo_hist = [U, go](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off, void *state,
+                       uint32_t *hist, int pass) {
+    UserTermsArg M = U.arg;
+    void *args[] = {&draws, &rows, &PR, &C, &cpd, &d0, &M, &sets, &obs_off, &state, &hist, &pass};
+    return go(U.loo_hist, grid, stream, args);
+  };
+  K.loo_compact = [U, go](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off,
+                          const int64_t *part_off, void *state, double *tail, uint32_t cap, double *parts) {
+    UserTermsArg M = U.arg;
+    void *args[] = {&draws, &rows, &PR, &C, &cpd, &d0, &M, &sets, &obs_off, &part_off, &state, &tail, &cap, &parts};
+    return go(U.loo_compact, grid, stream, args);
+  };
+}
+
 int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
                      int32_t *high, double *pointwise, double *loglik, hipStream_t stream) {
   if (!draws || !sets || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
@@ -259,6 +225,15 @@ int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR
   if (need < 0) return amwg_fail(AMWG_EINVAL, "%s: unknown model %d", call, model.model);
   if (PR < need) return amwg_fail(AMWG_EINVAL, "%s: the family reads %d components of a draw, the draws hold %d", call, need, PR);
   if (model.model == AMWG_MODEL_HIER_NORMAL && D != 1) return amwg_fail(AMWG_EINVAL, "%s: the hierarchical family runs on one dataset", call);
+  PointwiseLaunch K;
+  amwg_waic_family_kernels(K, model);
+  return amwg_waic_run(call, draws, rows, PR, C, D, K, sets, summary, high, pointwise, loglik, stream);
+}
+
+int amwg_waic_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
+                  int32_t *high, double *pointwise, double *loglik, hipStream_t stream) {
+  if (!draws || !sets || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  TRYB(amwg_waic_shape(call, rows, PR, C, D));
   int64_t n_max = 0;
   for (int d = 0; d < D; ++d) {
     if (sets[d].n_obs < 0) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: n_obs < 0", call, d);
@@ -284,12 +259,7 @@ int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR
   }
   double *dl = loglik ? d_ll.as<double>() : nullptr;
   const WaicDataset *ds = d_sets.as<WaicDataset>();
-  switch (model.model) {
-    case AMWG_MODEL_NORMAL: TRYB(run_family<AMWG_MODEL_NORMAL>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dl, stream)); break;
-    case AMWG_MODEL_BETA_BERN: TRYB(run_family<AMWG_MODEL_BETA_BERN>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dl, stream)); break;
-    case AMWG_MODEL_HIER_NORMAL: TRYB(run_family<AMWG_MODEL_HIER_NORMAL>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dl, stream)); break;
-    default: TRYB(run_family<AMWG_MODEL_POIS_GLM>(call, draws, rows, PR, C, D, model, sets, ds, n_max, d_pw.as<double>(), dl, stream)); break;
-  }
+  TRYB(run_kernels(call, draws, rows, PR, C, D, K, sets, ds, n_max, d_pw.as<double>(), dl, stream));
   std::vector<double> own;
   double *pw = pointwise;
   if (!pw) { own.resize(pw_count ? pw_count : 1); pw = own.data(); }
@@ -317,10 +287,43 @@ int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicMode
   return AMWG_OK;
 }
 
+// ... and of a closure whose pointwise text is set (amwg_set_pointwise): the code object compiled and loaded on first use, every dataset with kTermN observations
+int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, UserPointwise &u) {
+  TRYB(load_pointwise(s, s->user_arch.c_str()));
+  u.waic_partial = s->pw_fn[0]; u.waic_loglik = s->pw_fn[1]; u.loo_hist = s->pw_fn[2]; u.loo_compact = s->pw_fn[3];
+  u.arg.d = s->d;
+  u.arg.table = s->n_datasets > 1 ? s->d_user_ds_table : nullptr;
+  u.arg.row_stride = s->user_ds_row_stride;
+  u.arg.reserved = 0;
+  u.n_obs = s->pw_n_obs; u.state_n = s->pw_state_n;
+  sets.assign((size_t)s->n_datasets, WaicDataset{s->pw_n_obs, 0, 0, 0, 0, 0});
+  return AMWG_OK;
+}
+
+extern "C" int amwg_set_pointwise(amwg_sampler *s, const char *terms_source) {
+  static const char *call = "amwg_set_pointwise";
+  if (!s || !terms_source) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (!s->user) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a built-in family are known to the library; the text is for amwg_create_user* samplers only", call);
+  auto int_after = [&](const char *key) -> long {
+    const char *q = strstr(terms_source, key);
+    return q ? strtol(q + strlen(key), nullptr, 10) : -1;
+  };
+  const long n = int_after("kTermN = "), p = int_after("kStateN = ");
+  if (!strstr(terms_source, "struct UserTerms") || n < 1 || n >= (1l << 31)) return amwg_fail(AMWG_EINVAL, "%s: the text does not define struct amwg::UserTerms with kTermN >= 1 (translate.js, options.pointwise)", call);
+  if (p != s->P) return amwg_fail(AMWG_EINVAL, "%s: the text was made for a state of %ld components, the sampler's has %d", call, p, s->P);
+  HIP_TRY(hipSetDevice(s->device));
+  if (s->pw_module) { (void)hipModuleUnload(s->pw_module); s->pw_module = nullptr; }
+  s->pw_terms = terms_source;
+  s->pw_n_obs = (int)n; s->pw_state_n = (int)p;
+  return AMWG_OK;
+}
+
+extern "C" int64_t amwg_pointwise_n_obs(const amwg_sampler *s) { return s && s->user && !s->pw_terms.empty() ? s->pw_n_obs : 0; }
+
 extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
   static const char *call = "amwg_last_sample_dataset_waic";
   if (!s || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
-  if (s->user) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
+  if (s->user && s->pw_terms.empty()) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
   TRYB(amwg_refuse_summarised(s, call));
   if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "%s: no sample() call yet", call);
   const int D = s->n_datasets, PR = s->P + s->D;
@@ -328,6 +331,13 @@ extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, i
   if (s->mc.group_local) return amwg_fail(AMWG_EINVAL, "%s: a group_local sampler keeps its observations as a lane-major tile; the pointwise terms need them in index order", call);
   HIP_TRY(hipSetDevice(s->device));
   std::vector<WaicDataset> sets;
+  if (s->user) {
+    UserPointwise u;
+    TRYB(amwg_pointwise_describe_user(s, sets, u));
+    PointwiseLaunch K;
+    amwg_pointwise_user_kernels(K, u);
+    return amwg_waic_run(call, s->last_draws, s->last_rows, PR, s->C, D, K, sets.data(), summary, high, pointwise, nullptr, s->stream);
+  }
   WaicModel m{};
   TRYB(amwg_waic_describe(s, sets, m));
   return amwg_waic_launch(call, s->last_draws, s->last_rows, PR, s->C, D, m, sets.data(), summary, high, pointwise, nullptr, s->stream);

@@ -206,6 +206,8 @@ function AmwgSampler(params, log_post, data, options) {
   this.params = shared ? params : complete_params(params, this.param_init_fun);   // steppers take completed params (mcmc.js:419-421)
 
   let recog = (shared || opt('translate', false)) ? null : models.recognise(log_post);
+  // options.pointwise: true beside options.translate: true -- the translator also writes the closure's pointwise terms (the iterations of its final loop), and
+  // waic(), loo(), dataset_waic(), dataset_loo() and both compare_* then work as on a built-in family.  A family needs no flag: its terms are known to the library.
   // a recognised family whose parameters are declared in another order than the hand-written kernel lays them out (the reference
   // accepts any order, only the stepper order depends on it, mcmc.js:839): translate the closure like any other
   if (recog && recog.paramNames && recog.paramNames.join() !== this.param_names.join()) recog = null;
@@ -220,6 +222,8 @@ function AmwgSampler(params, log_post, data, options) {
     } catch (e) { ok = false; }
     if (!ok) recog = null;
   }
+  // (asked only once it is settled that the family's own kernel runs: a recognised closure that is translated after all takes the flag)
+  if (opt('pointwise', false) && recog) throw 'AmwgSampler (MI355X): options.pointwise is for translated closures (options.translate: true); a built-in family needs no flag: waic() and loo() know its pointwise terms';
   this.model = recog ? recog.family : 'translated';
   // (the translator folds data-dependent constants and storage types into the generated source: one source per dataset is not one sampler)
   // options.translate: true beside options.datasets asks for one source for all datasets (translate.js translate_datasets): opt-in, so that a call that threw keeps throwing
@@ -284,7 +288,7 @@ function AmwgSampler(params, log_post, data, options) {
     this.dataset_n_obs = dsDescs.map((d) => d.n_obs);
   } else if (recog) desc = buildModelDesc(recog, data, this.params);
   else {
-    const trOpts = { constants: options.constants, helpers: options.helpers,
+    const trOpts = { constants: options.constants, helpers: options.helpers, pointwise: opt('pointwise', false) ? true : undefined,
       lds_budget: options.lds_budget, max_threads: options.max_threads, unroll: options.unroll, state_object: shared ? shared.state : undefined };
     if (translatedDatasets && this.chains % datasets.length !== 0) throw 'AmwgSampler (MI355X): options.chains (' + this.chains + ', the total) must be a multiple of the ' + datasets.length + ' datasets';
     // (many datasets: ONE translation over all of them -- also with options.devices: the shards get slices of its arrays, and a chain's draws do not depend on its shard)
@@ -294,6 +298,7 @@ function AmwgSampler(params, log_post, data, options) {
       this.chains_per_dataset = this.chains / datasets.length;
       this.dataset_n_obs = datasets.map(() => 0);      // (a closure's arrays carry their own lengths: amwg_dataset_n_obs says 0)
     }
+    if (opt('pointwise', false) && !tr.pointwise) throw 'AmwgSampler (MI355X): ' + tr.pointwise_why;
     this.derived = tr.derived;
     this.translation = tr;
     user = { source: tr.source, arrays: translatedDatasets ? tr.arrays[0] : tr.arrays, array_types: tr.array_types, n_derived: tr.derived.length, lds_bytes: tr.lds_bytes, lds_bytes_one_lane: tr.lds_bytes_one_lane, parallel: tr.parallel,
@@ -324,6 +329,7 @@ function AmwgSampler(params, log_post, data, options) {
       lanes_per_chain: lanes, block_threads: opt('block_threads', 0),
       steps_per_launch: opt('steps_per_launch', 0), exact_division: opt('exact_division', 0), group_local: opt('group_local', 0) ? 1 : 0, full_evaluation: Number(opt('full_evaluation', 0)) | 0, test_bound_shift: Number(opt('test_bound_shift', 0)) | 0,
       sufficient_statistics: opt('sufficient_statistics', 0) ? 1 : 0 });
+    if (user && this.translation.pointwise) N.setPointwise(handle, this.translation.pointwise.source);
     this._shards.push({ handle, offset, count, device: devices[r], datasets: nSets ? nUnits : 0 });
     firstDataset += nUnits;
     // one summation order for the whole job: what the first shard picked (cost model, or the measurement of lanes_per_chain: -2)

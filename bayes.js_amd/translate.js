@@ -1374,6 +1374,24 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
     const single = split && isInt && boundV.int && endsInAcc && !accElsewhere && !containsKind(s.body, 'Return') &&
                    !containsKind(s.body, 'Continue') && !containsKind(s.body, 'Break');
     if (this.loopInfo) this.loopInfo.push({ name: canon.name, single: !!single, start: startV.cst, bound: boundV.cst, le: !!canon.le });
+    // options.pointwise: what this round saw of the closure's final loop (pointwisePlan words the refusal, or takes the texts the single form adds below)
+    const pwHere = this.pwTarget && s === this.pwTarget;
+    if (pwHere) {
+      const cnt = Number.isInteger(startV.cst) && Number.isInteger(boundV.cst) ? boundV.cst - startV.cst + (canon.le ? 1 : 0) : NaN;
+      this.pwSeen = {
+        single: !!single, acc: loopAcc,
+        why: !isInt || !Number.isInteger(startV.cst) || !Number.isInteger(boundV.cst) ? 'the bounds of the final loop are not integer constants'
+          : !(cnt >= 1) ? 'the final loop has no iteration'
+          : containsKind(s.body, 'Break') ? 'the final loop has a break'
+          : containsKind(s.body, 'Continue') ? 'the final loop has a continue'
+          : containsKind(s.body, 'Return') ? 'the final loop has a return'
+          : !endsInAcc ? 'the final loop does not end in `' + (this.acc || 'acc') + ' += term`'
+          : accElsewhere ? 'the final loop writes the accumulator ' + loopAcc + ' more than once in its body'
+          : loopAcc !== this.acc ? 'the final loop adds to ' + loopAcc + ', which is not the accumulator the closure returns'
+          : !split ? 'the final loop is not lane-split (an iteration reads what another one wrote)'
+          : !single ? 'the final loop is not of the single form' : '',
+      };
+    }
     if (single) {
       const pre = [];
       const heavyBefore = this.heavyLoop;
@@ -1395,6 +1413,8 @@ Translator.prototype.forLoop = function (s, out, indent, ctx) {
       // a softplus in the term (csrc/amwg_math.h log1p_exp_v8): the U terms are formed by its branch-free form, one after the other in a single basic
       // block, and a lane that met an argument it does not cover (flagged, a handful per million) forms its U terms again through the full functions
       const termText = this.asD(term), softplus = /\blog1p_exp_v8\(/.test(bodyText + termText) && !this.opts.no_open_softplus;
+      if (pwHere) Object.assign(this.pwSeen, { top: out === this.pwLines && !ctx.inLoop && !this.condDepth, head: out.slice(), preamble: L.preamble.slice(), body: bodyText, term: termText,
+                                               iv: canon.name, start: startV.cst, n: boundV.cst - startV.cst + (canon.le ? 1 : 0), assigned: Array.from(assigned) });
       if (softplus) {
         const open = (t) => t.replace(/\blog1p_exp_v8\(/g, 'log1p_exp_v8_open(rr_, '), cold = (t) => t.replace(/\blog1p_exp_v8\(/g, 'log1p_exp_cold(');
         loop.pop();
@@ -1934,6 +1954,9 @@ Translator.prototype.functionBody = function (numericParams, allowSplit) {
     this.otherSplitLoops = 0;
     this.loopInfo = [];      // every canonical loop of this round: {name, single, start, bound, le} (the row plan's proof reads it)
     lines = [];
+    this.pwSeen = null;
+    this.pwLines = lines;
+    this.pwTarget = this.opts.pointwise && !this.isHelper && stmts.length >= 2 && stmts[stmts.length - 2].k === 'For' ? stmts[stmts.length - 2] : null;
     for (const st of stmts) this.stmt(st, lines, '    ', { inLoop: false, split: false });
     if (!last || last.k !== 'Return') this.fail('log_post must end with a return statement');
     const stable = !this.retype && this.derivedFinal.join() === this.derived.join();
@@ -1947,6 +1970,7 @@ Translator.prototype.functionBody = function (numericParams, allowSplit) {
   }
   for (const nm of this.derived) decl.push('    double dq_' + nm + ' = 0;');
   for (const nm of Object.keys(this.localArrays)) decl.push('    double ' + nm + '[' + this.localArrays[nm] + '] = {0};');
+  if (this.pwSeen && this.pwSeen.head) this.pwSeen.head = decl.concat(renderNorm(this.pwSeen.head, 'inv'));
   return decl.concat(renderNorm(lines, 'inv'));
 };
 
@@ -1965,8 +1989,11 @@ Translator.prototype.run = function () {
       body = body.map(ren);
       this.helperSources = this.helperSources.map(ren);
       this.arrays = kept;
+      if (this.pwSeen && this.pwSeen.head) for (const f of ['head', 'preamble']) this.pwSeen[f] = this.pwSeen[f].map(ren);
+      if (this.pwSeen && this.pwSeen.head) for (const f of ['body', 'term']) this.pwSeen[f] = ren(this.pwSeen[f]);
     }
   }
+  const pointwise = this.opts.pointwise ? this.pointwisePlan() : null;
   // did any loop actually get split?
   const parallel = this.split && this.nSplit > 0;
   // ---- LDS staging plan: whole arrays, in order of first use, while they fit the budget
@@ -2233,7 +2260,8 @@ Translator.prototype.run = function () {
   src.push('  }');
   src.push('};');
   src.push('}  // namespace amwg');
-  return {
+  const fold = (t) => (this.opts.no_fold_norm_inv ? t : foldConstantNormInv(t)) + '\n';
+  return Object.assign(!pointwise ? {} : pointwise.why ? { pointwise: null, pointwise_why: pointwise.why } : { pointwise: { source: fold(pointwise.lines.join('\n')), n: pointwise.n, start: pointwise.start } }, {
     source: (this.opts.no_fold_norm_inv ? src.join('\n') : foldConstantNormInv(src.join('\n'))) + '\n',
     arrays: this.arrays.map((a) => a.flat),
     array_types: this.arrays.map((a) => a.type),
@@ -2272,7 +2300,125 @@ Translator.prototype.run = function () {
     pois_tail_n: gtail && !logit ? gtail.n : 0,
     // certified logistic tail (csrc/amwg_gtail.h LogitLink): observations of the closure's final logistic-regression loop; 0 = none (kLogitTail / kTailN of the source)
     logit_tail_n: logit ? gtail.n : 0,
-  };
+  });
+};
+
+// The POINTWISE PLAN of a closure (options.pointwise; csrc/amwg_pointwise.h): the observations of a closure are the iterations of its FINAL loop -- the last statement
+// before `return acc`, a counted loop at the top level of log_post with integer constant bounds that forLoop() takes in its single form (lane-split, ending in
+// `acc += term`, the accumulator written nowhere else, no return / break / continue) and that writes no derived quantity; nothing before it returns early.  Everything
+// before the loop is the head and counts as prior: it is no part of the terms.  The restrictions of the certified plans do not apply -- derived quantities in the head,
+// int and binary parameters, a head that does more than accumulate are all fine.
+// -> {why} or {lines, n, start}: the text of `struct amwg::UserTerms`, a second source compiled behind `source`:
+//   kTermN, kTermStart, kStateN; Draw: what an evaluation needs of a draw -- the head's locals, the loop's hoisted invariants and the state entries that the loop's
+//   statements and term read (a body that indexes the state by DATA reads the stored draw where it lies, through `base`);
+//   make_draw(at, C, d): once per draw, component p at at[p * C] -- the head with its data arrays read from global memory, one lane, the accumulator's value
+//   discarded and dv null, then the loop's hoisted preamble;
+//   term(w, d, i, draws, C): the loop's statements, then its term, for the iteration with counter i: the double that `acc += term` adds, the same generated expressions
+//   the step kernel evaluates (the softplus by the full function: the open / cold pair belongs to the unrolled step loop).
+Translator.prototype.pointwisePlan = function () {
+  const stmts = this.ast.body.body, no = (why) => ({ why: 'options.pointwise: ' + why });
+  const last = stmts[stmts.length - 1], loop = stmts.length >= 2 ? stmts[stmts.length - 2] : null;
+  if (!this.acc || !last || last.k !== 'Return') return no('log_post does not end in `return acc` with acc its one accumulator');
+  if (!loop || loop.k !== 'For') {
+    if (loop && loop.k === 'If' && containsKind(loop, 'For')) return no('the final loop stands under a conditional: it must be a statement at the top level of log_post');
+    return no('the last statement before `return ' + this.acc + '` is not a loop: the observations of a closure are the iterations of its final loop');
+  }
+  for (const st of stmts.slice(0, -2)) if (containsKind(st, 'Return')) return no('the closure returns early before its final loop');
+  const p = this.pwSeen;
+  if (!p) return no('the final loop is not a counted loop `for (i = a; i < b; i++)`');
+  if (p.why) return no(p.why);
+  if (!p.top) return no('the final loop is not at the top level of log_post');
+  const text = p.body + ' ' + p.term;
+  // (a derived quantity written in a loop never gets here: the translator refuses such a closure altogether, with or without the flag)
+  if (/\breturn\b/.test(p.head.join('\n'))) return no('the closure returns early before its final loop');
+  for (const nm of Object.keys(this.localArrays || {})) if (new RegExp('\\b' + nm.replace(/[$]/g, '\\$') + '\\b').test(text)) return no('the final loop reads the local array ' + nm);
+  const pre = renderNorm(p.preamble, 'inv').map((q) => q.trim());
+  // the Draw's fields
+  const fields = [], keep = [], locals = [];
+  for (const ln of pre) {
+    const m = /^const ([\w:]+(?:<[^>]*>)?) (k\d+) = /.exec(ln);
+    if (!m) return no('a hoisted invariant of the final loop has a form the plan does not know: `' + ln.slice(0, 60) + '`');
+    if (new RegExp('\\b' + m[2] + '\\b').test(text)) { fields.push(m[1] + ' ' + m[2] + ';'); keep.push('w.' + m[2] + ' = ' + m[2] + ';'); locals.push('const ' + m[1] + ' &' + m[2] + ' = w.' + m[2] + ';'); }
+  }
+  const priv = new Set(p.assigned), seen = new Set();
+  for (let m, re = /\b(v_|dq_)([\w$]+)/g; (m = re.exec(text));) {
+    const id = m[1] + m[2];
+    if (seen.has(id) || id === 'v_' + p.iv) continue;
+    seen.add(id);
+    const ty = m[1] === 'v_' && this.localTypes[m[2]] === 'int' ? 'int' : 'double';
+    if (m[1] === 'v_' && priv.has(m[2])) { locals.push(ty + ' ' + id + ' = 0;'); continue; }      // (the loop's own temporaries: private to an iteration, proved by splittable())
+    fields.push(ty + ' ' + id + ';'); keep.push('w.' + id + ' = ' + id + ';'); locals.push('const ' + ty + ' ' + id + ' = w.' + id + ';');
+  }
+  // ... and the state: entries at constant indices are kept; an index formed from data reads the stored draw; any other use keeps the whole state
+  const reads = [];
+  let whole = false, byData = false;
+  for (let at = 0; (at = text.indexOf('S', at)) >= 0; at++) {
+    if (/[\w.$]/.test(text[at - 1] || ' ') || /[\w$]/.test(text[at + 1] || ' ')) continue;
+    if (text[at + 1] !== '(') { whole = true; continue; }
+    const call = splitCallArgs(text, at + 1);
+    if (!call || call.args.length !== 1) { whole = true; continue; }
+    if (/^\d+$/.test(call.args[0])) { if (reads.indexOf(Number(call.args[0])) < 0) reads.push(Number(call.args[0])); }
+    else if (/\bA\d+\[/.test(call.args[0])) byData = true;
+    else whole = true;
+  }
+  let bodyT = p.body, termT = p.term, view = '';
+  if (whole) {
+    fields.push('double st[' + this.P + '];');
+    keep.push('for (int p_ = 0; p_ < ' + this.P + '; ++p_) w.st[p_] = st_[p_];');
+    view = 'const StateView S{w.st};';
+  } else if (byData) {
+    view = 'const Strided S{draws + w.base, C};';
+  } else {
+    reads.sort((a, b) => a - b);
+    for (const k of reads) { fields.push('double s' + k + ';'); keep.push('w.s' + k + ' = st_[' + k + '];'); }
+    const sub = (t) => t.replace(/(^|[^\w.$])S\((\d+)\)/g, '$1w.s$2');
+    bodyT = sub(bodyT); termT = sub(termT);
+  }
+  fields.push('int64_t base;');      // where component 0 of the draw lies among the stored draws (set_base)
+  // kStage (csrc/amwg_pointwise.h): at least kWaves = 4 Draws must fit in the 48 KiB of LDS a workgroup stages draws in.  A lower bound of sizeof(Draw) from its
+  // fields (8 bytes for each double, int64_t and state entry, 4 for an int, 40 for a NormInv, 16 for a BernInv) refuses here what could never compile
+  let drawBytes = 0;
+  for (const f of fields) { const m = /^([\w:]+(?:<[^>]*>)?) \w+(?:\[(\d+)\])?;$/.exec(f); drawBytes += (m && m[1] === 'int' ? 4 : m && m[1] === 'NormInv' ? 40 : m && m[1] === 'BernInv' ? 16 : 8) * (m && m[2] ? Number(m[2]) : 1); }
+  if (drawBytes * 4 > 48 * 1024) return no('what an evaluation keeps of a draw takes at least ' + drawBytes + ' bytes, and fewer than 4 of those fit in the 48 KiB of LDS a workgroup stages draws in');
+  const arrDecl = (j) => '    const ' + this.arrays[j].ctype + ' *A' + j + ' = static_cast<const ' + this.arrays[j].ctype + ' *>(user_arr<' + j + '>(d));';
+  const used = new Set();
+  for (let m, re = /\bA(\d+)\b/g; (m = re.exec(text));) used.add(Number(m[1]));
+  const L = [];
+  L.push('// generated by bayes.js_amd/translate.js from the user\'s log_post closure: the pointwise terms of its final loop (options.pointwise)');
+  L.push('namespace amwg {');
+  L.push('struct UserTerms {');
+  L.push('  static constexpr int kTermN = ' + p.n + ', kTermStart = ' + p.start + ', kStateN = ' + this.P + ';');
+  L.push('  struct Strided { const double *at; int64_t C; AMWG_HD double operator()(int p) const { return at[(int64_t)p * C]; } };');
+  L.push('  struct Draw { ' + fields.join(' ') + ' };');
+  L.push('  AMWG_HD static void set_base(Draw &w, int64_t base) { w.base = base; }');
+  L.push('  // once per draw (component p at at[p * C]): the closure up to its final loop, then the loop\'s hoisted invariants');
+  L.push('  AMWG_HD static Draw make_draw(const double *at, int64_t C, const DataRef &d) {');
+  L.push('    constexpr int G = 1; constexpr bool DERIVE = false;');
+  L.push('    const int sub = 0; const unsigned char *smem = nullptr; double *dv = nullptr;');
+  L.push('    double st_[' + this.P + '];');
+  L.push('    for (int p_ = 0; p_ < ' + this.P + '; ++p_) st_[p_] = at[(int64_t)p_ * C];');
+  L.push('    const StateView S{st_};');
+  this.arrays.forEach((a, j) => L.push(arrDecl(j)));
+  L.push('    (void)smem; (void)sub; (void)d; (void)dv; (void)S; (void)G; (void)DERIVE;');
+  for (const ln of p.head) L.push(ln);
+  for (const ln of pre) L.push('    ' + ln);
+  L.push('    Draw w;');
+  for (const k of keep) L.push('    ' + k);
+  L.push('    w.base = 0;');
+  L.push('    return w;');
+  L.push('  }');
+  L.push('  // iteration v_' + p.iv + ' of the final loop under the draw w: the loop\'s statements, then the double its `' + p.acc + ' += term` adds');
+  L.push('  AMWG_HD static double term(const Draw &w, const DataRef &d, const int v_' + p.iv + ', const double *draws, int64_t C) {');
+  L.push('    (void)w; (void)d; (void)draws; (void)C;');
+  for (const j of Array.from(used).sort((a, b) => a - b)) L.push(arrDecl(j));
+  if (view) L.push('    ' + view);
+  for (const ln of locals) L.push('    ' + ln);
+  for (const ln of renderNorm([bodyT], 'inv')) if (ln.trim()) L.push('    ' + ln);
+  L.push('    return ' + renderNorm([termT], 'inv')[0] + ';');
+  L.push('  }');
+  L.push('};');
+  L.push('}  // namespace amwg');
+  return { lines: L, n: p.n, start: p.start };
 };
 
 // The CERTIFIED TAIL of a closure (csrc/amwg_user.h norm_tail_approx): its LAST statement before `return acc` is the constant-mean normal loop forLoop() marked with
@@ -2581,6 +2727,7 @@ function translate_datasets(fn, params, datasets, options) {
   const differs = (rs) => {      // -> null, or {d, why}
     for (let d = 1; d < D; d++) {
       if (rs[d].source !== rs[0].source) return { d, text: true };
+      if ((rs[d].pointwise ? rs[d].pointwise.source : rs[d].pointwise_why) !== (rs[0].pointwise ? rs[0].pointwise.source : rs[0].pointwise_why)) return { d, field: 'pointwise' };      // (options.pointwise: one text of the terms too)
       for (const f of META) if (JSON.stringify(rs[d][f]) !== JSON.stringify(rs[0][f])) return { d, field: f };
     }
     return null;

@@ -256,8 +256,15 @@ int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n
  * built-in families only"; a group_local sampler (its observations lie as a lane-major tile).  Scratch -- the partials of the split, 32 bytes per observation and
  * run of draws -- is allocated per call on the sampler's device and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset
  * beyond it runs alone).  A failed allocation is AMWG_EHIP.
+ * A TRANSLATED CLOSURE WHOSE POINTWISE TEXT IS SET (amwg_set_pointwise below) is served like a family, with [D][kTermN] where the families have n_d; every other
+ * rule, bound, refusal and scratch budget is as stated.  THE OBSERVATIONS OF A CLOSURE are the iterations of its FINAL LOOP -- the last statement before `return acc`,
+ * a counted loop at the top level of log_post that ends in `acc += term` --, and l_si is the double that statement adds in iteration i under draw s: V8's value, bit
+ * for bit, formed by the same generated expressions the step kernel evaluates.  Everything before the loop counts as prior and is no part of l: a closure with
+ * likelihood terms outside its final loop gets the WAIC of the final loop's observations only.  The draws of a run are staged kStage = 256 at a time wherever 256 of
+ * the closure's Draw (what an evaluation keeps of a draw) fit in 48 KiB of LDS, otherwise the largest multiple of 4 that fits -- a function of sizeof(Draw) alone, so
+ * a dataset's bytes depend on its own draws and data, on (rows, C / D) and on the closure's text; a Draw of which fewer than 4 fit is refused when the text is compiled.
  * OUT OF SCOPE: WAIC after amwg_sample_summarize (per-observation accumulators could be folded; not built), a public pointwise log-likelihood matrix,
- * translated closures, a pooled WAIC across devices (no amwg_group_* / amwg_comm_* twin). */
+ * likelihood terms of a closure outside its final loop, a pooled WAIC across devices (no amwg_group_* / amwg_comm_* twin). */
 int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary /* [D][4]: elpd_waic, se, p_waic, lppd */, int32_t *high /* [D] or NULL */,
                                   double *pointwise /* NULL or [D][n_max][2]: lppd_i, p_i; NaN beyond n_d */);
 /* PSIS-LOO per dataset (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024): leave-one-out predictive accuracy by Pareto-smoothed importance
@@ -296,7 +303,8 @@ int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary /* [D][4]: el
  * Scratch -- per observation the tail (M + 1 padded to a power of two, at least 64 doubles), 512 bytes of counters, a double per run of draws -- is allocated per call
  * and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset beyond it runs alone).  A failed allocation is AMWG_EHIP.
  * OUT OF SCOPE: LOO after amwg_sample_summarize, moment matching or exact refits for observations of high khat, a relative-efficiency (r_eff) correction of the tail
- * length, translated closures, a pooled LOO across devices, tails beyond the LDS cap. */
+ * length, likelihood terms of a closure outside its final loop, a pooled LOO across devices, tails beyond the LDS cap.
+ * A translated closure whose pointwise text is set is served as by amwg_last_sample_dataset_waic: the same observations, the same doubles, the same kStage rule. */
 int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary /* [D][4]: elpd_loo, se, p_loo, lppd */, int32_t *high /* [D] or NULL: observations with khat_i > 0.7 */,
                                  double *pointwise /* NULL or [D][n_max][3]: elpd_loo_i, lppd_i, khat_i; NaN beyond n_d */);
 
@@ -363,6 +371,14 @@ int amwg_create_user_datasets(const amwg_user_model *models, int32_t n_datasets,
 
 /* hiprtc compilation of a translated closure without a device (build-time / CPU-test check).
  * arch e.g. "gfx950".  On failure returns AMWG_EINVAL and amwg_last_error() carries the compiler log. */
+/* THE POINTWISE TERMS OF A TRANSLATED CLOSURE (translate.js, options.pointwise: `struct amwg::UserTerms`, a second text beside `source`).  amwg_set_pointwise stores the
+ * text on an amwg_create_user* sampler -- any other sampler: AMWG_EINVAL, a built-in family needs no text --; it is compiled (hiprtc; the options and the on-disk cache
+ * of amwg_compile_user) at the first amwg_last_sample_dataset_waic / _loo call, where a text that does not compile gives AMWG_EINVAL with the hiprtc log.
+ * amwg_pointwise_n_obs: kTermN of the stored text, 0 without one (amwg_dataset_n_obs keeps reporting zeros for closures).  amwg_compile_pointwise: the device-less
+ * twin of amwg_compile_user -- compiles the program of (source, terms_source) for `arch`, *code_bytes (may be NULL) the size of the code object. */
+int amwg_set_pointwise(amwg_sampler *s, const char *terms_source);
+int64_t amwg_pointwise_n_obs(const amwg_sampler *s);
+int amwg_compile_pointwise(const char *source, const char *terms_source, const char *arch, size_t *code_bytes);
 int amwg_compile_user(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes);
 /* The same with the dataset twins compiled in (amwg_user_step_ds, amwg_user_step_cert_ds): the code object of an amwg_create_user_datasets sampler. */
 int amwg_compile_user_datasets(const char *source, int32_t lanes_per_chain, int32_t block_threads, const char *arch, size_t *code_bytes);

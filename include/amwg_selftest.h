@@ -77,6 +77,14 @@ int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t P
  * observation with a non-finite term -- more than 2^24 doubles are refused.  scratch_bytes: the scratch budget of this call (0: the default of csrc/amwg_loo.h). */
 int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                    int32_t *high, double *pointwise, double *tails);
+/* the same two for a TRANSLATED CLOSURE (amwg_set_pointwise): models[n_datasets] as amwg_create_user_datasets takes them (one source, arrays of equal shape), P the
+ * components of its state, terms_source the pointwise text of translate.js (options.pointwise).  No sampler is made: the arrays are uploaded as a sampler's, the
+ * code object is compiled and loaded as a sampler's first WAIC / LOO call does, and the same launchers run on draws[rows][PR][C].  Every dataset has kTermN
+ * observations; pointwise, loglik and tails are laid out as above with n_max = kTermN. */
+int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                         int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik);
+int amwg_user_loo_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                        int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails);
 /* what the last LOO call of this process did, for the measurement: *passes = the select passes over the terms; ms[4] = milliseconds of the lppd pass, the select,
  * the compaction, the sort and fit (-1 unless timing was on).  Then timing of later calls is switched on (1) or off (0).  Either pointer may be NULL. */
 int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms);
