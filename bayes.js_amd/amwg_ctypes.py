@@ -49,7 +49,7 @@ class UserModel(C.Structure):
 
 
 EXPORTS = ["amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+SELFTEST_EXPORTS = ["amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -166,6 +166,7 @@ def selftest_lib():
         L.amwg_device_eval.argtypes = [i32, i32, i64, pd, pd, pd, pd]
         L.amwg_two_valued_sum_check.argtypes = [i32, pd, i32, i64, pd, pd, pd, pd, pd]
         L.amwg_k_valued_sum_check.argtypes = [i32, i32, C.POINTER(C.c_uint8), i32, C.POINTER(C.c_uint32), i64, pd, pd, pd, pd]
+        L.amwg_two_valued_tables.argtypes = [C.POINTER(C.c_uint8), i32, C.POINTER(C.c_uint32)]
         L.amwg_stream_check.argtypes = [i32, i32, C.c_uint64, C.c_uint64, i64, C.POINTER(C.c_uint64), i64, C.POINTER(C.c_uint8), i64, pd, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.amwg_pow.restype = dbl
         L.amwg_pow.argtypes = [dbl, dbl]
@@ -1190,6 +1191,33 @@ def stream_check(kind, seed, chain0, consumed0, n_draws, calls=None, device=0):
     if flags is not None:
         res.update(ahead=out[:, n_draws:n_draws + 128], window=out[:, n_draws + 128:], flags=flags)
     return res
+
+
+def two_valued_sum_check(x, acc0, l1, l0, device=0):
+    """libamwg_selftest.so: csrc/amwg_twoval.h two_valued_sum and the plain loop acc = acc + (x[i] ? l1 : l0), both on the device, lane j from acc0[j] with the
+    addends l1[j], l0[j] over the observations x [n] (0 / 1), on the library's own tables -> (fast_forward [m], term_by_term [m])  (amwg_two_valued_sum_check)"""
+    xs = np.ascontiguousarray(x, dtype=np.float64)
+    a0, a1, b0 = (np.ascontiguousarray(v, dtype=np.float64) for v in (acc0, l1, l0))
+    if xs.ndim != 1 or a0.ndim != 1 or a1.shape != a0.shape or b0.shape != a0.shape:
+        raise AmwgError("amwg error: two_valued_sum_check: x [n], acc0, l1 and l0 [m]")
+    ff, seq = np.empty(a0.size), np.empty(a0.size)
+    L = selftest_lib()
+    if L.amwg_two_valued_sum_check(device, _dp(xs), xs.size, a0.size, _dp(a0), _dp(a1), _dp(b0), _dp(ff), _dp(seq)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return ff, seq
+
+
+def two_valued_tables(x):
+    """libamwg_selftest.so: the library's own two_valued_tables (csrc/amwg_create.hip) for the observations x [n] (bytes, non-zero = 1) -> uint32 [6 (n // 32 + 2)]:
+    w, pre, om1, po1, om0, po0 back to back.  Host only  (amwg_two_valued_tables)"""
+    xb = np.ascontiguousarray(x, dtype=np.uint8)
+    if xb.ndim != 1:
+        raise AmwgError("amwg error: two_valued_tables: x [n]")
+    out = np.empty(6 * (xb.size // 32 + 2), dtype=np.uint32)
+    L = selftest_lib()
+    if L.amwg_two_valued_tables(xb.ctypes.data_as(C.POINTER(C.c_uint8)), xb.size, out.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return out
 
 
 def k_valued_sum_check(K, idx, tab, acc0, c, device=0):

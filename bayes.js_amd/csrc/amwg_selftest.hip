@@ -191,6 +191,15 @@ int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_
   return AMWG_OK;
 }
 
+// the library's own copy of the table recipe (amwg_create.hip two_valued_tables), word for word as the samplers and the check above upload it.  No GPU involved.
+int amwg_two_valued_tables(const uint8_t *x, int32_t n, uint32_t *out_words) {
+  if ((!x && n > 0) || !out_words || n < 0) return amwg_fail(AMWG_EINVAL, "amwg_two_valued_tables: bad argument");
+  const std::vector<uint32_t> tab = two_valued_tables(x, n);
+  if (tab.size() != 6 * two_valued_words(n)) return amwg_fail(AMWG_EINVAL, "internal: two_valued_tables of %zu words, expected %zu", tab.size(), 6 * two_valued_words(n));
+  memcpy(out_words, tab.data(), tab.size() * 4);
+  return AMWG_OK;
+}
+
 int amwg_k_valued_sum_check(int32_t device, int32_t K, const uint8_t *idx, int32_t n, const uint32_t *tab, int64_t m, const double *acc0, const double *c,
                             double *out_fast_forward, double *out_term_by_term) {
   const char *call = "amwg_k_valued_sum_check";

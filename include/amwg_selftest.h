@@ -26,9 +26,13 @@ double amwg_ld_host(int32_t id, double x, double a, double b, double c);
 int amwg_ld_device(int32_t device, int64_t n, const double *records, double *out);
 /* out_fast_forward[j] = the two-valued sequential sum of csrc/amwg_twoval.h (exact fast-forward over binades) and
  * out_term_by_term[j] = the plain loop, both on the device, over the n observations x (0/1) from acc0[j] with addends
- * l1[j] (x_i = 1) and l0[j] (x_i = 0); j < m. */
+ * l1[j] (x_i = 1) and l0[j] (x_i = 0); j < m.  Lane j is thread j of 64-thread workgroups: every wavefront holds 64 different cases (tests/test_gpu_twoval.py
+ * relies on it).  The six tables are built here, by the library's own two_valued_tables. */
 int amwg_two_valued_sum_check(int32_t device, const double *x, int32_t n, int64_t m, const double *acc0, const double *l1, const double *l0,
                               double *out_fast_forward, double *out_term_by_term);
+/* Those tables themselves (csrc/amwg_create.hip two_valued_tables, the copy of the recipe that the samplers and the check above upload) for the n observations
+ * x (host bytes, non-zero = 1): out_words[6 * (n / 32 + 2)] = w, pre, om1, po1, om0, po0 back to back.  Host only: no device is opened. */
+int amwg_two_valued_tables(const uint8_t *x, int32_t n, uint32_t *out_words);
 /* The same for the K-valued sequential sum of csrc/amwg_kval.h, K in {1, 2, 3, 5, 8, 13, 16}: idx[n] (host bytes) is the value index of every observation, shared
  * by all lanes; tab the 2 K k_valued_words(n) table words AS THE CALLER BUILT THEM (per block of 32 observations pre[K] then mask[K]; they are not rebuilt here, so
  * that a translator's tables can be put to the test); lane j < m starts from acc0[j] with the addends c[j * K + k].  Lane j is thread j of 64-thread workgroups:

@@ -334,6 +334,39 @@ const BENCH = {
       }
       return log_post;
     } },
+  // (tests/test_gpu_twoval.py: bench_bern's closure over 777 STRUCTURED observations -- strictly alternating; runs of 32 k - 1, 32 k, 32 k + 1 observations that
+  // end one before, on and one behind a 32-bit word boundary of the two-valued tables -- where the fast-forward's closed form for one tying addend depends on
+  // the parity of the runs)
+  bern_alternating: { params: () => ({ theta: { type: 'real', lower: 0, upper: 1 } }), data: () => { const x = []; for (let i = 0; i < 777; i++) x.push(i & 1); return { x }; },
+    log_post: function(state, data) {
+      var log_post = 0;
+      log_post += ld.beta(state.theta, 2, 2);
+      var n = data.x.length;
+      for(var i = 0; i < n; i++) {
+        log_post += ld.bern(data.x[i], state.theta)
+      }
+      return log_post;
+    } },
+  bern_runs_32k: { params: () => ({ theta: { type: 'real', lower: 0, upper: 1 } }),
+    data: () => {
+      const x = [], off = [-1, 0, 1, 1, 0, -1, 0];      // where a run ends, relative to a word boundary: moves by at most one from run to run
+      let v = 1, end = 0;
+      for (let r = 0; x.length < 777; r++) {
+        end = 32 * (Math.floor((end + 1) / 32) + 1 + r % 3) + off[r % off.length];
+        while (x.length < end && x.length < 777) x.push(v);
+        v = 1 - v;
+      }
+      return { x };
+    },
+    log_post: function(state, data) {
+      var log_post = 0;
+      log_post += ld.beta(state.theta, 2, 2);
+      var n = data.x.length;
+      for(var i = 0; i < n; i++) {
+        log_post += ld.bern(data.x[i], state.theta)
+      }
+      return log_post;
+    } },
   // (round 6, the certified tail of translate.js tailPlan beyond the README shape: data too large for LDS, a ragged 65 observations, a head with
   // other densities and a mean / sd that are EXPRESSIONS of the state)
   bench_normal_50k: { params: CASES.readme_normal.params, data: () => synth.normal(50000, 20260926).x, log_post: CASES.readme_normal.log_post },

@@ -171,7 +171,8 @@ def test_two_valued_sum_fast_forward_is_exact_including_ties():
     """csrc/amwg_models.h two_valued_sum against the plain loop on the device, bit for bit: random addends, and addends whose
     significands end in z zero bits, which tie (sit exactly half-way between two multiples of ulp(acc)) in the binade where
     acc is 2^(z+1) times larger -- for large z a long binade, each of the four tie cases (none / one with even or odd other
-    increment / both), starting accumulators of either sign and magnitude."""
+    increment / both), starting accumulators of either sign and magnitude.  The data here are independent draws only; tests/test_gpu_twoval.py
+    (README.twoval.md) has structured data, lanes constructed for every tie case, the census that shows they arrive and the mutation table."""
     import ctypes as C
     L = A.selftest_lib()
     rng = np.random.default_rng(11)

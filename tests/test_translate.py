@@ -142,8 +142,13 @@ def test_hiprtc_errors_surface_with_the_compiler_log():
 
 def test_two_valued_sum_host_fuzz(tmp_path):
     """csrc/amwg_twoval.h compiled for the host: 200 000 random / adversarial (data, acc0, l1, l0) cases -- trailing-zero
-    significands (ties), either sign of acc0, non-finite and positive addends -- against the plain fp64 loop, bit for bit."""
+    significands (ties), either sign of acc0, non-finite and positive addends -- against the plain fp64 loop, bit for bit.  The data are independent
+    draws or structured (runs, runs around word boundaries, alternating, periodic, one value only, one value but for a few places), some starts and
+    addends are planted (README.twoval.md), and the harness says what it reached: its own census of the binade visits along the plain sum, by the
+    header's definitions -- every class is met, in the numbers its generator supports (a condition on the inputs; at 200 000 cases the generator
+    gives about three times each bound).  tests/test_twoval_host.py has the constructed cases and the full census."""
     import os
+    import re
     import subprocess
     exe = str(tmp_path / "twoval_fuzz")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -151,6 +156,11 @@ def test_two_valued_sum_host_fuzz(tmp_path):
                            os.path.join(root, "tests", "host", "twoval_fuzz.cpp"), "-o", exe])
     p = subprocess.run([exe, "200000"], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "mismatches=0" in p.stdout, p.stdout[-2000:]
+    visits = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", [ln for ln in p.stdout.splitlines() if ln.startswith("visits:")][0])}
+    least = {"tie_free": 230000, "stalled": 480, "mode1": 880, "mode2": 12000, "mode3": 5900, "mode3_ge64": 1400, "half_ulp_tie": 1200, "landing": 2500}
+    assert set(visits) == set(least) and all(visits[k] >= least[k] for k in least), visits
+    made = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", p.stdout.splitlines()[-1])}
+    assert made["structured_data"] >= 100000 and made["planted_starts"] >= 9000, made
 
 
 def test_k_valued_sum_host_fuzz(tmp_path):
