@@ -65,6 +65,8 @@ const FoldSummary *amwg_summary_of(const amwg_sampler *s);      // nullptr: none
 void amwg_summary_forget(const amwg_sampler *s);                // (amwg_destroy)
 // AMWG_EINVAL "<call>: ... amwg_sample_summarize ... the draws were not kept" when amwg_summarised(s), else AMWG_OK
 int amwg_refuse_summarised(const amwg_sampler *s, const char *call);
+// the precondition of the calls that read the stored draws: amwg_refuse_summarised, then AMWG_EINVAL "<call>: no sample() call yet" unless a sample call left draws
+int amwg_need_stored_draws(const amwg_sampler *s, const char *call);
 
 // ---- amwg_diag.hip: the kernels, enqueued on `stream`
 // rows [g0, g0 + nrows) of a chain's kept draws stand in window[0 .. nrows)[PR][C]: add them to acc

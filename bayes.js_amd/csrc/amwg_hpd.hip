@@ -330,8 +330,7 @@ int amwg_hpd_launch(const char *call, const double *draws, int64_t rows, int PR,
 
 extern "C" int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_hpd: bad argument");
-  TRYB(amwg_refuse_summarised(s, "amwg_last_sample_dataset_hpd"));
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_hpd: no sample() call yet");
+  TRYB(amwg_need_stored_draws(s, "amwg_last_sample_dataset_hpd"));
   TRYB(amwg_hpd_shape("amwg_last_sample_dataset_hpd", s->last_rows, s->P + s->D, s->C, s->n_datasets, n_probs));
   HIP_TRY(hipSetDevice(s->device));
   return amwg_hpd_launch("amwg_last_sample_dataset_hpd", s->last_draws, s->last_rows, s->P + s->D, s->C, s->n_datasets, probs, n_probs, out, s->stream);

@@ -4,7 +4,7 @@
 //
 // THE ROUTE.  S = rows * (C / D) draws per dataset, M = loo_tail_len(S), cap = max(64, M + 1 rounded up to a power of two) doubles of tail per observation; n = the
 // dataset's observations (the Bernoulli family: n = 2, expanded afterwards).  The S x n terms are never stored: every pass below forms them again.
-//   0 lppd         amwg_waic_launch: lppd_i is WAIC's own, byte for byte.
+//   0 lppd         amwg_waic_run: lppd_i is WAIC's own, byte for byte.
 //   1 select       loo_hist_kernel<Family>, the geometry of WAIC's partial kernel (a tile of 64 observations, a lane each; a run of draws staged in LDS and read as
 //                  broadcasts).  Most significant digit first over select_key of the terms, 7 bits a pass: 128 x 64 counters in LDS, added to the observation's 128
 //                  global counters with integer atomics; pass 0 also takes the smallest key (an integer atomic minimum) and flags a non-finite term.
@@ -20,7 +20,7 @@
 // Every sum is a function of the sorted tail, of (S, n) and of the observation's own terms: a dataset's bytes do not depend on its neighbours, on D, on the number
 // of select passes its batch took, or on the scratch budget.
 // SCRATCH per observation: cap doubles of tail, 512 bytes of counters, 48 bytes of state and a double per run of draws; allocated per call and freed before it
-// returns; the datasets go in batches under kLooScratchBytes, and a dataset beyond the budget runs alone.
+// returns; the datasets go in batches under the call's scratch budget (amwg_pointwise_plan, amwg_waic.h), and a dataset beyond the budget runs alone.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,7 +29,6 @@
 
 #include "amwg_waic.h"
 
-constexpr size_t kLooScratchBytes = (size_t)256 << 20;      // the default scratch budget of a call: 256 MiB, as amwg_waic.h
 constexpr int64_t kLooTailCap = 8192;                       // M + 1 at most: the tail (64 KB of doubles) one workgroup sorts and fits in LDS
 
 // the smallest r with r * r >= v, in integers
@@ -52,18 +51,16 @@ struct LooStats { int32_t passes, timed; float ms_lppd, ms_select, ms_compact, m
 #pragma GCC visibility push(hidden)
 // AMWG_EINVAL "<call>: ..." unless the shape can be served: amwg_waic_shape's limits and loo_tail_len(S) + 1 <= kLooTailCap.  Host only.
 int amwg_loo_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
-// draws [rows][PR][C] on the current device, D datasets of C / D columns each; sets [D] on the host.  Host outputs: summary [D][4] (elpd_loo, se, p_loo, lppd),
-// high [D] or nullptr, pointwise nullptr or [D][n_max][3] (elpd_loo_i, lppd_i, khat_i; NaN beyond n_d), tails nullptr or [D][n_max][M + 1] (the sorted smallest
-// terms; NaN beyond n_d and for an observation with a non-finite term; the test library only).  Returns after `stream` has drained.
-int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
-                    int32_t *high, double *pointwise, double *tails, hipStream_t stream);
-// amwg_loo_launch over any PointwiseLaunch (amwg_waic.h): the built-in families' kernels, or a closure's.  A closure: sets[d].n_obs = kTermN for every d.
+// The run over any PointwiseLaunch, as amwg_waic.h states it (PointwiseRunFn).  Host outputs: summary [D][4] (elpd_loo, se, p_loo, lppd), high [D] or nullptr,
+// pointwise nullptr or [D][n_max][3] (elpd_loo_i, lppd_i, khat_i; NaN beyond n_d), tails nullptr or [D][n_max][M + 1] (the sorted smallest terms; NaN beyond n_d
+// and for an observation with a non-finite term; the test library only).
 int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
-                 int32_t *high, double *pointwise, double *tails, hipStream_t stream);
+                 int32_t *high, double *pointwise, double *tails, size_t scratch_bytes, hipStream_t stream);
+// amwg_loo_run for a built-in family, behind the checks of the pointers, the shape and the family
+int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
+                    int32_t *high, double *pointwise, double *tails, size_t scratch_bytes, hipStream_t stream);
 // the finish of include/amwg.h over one dataset's triples pw[n][3]: summary[4], *high (may be nullptr)
 void amwg_loo_totals(const double *pw, int64_t n, double *summary, int32_t *high);
-// the scratch budget of later calls in bytes (0: kLooScratchBytes); returns the budget in force before.  For the test library: the product never calls it.
-size_t amwg_loo_set_budget(size_t bytes);
 // phase timing of later calls on or off (events around the phases); the record of the last call that ended (a call gathers its own and publishes it once, under a
 // lock: concurrent calls on several samplers do not share anything they write).  For the test library.
 void amwg_loo_set_timing(int on);

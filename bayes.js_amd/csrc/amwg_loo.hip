@@ -9,11 +9,8 @@
 #include <mutex>
 #include <vector>
 
-#include "amwg_dataset.h"
-#include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_loo.h"
-#include "amwg_sampler.h"
 #include "amwg_select.h"
 #include "amwg_terms.h"
 
@@ -26,11 +23,6 @@ constexpr int kFitExtra = 2 * kMaxTheta + 16;                     // doubles of 
 __global__ void __launch_bounds__(kThreads) loo_init_kernel(LooState *state, int64_t count) {
   const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (k < count) state[k] = LooState{0, 0, kMaxKey, 0, 0, 0, 0, 0, 0};
-}
-
-__global__ void __launch_bounds__(kThreads) loo_fill_nan_kernel(double *out, int64_t count) {
-  const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (k < count) out[k] = __builtin_nan("");
 }
 
 // one digit of the select (amwg_pointwise.h).  The atomics of the two kernels that walk the terms are there now, and as before every one is on an integer:
@@ -209,19 +201,6 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
   if (tid == 0) { res[0] = elpd; res[1] = khat; }
 }
 
-// the Bernoulli family: observation i takes the values of its x (two[d][0] for x = 1, two[d][1] for x = 0), `width` doubles each; an invalid x_i: NaN
-__global__ void __launch_bounds__(kThreads) loo_bern_expand_kernel(const WaicModel M, const WaicDataset *__restrict__ sets, const double *__restrict__ two, double *__restrict__ out,
-                                                                   int64_t n_max, int64_t width) {
-  const int d = blockIdx.y;
-  const WaicDataset ds = sets[d];
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= ds.n_obs) return;
-  const bool invalid = M.invalid && M.invalid[ds.off_xb + i];
-  const int k = M.xb[ds.off_xb + i] ? 0 : 1;
-  for (int64_t t = 0; t < width; ++t) out[(d * n_max + i) * width + t] = invalid ? __builtin_nan("") : two[(d * 2 + k) * width + t];
-}
-
-size_t g_budget = kLooScratchBytes;
 std::atomic<int> g_timing{0};      // the test library's switch
 std::mutex g_stats_lock;
 LooStats g_stats{};                // the last call's record, published once when it ends
@@ -251,10 +230,11 @@ inline uint32_t loo_cap(int64_t M) {
 inline int loo_thetas(int64_t M) { return 30 + (int)(loo_isqrt_up(M + 1) - 1); }      // 30 + floor(sqrt(M)): the largest r with r * r <= M is isqrt_up(M + 1) - 1
 
 int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, const WaicDataset *d_sets,
-                int64_t n_max, double *d_pw, double *d_tails, LooStats &stats, hipStream_t stream) {
+                int64_t n_max, double *d_pw, double *d_tails, LooStats &stats, size_t scratch_bytes, hipStream_t stream) {
   const bool bern = K.bern;
-  const int64_t cpd = C / D, S = rows * cpd, M = loo_tail_len(S);
-  const uint32_t cap = loo_cap(M);
+  int64_t cpd = C / D;      // (not const, nor cap: the args[] lists point at them)
+  const int64_t S = rows * cpd, M = loo_tail_len(S);
+  uint32_t cap = loo_cap(M);
   const int mm = loo_thetas(M);
   const size_t fit_lds = ((size_t)cap + kFitExtra) * 8;
   if (fit_lds > 65536) {
@@ -265,132 +245,81 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
   if (bern) {
     HIP_TRY(two.alloc((size_t)D * 4 * 8));
     if (d_tails) {
-      const int64_t count = (int64_t)D * 2 * (M + 1);
-      HIP_TRY(two_tails.alloc((size_t)count * 8));
-      hipLaunchKernelGGL(loo_fill_nan_kernel, dim3((unsigned)((count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, two_tails.as<double>(), count);
-      HIP_TRY(hipGetLastError());
+      HIP_TRY(two_tails.alloc((size_t)D * 2 * (size_t)(M + 1) * 8));
+      HIP_TRY(amwg_pointwise_fill_nan(two_tails.as<double>(), (int64_t)D * 2 * (M + 1), stream));
     }
   }
   double *out = bern ? two.as<double>() : d_pw;
   double *tails_out = d_tails ? (bern ? two_tails.as<double>() : d_tails) : nullptr;
   const int64_t out_stride = bern ? 2 : n_max;
-  // the batches: consecutive datasets whose scratch fits the budget together (a dataset beyond it runs alone)
-  const size_t per_obs = (size_t)cap * 8 + (size_t)kBins * 4 + sizeof(LooState);
-  std::vector<int64_t> n_eff((size_t)D), off((size_t)D * 2);      // off[d]: observations before d in its batch; off[D + d]: partials before it
-  std::vector<int> batch_end;
-  int64_t most_obs = 0, most_parts = 0;
-  {
-    size_t in_batch = 0;
-    int64_t obs = 0, prt = 0;
-    for (int d = 0; d < D; ++d) {
-      const int64_t n = bern ? (sets[d].n_obs > 0 ? 2 : 0) : sets[d].n_obs;
-      n_eff[(size_t)d] = n;
-      const int64_t np = waic_splits(S, n) * n;
-      const size_t bytes = (size_t)n * per_obs + (size_t)np * 8;
-      if (in_batch && in_batch + bytes > g_budget) { batch_end.push_back(d); in_batch = 0; obs = 0; prt = 0; }
-      off[(size_t)d] = obs; off[(size_t)D + (size_t)d] = prt;
-      in_batch += bytes; obs += n; prt += np;
-      most_obs = obs > most_obs ? obs : most_obs; most_parts = prt > most_parts ? prt : most_parts;
-    }
-    batch_end.push_back(D);
-  }
+  const PointwisePlan plan = amwg_pointwise_plan(K, sets, D, S, (size_t)cap * 8 + (size_t)kBins * 4 + sizeof(LooState), 8, scratch_bytes);
   HIP_TRY(offs.alloc((size_t)D * 16));
-  HIP_TRY(hipMemcpyAsync(offs.p, off.data(), (size_t)D * 16, hipMemcpyHostToDevice, stream));
-  HIP_TRY(state.alloc((size_t)most_obs * sizeof(LooState)));
-  HIP_TRY(hist.alloc((size_t)most_obs * kBins * 4));
-  HIP_TRY(tail.alloc((size_t)most_obs * cap * 8));
-  HIP_TRY(parts.alloc((size_t)most_parts * 8));
+  HIP_TRY(hipMemcpyAsync(offs.p, plan.off.data(), (size_t)D * 16, hipMemcpyHostToDevice, stream));
+  HIP_TRY(state.alloc((size_t)plan.most_obs * sizeof(LooState)));
+  HIP_TRY(hist.alloc((size_t)plan.most_obs * kBins * 4));
+  HIP_TRY(tail.alloc((size_t)plan.most_obs * cap * 8));
+  HIP_TRY(parts.alloc((size_t)plan.most_parts * 8));
   HIP_TRY(pending.alloc(sizeof(int)));
-  const int64_t *obs_off = offs.as<int64_t>(), *part_off = offs.as<int64_t>() + D;
-  int d0 = 0;
-  for (const int d1 : batch_end) {
-    int64_t tiles = 0, splits = 0, n_most = 0, obs = 0;
-    for (int d = d0; d < d1; ++d) {
-      const int64_t n = n_eff[(size_t)d], t = (n + kTile - 1) / kTile, sp = waic_splits(S, n);
-      tiles = t > tiles ? t : tiles; splits = sp > splits ? sp : splits; n_most = n > n_most ? n : n_most; obs += n;
-    }
-    if (tiles > 0) {
-      const dim3 walk((unsigned)tiles, (unsigned)splits, (unsigned)(d1 - d0)), per_obs_grid((unsigned)((n_most + kThreads - 1) / kThreads), (unsigned)(d1 - d0));
-      hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((obs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, state.as<LooState>(), obs);
-      HIP_TRY(hipGetLastError());
-      {
-        Phase ph(stream, stats.timed != 0);
-        int passes = 0;
-        for (int pass = 0; pass < kPasses; ++pass) {
-          int waiting = 0;
-          HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)obs * kBins * 4, stream));
-          HIP_TRY(hipMemsetAsync(pending.p, 0, sizeof(int), stream));
-          HIP_TRY(K.loo_hist(walk, stream, draws, rows, PR, C, cpd, d0, d_sets, obs_off + d0, state.as<LooState>(), hist.as<uint32_t>(), pass));
-          hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern ? 1 : 0, obs_off + d0, state.as<LooState>(), hist.as<uint32_t>(), pass,
-                             (uint32_t)M, cap, pending.as<int>());
-          HIP_TRY(hipGetLastError());
-          HIP_TRY(hipMemcpyAsync(&waiting, pending.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-          HIP_TRY(hipStreamSynchronize(stream));
-          ++passes;
-          if (!waiting) break;
-        }
-        stats.passes = passes > stats.passes ? passes : stats.passes;
-        ph.end(stats.ms_select);
-      }
-      {
-        Phase ph(stream, stats.timed != 0);
-        HIP_TRY(K.loo_compact(walk, stream, draws, rows, PR, C, cpd, d0, d_sets, obs_off + d0, part_off + d0, state.as<LooState>(), tail.as<double>(), cap, parts.as<double>()));
-        ph.end(stats.ms_compact);
-      }
-      {
-        Phase ph(stream, stats.timed != 0);
-        hipLaunchKernelGGL(loo_fit_kernel, dim3((unsigned)n_most, (unsigned)(d1 - d0)), dim3(fit_threads(cap)), fit_lds, stream, rows, cpd, d0, d_sets, bern ? 1 : 0, obs_off + d0,
-                           part_off + d0, state.as<LooState>(), tail.as<double>(), cap, parts.as<double>(), (uint32_t)M, mm, out, out_stride, tails_out);
+  LooState *d_state = state.as<LooState>();
+  uint32_t *d_hist = hist.as<uint32_t>();
+  double *d_tail = tail.as<double>(), *d_parts = parts.as<double>();
+  for (const PointwiseBatch &b : plan.batches) {
+    if (b.tiles == 0) continue;
+    int d0 = b.d0, pass = 0;
+    const int64_t obs = b.obs, *obs_off = offs.as<int64_t>() + d0, *part_off = offs.as<int64_t>() + D + d0;
+    const dim3 walk((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), per_obs_grid((unsigned)((b.n_most + kThreads - 1) / kThreads), (unsigned)(b.d1 - d0));
+    void *hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &d_state, &d_hist, &pass};
+    void *compact_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &part_off, &d_state, &d_tail, &cap, &d_parts};
+    hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((obs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_state, obs);
+    HIP_TRY(hipGetLastError());
+    {
+      Phase ph(stream, stats.timed != 0);
+      int passes = 0;
+      for (pass = 0; pass < kPasses; ++pass) {      // (hist_args reads `pass`)
+        int waiting = 0;
+        HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)obs * kBins * 4, stream));
+        HIP_TRY(hipMemsetAsync(pending.p, 0, sizeof(int), stream));
+        HIP_TRY(amwg_pointwise_go(K, kPwLooHist, walk, stream, hist_args));
+        hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern ? 1 : 0, obs_off, d_state, d_hist, pass, (uint32_t)M, cap, pending.as<int>());
         HIP_TRY(hipGetLastError());
-        ph.end(stats.ms_fit);
+        HIP_TRY(hipMemcpyAsync(&waiting, pending.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        ++passes;
+        if (!waiting) break;
       }
+      stats.passes = passes > stats.passes ? passes : stats.passes;
+      ph.end(stats.ms_select);
     }
-    d0 = d1;
+    {
+      Phase ph(stream, stats.timed != 0);
+      HIP_TRY(amwg_pointwise_go(K, kPwLooCompact, walk, stream, compact_args));
+      ph.end(stats.ms_compact);
+    }
+    {
+      Phase ph(stream, stats.timed != 0);
+      hipLaunchKernelGGL(loo_fit_kernel, dim3((unsigned)b.n_most, (unsigned)(b.d1 - d0)), dim3(fit_threads(cap)), fit_lds, stream, rows, cpd, d0, d_sets, bern ? 1 : 0, obs_off, part_off,
+                         d_state, d_tail, cap, d_parts, (uint32_t)M, mm, out, out_stride, tails_out);
+      HIP_TRY(hipGetLastError());
+      ph.end(stats.ms_fit);
+    }
   }
   if (bern) {
-    const dim3 grid((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)D);
-    hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, *K.family, d_sets, two.as<double>(), d_pw, n_max, (int64_t)2);
-    HIP_TRY(hipGetLastError());
-    if (d_tails) {
-      hipLaunchKernelGGL(loo_bern_expand_kernel, grid, dim3(kThreads), 0, stream, *K.family, d_sets, two_tails.as<double>(), d_tails, n_max, M + 1);
-      HIP_TRY(hipGetLastError());
-    }
+    HIP_TRY(amwg_pointwise_bern_expand(K, d_sets, D, two.as<double>(), d_pw, n_max, 2, stream));
+    if (d_tails) HIP_TRY(amwg_pointwise_bern_expand(K, d_sets, D, two_tails.as<double>(), d_tails, n_max, M + 1, stream));
   }
   HIP_TRY(hipStreamSynchronize(stream));      // (the scratch is freed on return)
-  (void)call;
   return AMWG_OK;
 }
 
-template <int MODEL>
-void family_kernels(PointwiseLaunch &K, const WaicModel &model) {
-  K.loo_hist = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off, void *state,
-                       uint32_t *hist, int pass) {
-    hipLaunchKernelGGL(loo_hist_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, sets, obs_off, static_cast<LooState *>(state), hist, pass);
-    return hipGetLastError();
-  };
-  K.loo_compact = [model](dim3 grid, hipStream_t stream, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicDataset *sets, const int64_t *obs_off,
-                          const int64_t *part_off, void *state, double *tail, uint32_t cap, double *parts) {
-    hipLaunchKernelGGL(loo_compact_kernel<MODEL>, grid, dim3(kThreads), 0, stream, draws, rows, PR, C, cpd, d0, model, sets, obs_off, part_off, static_cast<LooState *>(state), tail, cap, parts);
-    return hipGetLastError();
-  };
+template <int... MODEL> const void *family_fn(PointwiseModels<MODEL...>, int model, int k) {
+  const void *const fn[][2] = {{reinterpret_cast<const void *>(&loo_hist_kernel<MODEL>), reinterpret_cast<const void *>(&loo_compact_kernel<MODEL>)}...};
+  return fn[model - AMWG_MODEL_NORMAL][k];
 }
 
 }  // namespace
 
-void amwg_loo_family_kernels(PointwiseLaunch &K, const WaicModel &model) {
-  switch (model.model) {
-    case AMWG_MODEL_NORMAL: family_kernels<AMWG_MODEL_NORMAL>(K, model); break;
-    case AMWG_MODEL_BETA_BERN: family_kernels<AMWG_MODEL_BETA_BERN>(K, model); break;
-    case AMWG_MODEL_HIER_NORMAL: family_kernels<AMWG_MODEL_HIER_NORMAL>(K, model); break;
-    default: family_kernels<AMWG_MODEL_POIS_GLM>(K, model); break;
-  }
-}
+const void *amwg_loo_family_fn(int model, int k) { return family_fn(BuiltinModels{}, model, k); }
 
-size_t amwg_loo_set_budget(size_t bytes) {
-  const size_t before = g_budget;
-  g_budget = bytes ? bytes : kLooScratchBytes;
-  return before;
-}
 void amwg_loo_set_timing(int on) { g_timing.store(on); }
 LooStats amwg_loo_last_stats() {
   std::lock_guard<std::mutex> hold(g_stats_lock);
@@ -425,55 +354,36 @@ void amwg_loo_totals(const double *pw, int64_t n, double *summary, int32_t *high
 }
 
 int amwg_loo_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
-                    int32_t *high, double *pointwise, double *tails, hipStream_t stream) {
+                    int32_t *high, double *pointwise, double *tails, size_t scratch_bytes, hipStream_t stream) {
+  if (!draws || !sets || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  TRYB(amwg_loo_shape(call, rows, PR, C, D));
   PointwiseLaunch K;
-  amwg_waic_family_kernels(K, model);
-  amwg_loo_family_kernels(K, model);
-  return amwg_loo_run(call, draws, rows, PR, C, D, K, sets, summary, high, pointwise, tails, stream);
+  TRYB(amwg_pointwise_family(call, model, PR, D, K));
+  return amwg_loo_run(call, draws, rows, PR, C, D, K, sets, summary, high, pointwise, tails, scratch_bytes, stream);
 }
 
 int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
-                 int32_t *high, double *pointwise, double *tails, hipStream_t stream) {
-  if (!draws || !sets || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
-  TRYB(amwg_loo_shape(call, rows, PR, C, D));
+                 int32_t *high, double *pointwise, double *tails, size_t scratch_bytes, hipStream_t stream) {
   int64_t n_max = 0;
   for (int d = 0; d < D; ++d) n_max = sets[d].n_obs > n_max ? sets[d].n_obs : n_max;
-  const int64_t S = rows * (C / D), M = loo_tail_len(S);
+  const int64_t M = loo_tail_len(rows * (C / D));
   LooStats stats{0, g_timing.load(), 0.f, 0.f, 0.f, 0.f};      // this call's own; nothing shared is written while it runs
-  // lppd_i: WAIC's, which also checks the family, its components and the sizes
+  // lppd_i: WAIC's, which also refuses an n_obs < 0
   const size_t pairs = (size_t)D * (size_t)(n_max > 0 ? n_max : 1);
   std::vector<double> wsum((size_t)D * 4), wpw(pairs * 2), got(pairs * 2);
   {
     Phase ph(stream, stats.timed != 0);
-    if (K.family) TRYB(amwg_waic_launch(call, draws, rows, PR, C, D, *K.family, sets, wsum.data(), nullptr, wpw.data(), nullptr, stream));
-    else TRYB(amwg_waic_run(call, draws, rows, PR, C, D, K, sets, wsum.data(), nullptr, wpw.data(), nullptr, stream));
+    TRYB(amwg_waic_run(call, draws, rows, PR, C, D, K, sets, wsum.data(), nullptr, wpw.data(), nullptr, scratch_bytes, stream));
     ph.end(stats.ms_lppd);
   }
-  const size_t pw_count = (size_t)D * (size_t)n_max * 2, tl_count = tails ? (size_t)D * (size_t)n_max * (size_t)(M + 1) : 0;
-  DevBuf d_sets, d_pw, d_tl;
-  HIP_TRY(d_sets.alloc((size_t)D * sizeof(WaicDataset)));
-  HIP_TRY(hipMemcpyAsync(d_sets.p, sets, (size_t)D * sizeof(WaicDataset), hipMemcpyHostToDevice, stream));
-  HIP_TRY(d_pw.alloc(pw_count * 8));
-  if (pw_count) {
-    hipLaunchKernelGGL(loo_fill_nan_kernel, dim3((unsigned)((pw_count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_pw.as<double>(), (int64_t)pw_count);
-    HIP_TRY(hipGetLastError());
-  }
-  if (tails) {
-    HIP_TRY(d_tl.alloc(tl_count * 8));
-    if (tl_count) {
-      hipLaunchKernelGGL(loo_fill_nan_kernel, dim3((unsigned)((tl_count + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_tl.as<double>(), (int64_t)tl_count);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  double *dt = tails ? d_tl.as<double>() : nullptr;
-  const WaicDataset *ds = d_sets.as<WaicDataset>();
-  TRYB(run_kernels(call, draws, rows, PR, C, D, K, sets, ds, n_max, d_pw.as<double>(), dt, stats, stream));
+  PointwiseOut o;
+  TRYB(amwg_pointwise_begin(call, sets, D, tails ? M + 1 : 0, stream, o));
+  TRYB(run_kernels(call, draws, rows, PR, C, D, K, sets, o.sets.as<WaicDataset>(), n_max, o.pw.as<double>(), tails ? o.extra.as<double>() : nullptr, stats, scratch_bytes, stream));
   {
     std::lock_guard<std::mutex> hold(g_stats_lock);
     g_stats = stats;
   }
-  if (pw_count) HIP_TRY(hipMemcpy(got.data(), d_pw.p, pw_count * 8, hipMemcpyDeviceToHost));
-  if (tl_count) HIP_TRY(hipMemcpy(tails, d_tl.p, tl_count * 8, hipMemcpyDeviceToHost));
+  TRYB(amwg_pointwise_fetch(o, got.data(), tails));
   // the triples: (elpd_loo_i, WAIC's lppd_i, khat_i); all three NaN where either pass found the terms of (d, i) unfit
   std::vector<double> own;
   double *pw = pointwise;
@@ -489,24 +399,5 @@ int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, in
 }
 
 extern "C" int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
-  static const char *call = "amwg_last_sample_dataset_loo";
-  if (!s || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
-  if (s->user && s->pw_terms.empty()) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
-  TRYB(amwg_refuse_summarised(s, call));
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "%s: no sample() call yet", call);
-  const int D = s->n_datasets, PR = s->P + s->D;
-  TRYB(amwg_loo_shape(call, s->last_rows, PR, s->C, D));
-  if (s->mc.group_local) return amwg_fail(AMWG_EINVAL, "%s: a group_local sampler keeps its observations as a lane-major tile; the pointwise terms need them in index order", call);
-  HIP_TRY(hipSetDevice(s->device));
-  std::vector<WaicDataset> sets;
-  if (s->user) {
-    UserPointwise u;
-    TRYB(amwg_pointwise_describe_user(s, sets, u));
-    PointwiseLaunch K;
-    amwg_pointwise_user_kernels(K, u);
-    return amwg_loo_run(call, s->last_draws, s->last_rows, PR, s->C, D, K, sets.data(), summary, high, pointwise, nullptr, s->stream);
-  }
-  WaicModel m{};
-  TRYB(amwg_waic_describe(s, sets, m));
-  return amwg_loo_launch(call, s->last_draws, s->last_rows, PR, s->C, D, m, sets.data(), summary, high, pointwise, nullptr, s->stream);
+  return amwg_pointwise_entry("amwg_last_sample_dataset_loo", s, summary, high, pointwise, amwg_loo_shape, amwg_loo_run);
 }

@@ -2,7 +2,7 @@
 // argument MA: WAIC's partial kernel and loglik kernel, LOO's histogram kernel and compaction kernel.  amwg_waic.hip and amwg_loo.hip instantiate it for the four
 // built-in families (Family<MODEL>, WaicModel: amwg_terms.h); hiprtc instantiates the very same text for the pointwise terms of a translated closure (UserTerms:
 // translate.js pointwisePlan; UserTermsArg) as the extern "C" entries at the end of this file, in one code object (amwg_rtc.hip compile_pointwise).  What does not
-// depend on the model -- merge, pick, fit, fill, totals -- stays in the two .hip files and serves both.
+// depend on the model serves both: merge, pick, fit and totals in the two .hip files, fill, the Bernoulli expand and the host path around them in amwg_pointwise_host.hip.
 //
 // A family class F has: Draw (what an evaluation needs of a draw; staged in LDS), Obs (what it needs of an observation; registers), n_eff(ds), make_draw(at, C, M, ds),
 // set_base(w, base), load_obs(M, ds, i) and term(M, o, w, i, draws, C).  M is the model argument as dataset d sees it: dataset_model(MA, d).

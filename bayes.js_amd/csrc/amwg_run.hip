@@ -283,6 +283,11 @@ int amwg_refuse_summarised(const amwg_sampler *s, const char *call) {
     return amwg_fail(AMWG_EINVAL, "%s: the last sample call was amwg_sample_summarize: its draws were folded into per-chain accumulators and not kept (moments and diagnostics answer from those; this call needs the draws of amwg_sample*)", call);
   return AMWG_OK;
 }
+int amwg_need_stored_draws(const amwg_sampler *s, const char *call) {
+  TRYB(amwg_refuse_summarised(s, call));
+  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "%s: no sample() call yet", call);
+  return AMWG_OK;
+}
 
 // The rows of a sample call are final launch by launch (launch_steps records an event after each): the rows of launch j leave the
 // device on copy_stream while launches j + 1, ... run on the sampler's stream -- a pageable destination (a JavaScript typed array, a numpy

@@ -436,16 +436,7 @@ static int pointwise_check(const char *call, bool loo, int32_t device, const dou
     for (int d = 0; d < D; ++d) sets[(size_t)d].off_lfact = off[(size_t)d];
     wm.x = dx.as<double>(); wm.y = dy.as<double>(); wm.lfact = dlf.as<double>();
   }
-  if (loo) {
-    const size_t before = amwg_loo_set_budget((size_t)scratch_bytes);
-    const int rc = amwg_loo_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, nullptr);
-    amwg_loo_set_budget(before);
-    return rc;
-  }
-  const size_t before = amwg_waic_set_budget((size_t)scratch_bytes);
-  const int rc = amwg_waic_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, loglik, nullptr);
-  amwg_waic_set_budget(before);
-  return rc;
+  return (loo ? amwg_loo_launch : amwg_waic_launch)(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
 }
 extern "C" {
 
@@ -490,15 +481,9 @@ static int user_pointwise_check(const char *call, bool loo, int32_t device, cons
   HIP_TRY(dd.alloc(bytes));
   HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
   std::vector<WaicDataset> sets;
-  UserPointwise u;
-  TRYB(amwg_pointwise_describe_user(s, sets, u));
   PointwiseLaunch K;
-  amwg_pointwise_user_kernels(K, u);
-  const size_t before = loo ? amwg_loo_set_budget((size_t)scratch_bytes) : amwg_waic_set_budget((size_t)scratch_bytes);
-  const int rc = loo ? amwg_loo_run(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, nullptr)
-                     : amwg_waic_run(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, nullptr);
-  if (loo) amwg_loo_set_budget(before); else amwg_waic_set_budget(before);
-  return rc;
+  TRYB(amwg_pointwise_describe_user(s, sets, K));
+  return (loo ? amwg_loo_run : amwg_waic_run)(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
 }
 
 int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR, int64_t C,

@@ -40,8 +40,7 @@ __global__ void pick_quantiles_kernel(const double *sorted, int64_t n, const dou
 extern "C" int amwg_last_sample_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: bad argument");
   TRYB(amwg_refuse_pooled(s, "amwg_last_sample_quantiles"));
-  TRYB(amwg_refuse_summarised(s, "amwg_last_sample_quantiles"));
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: no sample() call yet");
+  TRYB(amwg_need_stored_draws(s, "amwg_last_sample_quantiles"));
   const int PR = s->P + s->D;
   const int64_t n = s->last_rows * s->C;
   if (n > 2147483647) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_quantiles: more than 2^31 values per component");      // (the sort counts in int)
@@ -239,8 +238,7 @@ int amwg_dataset_quantiles_launch(const char *call, const double *draws, int64_t
 
 extern "C" int amwg_last_sample_dataset_quantiles(amwg_sampler *s, const double *probs, int32_t n_probs, double *out) {
   if (!s || !probs || !out || n_probs < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_quantiles: bad argument");
-  TRYB(amwg_refuse_summarised(s, "amwg_last_sample_dataset_quantiles"));
-  if (!s->last_draws || s->last_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_last_sample_dataset_quantiles: no sample() call yet");
+  TRYB(amwg_need_stored_draws(s, "amwg_last_sample_dataset_quantiles"));
   HIP_TRY(hipSetDevice(s->device));
   return amwg_dataset_quantiles_launch("amwg_last_sample_dataset_quantiles", s->last_draws, s->last_rows, s->P + s->D, s->C, s->n_datasets, probs, n_probs, out, s->stream);
 }

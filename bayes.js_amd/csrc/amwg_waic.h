@@ -16,21 +16,24 @@
 //                  gives NaN for both.
 //   3 totals       on the host, in index order (amwg_waic_totals).
 // splits = waic_splits(S, n), a function of those two alone: a dataset's bytes do not depend on its neighbours, on D, or on the scratch budget.
-// SCRATCH: splits * n partials of 32 bytes per dataset, allocated per call and freed before it returns; the datasets go in batches under kWaicScratchBytes, and a
-// dataset whose partials exceed the budget runs alone.
+// SCRATCH: splits * n partials of 32 bytes per dataset, allocated per call and freed before it returns; the datasets go in batches under the call's scratch budget
+// (kPointwiseScratchBytes by default), and a dataset whose partials exceed the budget runs alone.
+//
+// WHAT WAIC AND PSIS-LOO SHARE ON THE HOST (amwg_pointwise_host.hip) is declared here too: how a call launches the kernels that evaluate the model (PointwiseLaunch),
+// the batches under the budget, the device outputs of a call, and the one body of the two amwg_last_sample_dataset_* entries.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
-#include <functional>
 #include <vector>
 
+#include "amwg_host.h"                 // DevBuf
 #include "amwg_pointwise_types.h"      // WaicDataset, UserTermsArg
 
 struct amwg_sampler;
 
-constexpr size_t kWaicScratchBytes = (size_t)256 << 20;      // the default scratch budget of a call: 256 MiB, as amwg_hpd.h
+constexpr size_t kPointwiseScratchBytes = (size_t)256 << 20;      // the default scratch budget of a WAIC or LOO call: 256 MiB, as amwg_hpd.h
 
 // the family and its arrays on the device, in the sampler's own layout (DataRef, amwg_types.h)
 struct WaicModel {
@@ -41,43 +44,77 @@ struct WaicModel {
   const uint8_t *invalid;                          // BETA_BERN: 1 where x_i is neither 0 nor 1, laid out like xb; nullptr: no such observation anywhere
 };
 
-// HOW A CALL LAUNCHES THE KERNELS THAT EVALUATE THE MODEL (amwg_pointwise.h): the instantiations for a built-in family (amwg_waic_family_kernels,
-// amwg_loo_family_kernels), or the entries of a closure's code object (amwg_pointwise_user_kernels).  Everything else of a call is the same code for both.
+// HOW A CALL LAUNCHES THE KERNELS THAT EVALUATE THE MODEL (amwg_pointwise.h), as plain data: the instantiations for a built-in family (amwg_pointwise_family), or the
+// entries of a closure's code object (amwg_pointwise_describe_user).  The two take the same argument lists, the model in the same slot; everything else of a call is
+// the same code for both.
+enum PointwiseKernel { kPwWaicPartial, kPwWaicLoglik, kPwLooHist, kPwLooCompact, kPwKernels };      // (the order of amwg_sampler::pw_fn)
 struct PointwiseLaunch {
-  bool bern = false;                     // the family of two observations per dataset (its pairs are picked by x_i afterwards)
-  const WaicModel *family = nullptr;     // the built-in family's model (nullptr: a closure)
-  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, void *)> waic_partial;
-  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, const WaicDataset *, double *, int64_t)> waic_loglik;
-  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, void *, uint32_t *, int)> loo_hist;
-  std::function<hipError_t(dim3, hipStream_t, const double *, int64_t, int, int64_t, int64_t, int, const WaicDataset *, const int64_t *, const int64_t *, void *, double *, uint32_t, double *)> loo_compact;
-};
-// the pointwise code object of a translated closure, loaded on the sampler's device (amwg_rtc.hip load_pointwise), and its model argument
-struct UserPointwise {
-  hipFunction_t waic_partial = nullptr, waic_loglik = nullptr, loo_hist = nullptr, loo_compact = nullptr;
-  amwg::UserTermsArg arg{};
-  int32_t n_obs = 0, state_n = 0;      // kTermN, kStateN of the terms text
+  bool bern = false;                   // the family of two observations per dataset (its pairs are picked by x_i afterwards)
+  bool builtin = false;                // a built-in family: `family` is the model argument and fn[] are addresses of the kernels' instantiations (hipLaunchKernel);
+  WaicModel family{};                  // a closure: `user`, and fn[] are the hipFunction_t of its code object (hipModuleLaunchKernel)
+  amwg::UserTermsArg user{};
+  const void *fn[kPwKernels] = {};
+  void *model_arg() const { return builtin ? (void *)&family : (void *)&user; }      // the model's slot of an args[] list
 };
 
+// the batches of a call: consecutive datasets whose scratch fits the budget together (a dataset beyond it runs alone)
+struct PointwiseBatch { int d0, d1; int64_t tiles, splits, n_most, obs; };      // datasets [d0, d1): the largest tiles, splits and n among them; their observations
+struct PointwisePlan {
+  std::vector<int64_t> off;      // off[d]: observations before d in its batch; off[D + d]: partials (splits * n per dataset) before it
+  std::vector<PointwiseBatch> batches;
+  int64_t most_obs = 0, most_parts = 0;      // of the largest batch
+};
+// the device side of a call's outputs: sets [D], pw [D][n_max][2] and, when asked for, extra [D][n_max * extra_per_obs], both filled with NaN
+struct PointwiseOut {
+  int64_t n_max = 0;      // the largest n_obs
+  size_t pw_count = 0, extra_count = 0;
+  DevBuf sets, pw, extra;
+};
+
+// the built-in families, in the order of AMWG_MODEL_* from AMWG_MODEL_NORMAL on: the one list the two units expand into their instantiations
+template <int... MODEL> struct PointwiseModels {};
+typedef PointwiseModels<AMWG_MODEL_NORMAL, AMWG_MODEL_BETA_BERN, AMWG_MODEL_HIER_NORMAL, AMWG_MODEL_POIS_GLM> BuiltinModels;
+static_assert(AMWG_MODEL_BETA_BERN == AMWG_MODEL_NORMAL + 1 && AMWG_MODEL_HIER_NORMAL == AMWG_MODEL_NORMAL + 2 && AMWG_MODEL_POIS_GLM == AMWG_MODEL_NORMAL + 3, "BuiltinModels is indexed by model - AMWG_MODEL_NORMAL");
+
 #pragma GCC visibility push(hidden)
-void amwg_waic_family_kernels(PointwiseLaunch &K, const WaicModel &model);      // (keeps &model: the launch must not outlive it)
-void amwg_loo_family_kernels(PointwiseLaunch &K, const WaicModel &model);
-void amwg_pointwise_user_kernels(PointwiseLaunch &K, const UserPointwise &u);
-// amwg_waic_launch behind its family checks: the same call over any PointwiseLaunch.  A closure: sets[d].n_obs = kTermN for every d.
+// the address of a built-in family's instantiation, model one of BuiltinModels (amwg_waic.hip: k = 0 the partial kernel, 1 loglik; amwg_loo.hip: k = 0 hist, 1 compact)
+const void *amwg_waic_family_fn(int model, int k);
+const void *amwg_loo_family_fn(int model, int k);
+// K of a built-in family.  AMWG_EINVAL "<call>: ..." for an unknown model, draws of fewer components than the family reads, the hierarchical family on D != 1.
+int amwg_pointwise_family(const char *call, const WaicModel &model, int PR, int D, PointwiseLaunch &K);
+// entry k of K over `grid` workgroups of kThreads; args: the kernel's argument list, K.model_arg() in the model's slot
+hipError_t amwg_pointwise_go(const PointwiseLaunch &K, int k, dim3 grid, hipStream_t stream, void **args);
+hipError_t amwg_pointwise_fill_nan(double *out, int64_t count, hipStream_t stream);
+// the Bernoulli family: out[d][i][width] = two[d][x_i == 1 ? 0 : 1][width] for i < n_d; an invalid x_i: NaN
+hipError_t amwg_pointwise_bern_expand(const PointwiseLaunch &K, const WaicDataset *d_sets, int D, const double *two, double *out, int64_t n_max, int64_t width, hipStream_t stream);
+// obs_bytes of scratch per observation and part_bytes per partial; scratch_bytes: the budget (0: kPointwiseScratchBytes).  A new batch starts when the batch is not
+// empty and the next dataset would exceed the budget.
+PointwisePlan amwg_pointwise_plan(const PointwiseLaunch &K, const WaicDataset *sets, int D, int64_t S, size_t obs_bytes, size_t part_bytes, size_t scratch_bytes);
+// AMWG_EINVAL for an n_obs < 0; else n_max, sets uploaded, the outputs allocated and filled (extra_per_obs = 0: no extra).  amwg_pointwise_fetch: after the stream
+// has drained, pw [D][n_max][2] and extra to the host
+int amwg_pointwise_begin(const char *call, const WaicDataset *sets, int D, int64_t extra_per_obs, hipStream_t stream, PointwiseOut &o);
+int amwg_pointwise_fetch(const PointwiseOut &o, double *pw, double *extra);
+// The run of a statistic over any PointwiseLaunch: amwg_waic_run, amwg_loo_run.  draws [rows][PR][C] on the current device, D datasets of C / D columns each; sets [D]
+// on the host (a closure: n_obs = kTermN for every d).  The caller has checked the pointers and the shape (amwg_waic_shape, amwg_loo_shape).  scratch_bytes: the budget
+// of this call (0: the default; the product passes 0).  Returns after `stream` has drained.
+typedef int (*PointwiseRunFn)(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
+                              int32_t *high, double *pointwise, double *extra, size_t scratch_bytes, hipStream_t stream);
+typedef int (*PointwiseShapeFn)(const char *call, int64_t rows, int PR, int64_t C, int D);
+// the body of amwg_last_sample_dataset_waic and amwg_last_sample_dataset_loo: the refusals, the sampler's datasets and model described, `run`
+int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int32_t *high, double *pointwise, PointwiseShapeFn shape, PointwiseRunFn run);
+// Host outputs: summary [D][4] (elpd_waic, se, p_waic, lppd), high [D] or nullptr, pointwise nullptr or [D][n_max][2] (NaN beyond n_d; n_max the largest n_obs), loglik
+// nullptr or [D][S][n_max] (the terms themselves; the test library only).
 int amwg_waic_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
-                  int32_t *high, double *pointwise, double *loglik, hipStream_t stream);
+                  int32_t *high, double *pointwise, double *loglik, size_t scratch_bytes, hipStream_t stream);
 // AMWG_EINVAL "<call>: ..." unless the shape can be served: amwg_dataset_quantiles_shape's limits and at least 2 draws per dataset.  Host only.
 int amwg_waic_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
-// draws [rows][PR][C] on the current device, D datasets of C / D columns each; sets [D] on the host.  Host outputs: summary [D][4] (elpd_waic, se, p_waic, lppd),
-// high [D] or nullptr, pointwise nullptr or [D][n_max][2] (NaN beyond n_d; n_max the largest n_obs), loglik nullptr or [D][S][n_max] (the terms themselves; the test
-// library only).  Returns after `stream` has drained.
+// amwg_waic_run for a built-in family, behind the checks of the pointers, the shape and the family
 int amwg_waic_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &model, const WaicDataset *sets, double *summary,
-                     int32_t *high, double *pointwise, double *loglik, hipStream_t stream);
+                     int32_t *high, double *pointwise, double *loglik, size_t scratch_bytes, hipStream_t stream);
 // sets [D] and model of a sampler's own data, as the launchers take them; the sampler's device is current (one copy from it when D > 1)
 int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicModel &model);
 // the same for a closure sampler whose pointwise text is set: compiles and loads the code object on first use; every dataset has kTermN observations
-int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, UserPointwise &u);
+int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, PointwiseLaunch &K);
 // the finish of include/amwg.h over one dataset's pairs pw[n][2]: summary[4], *high (may be nullptr)
 void amwg_waic_totals(const double *pw, int64_t n, double *summary, int32_t *high);
-// the scratch budget of later calls in bytes (0: kWaicScratchBytes); returns the budget in force before.  For the test library: the product never calls it.
-size_t amwg_waic_set_budget(size_t bytes);
 #pragma GCC visibility pop

@@ -91,6 +91,18 @@ def test_shapes_of_the_other_families(model, rows, cpd):
         assert np.isnan(got["pointwise"][0][0]).all() and np.isnan(got["summary"][0]).all() and not np.isnan(got["summary"][1:]).any()
 
 
+def test_the_bernoulli_expand_at_the_tail_width_with_an_invalid_x_in_the_second_dataset():
+    """tails asked for, two datasets, one x that is neither 0 nor 1 beyond dataset 0: the expand kernel at width M + 1 reads xb and the invalid bytes at the dataset's offset"""
+    rng = np.random.default_rng(SEED + 40)
+    specs = [lr.spec_of("beta_bern", n, rng) for n in (3, 70)]
+    specs[1]["data"]["x"][5] = 0.5
+    got = held(lr.draws_for("beta_bern", 1, 2 * 65, rng), specs)      # S = 65, M = 13: tails and triples against the reference, under this file's bounds
+    nan = np.isnan(got["pointwise"]).all(axis=2)
+    assert nan[1][5] and nan[0][3:].all() and nan.sum() == 1 + 67      # NaN at the invalid observation and beyond dataset 0's three, nowhere else
+    assert np.isnan(got["tails"][1][5]).all() and not np.isnan(got["tails"][1][:5]).any() and not np.isnan(got["tails"][1][6:]).any() and not np.isnan(got["tails"][0][:3]).any()
+    assert np.isnan(got["summary"][1]).all() and not np.isnan(got["summary"][0]).any()
+
+
 @pytest.mark.parametrize("name", lr.PATTERNS)
 def test_draw_patterns(name):
     draws, specs = lr.pattern_case(name)
