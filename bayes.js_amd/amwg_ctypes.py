@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -76,6 +76,8 @@ def lib():
         L.amwg_last_sample_dataset_hpd.argtypes = [vp, pd, i32, pd]
         L.amwg_last_sample_dataset_waic.argtypes = [vp, pd, pi32, pd]
         L.amwg_last_sample_dataset_loo.argtypes = [vp, pd, pi32, pd]
+        L.amwg_set_waic.argtypes = [vp, i32]
+        L.amwg_waic_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_burn.argtypes = [vp, i64]
         L.amwg_burn_async.argtypes = [vp, i64]
         L.amwg_sample_async.argtypes = [vp, i64, i64]
@@ -187,6 +189,7 @@ def selftest_lib():
         L.amwg_hpd_check.argtypes = [i32, pd, i64, i32, i64, i32, pd, i32, pd]
         L.amwg_hpd_limits.argtypes = [i32, i64, C.POINTER(i64), C.POINTER(i64)]
         L.amwg_waic_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
+        L.amwg_waic_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, C.POINTER(C.c_size_t)]
         L.amwg_loo_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_user_waic_check.argtypes = [i32, C.POINTER(UserModel), i32, i32, C.c_char_p, pd, i64, i32, i64, i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_user_loo_check.argtypes = L.amwg_user_waic_check.argtypes
@@ -379,6 +382,16 @@ class Sampler:
         sizes = (C.c_size_t * max(n, 1))(*[o.nbytes for o in outs])
         _check(lib().amwg_fetch_draws_slices(self.h, n, base, ln, ptrs, sizes))
         return outs
+
+    def set_waic(self, on=True):
+        """Arms (or disarms) the WAIC fold for every later summarize() (amwg_set_waic): dataset_waic() / waic() then answer after the call, without stored draws."""
+        _check(lib().amwg_set_waic(self.h, 1 if on else 0))
+
+    def waic_info(self):
+        """{"armed": bool, "bytes": the device bytes of the records of the last armed summarize()} (amwg_waic_info)"""
+        a, n = C.c_int32(), C.c_size_t()
+        _check(lib().amwg_waic_info(self.h, C.byref(a), C.byref(n)))
+        return {"armed": bool(a.value), "bytes": n.value}
 
     def summarize(self, n, thin=1, window_rows=0, covariance=None):
         """The steps of sample_async(n, thin) + sync(), the kept draws folded window by window into per-chain accumulators instead of stored
@@ -897,6 +910,29 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
         out["pointwise"] = pw
     if loglik:
         out["loglik"] = ll
+    return out
+
+
+def waic_fold_check(draws, specs, window_rows, pointwise=True, device=0):
+    """libamwg_selftest.so: the WAIC fold of an armed summarize() on any array draws [rows][PR][C] cut into windows of window_rows rows, and the data of `specs` (as
+    waic_check takes them) -> dict(summary [D][4], high [D], state_bytes[, pointwise [D][n_max][2]]) (amwg_waic_fold_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: waic_fold_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    D = len(specs)
+    mds, keep = _model_descs(specs)
+    n_max = max([int(q["n_obs"]) for q in specs] + [1])
+    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    pw = np.empty((max(1, D), n_max, 2)) if pointwise else None
+    state = C.c_size_t()
+    L = selftest_lib()
+    if L.amwg_waic_fold_check(device, _dp(dr), rows, PR, Cn, D, mds, int(window_rows), _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
+                              _dp(pw) if pointwise else None, C.byref(state)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    out = {"summary": summary, "high": high, "state_bytes": state.value}
+    if pointwise:
+        out["pointwise"] = pw
     return out
 
 

@@ -16,6 +16,7 @@
 #include "amwg_dataset.h"
 #include "amwg_kernel.h"
 #include "amwg_models.h"
+#include "amwg_waic.h"
 
 using namespace amwg;
 
@@ -738,6 +739,7 @@ int amwg_destroy(amwg_sampler *s) {
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   for (void *p : s->dev_allocs) (void)hipFree(p);
   amwg_summary_forget(s);      // (amwg_fold.h: the accumulators of a summarising call were among dev_allocs)
+  amwg_waic_forget(s);         // (amwg_waic.h: the records of an armed WAIC fold)
   amwg_histogram_forget(s);    // (amwg_histogram.h: the edges and counts of an armed histogram)
   amwg_covariance_forget(s);   // (amwg_covariance.h: the co-moments and values of an armed covariance)
   amwg_autocov_forget(s);      // (amwg_autocov.h: the lag sums, rows and values of an armed autocovariance)

@@ -51,12 +51,14 @@ struct FoldSummary {
 struct HistArm;      // (amwg_histogram.h)
 struct CovArm;       // (amwg_covariance.h)
 struct AutocovArm;   // (amwg_autocov.h)
+struct WaicFold;     // (amwg_waic.h)
 struct FoldWindow {
   int64_t window_rows = 0, total_rows = 0;
   double *acc = nullptr;
   int64_t windows = 0;      // out: folds enqueued
   const HistArm *hist = nullptr;      // the histogram armed for the call (amwg_set_histogram): after each fold, the window's rows are counted into it too
   const CovArm *cov = nullptr;        // the covariance armed for the call (amwg_set_covariance): BEFORE each fold, the window's co-moments are added from the means it starts at
+  const WaicFold *waic = nullptr;     // the WAIC fold armed for the call (amwg_set_waic): after the fold of a window, its pointwise terms are folded into the records
   const AutocovArm *acf = nullptr;    // the autocovariance armed for the call (amwg_set_autocovariance): after the fold and the histogram, the window's lag sums, then its carry
 };
 // true when the last sample call of `s` was a summarising one (its draws were folded, not kept): last_rows > 0 without last_draws

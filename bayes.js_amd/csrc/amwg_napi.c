@@ -836,6 +836,37 @@ static napi_value DatasetWaic(napi_env env, napi_callback_info info) { return da
  * khat_i > 0.7), pointwise [datasets][n_max][3] (elpd_loo_i, lppd_i, khat_i) */
 static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo, 3); }
 
+/* setWaic(handle, bool on): amwg_set_waic -- arms (false: disarms) the WAIC fold for later summarising calls */
+static napi_value SetWaic(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  if (!get_args(env, info, 2, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  bool on = false;
+  NAPI_OK(napi_get_value_bool(env, a[1], &on));
+  int rc = amwg_set_waic(s, on ? 1 : 0);
+  return rc == AMWG_OK ? NULL : throw_amwg(env, rc);
+}
+
+/* waicInfo(handle) -> {armed, bytes}: whether the fold is armed and the device bytes of the records of the last armed summarising call (amwg_waic_info) */
+static napi_value WaicInfo(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  if (!get_args(env, info, 1, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  int32_t armed = 0;
+  size_t bytes = 0;
+  int rc = amwg_waic_info(s, &armed, &bytes);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_get_boolean(env, armed != 0, &t);
+  napi_set_named_property(env, o, "armed", t);
+  napi_create_int64(env, (int64_t)bytes, &t);
+  napi_set_named_property(env, o, "bytes", t);
+  return o;
+}
+
 /* setHistogram(handle, Float64Array edges [recorded][bins + 1] | null, bins): amwg_set_histogram -- arms (null, 0: disarms) a histogram for later summarising calls */
 static napi_value SetHistogram(napi_env env, napi_callback_info info) {
   napi_value a[3];
@@ -1251,7 +1282,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
       {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
-      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
+      {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setWaic", SetWaic}, {"waicInfo", WaicInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};
   for (size_t i = 0; i < sizeof fns / sizeof fns[0]; i++) {

@@ -1,5 +1,5 @@
 // amwg_pointwise.h -- the kernels of WAIC (amwg_waic.hip) and PSIS-LOO (amwg_loo.hip) that evaluate the model, as ONE text over the family class F and its model
-// argument MA: WAIC's partial kernel and loglik kernel, LOO's histogram kernel and compaction kernel.  amwg_waic.hip and amwg_loo.hip instantiate it for the four
+// argument MA: WAIC's partial kernel, fold kernel and loglik kernel, LOO's histogram kernel and compaction kernel.  amwg_waic.hip and amwg_loo.hip instantiate it for the four
 // built-in families (Family<MODEL>, WaicModel: amwg_terms.h); hiprtc instantiates the very same text for the pointwise terms of a translated closure (UserTerms:
 // translate.js pointwisePlan; UserTermsArg) as the extern "C" entries at the end of this file, in one code object (amwg_rtc.hip compile_pointwise).  What does not
 // depend on the model serves both: merge, pick, fit and totals in the two .hip files, fill, the Bernoulli expand and the host path around them in amwg_pointwise_host.hip.
@@ -154,6 +154,104 @@ __device__ __forceinline__ void waic_partial_body(const double *__restrict__ dra
     merge_parts(a, cnt, wave_part[w - 1][lane], nw);
   }
   parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + i] = a;
+}
+
+// ---- WAIC folded window by window (amwg_sample_summarize armed by amwg_set_waic; amwg_waic_fold.hip).  The draws are never all there: a window of `nrows` rows
+// stands in window[0 .. nrows)[PR][C], and a persistent record per (dataset, split, observation) carries (m, sum, mean, M2) from window to window.
+// THE SPLIT RULE.  fold_splits(Sw, n) runs, Sw = window_rows * cpd the draws of a FULL window and n the dataset's observations: fixed for the whole call.  Every
+// window -- the shorter last one too -- is cut by split_begin over its OWN draw count, so split k's record holds the k-th run of every window.  The target per
+// dataset is max(kFoldMinBlocks, Sw / kFoldDrawsPerBlock) workgroups: splits * n records of 32 bytes are then at most 16 Sw bytes, the dataset's share of a window
+// of two recorded values, beyond the floor of kFoldMinBlocks (256 datasets x 256 chains x 1000 observations under the default window: 8 splits, 62.5 MiB).
+// THE COUNT of a record is a function of the indices: fold_count.
+constexpr int64_t kFoldMinBlocks = 128;            // workgroups per dataset the split aims at, at least
+constexpr int64_t kFoldDrawsPerBlock = 128;        // ... and one per this many draws of a full window and tile
+constexpr int64_t kFoldMaxSplits = 65535;          // (a grid dimension)
+
+__host__ __device__ inline int64_t fold_splits(int64_t Sw, int64_t n) {
+  const int64_t tiles = (n + kTile - 1) / kTile;
+  const int64_t target = Sw / kFoldDrawsPerBlock > kFoldMinBlocks ? Sw / kFoldDrawsPerBlock : kFoldMinBlocks;
+  int64_t want = tiles > 0 ? target / tiles : 1;
+  want = want < 1 ? 1 : want;
+  int64_t by_len = Sw / kMinRun;
+  by_len = by_len < 1 ? 1 : by_len;
+  const int64_t k = want < by_len ? want : by_len;
+  return k < kFoldMaxSplits ? k : kFoldMaxSplits;
+}
+__host__ __device__ inline int64_t split_len(int64_t S, int64_t splits, int64_t k) { return split_begin(S, splits, k + 1) - split_begin(S, splits, k); }
+// the draws split k holds after `windows` full windows of Sw draws and a last one of Sl (0: none)
+__host__ __device__ inline double fold_count(int64_t Sw, int64_t windows, int64_t Sl, int64_t splits, int64_t k) {
+  return (double)(windows * split_len(Sw, splits, k) + (Sl > 0 ? split_len(Sl, splits, k) : 0));
+}
+
+// state[state_off[d] + split * n + i].  g0: the rows folded before this window, all of them in full windows of window_rows rows.  A workgroup continues its split's
+// records: wavefront 0 takes them up where the window before left them, wavefronts 1 .. 3 start empty, and the four are merged in the order 0, 1, 2, 3 before the
+// records are written back.  A run that is empty in this window leaves its records as they are.  The recurrences are waic_partial_body's.
+template <class F, class MA>
+__device__ __forceinline__ void waic_fold_body(const double *__restrict__ window, int64_t nrows, int64_t g0, int64_t window_rows, int PR, int64_t C, int64_t cpd, const MA &M,
+                                               const WaicDataset *__restrict__ sets, const int64_t *__restrict__ state_off, Part *__restrict__ state) {
+  constexpr int kRun = stage_len<F>();
+  static_assert(kRun >= kWaves, "the Draw of this model is too large: fewer than kWaves of them fit in the 48 KiB of LDS a workgroup stages draws in");
+  __shared__ typename F::Draw stage[kRun];
+  __shared__ Part wave_part[kWaves - 1][kTile];
+  const int d = (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WaicDataset ds = sets[d];
+  const int64_t n = F::n_eff(ds), S = nrows * cpd, Sw = window_rows * cpd, splits = fold_splits(Sw, n), k = blockIdx.y;
+  if ((int64_t)blockIdx.x * kTile >= n || k >= splits) return;      // (uniform over the workgroup)
+  const int64_t s_begin = split_begin(S, splits, k), s_end = split_begin(S, splits, k + 1);
+  if (s_begin >= s_end) return;                                     // (an empty run: a short last window)
+  const auto &Md = dataset_model(M, d);
+  const int64_t i = (int64_t)blockIdx.x * kTile + lane;
+  const bool active = i < n;
+  const typename F::Obs o = F::load_obs(Md, ds, active ? i : n - 1);
+  Part *rec = state + state_off[d] + k * n + (active ? i : n - 1);
+  Part a{-kInf, 0.0, 0.0, 0.0};
+  double cnt = 0.0;
+  const double before = fold_count(Sw, g0 / window_rows, 0, splits, k);
+  if (wave == 0 && before > 0.0) { a = *rec; cnt = before; }
+  for (int64_t s0 = s_begin; s0 < s_end; s0 += kRun) {
+    const int L = (int)(s_end - s0 < kRun ? s_end - s0 : kRun);
+    __syncthreads();
+    if (tid < L) stage[tid] = draw_at<F>(window, PR, C, cpd, d, s0 + tid, Md, ds);
+    __syncthreads();
+    if (wave >= L) continue;      // (uniform over the wavefront; the barriers above are reached by all)
+    const double K = cnt == 0.0 ? F::term(Md, o, stage[wave], active ? i : n - 1, window, C) : a.mean;
+    double s1 = 0.0, s2 = 0.0;
+    int nb = 0;
+    for (int j = wave; j < L; j += kWaves) {
+      const double l = F::term(Md, o, stage[j], active ? i : n - 1, window, C);
+      const double dm = l - a.m;
+      const double e = waic_exp(-__builtin_fabs(dm));
+      const bool up = dm > 0.0;
+      a.sum = up ? __builtin_fma(a.sum, e, 1.0) : a.sum + e;
+      a.m = up ? l : a.m;
+      const double dk = l - K;
+      s1 += dk;
+      s2 = __builtin_fma(dk, dk, s2);
+      ++nb;
+    }
+    const double nbd = (double)nb, q = s1 / nbd;
+    double M2b = s2 - s1 * q;
+    M2b = M2b < 0.0 ? 0.0 : M2b;      // (a NaN stays a NaN)
+    const double mean_b = K + q;
+    if (cnt == 0.0) { a.mean = mean_b; a.M2 = M2b; cnt = nbd; }
+    else {
+      const double nt = cnt + nbd, delta = mean_b - a.mean;
+      a.mean = a.mean + delta * (nbd / nt);
+      a.M2 = a.M2 + M2b + delta * delta * (cnt * nbd / nt);
+      cnt = nt;
+    }
+  }
+  __syncthreads();
+  if (wave > 0) wave_part[wave - 1][lane] = a;
+  __syncthreads();
+  if (wave != 0 || !active) return;
+  const int64_t len = s_end - s_begin, full = len / kRun, rest = len % kRun;
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) {
+    const double nw = (double)(full * (kRun / kWaves) + (rest > w ? (rest - w + kWaves - 1) / kWaves : 0));
+    merge_parts(a, cnt, wave_part[w - 1][lane], nw);
+  }
+  *rec = a;
 }
 
 // the terms themselves, out[(d * S + s) * n_max + i]: the test library's view of what the partial kernel accumulates (the same device functions).  BERN: the family
@@ -330,5 +428,9 @@ extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_loo_compact
                                                                                  const WaicDataset *sets, const int64_t *obs_off, const int64_t *part_off, amwg::LooState *state,
                                                                                  double *tail, uint32_t cap, double *parts) {
   amwg::loo_compact_body<amwg::UserFamily>(draws, rows, PR, C, cpd, d0, M, sets, obs_off, part_off, state, tail, cap, parts);
+}
+extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_waic_fold(const double *window, int64_t nrows, int64_t g0, int64_t window_rows, int PR, int64_t C, int64_t cpd,
+                                                                               const amwg::UserTermsArg M, const WaicDataset *sets, const int64_t *state_off, amwg::Part *state) {
+  amwg::waic_fold_body<amwg::UserFamily>(window, nrows, g0, window_rows, PR, C, cpd, M, sets, state_off, state);
 }
 #endif

@@ -49,6 +49,7 @@ int amwg_pointwise_family(const char *call, const WaicModel &model, int PR, int 
   K.builtin = true;
   K.family = model;
   for (int k = 0; k < 2; ++k) { K.fn[kPwWaicPartial + k] = amwg_waic_family_fn(model.model, k); K.fn[kPwLooHist + k] = amwg_loo_family_fn(model.model, k); }
+  K.fn[kPwWaicFold] = amwg_waic_family_fn(model.model, 2);
   return AMWG_OK;
 }
 
@@ -131,12 +132,15 @@ int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicMode
   return AMWG_OK;
 }
 
-// ... and of a closure whose pointwise text is set (amwg_set_pointwise): the code object compiled and loaded on first use (amwg_rtc.hip load_pointwise), its four
+// ... and of a closure whose pointwise text is set (amwg_set_pointwise): the code object compiled and loaded on first use (amwg_rtc.hip load_pointwise), its
 // entries and its model argument; every dataset with kTermN observations
 int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, PointwiseLaunch &K) {
   TRYB(load_pointwise(s, s->user_arch.c_str()));
   K = PointwiseLaunch{};
-  for (int k = 0; k < kPwKernels; ++k) K.fn[k] = s->pw_fn[k];
+  for (int k = 0; k < kPwWaicFold; ++k) K.fn[k] = s->pw_fn[k];
+  hipFunction_t fold = nullptr;      // (the fifth entry is looked up where it is asked for: the handle's layout stays as it is)
+  HIP_TRY(hipModuleGetFunction(&fold, s->pw_module, "amwg_pw_waic_fold"));
+  K.fn[kPwWaicFold] = fold;
   K.user.d = s->d;
   K.user.table = s->n_datasets > 1 ? s->d_user_ds_table : nullptr;
   K.user.row_stride = s->user_ds_row_stride;

@@ -18,6 +18,7 @@
 #include "amwg_kernel.h"      // (StepArgs, and the kErr* bits the step kernels report)
 #include "amwg_dataset.h"     // (DatasetArgs: the second argument of a dataset sampler's kernel)
 #include "amwg_user_dataset.h"      // (UserDatasetArgs: the same for a translated closure)
+#include "amwg_waic.h"              // (WaicFold: the WAIC fold armed for a summarising call)
 
 using namespace amwg;
 
@@ -171,6 +172,8 @@ int launch_steps(amwg_sampler *s, int64_t n, int64_t thin, double *d_draws, bool
       if (win->cov)      // (reads acc[4] as the fold of the window before left it: the running means its rows start from)
         TRYB(amwg_comoment_window(d_draws, folded, row, s->P + s->D, s->C, win->cov->d_values, win->cov->n_values, win->acc, win->cov->d_co, s->stream));
       TRYB(amwg_fold_window(d_draws, folded, row, win->total_rows / 2, s->P + s->D, s->C, win->acc, s->stream));
+      if (win->waic)      // (the pointwise terms of the same rows into the records of amwg_set_waic, behind the fold on the same stream)
+        TRYB(amwg_waic_fold_window(*win->waic, d_draws, folded, row, s->stream));
       if (win->hist)      // (the same rows once more, on the same stream: the counts add up over the windows)
         TRYB(amwg_histogram_launch("amwg_sample_summarize", d_draws, row, s->P + s->D, s->C, s->n_datasets, win->hist->d_edges, win->hist->bins, win->hist->uniform, win->hist->d_counts, s->stream));
       if (win->acf)       // (the lag sums read the ring as the windows before left it; the carry kernel behind them, on the same stream, moves it on)
@@ -351,6 +354,8 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   const size_t need = (size_t)W * row_bytes, acc_bytes = (size_t)kFoldStats * row_bytes;
   HIP_TRY(hipSetDevice(s->device));
   AutocovArm *acf = nullptr;
+  WaicFold *waic = nullptr;
+  TRYB(amwg_waic_begin(s, W, rows, &waic));      // (amwg_set_waic: refuses a call of fewer than 2 kept draws per dataset before anything is touched; its records start afresh)
   TRYB(amwg_autocov_begin(s, rows, &acf));      // (amwg_set_autocovariance: refuses a call of too few kept rows before anything is touched; its state starts afresh too)
   if (need > s->d_draws_cap) {
     if (s->d_draws) { (void)hipFree(s->d_draws); s->d_draws = nullptr; s->d_draws_cap = 0; }
@@ -375,6 +380,7 @@ int amwg_sample_summarize_async(amwg_sampler *s, int64_t n, int64_t thin, int64_
   TRYB(amwg_covariance_begin(s, &cov));      // (amwg_set_covariance: its co-moments start afresh too)
   win.cov = cov;
   win.acf = acf;
+  win.waic = waic;
   TRYB(launch_steps(s, n, thin, s->d_draws, false, &win));
   f.rows = rows; f.window_rows = W; f.windows = win.windows; f.window_bytes = need;
   s->last_rows = rows;      // (rows > 0 without last_draws: the mark of a summary -- amwg_summarised)

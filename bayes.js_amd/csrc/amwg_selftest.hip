@@ -368,7 +368,7 @@ static int waic_pack(int D, Len len, Fill fill, std::vector<int64_t> &off, DevBu
 // amwg_waic_check and amwg_loo_check: the arguments checked, the draws and the family's data on the device as the sampler lays them, then the launcher of either
 // (extra: WAIC's loglik, or LOO's tails)
 static int pointwise_check(const char *call, bool loo, int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models,
-                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra) {
+                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra, int64_t window_rows = 0, size_t *state_bytes = nullptr) {
   double *loglik = loo ? nullptr : extra;
   if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
   if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
@@ -436,6 +436,16 @@ static int pointwise_check(const char *call, bool loo, int32_t device, const dou
     for (int d = 0; d < D; ++d) sets[(size_t)d].off_lfact = off[(size_t)d];
     wm.x = dx.as<double>(); wm.y = dy.as<double>(); wm.lfact = dlf.as<double>();
   }
+  if (window_rows > 0) {      // amwg_waic_fold_check: the array cut into windows of window_rows rows, through the three steps of a summarising call (amwg_waic.h)
+    PointwiseLaunch K;
+    TRYB(amwg_pointwise_family(call, wm, PR, D, K));
+    WaicFold f;
+    TRYB(amwg_waic_fold_begin(call, K, sets.data(), D, PR, C, window_rows, rows, nullptr, f));
+    for (int64_t g0 = 0; g0 < rows; g0 += window_rows)
+      TRYB(amwg_waic_fold_window(f, dd.as<double>() + (size_t)g0 * (size_t)PR * (size_t)C, g0, rows - g0 < window_rows ? rows - g0 : window_rows, nullptr));
+    if (state_bytes) *state_bytes = f.state_bytes;
+    return amwg_waic_fold_finish(call, f, summary, high, pointwise, nullptr);
+  }
   return (loo ? amwg_loo_launch : amwg_waic_launch)(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
 }
 extern "C" {
@@ -443,6 +453,12 @@ extern "C" {
 int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                     int32_t *high, double *pointwise, double *loglik) {
   return pointwise_check("amwg_waic_check", false, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, loglik);
+}
+
+int amwg_waic_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t window_rows, double *summary,
+                         int32_t *high, double *pointwise, size_t *state_bytes) {
+  if (window_rows < 1) return amwg_fail(AMWG_EINVAL, "amwg_waic_fold_check: bad argument (window_rows %lld)", (long long)window_rows);
+  return pointwise_check("amwg_waic_fold_check", false, device, draws, rows, PR, C, D, models, 0, summary, high, pointwise, nullptr, window_rows, state_bytes);
 }
 
 int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,

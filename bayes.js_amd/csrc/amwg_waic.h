@@ -47,7 +47,7 @@ struct WaicModel {
 // HOW A CALL LAUNCHES THE KERNELS THAT EVALUATE THE MODEL (amwg_pointwise.h), as plain data: the instantiations for a built-in family (amwg_pointwise_family), or the
 // entries of a closure's code object (amwg_pointwise_describe_user).  The two take the same argument lists, the model in the same slot; everything else of a call is
 // the same code for both.
-enum PointwiseKernel { kPwWaicPartial, kPwWaicLoglik, kPwLooHist, kPwLooCompact, kPwKernels };      // (the order of amwg_sampler::pw_fn)
+enum PointwiseKernel { kPwWaicPartial, kPwWaicLoglik, kPwLooHist, kPwLooCompact, kPwWaicFold, kPwKernels };      // (the first four: the order of amwg_sampler::pw_fn)
 struct PointwiseLaunch {
   bool bern = false;                   // the family of two observations per dataset (its pairs are picked by x_i afterwards)
   bool builtin = false;                // a built-in family: `family` is the model argument and fn[] are addresses of the kernels' instantiations (hipLaunchKernel);
@@ -77,7 +77,7 @@ typedef PointwiseModels<AMWG_MODEL_NORMAL, AMWG_MODEL_BETA_BERN, AMWG_MODEL_HIER
 static_assert(AMWG_MODEL_BETA_BERN == AMWG_MODEL_NORMAL + 1 && AMWG_MODEL_HIER_NORMAL == AMWG_MODEL_NORMAL + 2 && AMWG_MODEL_POIS_GLM == AMWG_MODEL_NORMAL + 3, "BuiltinModels is indexed by model - AMWG_MODEL_NORMAL");
 
 #pragma GCC visibility push(hidden)
-// the address of a built-in family's instantiation, model one of BuiltinModels (amwg_waic.hip: k = 0 the partial kernel, 1 loglik; amwg_loo.hip: k = 0 hist, 1 compact)
+// the address of a built-in family's instantiation, model one of BuiltinModels (amwg_waic.hip: k = 0 the partial kernel, 1 loglik, 2 the fold; amwg_loo.hip: k = 0 hist, 1 compact)
 const void *amwg_waic_family_fn(int model, int k);
 const void *amwg_loo_family_fn(int model, int k);
 // K of a built-in family.  AMWG_EINVAL "<call>: ..." for an unknown model, draws of fewer components than the family reads, the hierarchical family on D != 1.
@@ -117,4 +117,37 @@ int amwg_waic_describe(amwg_sampler *s, std::vector<WaicDataset> &sets, WaicMode
 int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets, PointwiseLaunch &K);
 // the finish of include/amwg.h over one dataset's pairs pw[n][2]: summary[4], *high (may be nullptr)
 void amwg_waic_totals(const double *pw, int64_t n, double *summary, int32_t *high);
+
+// ---- WAIC FOLDED WINDOW BY WINDOW (amwg_waic_fold.hip): amwg_set_waic arms it for a sampler's summarising calls, the test library (amwg_waic_fold_check) drives the
+// same three steps over any array cut into windows.
+//   begin    the records [dataset][split][observation] of 32 bytes (amwg_pointwise.h: fold_splits of (window_rows * C / D, n_d)) allocated and zeroed
+//   window   waic_fold_body<Family> over the rows of one window, enqueued behind the fold of the same window: every workgroup continues its split's records
+//   finish   a thread per observation merges its splits in ascending order, the counts from the indices (fold_count), and writes lppd_i and p_i by the stored call's
+//            rules; the Bernoulli family's two observations are expanded; the totals on the host (amwg_waic_totals)
+// The records cannot be batched under a scratch budget: they live from the first window to the query.  A dataset's bytes depend on its own draws and data, on
+// (rows, C / D) and on window_rows.
+struct WaicFold {
+  bool armed = false, folded = false;      // amwg_set_waic; the records are those of the sampler's last summarising call
+  PointwiseLaunch K;
+  std::vector<WaicDataset> sets;           // [D], host
+  std::vector<int64_t> off;                // [D]: records before dataset d
+  int D = 0, PR = 0;
+  int64_t C = 0, window_rows = 0, total_rows = 0, tiles = 0, splits = 0, n_most = 0;      // the largest tiles, splits and n among the datasets
+  DevBuf d_sets, d_off, d_state;           // (never copied: the map of amwg_waic_fold.hip holds it in place)
+  size_t state_bytes = 0;
+};
+// the device bytes of the records of D datasets under windows of window_rows rows (the split rule, restated for amwg_waic_info and the tests)
+size_t amwg_waic_fold_bytes(const PointwiseLaunch &K, const WaicDataset *sets, int D, int64_t window_rows, int64_t cpd);
+// AMWG_EINVAL "<call>: ..." unless amwg_waic_shape serves (total_rows, PR, C, D) and window_rows >= 1; the records allocated and zeroed on `stream`
+int amwg_waic_fold_begin(const char *call, const PointwiseLaunch &K, const WaicDataset *sets, int D, int PR, int64_t C, int64_t window_rows, int64_t total_rows,
+                         hipStream_t stream, WaicFold &f);
+// rows [g0, g0 + nrows) of the call stand in window[0 .. nrows)[PR][C]; g0 a multiple of window_rows, nrows <= window_rows.  Enqueued on `stream`; no synchronisation
+int amwg_waic_fold_window(const WaicFold &f, const double *window, int64_t g0, int64_t nrows, hipStream_t stream);
+// the outputs of amwg_waic_run from the records.  Returns after `stream` has drained
+int amwg_waic_fold_finish(const char *call, const WaicFold &f, double *summary, int32_t *high, double *pointwise, hipStream_t stream);
+// the fold armed for `s` (amwg_set_waic), or nullptr; amwg_sample_summarize_async, before its launches: the sampler described, the records of this call begun -> the
+// arm, or nullptr (none armed); amwg_destroy
+WaicFold *amwg_waic_armed(const amwg_sampler *s);
+int amwg_waic_begin(amwg_sampler *s, int64_t window_rows, int64_t rows, WaicFold **arm);
+void amwg_waic_forget(const amwg_sampler *s);
 #pragma GCC visibility pop

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "amwg_dataset_quantiles.h"
+#include "amwg_fold.h"
 #include "amwg_host.h"
 #include "amwg_terms.h"
 #include "amwg_waic.h"
@@ -21,6 +22,13 @@ template <int MODEL>
 __global__ void __launch_bounds__(kThreads) waic_partial_kernel(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const WaicModel M,
                                                                 const WaicDataset *__restrict__ sets, const int64_t *__restrict__ part_off, Part *__restrict__ parts) {
   waic_partial_body<Family<MODEL>>(draws, rows, PR, C, cpd, d0, M, sets, part_off, parts);
+}
+
+// the same terms over one window of a summarising call, continued from and written back to state[state_off[d] + split * n + i] (amwg_pointwise.h; amwg_waic_fold.hip)
+template <int MODEL>
+__global__ void __launch_bounds__(kThreads) waic_fold_kernel(const double *__restrict__ window, int64_t nrows, int64_t g0, int64_t window_rows, int PR, int64_t C, int64_t cpd,
+                                                             const WaicModel M, const WaicDataset *__restrict__ sets, const int64_t *__restrict__ state_off, Part *__restrict__ state) {
+  waic_fold_body<Family<MODEL>>(window, nrows, g0, window_rows, PR, C, cpd, M, sets, state_off, state);
 }
 
 // out[(d * out_stride + i) * 2 + (0 | 1)] = lppd_i | p_i for i < n: the splits merged in ascending order
@@ -83,7 +91,8 @@ int run_kernels(const double *draws, int64_t rows, int PR, int64_t C, int D, con
 }
 
 template <int... MODEL> const void *family_fn(PointwiseModels<MODEL...>, int model, int k) {
-  const void *const fn[][2] = {{reinterpret_cast<const void *>(&waic_partial_kernel<MODEL>), reinterpret_cast<const void *>(&waic_loglik_kernel<MODEL>)}...};
+  const void *const fn[][3] = {{reinterpret_cast<const void *>(&waic_partial_kernel<MODEL>), reinterpret_cast<const void *>(&waic_loglik_kernel<MODEL>),
+                                reinterpret_cast<const void *>(&waic_fold_kernel<MODEL>)}...};
   return fn[model - AMWG_MODEL_NORMAL][k];
 }
 
@@ -139,5 +148,13 @@ int amwg_waic_run(const char *call, const double *draws, int64_t rows, int PR, i
 }
 
 extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
-  return amwg_pointwise_entry("amwg_last_sample_dataset_waic", s, summary, high, pointwise, amwg_waic_shape, amwg_waic_run);
+  static const char *call = "amwg_last_sample_dataset_waic";
+  if (s && summary && amwg_summarised(s)) {      // the draws were not kept: only what was folded while they passed can answer
+    const WaicFold *f = amwg_waic_armed(s);
+    if (!f || !f->folded)
+      return amwg_fail(AMWG_EINVAL, "%s: the last sample call was amwg_sample_summarize, which kept no draw, and no WAIC fold was armed for it (amwg_set_waic before the call)", call);
+    HIP_TRY(hipSetDevice(s->device));
+    return amwg_waic_fold_finish(call, *f, summary, high, pointwise, s->stream);
+  }
+  return amwg_pointwise_entry(call, s, summary, high, pointwise, amwg_waic_shape, amwg_waic_run);
 }

@@ -435,7 +435,9 @@ AmwgSampler.prototype.sample_on_device = function (n_iterations) {
 /** Like sample_on_device(n), but not even the device keeps the draws: they pass through a window of `options.window_rows` kept draws (default: what fits into
  *  64 MiB) and are folded into per-chain accumulators, so the memory of a run does not grow with its length.  moments(), convergence(), dataset_moments() and
  *  dataset_convergence() then answer from the accumulators -- R-hat and ESS bit for bit those of the stored run --; quantiles() and dataset_quantiles() need the
- *  draws and throw the library's refusal.  One device only.  Returns the number of kept draws. */
+ *  draws and throw the library's refusal; waic() and dataset_waic() answer after a call with options.waic (waic_info(): the device bytes of its records).  One
+ *  device only.  Returns the number of kept draws. */
+AmwgSampler.prototype.waic_info = function () { return native().waicInfo(this._shards[0].handle); };
 AmwgSampler.prototype.summarize = function (n_iterations, options) {
   const N = native(), w = options && options.window_rows !== undefined ? options.window_rows : 0;
   if (this._shards.length > 1 || (options && options.devices && options.devices.length > 1))
@@ -449,6 +451,15 @@ AmwgSampler.prototype.summarize = function (n_iterations, options) {
   } else if (this._hist_bins) {
     N.setHistogram(this._shards[0].handle, null, 0);
     this._hist_bins = 0;
+  }
+  // options.waic: true -- the pointwise terms are folded into per-observation records while the draws pass (amwg_set_waic); waic(), dataset_waic() and
+  // compare_waic() then work as after sample().  Like options.histogram it holds for THIS call.
+  if (options && options.waic) {
+    N.setWaic(this._shards[0].handle, true);
+    this._waic_armed = true;
+  } else if (this._waic_armed) {
+    N.setWaic(this._shards[0].handle, false);
+    this._waic_armed = false;
   }
   // options.covariance: true (every recorded value) or [names] -- the covariance of those values is folded while the draws pass (amwg_set_covariance);
   // dataset_covariance() / covariance() without an argument answer afterwards.  Like options.histogram it holds for THIS call: a call without it folds none

@@ -36,7 +36,8 @@ for (const name of ['mu', 'sigma']) {
 // the long run counts its draws under those edges while they pass: the 95 % interval of the stored run's quantiles() lies inside the brackets printed below
 // ... and folds the co-moment of mu and sigma beside the fold of each window: a correlation for a run that kept no draw
 // ... and the lagged sums of each chain at lags 0 .. 100: the integrated autocorrelation time tau and an ESS that looks along the chains, beside the between-chain one
-var kept = sampler.summarize(200000, { histogram: edges, covariance: true, autocorrelation: { max_lag: 100 } });
+// ... and the pointwise terms of the ten observations into per-observation records: a WAIC for a run that kept no draw (compare two models with mcmc.compare_waic)
+var kept = sampler.summarize(200000, { histogram: edges, covariance: true, autocorrelation: { max_lag: 100 }, waic: true });
 var m = sampler.moments(), c = sampler.convergence(), h = sampler.histogram(), cv = sampler.covariance(), ac = sampler.autocorrelation();
 console.log('kept draws per chain:', kept);
 for (const name of ['mu', 'sigma']) {
@@ -47,5 +48,7 @@ for (const name of ['mu', 'sigma']) {
               b[0][0].toFixed(3), b[0][1].toFixed(3), b[1][0].toFixed(3), b[1][1].toFixed(3));
 }
 console.log('cor(%s, %s) = %s  (cov %s)', cv.labels[0], cv.labels[1], cv.cor[0][1].toFixed(4), cv.cov[0][1].toExponential(3));
+var w = sampler.waic();
+console.log('elpd_waic %s +- %s  p_waic %s  (records: %d bytes)', w.elpd_waic.toFixed(3), w.se.toFixed(3), w.p_waic.toFixed(3), sampler.waic_info().bytes);
 console.log('held on the device:', JSON.stringify(sampler.summary_info()));
 sampler.close();

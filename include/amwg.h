@@ -263,10 +263,32 @@ int amwg_last_sample_dataset_hpd(amwg_sampler *s, const double *probs, int32_t n
  * likelihood terms outside its final loop gets the WAIC of the final loop's observations only.  The draws of a run are staged kStage = 256 at a time wherever 256 of
  * the closure's Draw (what an evaluation keeps of a draw) fit in 48 KiB of LDS, otherwise the largest multiple of 4 that fits -- a function of sizeof(Draw) alone, so
  * a dataset's bytes depend on its own draws and data, on (rows, C / D) and on the closure's text; a Draw of which fewer than 4 fit is refused when the text is compiled.
- * OUT OF SCOPE: WAIC after amwg_sample_summarize (per-observation accumulators could be folded; not built), a public pointwise log-likelihood matrix,
+ * WITHOUT STORED DRAWS (amwg_set_waic): lppd_i needs only a running (m, sum exp(l - m)) and p_i a running (count, mean, M2), so a summarising call can fold them.
+ *   amwg_set_waic(s, on) -- arms (on != 0) or disarms the fold for every later amwg_sample_summarize[_async] of this sampler.  When such a call starts, records of 32
+ *     bytes per (dataset, split, observation) are allocated and zeroed on the sampler's device (never between windows); after the fold of each window the pointwise
+ *     terms of the same rows are folded into them by a kernel of its own on the same stream, without a host synchronisation: a workgroup of 256 threads serves 64
+ *     observations and one of `splits` contiguous runs of THIS window's draws, continues that split's records by the recurrences of the stored call, and writes them
+ *     back.  splits is a function of (window_rows * C / D, n_d) alone, fixed for the call -- per dataset max(128, window draws / 128) workgroups over its tiles of 64
+ *     observations, at most one split per 256 draws of a full window --, and every window, the shorter last one too, is cut in that many runs of its own draws.
+ *     The records are persistent and cannot be batched under a budget; under the default window they are no larger than the window wherever a draw has two or more
+ *     recorded values (256 datasets x 256 chains x 1000 observations: 8 splits, 62.5 MiB).  Moments, R-hat, ESS, the chains' state, n_launches and
+ *     amwg_summary_info are those of the unarmed call.
+ *   amwg_last_sample_dataset_waic after an armed summarising call merges every observation's splits in ascending order (the counts are functions of the indices) and
+ *     answers with the outputs, refusals and NaN rules stated above; S is the whole call's draws and THE SAME BOUNDS hold.  The result is deterministic -- two
+ *     identical calls return the same bytes -- but is NOT promised to equal the stored run's bytes: a dataset's bytes depend on its own draws, its own data,
+ *     (rows, C / D) and window_rows -- not on D, the other datasets or any budget.  Unarmed, the call is refused as before (the message names amwg_sample_summarize
+ *     and amwg_set_waic).  amwg_last_sample_dataset_loo keeps refusing: PSIS-LOO needs the draws.
+ *   amwg_waic_info -- whether the fold is armed, and the device bytes of the records of the last armed summarising call (either pointer may be NULL).
+ *   Served: ordinary, dataset and ragged dataset samplers, closures whose pointwise text is set.  AMWG_EINVAL naming amwg_set_waic: a null sampler, a group_local
+ *   sampler, a closure without a pointwise text, the hierarchical family on D != 1.  An armed amwg_sample_summarize* that would keep fewer than 2 draws per dataset is
+ *   itself AMWG_EINVAL before its first launch, the chains' state untouched.  The fold does not continue across summarising calls.
+ * OUT OF SCOPE: WAIC after a summarising call that was not armed (its draws are gone), a fold continued across summarising calls, quantiles or HPD after
+ * amwg_sample_summarize (they need the draws, as the leave-one-out call below does), a public pointwise log-likelihood matrix,
  * likelihood terms of a closure outside its final loop, a pooled WAIC across devices (no amwg_group_* / amwg_comm_* twin). */
 int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary /* [D][4]: elpd_waic, se, p_waic, lppd */, int32_t *high /* [D] or NULL */,
                                   double *pointwise /* NULL or [D][n_max][2]: lppd_i, p_i; NaN beyond n_d */);
+int amwg_set_waic(amwg_sampler *s, int32_t on);
+int amwg_waic_info(const amwg_sampler *s, int32_t *armed, size_t *bytes);
 /* PSIS-LOO per dataset (Vehtari, Gelman & Gabry 2017; Vehtari, Simpson, Gelman, Yao & Gabry 2024): leave-one-out predictive accuracy by Pareto-smoothed importance
  * sampling from the stored draws, on the device -- what to use where WAIC's high[d] is not zero.
  *   summary[D][4] = elpd_loo, se, p_loo, lppd;  high[D] (or NULL) = the number of observations with khat_i > 0.7, where the estimate is unreliable;
@@ -430,7 +452,8 @@ int amwg_sample_device(amwg_sampler *s, int64_t n, int64_t thin, double *out_dra
  * agree with the stored path's to rounding.  Calls that need the draws themselves -- amwg_last_sample_quantiles, amwg_last_sample_dataset_quantiles, amwg_last_sample_dataset_hpd, amwg_last_sample_dataset_waic, amwg_last_sample_dataset_loo, amwg_fetch_draws*,
  * amwg_group_*, amwg_comm_gather_draws, amwg_comm_moments -- return AMWG_EINVAL with a message that names amwg_sample_summarize; so do
  * amwg_last_sample_dataset_histogram, amwg_last_sample_dataset_covariance and amwg_last_sample_dataset_autocovariance unless they were armed before the call
- * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL).  An
+ * (amwg_set_histogram, amwg_set_covariance, amwg_set_autocovariance) and are asked for what was folded while the draws passed (edges = NULL, values = NULL);
+ * amwg_last_sample_dataset_waic answers after a call armed with amwg_set_waic.  An
  * armed autocovariance whose max_lag is not below the kept draws makes the summarising call itself AMWG_EINVAL, before its first launch.  A later amwg_sample* call replaces
  * the summary, amwg_burn leaves it alone, and every summarising call starts its accumulators afresh.  n = 0 succeeds and leaves nothing to summarise.
  * amwg_launch_info's n_launches (step-kernel launches) and kernel_ms (which includes the folds) cover the whole call.

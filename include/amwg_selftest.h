@@ -76,6 +76,11 @@ int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, in
  * (0: the default of csrc/amwg_waic.h).  The arguments are checked before a device is opened. */
 int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                     int32_t *high, double *pointwise, double *loglik);
+/* the WAIC fold of an armed summarising call (amwg_set_waic) on the same inputs: the array is cut into windows of window_rows rows (the last may be shorter, and
+ * window_rows may exceed rows) and driven through the launcher the summarising call uses -- records allocated and zeroed, one fold per window, the finish.
+ * state_bytes (may be NULL): the device bytes of the records. */
+int amwg_waic_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t window_rows, double *summary,
+                         int32_t *high, double *pointwise, size_t *state_bytes);
 /* the kernels of amwg_last_sample_dataset_loo likewise: summary[D][4], high[D] (or NULL), pointwise (NULL, or [D][n_max][3]) as that call returns them.  tails (NULL,
  * or [D][n_max][M + 1], M the tail length of S = rows * (C / D)): the M + 1 smallest terms of each observation, sorted, as the fit read them; NaN beyond n_d and for an
  * observation with a non-finite term -- more than 2^24 doubles are refused.  scratch_bytes: the scratch budget of this call (0: the default of csrc/amwg_loo.h). */
