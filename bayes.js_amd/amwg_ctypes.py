@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_waic_grouped", "amwg_last_sample_dataset_loo_grouped", "amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_waic_grouped_check", "amwg_loo_grouped_check", "amwg_user_waic_grouped_check", "amwg_user_loo_grouped_check", "amwg_group_csr_check", "amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -76,6 +76,8 @@ def lib():
         L.amwg_last_sample_dataset_hpd.argtypes = [vp, pd, i32, pd]
         L.amwg_last_sample_dataset_waic.argtypes = [vp, pd, pi32, pd]
         L.amwg_last_sample_dataset_loo.argtypes = [vp, pd, pi32, pd]
+        L.amwg_last_sample_dataset_waic_grouped.argtypes = [vp, pi32, pd, pi32, pd, pi32]
+        L.amwg_last_sample_dataset_loo_grouped.argtypes = [vp, pi32, pd, pi32, pd, pi32]
         L.amwg_set_waic.argtypes = [vp, i32]
         L.amwg_waic_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_burn.argtypes = [vp, i64]
@@ -193,6 +195,12 @@ def selftest_lib():
         L.amwg_loo_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_user_waic_check.argtypes = [i32, C.POINTER(UserModel), i32, i32, C.c_char_p, pd, i64, i32, i64, i64, pd, C.POINTER(i32), pd, pd]
         L.amwg_user_loo_check.argtypes = L.amwg_user_waic_check.argtypes
+        pi32 = C.POINTER(i32)
+        L.amwg_waic_grouped_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), pi32, i64, pd, pi32, pd, pd, pi32]
+        L.amwg_loo_grouped_check.argtypes = L.amwg_waic_grouped_check.argtypes
+        L.amwg_user_waic_grouped_check.argtypes = [i32, C.POINTER(UserModel), i32, i32, C.c_char_p, pd, i64, i32, i64, pi32, i64, pd, pi32, pd, pd, pi32]
+        L.amwg_user_loo_grouped_check.argtypes = L.amwg_user_waic_grouped_check.argtypes
+        L.amwg_group_csr_check.argtypes = [pi32, i32, pi32, pi32, pi32, pi32]
         L.amwg_loo_stats.argtypes = [i32, C.POINTER(i32), pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
         L.amwg_summaries_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd, pd, pd]
@@ -594,10 +602,30 @@ class Sampler:
                             "(dataset_hpd)" % self.D)      # (the words of amwg_refuse_pooled; the library has no pooled call to ask)
         return self.dataset_hpd(probs)[0]
 
-    def dataset_waic(self, pointwise=False):
+    def _grouped(self, call, groups, width, pointwise):
+        """dataset_waic / dataset_loo over groups of observations: groups = one label array per dataset (an ordinary sampler: one array) -> the ungrouped call's
+        dict with groups for observations, pointwise [datasets][G_max][width], and n_groups [datasets]"""
+        per = [groups] if self.D == 1 and np.ndim(groups[0]) == 0 else list(groups)
+        labels = np.ascontiguousarray(np.concatenate([np.asarray(g).ravel() for g in per]), dtype=np.int32)
+        sizes = [n or self.pointwise_n_obs() for n in self.dataset_n_obs()]
+        if len(per) != self.D or [np.size(g) for g in per] != sizes:
+            raise AmwgError("amwg error -1: groups: one label per observation and dataset (sizes %s)" % sizes)
+        pi32 = C.POINTER(C.c_int32)
+        summary, high, ng = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32), np.zeros(self.D, dtype=np.int32)
+        g_max = max(len(np.unique(g)) for g in per)
+        pw = np.empty((self.D, g_max, width)) if pointwise else None
+        _check(call(self.h, labels.ctypes.data_as(pi32), _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None, ng.ctypes.data_as(pi32)))
+        out = {"summary": summary, "high": high, "n_groups": ng}
+        if pointwise:
+            out["pointwise"] = pw
+        return out
+
+    def dataset_waic(self, pointwise=False, groups=None):
         """-> dict(summary [datasets][4] = elpd_waic, se, p_waic, lppd; high [datasets] = observations with p_i > 0.4; with pointwise=True also
         pointwise [datasets][n_max][2] = lppd_i, p_i, NaN beyond a dataset's n_obs): WAIC per dataset by the rule of include/amwg.h, the families' pointwise
-        terms over the stored draws on the device (amwg_last_sample_dataset_waic)"""
+        terms over the stored draws on the device (amwg_last_sample_dataset_waic).  groups: leave-one-group-out (amwg_last_sample_dataset_waic_grouped, _grouped)"""
+        if groups is not None:
+            return self._grouped(lib().amwg_last_sample_dataset_waic_grouped, groups, 2, pointwise)
         summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
         pw = np.empty((self.D, self._n_max(), 2)) if pointwise else None
         _check(lib().amwg_last_sample_dataset_waic(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
@@ -617,10 +645,12 @@ class Sampler:
             out["pointwise"] = r["pointwise"][0]
         return out
 
-    def dataset_loo(self, pointwise=False):
+    def dataset_loo(self, pointwise=False, groups=None):
         """-> dict(summary [datasets][4] = elpd_loo, se, p_loo, lppd; high [datasets] = observations with khat_i > 0.7; with pointwise=True also
         pointwise [datasets][n_max][3] = elpd_loo_i, lppd_i, khat_i, NaN beyond a dataset's n_obs): PSIS-LOO per dataset by the rule of include/amwg.h, the
-        families' pointwise terms over the stored draws on the device (amwg_last_sample_dataset_loo)"""
+        families' pointwise terms over the stored draws on the device (amwg_last_sample_dataset_loo).  groups: leave-one-group-out (amwg_last_sample_dataset_loo_grouped)"""
+        if groups is not None:
+            return self._grouped(lib().amwg_last_sample_dataset_loo_grouped, groups, 3, pointwise)
         summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
         pw = np.empty((self.D, self._n_max(), 3)) if pointwise else None
         _check(lib().amwg_last_sample_dataset_loo(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
@@ -884,8 +914,28 @@ def _model_descs(specs):
     return mds, keep
 
 
-def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
-    """libamwg_selftest.so: the kernels of Sampler.dataset_waic on any array draws [rows][PR][C] and the data of `specs`, one dict(model, n_obs, data{x[,y,g]}[, G, K])
+def _labels(groups, sizes):
+    """groups: one label array per dataset -> (labels back to back as int32, G_max, a pointer to them)"""
+    if len(groups) != len(sizes) or [np.size(g) for g in groups] != [int(n) for n in sizes]:
+        raise AmwgError("amwg error: groups: one label per observation and dataset")
+    labels = np.ascontiguousarray(np.concatenate([np.asarray(g).ravel() for g in groups]), dtype=np.int32)
+    return labels, max(len(np.unique(g)) for g in groups), labels.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def group_csr(labels):
+    """libamwg_selftest.so: the groups the host makes of one dataset's labels, no device -> (start [G + 1], member [n], deal [G]) (amwg_group_csr_check)"""
+    lb = np.ascontiguousarray(labels, dtype=np.int32)
+    n, pi32 = lb.size, C.POINTER(C.c_int32)
+    start, member, deal, G = np.zeros(n + 1, dtype=np.int32), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32), C.c_int32(0)
+    L = selftest_lib()
+    if L.amwg_group_csr_check(lb.ctypes.data_as(pi32), n, start.ctypes.data_as(pi32), member.ctypes.data_as(pi32), deal.ctypes.data_as(pi32), C.byref(G)) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return start[:G.value + 1], member, deal[:G.value]
+
+
+def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, device=0, groups=None):
+    """groups (one label array per dataset): over groups of observations -- n_max is then G_max, and the dict also holds n_groups [D] (amwg_waic_grouped_check).
+    libamwg_selftest.so: the kernels of Sampler.dataset_waic on any array draws [rows][PR][C] and the data of `specs`, one dict(model, n_obs, data{x[,y,g]}[, G, K])
     per dataset (one family; ragged sizes allowed), C / len(specs) columns each -> dict(summary [D][4], high [D][, pointwise [D][n_max][2]][, loglik [D][S][n_max],
     the terms themselves in draw order s = row * (C / D) + chain]) (amwg_waic_check)"""
     dr = np.ascontiguousarray(draws, dtype=np.float64)
@@ -895,17 +945,26 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
     D = len(specs)
     mds, keep = _model_descs(specs)
     n_max = max([int(q["n_obs"]) for q in specs] + [1])
+    if groups is not None:
+        labels, n_max, lp = _labels(groups, [q["n_obs"] for q in specs])
     S = rows * (Cn // D) if D and Cn % D == 0 else 0
-    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    summary, high, ng = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32), np.zeros(max(1, D), dtype=np.int32)
     pw = np.empty((max(1, D), n_max, 2)) if pointwise else None
     ll = np.empty((max(1, D), S, n_max)) if loglik and S * n_max * max(1, D) <= (1 << 24) else None
     if loglik and ll is None:
         ll = np.empty(1)      # (refused by the library before it is written: more than 2^24 doubles)
     L = selftest_lib()
-    if L.amwg_waic_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
-                         _dp(pw) if pointwise else None, _dp(ll) if loglik else None) != 0:
+    pi32 = C.POINTER(C.c_int32)
+    if groups is not None:
+        rc = L.amwg_waic_grouped_check(device, _dp(dr), rows, PR, Cn, D, mds, lp, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None,
+                                       _dp(ll) if loglik else None, ng.ctypes.data_as(pi32))
+    else:
+        rc = L.amwg_waic_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None, _dp(ll) if loglik else None)
+    if rc != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     out = {"summary": summary, "high": high}
+    if groups is not None:
+        out["n_groups"] = ng
     if pointwise:
         out["pointwise"] = pw
     if loglik:
@@ -951,7 +1010,7 @@ def _user_models(users):
     return ums, keep
 
 
-def _user_check(loo, draws, users, terms, P, n_obs, pointwise, extra, scratch_bytes, device):
+def _user_check(loo, draws, users, terms, P, n_obs, pointwise, extra, scratch_bytes, device, groups=None):
     dr = np.ascontiguousarray(draws, dtype=np.float64)
     if dr.ndim != 3:
         raise AmwgError("amwg error: user_%s_check: draws must be [rows][PR][C]" % ("loo" if loo else "waic"))
@@ -959,19 +1018,30 @@ def _user_check(loo, draws, users, terms, P, n_obs, pointwise, extra, scratch_by
     D = len(users)
     ums, keep = _user_models(users)
     n_max = max(1, int(n_obs))
+    if groups is not None:
+        labels, n_max, lp = _labels(groups, [n_obs] * D)
     S = rows * (Cn // D) if D and Cn % D == 0 else 0
     width = (loo_tail_len(S) + 1) if loo else S
-    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    summary, high, ng = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32), np.zeros(max(1, D), dtype=np.int32)
     pw = np.empty((max(1, D), n_max, 3 if loo else 2)) if pointwise else None
     ex = None
     if extra:
         ex = (np.empty((max(1, D), n_max, width)) if loo else np.empty((max(1, D), S, n_max))) if width * n_max * max(1, D) <= (1 << 24) else np.empty(1)
     L = selftest_lib()
-    call = L.amwg_user_loo_check if loo else L.amwg_user_waic_check
-    if call(device, ums, D, int(P), terms.encode() if isinstance(terms, str) else terms, _dp(dr), rows, PR, Cn, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
-            _dp(pw) if pointwise else None, _dp(ex) if extra else None) != 0:
+    pi32 = C.POINTER(C.c_int32)
+    text = terms.encode() if isinstance(terms, str) else terms
+    if groups is not None:
+        call = L.amwg_user_loo_grouped_check if loo else L.amwg_user_waic_grouped_check
+        rc = call(device, ums, D, int(P), text, _dp(dr), rows, PR, Cn, lp, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None,
+                  _dp(ex) if extra else None, ng.ctypes.data_as(pi32))
+    else:
+        call = L.amwg_user_loo_check if loo else L.amwg_user_waic_check
+        rc = call(device, ums, D, int(P), text, _dp(dr), rows, PR, Cn, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None, _dp(ex) if extra else None)
+    if rc != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     out = {"summary": summary, "high": high}
+    if groups is not None:
+        out["n_groups"] = ng
     if pointwise:
         out["pointwise"] = pw
     if extra:
@@ -979,15 +1049,15 @@ def _user_check(loo, draws, users, terms, P, n_obs, pointwise, extra, scratch_by
     return out
 
 
-def user_waic_check(draws, users, terms, P, n_obs, pointwise=True, loglik=False, scratch_bytes=0, device=0):
+def user_waic_check(draws, users, terms, P, n_obs, pointwise=True, loglik=False, scratch_bytes=0, device=0, groups=None):
     """libamwg_selftest.so: waic_check for a translated closure -- users: one dict(source, arrays[, array_types]) per dataset (one source), terms: the pointwise
     text of translate.js (options.pointwise), P the components of the state, n_obs its kTermN -> what waic_check returns (amwg_user_waic_check)"""
-    return _user_check(False, draws, users, terms, P, n_obs, pointwise, loglik, scratch_bytes, device)
+    return _user_check(False, draws, users, terms, P, n_obs, pointwise, loglik, scratch_bytes, device, groups)
 
 
-def user_loo_check(draws, users, terms, P, n_obs, pointwise=True, tails=False, scratch_bytes=0, device=0):
+def user_loo_check(draws, users, terms, P, n_obs, pointwise=True, tails=False, scratch_bytes=0, device=0, groups=None):
     """libamwg_selftest.so: loo_check for a translated closure, as user_waic_check (amwg_user_loo_check)"""
-    return _user_check(True, draws, users, terms, P, n_obs, pointwise, tails, scratch_bytes, device)
+    return _user_check(True, draws, users, terms, P, n_obs, pointwise, tails, scratch_bytes, device, groups)
 
 
 def compile_pointwise(source, terms, arch="gfx950"):
@@ -1028,8 +1098,9 @@ def loo_totals(pointwise, n_obs):
         return np.array([elpd, se, lppd - elpd, lppd]), high
 
 
-def loo_check(draws, specs, pointwise=True, tails=False, scratch_bytes=0, device=0):
-    """libamwg_selftest.so: the kernels of Sampler.dataset_loo on any array draws [rows][PR][C] and the data of `specs` (as waic_check takes them) ->
+def loo_check(draws, specs, pointwise=True, tails=False, scratch_bytes=0, device=0, groups=None):
+    """groups (one label array per dataset): over groups of observations, as waic_check (amwg_loo_grouped_check).
+    libamwg_selftest.so: the kernels of Sampler.dataset_loo on any array draws [rows][PR][C] and the data of `specs` (as waic_check takes them) ->
     dict(summary [D][4], high [D][, pointwise [D][n_max][3]][, tails [D][n_max][M + 1], the sorted smallest terms the fit read]) (amwg_loo_check)"""
     dr = np.ascontiguousarray(draws, dtype=np.float64)
     if dr.ndim != 3:
@@ -1038,18 +1109,27 @@ def loo_check(draws, specs, pointwise=True, tails=False, scratch_bytes=0, device
     D = len(specs)
     mds, keep = _model_descs(specs)
     n_max = max([int(q["n_obs"]) for q in specs] + [1])
+    if groups is not None:
+        labels, n_max, lp = _labels(groups, [q["n_obs"] for q in specs])
     S = rows * (Cn // D) if D and Cn % D == 0 else 0
     M = loo_tail_len(S)
-    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    summary, high, ng = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32), np.zeros(max(1, D), dtype=np.int32)
     pw = np.empty((max(1, D), n_max, 3)) if pointwise else None
     tl = np.empty((max(1, D), n_max, M + 1)) if tails and (M + 1) * n_max * max(1, D) <= (1 << 24) else None
     if tails and tl is None:
         tl = np.empty(1)      # (refused by the library before it is written: more than 2^24 doubles)
     L = selftest_lib()
-    if L.amwg_loo_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)),
-                        _dp(pw) if pointwise else None, _dp(tl) if tails else None) != 0:
+    pi32 = C.POINTER(C.c_int32)
+    if groups is not None:
+        rc = L.amwg_loo_grouped_check(device, _dp(dr), rows, PR, Cn, D, mds, lp, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None,
+                                      _dp(tl) if tails else None, ng.ctypes.data_as(pi32))
+    else:
+        rc = L.amwg_loo_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(pi32), _dp(pw) if pointwise else None, _dp(tl) if tails else None)
+    if rc != 0:
         raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     out = {"summary": summary, "high": high}
+    if groups is not None:
+        out["n_groups"] = ng
     if pointwise:
         out["pointwise"] = pw
     if tails:

@@ -263,6 +263,11 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
   LooState *d_state = state.as<LooState>();
   uint32_t *d_hist = hist.as<uint32_t>();
   double *d_tail = tail.as<double>(), *d_parts = parts.as<double>();
+  // a grouped call: `sets` and d_sets count groups; the walking kernels take the observations' sets and the groups in their place
+  const int walk_fn = K.groups ? kPwGrouped : 0;
+  const WaicDataset *obs_sets = K.groups ? K.groups->d_sets.as<WaicDataset>() : d_sets;
+  const GroupSet *gsets = K.groups ? K.groups->d_gsets.as<GroupSet>() : nullptr;
+  const int32_t *csr = K.groups ? K.groups->d_csr.as<int32_t>() : nullptr;
   for (const PointwiseBatch &b : plan.batches) {
     if (b.tiles == 0) continue;
     int d0 = b.d0, pass = 0;
@@ -270,6 +275,8 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
     const dim3 walk((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), per_obs_grid((unsigned)((b.n_most + kThreads - 1) / kThreads), (unsigned)(b.d1 - d0));
     void *hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &d_state, &d_hist, &pass};
     void *compact_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &part_off, &d_state, &d_tail, &cap, &d_parts};
+    void *grouped_hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &obs_off, &d_state, &d_hist, &pass};
+    void *grouped_compact_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &obs_off, &part_off, &d_state, &d_tail, &cap, &d_parts};
     hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((obs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_state, obs);
     HIP_TRY(hipGetLastError());
     {
@@ -279,7 +286,7 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
         int waiting = 0;
         HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)obs * kBins * 4, stream));
         HIP_TRY(hipMemsetAsync(pending.p, 0, sizeof(int), stream));
-        HIP_TRY(amwg_pointwise_go(K, kPwLooHist, walk, stream, hist_args));
+        HIP_TRY(amwg_pointwise_go(K, walk_fn + kPwLooHist, walk, stream, K.groups ? grouped_hist_args : hist_args));
         hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern ? 1 : 0, obs_off, d_state, d_hist, pass, (uint32_t)M, cap, pending.as<int>());
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&waiting, pending.p, sizeof(int), hipMemcpyDeviceToHost, stream));
@@ -292,7 +299,7 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
     }
     {
       Phase ph(stream, stats.timed != 0);
-      HIP_TRY(amwg_pointwise_go(K, kPwLooCompact, walk, stream, compact_args));
+      HIP_TRY(amwg_pointwise_go(K, walk_fn + kPwLooCompact, walk, stream, K.groups ? grouped_compact_args : compact_args));
       ph.end(stats.ms_compact);
     }
     {
@@ -400,4 +407,8 @@ int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, in
 
 extern "C" int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary, int32_t *high, double *pointwise) {
   return amwg_pointwise_entry("amwg_last_sample_dataset_loo", s, summary, high, pointwise, amwg_loo_shape, amwg_loo_run);
+}
+
+extern "C" int amwg_last_sample_dataset_loo_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out) {
+  return amwg_pointwise_entry("amwg_last_sample_dataset_loo_grouped", s, summary, high, pointwise, amwg_loo_shape, amwg_loo_run, true, labels, n_groups_out);
 }

@@ -794,15 +794,29 @@ static napi_value DatasetHpd(napi_env env, napi_callback_info info) {
   return o;
 }
 
-/* what DatasetWaic and DatasetLoo share: `width` doubles per observation in pointwise */
+/* what DatasetWaic and DatasetLoo share: `width` doubles per observation in pointwise.  With `grouped` (the leave-one-group-out twins): a third argument, the
+ * datasets' labels back to back as an Int32Array, a label per observation; the object then counts GROUPS where it counts observations -- n_obs [datasets] = G_d,
+ * n_max = the largest G_d, pointwise [datasets][n_max][width] in front of a buffer sized for the observations */
 typedef int (*pointwise_call)(amwg_sampler *, double *, int32_t *, double *);
-static napi_value dataset_pointwise(napi_env env, napi_callback_info info, pointwise_call call, size_t width) {
-  napi_value a[2];
-  if (!get_args(env, info, 2, a)) return NULL;
+typedef int (*grouped_call)(amwg_sampler *, const int32_t *, double *, int32_t *, double *, int32_t *);
+static napi_value dataset_pointwise(napi_env env, napi_callback_info info, pointwise_call call, grouped_call grouped, size_t width) {
+  napi_value a[3];
+  if (!get_args(env, info, grouped ? 3 : 2, a)) return NULL;
   amwg_sampler *s = unwrap(env, a[0]);
   if (!s) return NULL;
   bool want = false;
   napi_get_value_bool(env, a[1], &want);
+  const int32_t *labels = NULL;
+  size_t n_labels = 0;
+  if (grouped) {
+    napi_typedarray_type type;
+    void *data = NULL;
+    if (napi_get_typedarray_info(env, a[2], &type, &n_labels, &data, NULL, NULL) != napi_ok || type != napi_int32_array) {
+      napi_throw_error(env, "AMWG_EINVAL", "amwg_napi: the labels of a grouped call are an Int32Array, a label per observation");
+      return NULL;
+    }
+    labels = (const int32_t *)data;
+  }
   const size_t D = (size_t)amwg_num_datasets(s);
   int32_t *n_obs = NULL, *high = NULL;
   double *summary = NULL, *pw = NULL;
@@ -815,7 +829,18 @@ static napi_value dataset_pointwise(napi_env env, napi_callback_info info, point
   int32_t n_max = 0;
   for (size_t d = 0; d < D; ++d) n_max = n_obs[d] > n_max ? n_obs[d] : n_max;
   if (want) { vp = new_f64(env, D * (size_t)n_max * width, &pw); if (!vp) return NULL; }
-  rc = call(s, summary, high, want ? pw : NULL);
+  if (grouped) {
+    size_t total = 0;
+    for (size_t d = 0; d < D; ++d) total += (size_t)n_obs[d];
+    if (n_labels != total) {
+      napi_throw_error(env, "AMWG_EINVAL", "amwg_napi: a grouped call needs one label per observation of every dataset");
+      return NULL;
+    }
+    rc = grouped(s, labels, summary, high, want ? pw : NULL, n_obs);      /* (n_obs becomes the group counts) */
+    for (size_t d = 0; d < D; ++d) n_max = d == 0 || n_obs[d] > n_max ? n_obs[d] : n_max;
+  } else {
+    rc = call(s, summary, high, want ? pw : NULL);
+  }
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   napi_value o, t;
   NAPI_OK(napi_create_object(env, &o));
@@ -831,10 +856,14 @@ static napi_value dataset_pointwise(napi_env env, napi_callback_info info, point
 }
 /* datasetWaic(handle, bool pointwise) -> {datasets, n_max, n_obs: Int32Array [datasets], summary: Float64Array [datasets][4] (elpd_waic, se, p_waic, lppd),
  * high: Int32Array [datasets][, pointwise: Float64Array [datasets][n_max][2] (lppd_i, p_i; NaN beyond a dataset's n_obs)]} over the last sample() */
-static napi_value DatasetWaic(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_waic, 2); }
+static napi_value DatasetWaic(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_waic, NULL, 2); }
 /* datasetLoo(handle, bool pointwise) -> the same object over amwg_last_sample_dataset_loo: summary [datasets][4] (elpd_loo, se, p_loo, lppd), high (observations with
  * khat_i > 0.7), pointwise [datasets][n_max][3] (elpd_loo_i, lppd_i, khat_i) */
-static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo, 3); }
+static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo, NULL, 3); }
+/* datasetWaicGrouped(handle, bool pointwise, Int32Array labels), datasetLooGrouped(...): the same objects over groups of observations
+ * (amwg_last_sample_dataset_waic_grouped, amwg_last_sample_dataset_loo_grouped) */
+static napi_value DatasetWaicGrouped(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, NULL, amwg_last_sample_dataset_waic_grouped, 2); }
+static napi_value DatasetLooGrouped(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, NULL, amwg_last_sample_dataset_loo_grouped, 3); }
 
 /* setWaic(handle, bool on): amwg_set_waic -- arms (false: disarms) the WAIC fold for later summarising calls */
 static napi_value SetWaic(napi_env env, napi_callback_info info) {
@@ -1281,7 +1310,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setWaic", SetWaic}, {"waicInfo", WaicInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

@@ -1,5 +1,6 @@
 // amwg_pointwise.h -- the kernels of WAIC (amwg_waic.hip) and PSIS-LOO (amwg_loo.hip) that evaluate the model, as ONE text over the family class F and its model
-// argument MA: WAIC's partial kernel, fold kernel and loglik kernel, LOO's histogram kernel and compaction kernel.  amwg_waic.hip and amwg_loo.hip instantiate it for the four
+// argument MA: WAIC's partial kernel, fold kernel and loglik kernel, LOO's histogram kernel and compaction kernel, and the twins of four of them over GROUPS of
+// observations (below; amwg_grouped.hip).  amwg_waic.hip and amwg_loo.hip instantiate it for the four
 // built-in families (Family<MODEL>, WaicModel: amwg_terms.h); hiprtc instantiates the very same text for the pointwise terms of a translated closure (UserTerms:
 // translate.js pointwisePlan; UserTermsArg) as the extern "C" entries at the end of this file, in one code object (amwg_rtc.hip compile_pointwise).  What does not
 // depend on the model serves both: merge, pick, fit and totals in the two .hip files, fill, the Bernoulli expand and the host path around them in amwg_pointwise_host.hip.
@@ -394,6 +395,286 @@ __device__ __forceinline__ void loo_compact_body(const double *__restrict__ draw
   parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + i] = b;
 }
 
+// ---- GROUPS OF OBSERVATIONS: leave-one-group-out (include/amwg.h).  The term of group g under draw s is L_sg = ((l_s,i1 + l_s,i2) + l_s,i3) + ... over its members in
+// ascending observation index; from L on, everything is the code above with G for n.  The grouped twins of the three walking kernels and of the loglik kernel:
+//   A LANE OWNS A GROUP (GroupSet: the CSR the host made of the labels; the groups dealt to the tiles by falling size, results under the group's own number).
+//   THE DRAWS are staged as above.  A lane walks its share of the staged run in BLOCKS of R draws: the R Draws go to registers once, then the MEMBER LOOP runs
+//   outermost -- the member's Obs is loaded once per block and feeds R independent term + add pairs, so the load is amortised R-fold and R add chains are in flight
+//   where a loop over the members inside one evaluation would have one.  R = group_block<F>(), a function of sizeof(Draw) alone: 8 up to 48 bytes (the Normal and the
+//   hierarchical family), 4 up to 96 (the Poisson family: 72), then 2 and 1.  The built-in families' kernels take 113 to 187 of the 256 vector registers a lane of
+//   a 256-thread workgroup may have, without scratch; a closure's Draw beyond 512 / R bytes is not copied but read where it is staged.
+//   The R finished sums then feed the recurrences of the kernels above, unchanged and in the same order of draws: wavefront w still takes the staged draws
+//   w, w + 4, ..., so singleton groups give the bytes of the ungrouped kernels.
+//   FEW GROUPS.  In the select kernel a tile of at most 32 groups spreads every group over 64 / Gp lanes (Gp the tile's groups rounded up to a power of two):
+//   lanes g, g + Gp, g + 2 Gp, ... split the staged draws between them, and the counters, the minimum and the flag they feed are integer atomics, so nothing
+//   depends on the split.  The WAIC partial and the compaction's B are floating-point sums in a pinned order of draws: they keep a lane per group, and the
+//   lanes of a tile beyond its groups evaluate nothing.
+constexpr int group_block_of(size_t draw_bytes) { return draw_bytes <= 48 ? 8 : draw_bytes <= 96 ? 4 : draw_bytes <= 192 ? 2 : 1; }
+template <class F> constexpr int group_block() { return group_block_of(sizeof(typename F::Draw)); }
+
+// what a lane of tile `tile` works on: group g = members [m0, m1) of the CSR; of every staged run the draws unit, unit + units, ...; slot_mask: lane & slot_mask is
+// the lane's slot in the tile.  split: spread a tile of at most 32 groups over the spare lanes
+struct GroupLane { int64_t g; int32_t m0, m1; int unit, units, slot_mask; bool active; };
+__device__ __forceinline__ GroupLane group_lane(const GroupSet &gs, const int32_t *__restrict__ csr, int64_t tile, int lane, int wave, bool split) {
+  const int64_t left = (int64_t)gs.G - tile * kTile;
+  const int Gt = left < kTile ? (int)left : kTile;
+  int Gp = kTile;
+  if (split) { Gp = 1; while (Gp < Gt) Gp <<= 1; }
+  const int sub = kTile / Gp, slot = lane & (Gp - 1);
+  GroupLane x;
+  x.active = slot < Gt;
+  x.g = csr[gs.at_deal + tile * kTile + (x.active ? slot : Gt - 1)];
+  x.m0 = csr[gs.at_start + x.g];
+  x.m1 = csr[gs.at_start + x.g + 1];
+  x.unit = wave * sub + lane / Gp;
+  x.units = kWaves * sub;
+  x.slot_mask = Gp - 1;
+  return x;
+}
+
+// acc[r] = L of the lane's group under the staged draw jb + stride * r, r < R; a draw at or beyond L is evaluated as draw jb (a staged one) and is the caller's to drop
+template <class F, int R, class M>
+__device__ __forceinline__ void group_terms(const M &Md, const WaicDataset &ds, const int32_t *__restrict__ member, int m0, int m1, const typename F::Draw *stage, int jb,
+                                            int stride, int L, const double *draws, int64_t C, double (&acc)[R]) {
+  constexpr bool kInRegisters = (size_t)R * sizeof(typename F::Draw) <= 512;      // (a closure's larger Draw is read where it is staged)
+  typename F::Draw w[kInRegisters ? R : 1];
+  int at[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int j = jb + stride * r;
+    at[r] = j < L ? j : jb;
+    if constexpr (kInRegisters) w[r] = stage[at[r]];
+  }
+  {
+    const int64_t i = member[m0];
+    const typename F::Obs o = F::load_obs(Md, ds, i);
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = F::term(Md, o, kInRegisters ? w[r] : stage[at[r]], i, draws, C);
+  }
+  for (int m = m0 + 1; m < m1; ++m) {
+    const int64_t i = member[m];
+    const typename F::Obs o = F::load_obs(Md, ds, i);
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = acc[r] + F::term(Md, o, kInRegisters ? w[r] : stage[at[r]], i, draws, C);
+  }
+}
+
+// waic_partial_body over groups: parts[part_off[z] + split * G + g]
+template <class F, class MA>
+__device__ __forceinline__ void waic_partial_grouped_body(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const MA &M,
+                                                          const WaicDataset *__restrict__ sets, const GroupSet *__restrict__ gsets, const int32_t *__restrict__ csr,
+                                                          const int64_t *__restrict__ part_off, Part *__restrict__ parts) {
+  constexpr int kRun = stage_len<F>(), R = group_block<F>();
+  static_assert(kRun >= kWaves, "the Draw of this model is too large: fewer than kWaves of them fit in the 48 KiB of LDS a workgroup stages draws in");
+  __shared__ typename F::Draw stage[kRun];
+  __shared__ Part wave_part[kWaves - 1][kTile];
+  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WaicDataset ds = sets[d];
+  const GroupSet gs = gsets[d];
+  const int64_t n = gs.G, S = rows * cpd, splits = waic_splits(S, n);
+  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
+  const auto &Md = dataset_model(M, d);
+  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
+  const GroupLane me = group_lane(gs, csr, blockIdx.x, lane, wave, false);
+  const int32_t *member = csr + gs.at_member;
+  Part a{-kInf, 0.0, 0.0, 0.0};
+  double cnt = 0.0;
+  for (int64_t s0 = s_begin; s0 < s_end; s0 += kRun) {
+    const int L = (int)(s_end - s0 < kRun ? s_end - s0 : kRun);
+    __syncthreads();
+    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, Md, ds);
+    __syncthreads();
+    if (wave >= L || !me.active) continue;      // (the barriers above are reached by all; a lane beyond the tile's groups evaluates nothing)
+    double K = a.mean, s1 = 0.0, s2 = 0.0;
+    int nb = 0;
+    for (int jb = wave; jb < L; jb += kWaves * R) {
+      double l[R];
+      group_terms<F, R>(Md, ds, member, me.m0, me.m1, stage, jb, kWaves, L, draws, C, l);
+      if (jb == wave && cnt == 0.0) K = l[0];      // (the shift of the first run: the term of the wavefront's first draw, as waic_partial_body)
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (jb + kWaves * r >= L) break;
+        const double dm = l[r] - a.m;
+        const double e = waic_exp(-__builtin_fabs(dm));
+        const bool up = dm > 0.0;
+        a.sum = up ? __builtin_fma(a.sum, e, 1.0) : a.sum + e;
+        a.m = up ? l[r] : a.m;
+        const double dk = l[r] - K;
+        s1 += dk;
+        s2 = __builtin_fma(dk, dk, s2);
+        ++nb;
+      }
+    }
+    const double nbd = (double)nb, q = s1 / nbd;
+    double M2b = s2 - s1 * q;
+    M2b = M2b < 0.0 ? 0.0 : M2b;      // (a NaN stays a NaN)
+    const double mean_b = K + q;
+    if (cnt == 0.0) { a.mean = mean_b; a.M2 = M2b; cnt = nbd; }
+    else {
+      const double nt = cnt + nbd, delta = mean_b - a.mean;
+      a.mean = a.mean + delta * (nbd / nt);
+      a.M2 = a.M2 + M2b + delta * delta * (cnt * nbd / nt);
+      cnt = nt;
+    }
+  }
+  __syncthreads();
+  if (wave > 0) wave_part[wave - 1][lane] = a;
+  __syncthreads();
+  if (wave != 0 || !me.active) return;
+  const int64_t len = s_end - s_begin, full = len / kRun, rest = len % kRun;
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) {
+    const double nw = (double)(full * (kRun / kWaves) + (rest > w ? (rest - w + kWaves - 1) / kWaves : 0));
+    merge_parts(a, cnt, wave_part[w - 1][lane], nw);
+  }
+  parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + me.g] = a;
+}
+
+// the joint terms themselves, out[(d * S + s) * g_max + g]: the test library's view of what the grouped kernels accumulate (group_terms, as they call it).  A
+// workgroup takes the draws kWaves * R at a time, wavefront w those with (s - s0) % kWaves == w; any gridDim.y serves
+template <class F, class MA>
+__device__ __forceinline__ void waic_loglik_grouped_body(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, const MA &M,
+                                                         const WaicDataset *__restrict__ sets, const GroupSet *__restrict__ gsets, const int32_t *__restrict__ csr,
+                                                         double *__restrict__ out, int64_t g_max) {
+  constexpr int R = group_block<F>(), kPer = kWaves * R;
+  __shared__ typename F::Draw stage[kPer];
+  const int d = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WaicDataset ds = sets[d];
+  const GroupSet gs = gsets[d];
+  const int64_t S = rows * cpd;
+  if ((int64_t)blockIdx.x * kTile >= gs.G) return;      // (uniform over the workgroup)
+  const auto &Md = dataset_model(M, d);
+  const GroupLane me = group_lane(gs, csr, blockIdx.x, lane, wave, false);
+  const int32_t *member = csr + gs.at_member;
+  for (int64_t s0 = (int64_t)blockIdx.y * kPer; s0 < S; s0 += (int64_t)gridDim.y * kPer) {
+    const int L = (int)(S - s0 < kPer ? S - s0 : kPer);
+    __syncthreads();
+    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, Md, ds);
+    __syncthreads();
+    if (wave >= L) continue;
+    double l[R];
+    group_terms<F, R>(Md, ds, member, me.m0, me.m1, stage, wave, kWaves, L, draws, C, l);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+      if (wave + kWaves * r < L && me.active) out[((int64_t)d * S + s0 + wave + kWaves * r) * g_max + me.g] = l[r];
+  }
+}
+
+// loo_hist_body over groups: hist[(obs_off[z] + g) * kBins + bin].  The spare lanes of a tile of at most 32 groups take draws of their own (group_lane, split)
+template <class F, class MA>
+__device__ __forceinline__ void loo_hist_grouped_body(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const MA &M,
+                                                      const WaicDataset *__restrict__ sets, const GroupSet *__restrict__ gsets, const int32_t *__restrict__ csr,
+                                                      const int64_t *__restrict__ obs_off, LooState *__restrict__ state, uint32_t *__restrict__ hist, int pass) {
+  constexpr int kRun = stage_len<F>(), R = group_block<F>();
+  static_assert(kRun >= kWaves, "the Draw of this model is too large: fewer than kWaves of them fit in the 48 KiB of LDS a workgroup stages draws in");
+  __shared__ typename F::Draw stage[kRun];
+  __shared__ uint32_t cnt[kBins * kTile];      // [bin][lane]: a column per lane, whatever group it counts for
+  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WaicDataset ds = sets[d];
+  const GroupSet gs = gsets[d];
+  const int64_t n = gs.G, S = rows * cpd, splits = waic_splits(S, n);
+  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
+  const auto &Md = dataset_model(M, d);
+  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
+  const GroupLane me = group_lane(gs, csr, blockIdx.x, lane, wave, true);
+  const int32_t *member = csr + gs.at_member;
+  const int64_t o_at = obs_off[blockIdx.z] + me.g;
+  const LooState st = state[o_at];
+  const bool counting = me.active && !st.done;
+  if (!__syncthreads_or(counting ? 1 : 0)) return;      // every group of the tile is done
+  for (int k = tid; k < kBins * kTile; k += kThreads) cnt[k] = 0;
+  const int shift = pass_shift(pass), shift_prev = 64 - kDigitBits * pass;
+  const uint32_t mask = (uint32_t)pass_bins(pass) - 1u;
+  uint64_t kmin = kMaxKey;
+  bool bad = false;
+  for (int64_t s0 = s_begin; s0 < s_end; s0 += kRun) {
+    const int L = (int)(s_end - s0 < kRun ? s_end - s0 : kRun);
+    __syncthreads();
+    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, Md, ds);
+    __syncthreads();
+    for (int jb = me.active ? me.unit : L; jb < L; jb += me.units * R) {      // (a lane beyond the tile's groups evaluates nothing)
+      double l[R];
+      group_terms<F, R>(Md, ds, member, me.m0, me.m1, stage, jb, me.units, L, draws, C, l);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (jb + me.units * r >= L) break;
+        const uint64_t key = select_key(l[r]);
+        if (pass == 0) {
+          kmin = key < kmin ? key : kmin;
+          bad = bad || !(__builtin_fabs(l[r]) < kInf);
+        }
+        const bool match = pass == 0 || ((key ^ st.prefix) >> shift_prev) == 0;
+        if (counting && match) atomicAdd(&cnt[(((uint32_t)(key >> shift)) & mask) * kTile + lane], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  uint32_t *h = hist + obs_off[blockIdx.z] * kBins;
+  for (int k = tid; k < kBins * kTile; k += kThreads) {
+    const uint32_t c = cnt[k];      // (a lane that counted holds a group of the tile)
+    if (c) atomicAdd(&h[(int64_t)csr[gs.at_deal + (int64_t)blockIdx.x * kTile + ((k & (kTile - 1)) & me.slot_mask)] * kBins + (k >> 6)], c);
+  }
+  if (pass == 0 && me.active) {
+    atomicMin((unsigned long long *)&state[o_at].minkey, (unsigned long long)kmin);
+    if (bad) atomicOr(&state[o_at].bad, 1u);
+  }
+}
+
+// loo_compact_body over groups: the tail of group g, and parts[part_off[z] + split * G + g]
+template <class F, class MA>
+__device__ __forceinline__ void loo_compact_grouped_body(const double *__restrict__ draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const MA &M,
+                                                         const WaicDataset *__restrict__ sets, const GroupSet *__restrict__ gsets, const int32_t *__restrict__ csr,
+                                                         const int64_t *__restrict__ obs_off, const int64_t *__restrict__ part_off, LooState *__restrict__ state,
+                                                         double *__restrict__ tail, uint32_t cap, double *__restrict__ parts) {
+  constexpr int kRun = stage_len<F>(), R = group_block<F>();
+  static_assert(kRun >= kWaves, "the Draw of this model is too large: fewer than kWaves of them fit in the 48 KiB of LDS a workgroup stages draws in");
+  __shared__ typename F::Draw stage[kRun];
+  __shared__ double wave_b[kWaves - 1][kTile];
+  const int d = d0 + (int)blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WaicDataset ds = sets[d];
+  const GroupSet gs = gsets[d];
+  const int64_t n = gs.G, S = rows * cpd, splits = waic_splits(S, n);
+  if ((int64_t)blockIdx.x * kTile >= n || (int64_t)blockIdx.y >= splits) return;      // (uniform over the workgroup)
+  const auto &Md = dataset_model(M, d);
+  const int64_t s_begin = split_begin(S, splits, blockIdx.y), s_end = split_begin(S, splits, (int64_t)blockIdx.y + 1);
+  const GroupLane me = group_lane(gs, csr, blockIdx.x, lane, wave, false);
+  const int32_t *member = csr + gs.at_member;
+  const int64_t o_at = obs_off[blockIdx.z] + me.g;
+  const LooState st = state[o_at];
+  const double a0 = select_value(st.minkey);
+  double *my_tail = tail + o_at * cap;
+  double b = 0.0;
+  for (int64_t s0 = s_begin; s0 < s_end; s0 += kRun) {
+    const int L = (int)(s_end - s0 < kRun ? s_end - s0 : kRun);
+    __syncthreads();
+    if (tid < L) stage[tid] = draw_at<F>(draws, PR, C, cpd, d, s0 + tid, Md, ds);
+    __syncthreads();
+    for (int jb = me.active ? wave : L; jb < L; jb += kWaves * R) {      // (a lane beyond the tile's groups evaluates nothing)
+      double l[R];
+      group_terms<F, R>(Md, ds, member, me.m0, me.m1, stage, jb, kWaves, L, draws, C, l);
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (jb + kWaves * r >= L) break;
+        const uint64_t key = select_key(l[r]);
+        const bool take = st.inclusive ? key <= st.thr : key < st.thr;
+        if (take) {
+          const uint32_t at = atomicAdd(&state[o_at].cursor, 1u);
+          if (at < cap) my_tail[at] = l[r];      // (as loo_compact_body: the comparison keeps a wrong count inside the buffer)
+        } else if (key > st.thr) {
+          b += waic_exp(a0 - l[r]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (wave > 0) wave_b[wave - 1][lane] = b;
+  __syncthreads();
+  if (wave != 0 || !me.active) return;
+#pragma unroll
+  for (int w = 1; w < kWaves; ++w) b += wave_b[w - 1][lane];
+  parts[part_off[blockIdx.z] + (int64_t)blockIdx.y * n + me.g] = b;
+}
+
 }  // namespace amwg
 
 // ---- a translated closure's pointwise terms (hiprtc; the program is `source`, the UserTerms text, then this header under AMWG_POINTWISE_USER: amwg_rtc.hip)
@@ -432,5 +713,25 @@ extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_loo_compact
 extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_waic_fold(const double *window, int64_t nrows, int64_t g0, int64_t window_rows, int PR, int64_t C, int64_t cpd,
                                                                                const amwg::UserTermsArg M, const WaicDataset *sets, const int64_t *state_off, amwg::Part *state) {
   amwg::waic_fold_body<amwg::UserFamily>(window, nrows, g0, window_rows, PR, C, cpd, M, sets, state_off, state);
+}
+// ... and over groups of observations
+extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_waic_partial_grouped(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const amwg::UserTermsArg M,
+                                                                                          const WaicDataset *sets, const GroupSet *gsets, const int32_t *csr, const int64_t *part_off,
+                                                                                          amwg::Part *parts) {
+  amwg::waic_partial_grouped_body<amwg::UserFamily>(draws, rows, PR, C, cpd, d0, M, sets, gsets, csr, part_off, parts);
+}
+extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_waic_loglik_grouped(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, const amwg::UserTermsArg M,
+                                                                                         const WaicDataset *sets, const GroupSet *gsets, const int32_t *csr, double *out, int64_t g_max) {
+  amwg::waic_loglik_grouped_body<amwg::UserFamily>(draws, rows, PR, C, cpd, M, sets, gsets, csr, out, g_max);
+}
+extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_loo_hist_grouped(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const amwg::UserTermsArg M,
+                                                                                      const WaicDataset *sets, const GroupSet *gsets, const int32_t *csr, const int64_t *obs_off,
+                                                                                      amwg::LooState *state, uint32_t *hist, int pass) {
+  amwg::loo_hist_grouped_body<amwg::UserFamily>(draws, rows, PR, C, cpd, d0, M, sets, gsets, csr, obs_off, state, hist, pass);
+}
+extern "C" __global__ void __launch_bounds__(amwg::kThreads) amwg_pw_loo_compact_grouped(const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, int d0, const amwg::UserTermsArg M,
+                                                                                         const WaicDataset *sets, const GroupSet *gsets, const int32_t *csr, const int64_t *obs_off,
+                                                                                         const int64_t *part_off, amwg::LooState *state, double *tail, uint32_t cap, double *parts) {
+  amwg::loo_compact_grouped_body<amwg::UserFamily>(draws, rows, PR, C, cpd, d0, M, sets, gsets, csr, obs_off, part_off, state, tail, cap, parts);
 }
 #endif

@@ -4,8 +4,10 @@
 // totals are in their files.  Part of libamwg.so; not a source of the step kernels (tools/build_id.py).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 #include <vector>
 
 #include "amwg_dataset.h"
@@ -50,6 +52,55 @@ int amwg_pointwise_family(const char *call, const WaicModel &model, int PR, int 
   K.family = model;
   for (int k = 0; k < 2; ++k) { K.fn[kPwWaicPartial + k] = amwg_waic_family_fn(model.model, k); K.fn[kPwLooHist + k] = amwg_loo_family_fn(model.model, k); }
   K.fn[kPwWaicFold] = amwg_waic_family_fn(model.model, 2);
+  for (int k = 0; k < 4; ++k) K.fn[kPwGrouped + k] = amwg_grouped_family_fn(model.model, k);
+  return AMWG_OK;
+}
+
+int32_t amwg_group_csr(const int32_t *labels, int32_t n, std::vector<int32_t> &start, std::vector<int32_t> &member, std::vector<int32_t> &deal) {
+  member.resize((size_t)n);
+  std::iota(member.begin(), member.end(), 0);
+  std::stable_sort(member.begin(), member.end(), [&](int32_t a, int32_t b) { return labels[a] < labels[b]; });
+  start.clear();
+  for (int32_t m = 0; m < n; ++m) if (m == 0 || labels[member[(size_t)m]] != labels[member[(size_t)m - 1]]) start.push_back(m);
+  const int32_t G = (int32_t)start.size();
+  start.push_back(n);
+  deal.resize((size_t)G);
+  std::iota(deal.begin(), deal.end(), 0);
+  std::stable_sort(deal.begin(), deal.end(), [&](int32_t a, int32_t b) { return start[(size_t)a + 1] - start[(size_t)a] > start[(size_t)b + 1] - start[(size_t)b]; });
+  return G;
+}
+
+int amwg_pointwise_labels(const char *call, const int32_t *labels) {
+  return labels ? AMWG_OK : amwg_fail(AMWG_EINVAL, "%s: NULL labels: a grouped call needs a label per observation", call);
+}
+
+int amwg_pointwise_groups(const char *call, PointwiseLaunch &K, const WaicDataset *sets, int D, const int32_t *labels, hipStream_t stream, PointwiseGroups &g) {
+  if (K.bern)
+    return amwg_fail(AMWG_EINVAL, "%s: the Bernoulli family is served through the two values an observation can take, which does not carry over to sums over groups: "
+                     "not served by the grouped calls", call);
+  g.by_group.assign(sets, sets + D);
+  g.gsets.assign((size_t)D, GroupSet{});
+  g.csr.clear();
+  std::vector<int32_t> start, member, deal;
+  for (int d = 0; d < D; ++d) {
+    const int32_t n = sets[d].n_obs;
+    if (n < 0) return amwg_fail(AMWG_EINVAL, "%s: dataset %d: n_obs < 0", call, d);
+    const int32_t G = amwg_group_csr(labels, n, start, member, deal);
+    GroupSet &gs = g.gsets[(size_t)d];
+    gs.G = G;
+    gs.at_start = (int64_t)g.csr.size(); g.csr.insert(g.csr.end(), start.begin(), start.end());
+    gs.at_member = (int64_t)g.csr.size(); g.csr.insert(g.csr.end(), member.begin(), member.end());
+    gs.at_deal = (int64_t)g.csr.size(); g.csr.insert(g.csr.end(), deal.begin(), deal.end());
+    g.by_group[(size_t)d].n_obs = G;
+    labels += n;
+  }
+  HIP_TRY(g.d_sets.alloc((size_t)D * sizeof(WaicDataset)));
+  HIP_TRY(g.d_gsets.alloc((size_t)D * sizeof(GroupSet)));
+  HIP_TRY(g.d_csr.alloc(g.csr.size() * 4));
+  HIP_TRY(hipMemcpyAsync(g.d_sets.p, sets, (size_t)D * sizeof(WaicDataset), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(g.d_gsets.p, g.gsets.data(), (size_t)D * sizeof(GroupSet), hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(g.d_csr.p, g.csr.data(), g.csr.size() * 4, hipMemcpyHostToDevice, stream));
+  K.groups = &g;
   return AMWG_OK;
 }
 
@@ -141,6 +192,12 @@ int amwg_pointwise_describe_user(amwg_sampler *s, std::vector<WaicDataset> &sets
   hipFunction_t fold = nullptr;      // (the fifth entry is looked up where it is asked for: the handle's layout stays as it is)
   HIP_TRY(hipModuleGetFunction(&fold, s->pw_module, "amwg_pw_waic_fold"));
   K.fn[kPwWaicFold] = fold;
+  static const char *const kGrouped[4] = {"amwg_pw_waic_partial_grouped", "amwg_pw_waic_loglik_grouped", "amwg_pw_loo_hist_grouped", "amwg_pw_loo_compact_grouped"};
+  for (int k = 0; k < 4; ++k) {
+    hipFunction_t f = nullptr;
+    HIP_TRY(hipModuleGetFunction(&f, s->pw_module, kGrouped[k]));
+    K.fn[kPwGrouped + k] = f;
+  }
   K.user.d = s->d;
   K.user.table = s->n_datasets > 1 ? s->d_user_ds_table : nullptr;
   K.user.row_stride = s->user_ds_row_stride;
@@ -169,8 +226,10 @@ extern "C" int amwg_set_pointwise(amwg_sampler *s, const char *terms_source) {
 
 extern "C" int64_t amwg_pointwise_n_obs(const amwg_sampler *s) { return s && s->user && !s->pw_terms.empty() ? s->pw_n_obs : 0; }
 
-int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int32_t *high, double *pointwise, PointwiseShapeFn shape, PointwiseRunFn run) {
+int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int32_t *high, double *pointwise, PointwiseShapeFn shape, PointwiseRunFn run, bool grouped,
+                         const int32_t *labels, int32_t *n_groups_out) {
   if (!s || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (grouped) TRYB(amwg_pointwise_labels(call, labels));
   if (s->user && s->pw_terms.empty()) return amwg_fail(AMWG_EINVAL, "%s: the pointwise terms of a closure are not known to the library; built-in families only", call);
   TRYB(amwg_need_stored_draws(s, call));
   const int D = s->n_datasets, PR = s->P + s->D;
@@ -186,5 +245,9 @@ int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int
     TRYB(amwg_waic_describe(s, sets, m));
     TRYB(amwg_pointwise_family(call, m, PR, D, K));
   }
-  return run(call, s->last_draws, s->last_rows, PR, s->C, D, K, sets.data(), summary, high, pointwise, nullptr, 0, s->stream);
+  if (!grouped) return run(call, s->last_draws, s->last_rows, PR, s->C, D, K, sets.data(), summary, high, pointwise, nullptr, 0, s->stream);
+  PointwiseGroups groups;
+  TRYB(amwg_pointwise_groups(call, K, sets.data(), D, labels, s->stream, groups));
+  if (n_groups_out) for (int d = 0; d < D; ++d) n_groups_out[d] = groups.gsets[(size_t)d].G;
+  return run(call, s->last_draws, s->last_rows, PR, s->C, D, K, groups.by_group.data(), summary, high, pointwise, nullptr, 0, s->stream);
 }

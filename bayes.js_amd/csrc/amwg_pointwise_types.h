@@ -10,6 +10,14 @@ struct WaicDataset {
   int64_t off_x, off_y, off_lfact, off_xb;
 };
 
+// one dataset's groups of observations as the grouped kernels read them (leave-one-group-out: include/amwg.h), places in the call's one int32 array `csr`:
+// start[G + 1] by group number (the distinct labels ascending), member[n_obs] the observation indices by (label, index), deal[G] the group a slot of the tiles
+// holds -- the groups by falling size, equal sizes by rising number, so that a wavefront's 64 lanes hold groups of similar length
+struct GroupSet {
+  int32_t G, pad;
+  int64_t at_start, at_member, at_deal;
+};
+
 namespace amwg {
 // the model argument of a translated closure: its DataRef; a dataset sampler's table of pointers [n_datasets][row_stride] (amwg_user_dataset.h), nullptr otherwise
 struct UserTermsArg {

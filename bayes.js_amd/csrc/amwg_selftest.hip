@@ -1,5 +1,6 @@
 // amwg_selftest.hip -- the test-only entry points of include/amwg_selftest.h: the building blocks one by one, for the test suite.  Linked into
 // libamwg_selftest.so beside the product's own objects (csrc/Makefile, -DAMWG_SELFTEST); NOT part of libamwg.so.
+#include <algorithm>
 #include <cstring>
 
 #include "../../include/amwg_selftest.h"
@@ -368,9 +369,11 @@ static int waic_pack(int D, Len len, Fill fill, std::vector<int64_t> &off, DevBu
 // amwg_waic_check and amwg_loo_check: the arguments checked, the draws and the family's data on the device as the sampler lays them, then the launcher of either
 // (extra: WAIC's loglik, or LOO's tails)
 static int pointwise_check(const char *call, bool loo, int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models,
-                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra, int64_t window_rows = 0, size_t *state_bytes = nullptr) {
+                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra, int64_t window_rows = 0, size_t *state_bytes = nullptr,
+                           bool grouped = false, const int32_t *labels = nullptr, int32_t *n_groups_out = nullptr) {
   double *loglik = loo ? nullptr : extra;
   if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (grouped) TRYB(amwg_pointwise_labels(call, labels));
   if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
   TRYB(loo ? amwg_loo_shape(call, rows, PR, C, D) : amwg_waic_shape(call, rows, PR, C, D));
   if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
@@ -446,6 +449,14 @@ static int pointwise_check(const char *call, bool loo, int32_t device, const dou
     if (state_bytes) *state_bytes = f.state_bytes;
     return amwg_waic_fold_finish(call, f, summary, high, pointwise, nullptr);
   }
+  if (grouped) {      // the grouped calls' route (amwg_pointwise_entry): the family described, the groups made of the labels, the run over the datasets by group
+    PointwiseLaunch K;
+    TRYB(amwg_pointwise_family(call, wm, PR, D, K));
+    PointwiseGroups groups;
+    TRYB(amwg_pointwise_groups(call, K, sets.data(), D, labels, nullptr, groups));
+    if (n_groups_out) for (int d = 0; d < D; ++d) n_groups_out[d] = groups.gsets[(size_t)d].G;
+    return (loo ? amwg_loo_run : amwg_waic_run)(call, dd.as<double>(), rows, PR, C, D, K, groups.by_group.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
+  }
   return (loo ? amwg_loo_launch : amwg_waic_launch)(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
 }
 extern "C" {
@@ -466,11 +477,33 @@ int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR
   return pointwise_check("amwg_loo_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, tails);
 }
 
+int amwg_waic_grouped_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const int32_t *labels,
+                            int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik, int32_t *n_groups_out) {
+  return pointwise_check("amwg_waic_grouped_check", false, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, loglik, 0, nullptr, true, labels, n_groups_out);
+}
+
+int amwg_loo_grouped_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const int32_t *labels,
+                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails, int32_t *n_groups_out) {
+  return pointwise_check("amwg_loo_grouped_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, tails, 0, nullptr, true, labels, n_groups_out);
+}
+
+int amwg_group_csr_check(const int32_t *labels, int32_t n, int32_t *start, int32_t *member, int32_t *deal, int32_t *n_groups) {
+  if (!labels || n < 1 || !start || !member || !deal || !n_groups) return amwg_fail(AMWG_EINVAL, "amwg_group_csr_check: null argument or n < 1");
+  std::vector<int32_t> st, mb, dl;
+  *n_groups = amwg_group_csr(labels, n, st, mb, dl);
+  std::copy(st.begin(), st.end(), start);
+  std::copy(mb.begin(), mb.end(), member);
+  std::copy(dl.begin(), dl.end(), deal);
+  return AMWG_OK;
+}
+
 // amwg_user_waic_check and amwg_user_loo_check: a closure's source and pointwise text, its arrays per dataset as amwg_create_user_datasets takes them, on a handle
 // that holds nothing but those (no chains, no step kernel): the arrays uploaded as a sampler's, the code object compiled and loaded as its first WAIC / LOO call does
 static int user_pointwise_check(const char *call, bool loo, int32_t device, const amwg_user_model *models, int32_t D, int32_t P, const char *terms, const double *draws, int64_t rows,
-                                int32_t PR, int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra) {
+                                int32_t PR, int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra, bool grouped = false,
+                                const int32_t *labels = nullptr, int32_t *n_groups_out = nullptr) {
   if (!models || !terms || !draws || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (grouped) TRYB(amwg_pointwise_labels(call, labels));
   if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
   TRYB(loo ? amwg_loo_shape(call, rows, PR, C, D) : amwg_waic_shape(call, rows, PR, C, D));
   if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
@@ -499,7 +532,13 @@ static int user_pointwise_check(const char *call, bool loo, int32_t device, cons
   std::vector<WaicDataset> sets;
   PointwiseLaunch K;
   TRYB(amwg_pointwise_describe_user(s, sets, K));
-  return (loo ? amwg_loo_run : amwg_waic_run)(call, dd.as<double>(), rows, PR, C, D, K, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
+  PointwiseGroups groups;
+  if (grouped) {
+    TRYB(amwg_pointwise_groups(call, K, sets.data(), D, labels, nullptr, groups));
+    if (n_groups_out) for (int d = 0; d < D; ++d) n_groups_out[d] = groups.gsets[(size_t)d].G;
+  }
+  return (loo ? amwg_loo_run : amwg_waic_run)(call, dd.as<double>(), rows, PR, C, D, K, grouped ? groups.by_group.data() : sets.data(), summary, high, pointwise, extra,
+                                              (size_t)scratch_bytes, nullptr);
 }
 
 int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR, int64_t C,
@@ -510,6 +549,18 @@ int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t 
 int amwg_user_loo_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR, int64_t C,
                         int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails) {
   return user_pointwise_check("amwg_user_loo_check", true, device, models, n_datasets, P, terms_source, draws, rows, PR, C, scratch_bytes, summary, high, pointwise, tails);
+}
+
+int amwg_user_waic_grouped_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                                 int64_t C, const int32_t *labels, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik, int32_t *n_groups_out) {
+  return user_pointwise_check("amwg_user_waic_grouped_check", false, device, models, n_datasets, P, terms_source, draws, rows, PR, C, scratch_bytes, summary, high, pointwise, loglik,
+                              true, labels, n_groups_out);
+}
+
+int amwg_user_loo_grouped_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                                int64_t C, const int32_t *labels, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails, int32_t *n_groups_out) {
+  return user_pointwise_check("amwg_user_loo_grouped_check", true, device, models, n_datasets, P, terms_source, draws, rows, PR, C, scratch_bytes, summary, high, pointwise, tails,
+                              true, labels, n_groups_out);
 }
 
 int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms) {

@@ -47,13 +47,16 @@ struct WaicModel {
 // HOW A CALL LAUNCHES THE KERNELS THAT EVALUATE THE MODEL (amwg_pointwise.h), as plain data: the instantiations for a built-in family (amwg_pointwise_family), or the
 // entries of a closure's code object (amwg_pointwise_describe_user).  The two take the same argument lists, the model in the same slot; everything else of a call is
 // the same code for both.
-enum PointwiseKernel { kPwWaicPartial, kPwWaicLoglik, kPwLooHist, kPwLooCompact, kPwWaicFold, kPwKernels };      // (the first four: the order of amwg_sampler::pw_fn)
+// The four grouped twins (leave-one-group-out) stand kPwGrouped after the kernel they replace.
+enum PointwiseKernel { kPwWaicPartial, kPwWaicLoglik, kPwLooHist, kPwLooCompact, kPwWaicFold, kPwGrouped, kPwKernels = kPwGrouped + 4 };      // (the first four: the order of amwg_sampler::pw_fn)
+struct PointwiseGroups;
 struct PointwiseLaunch {
   bool bern = false;                   // the family of two observations per dataset (its pairs are picked by x_i afterwards)
   bool builtin = false;                // a built-in family: `family` is the model argument and fn[] are addresses of the kernels' instantiations (hipLaunchKernel);
   WaicModel family{};                  // a closure: `user`, and fn[] are the hipFunction_t of its code object (hipModuleLaunchKernel)
   amwg::UserTermsArg user{};
   const void *fn[kPwKernels] = {};
+  const PointwiseGroups *groups = nullptr;      // a grouped call (amwg_pointwise_groups): the walking kernels are fn[kPwGrouped + k] and take the groups after `sets`
   void *model_arg() const { return builtin ? (void *)&family : (void *)&user; }      // the model's slot of an args[] list
 };
 
@@ -71,6 +74,16 @@ struct PointwiseOut {
   DevBuf sets, pw, extra;
 };
 
+// THE GROUPS OF A GROUPED CALL (include/amwg.h, leave-one-group-out).  From the joint terms on, a group is what an observation is to an ungrouped call: the plan, the
+// merge, pick and fit kernels, the outputs and the totals take `by_group` -- the datasets with n_obs = G_d -- for `sets`; only the walking kernels read the
+// observations' own sets and the CSR (GroupSet, amwg_pointwise_types.h), uploaded once per call.
+struct PointwiseGroups {
+  std::vector<WaicDataset> by_group;      // [D], host: the call's `sets`
+  std::vector<GroupSet> gsets;            // [D], host
+  std::vector<int32_t> csr;               // every dataset's start, member and deal, back to back
+  DevBuf d_sets, d_gsets, d_csr;          // the observations' sets [D], gsets and csr on the device
+};
+
 // the built-in families, in the order of AMWG_MODEL_* from AMWG_MODEL_NORMAL on: the one list the two units expand into their instantiations
 template <int... MODEL> struct PointwiseModels {};
 typedef PointwiseModels<AMWG_MODEL_NORMAL, AMWG_MODEL_BETA_BERN, AMWG_MODEL_HIER_NORMAL, AMWG_MODEL_POIS_GLM> BuiltinModels;
@@ -80,8 +93,18 @@ static_assert(AMWG_MODEL_BETA_BERN == AMWG_MODEL_NORMAL + 1 && AMWG_MODEL_HIER_N
 // the address of a built-in family's instantiation, model one of BuiltinModels (amwg_waic.hip: k = 0 the partial kernel, 1 loglik, 2 the fold; amwg_loo.hip: k = 0 hist, 1 compact)
 const void *amwg_waic_family_fn(int model, int k);
 const void *amwg_loo_family_fn(int model, int k);
+// ... of its grouped twin of kernel k < 4 (amwg_grouped.hip; nullptr for the Bernoulli family, which the grouped calls refuse)
+const void *amwg_grouped_family_fn(int model, int k);
 // K of a built-in family.  AMWG_EINVAL "<call>: ..." for an unknown model, draws of fewer components than the family reads, the hierarchical family on D != 1.
 int amwg_pointwise_family(const char *call, const WaicModel &model, int PR, int D, PointwiseLaunch &K);
+// The groups of D datasets from their labels back to back (n_d each), by the rule of include/amwg.h, uploaded on `stream`; K.groups = &g, which must outlive the
+// run.  AMWG_EINVAL "<call>: ..." for the Bernoulli family; nothing is launched.  labels are not NULL: amwg_pointwise_labels is the one refusal of NULL labels, which
+// the bodies of the grouped entries ask before they open a device or compile a closure's text.  The groups' own device memory (below) is no part of the scratch
+// budget: it lives for the whole call, across its batches.  amwg_group_csr: one dataset's start [G + 1], member [n] and
+// deal [G] from its labels alone -> G (host only)
+int amwg_pointwise_groups(const char *call, PointwiseLaunch &K, const WaicDataset *sets, int D, const int32_t *labels, hipStream_t stream, PointwiseGroups &g);
+int amwg_pointwise_labels(const char *call, const int32_t *labels);
+int32_t amwg_group_csr(const int32_t *labels, int32_t n, std::vector<int32_t> &start, std::vector<int32_t> &member, std::vector<int32_t> &deal);
 // entry k of K over `grid` workgroups of kThreads; args: the kernel's argument list, K.model_arg() in the model's slot
 hipError_t amwg_pointwise_go(const PointwiseLaunch &K, int k, dim3 grid, hipStream_t stream, void **args);
 hipError_t amwg_pointwise_fill_nan(double *out, int64_t count, hipStream_t stream);
@@ -100,8 +123,10 @@ int amwg_pointwise_fetch(const PointwiseOut &o, double *pw, double *extra);
 typedef int (*PointwiseRunFn)(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,
                               int32_t *high, double *pointwise, double *extra, size_t scratch_bytes, hipStream_t stream);
 typedef int (*PointwiseShapeFn)(const char *call, int64_t rows, int PR, int64_t C, int D);
-// the body of amwg_last_sample_dataset_waic and amwg_last_sample_dataset_loo: the refusals, the sampler's datasets and model described, `run`
-int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int32_t *high, double *pointwise, PointwiseShapeFn shape, PointwiseRunFn run);
+// the body of amwg_last_sample_dataset_waic and amwg_last_sample_dataset_loo: the refusals, the sampler's datasets and model described, `run`.  grouped: the body of
+// their _grouped twins -- labels as amwg_pointwise_groups takes them, n_groups_out [D] or nullptr, pointwise [D][G_max][..]
+int amwg_pointwise_entry(const char *call, amwg_sampler *s, double *summary, int32_t *high, double *pointwise, PointwiseShapeFn shape, PointwiseRunFn run,
+                         bool grouped = false, const int32_t *labels = nullptr, int32_t *n_groups_out = nullptr);
 // Host outputs: summary [D][4] (elpd_waic, se, p_waic, lppd), high [D] or nullptr, pointwise nullptr or [D][n_max][2] (NaN beyond n_d; n_max the largest n_obs), loglik
 // nullptr or [D][S][n_max] (the terms themselves; the test library only).
 int amwg_waic_run(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, double *summary,

@@ -71,18 +71,28 @@ int run_kernels(const double *draws, int64_t rows, int PR, int64_t C, int D, con
   HIP_TRY(hipMemcpyAsync(off.p, plan.off.data() + D, (size_t)D * 8, hipMemcpyHostToDevice, stream));
   HIP_TRY(parts.alloc((size_t)plan.most_parts * sizeof(Part)));
   Part *d_parts = parts.as<Part>();
+  // a grouped call: `sets` and d_sets count groups; the walking kernels take the observations' sets and the groups in their place
+  const int walk = K.groups ? kPwGrouped : 0;
+  const WaicDataset *obs_sets = K.groups ? K.groups->d_sets.as<WaicDataset>() : d_sets;
+  const GroupSet *gsets = K.groups ? K.groups->d_gsets.as<GroupSet>() : nullptr;
+  const int32_t *csr = K.groups ? K.groups->d_csr.as<int32_t>() : nullptr;
   for (const PointwiseBatch &b : plan.batches) {
     if (b.tiles == 0) continue;
     int d0 = b.d0;
     const int64_t *part_off = off.as<int64_t>() + d0;
     void *args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &part_off, &d_parts};
-    HIP_TRY(amwg_pointwise_go(K, kPwWaicPartial, dim3((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), stream, args));
+    void *grouped_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &part_off, &d_parts};
+    HIP_TRY(amwg_pointwise_go(K, walk + kPwWaicPartial, dim3((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), stream, K.groups ? grouped_args : args));
     hipLaunchKernelGGL(waic_merge_kernel, dim3((unsigned)((b.n_most + kThreads - 1) / kThreads), (unsigned)(b.d1 - d0)), dim3(kThreads), 0, stream, rows, cpd, d0, d_sets, K.bern ? 1 : 0,
                        part_off, d_parts, out, out_stride);
     HIP_TRY(hipGetLastError());
   }
   if (K.bern) HIP_TRY(amwg_pointwise_bern_expand(K, d_sets, D, two.as<double>(), d_pw, n_max, 2, stream));
-  if (d_loglik) {
+  if (d_loglik && K.groups) {      // [D][S][G_max]: a tile of 64 groups per workgroup, the draws in as many rows of workgroups as a grid takes
+    void *args[] = {&draws, &rows, &PR, &C, &cpd, K.model_arg(), &obs_sets, &gsets, &csr, &d_loglik, &n_max};
+    const int64_t rows_of_blocks = (S + kWaves - 1) / kWaves;
+    HIP_TRY(amwg_pointwise_go(K, kPwGrouped + kPwWaicLoglik, dim3((unsigned)((n_max + kTile - 1) / kTile), (unsigned)(rows_of_blocks < 65535 ? rows_of_blocks : 65535), (unsigned)D), stream, args));
+  } else if (d_loglik) {
     void *args[] = {&draws, &rows, &PR, &C, &cpd, K.model_arg(), &d_sets, &d_loglik, &n_max};
     HIP_TRY(amwg_pointwise_go(K, kPwWaicLoglik, dim3((unsigned)((n_max + kThreads - 1) / kThreads), (unsigned)S, (unsigned)D), stream, args));
   }
@@ -157,4 +167,8 @@ extern "C" int amwg_last_sample_dataset_waic(amwg_sampler *s, double *summary, i
     return amwg_waic_fold_finish(call, *f, summary, high, pointwise, s->stream);
   }
   return amwg_pointwise_entry(call, s, summary, high, pointwise, amwg_waic_shape, amwg_waic_run);
+}
+
+extern "C" int amwg_last_sample_dataset_waic_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out) {
+  return amwg_pointwise_entry("amwg_last_sample_dataset_waic_grouped", s, summary, high, pointwise, amwg_waic_shape, amwg_waic_run, true, labels, n_groups_out);
 }

@@ -647,12 +647,35 @@ AmwgSampler.prototype.hpd = function (probs) {
  *  p_i > 0.4: WAIC is unreliable there)[, pointwise: [[lppd_i, p_i] per observation]]}, ...].  The rule of include/amwg.h: the family's own pointwise terms over the
  *  dataset's chains x kept draws on the device, lppd_i by log-sum-exp and p_i the variance of the terms; the totals in index order.  Built-in families only.  A
  *  dataset lives wholly on one shard: no collective. */
+// opts.groups of dataset_waic / dataset_loo -- leave-one-group-out (include/amwg.h): one Int32Array or array of integer labels, a label per observation, for an
+// ordinary sampler; one per dataset for a dataset sampler -> per shard the Int32Array the library takes, the labels of the shard's datasets back to back
+AmwgSampler.prototype._groupLabels = function (groups, call) {
+  const labels = (g) => {
+    if (!(Array.isArray(g) || ArrayBuffer.isView(g))) throw call + ': options.groups holds arrays of integer labels, one label per observation';
+    const v = Array.from(g);
+    if (!v.every((q) => Number.isInteger(q) && q >= -2147483648 && q <= 2147483647)) throw call + ': a label is an int32';
+    return v;
+  };
+  if (!(this.options && this.options.datasets)) { const one = Int32Array.from(labels(groups)); return this._shards.map(() => one); }      // (every shard holds the one dataset)
+  if (!Array.isArray(groups) || groups.length !== this.n_datasets) throw call + ': options.groups needs one array of labels per dataset (' + this.n_datasets + ')';
+  let at = 0;
+  return this._shards.map((sh) => {
+    const flat = [];
+    for (let d = 0; d < sh.datasets; d++) flat.push(...labels(groups[at++]));
+    return Int32Array.from(flat);
+  });
+};
+
+/** With opts.groups (see _groupLabels): over GROUPS of observations, leave-one-group-out -- every entry counts groups (the distinct labels in ascending order) where
+ *  it counts observations, pointwise has an entry per group, and n_groups says how many (amwg_last_sample_dataset_waic_grouped). */
 AmwgSampler.prototype.dataset_waic = function (opts) {
   const N = native(), want = !!(opts && opts.pointwise), out = [];
-  for (const sh of this._shards) {
-    const r = N.datasetWaic(sh.handle, want);
+  const labels = opts && opts.groups ? this._groupLabels(opts.groups, 'dataset_waic') : null;
+  for (const [k, sh] of this._shards.entries()) {
+    const r = labels ? N.datasetWaicGrouped(sh.handle, want, labels[k]) : N.datasetWaic(sh.handle, want);
     for (let d = 0; d < r.datasets; d++) {
       const o = { elpd_waic: r.summary[d * 4], se: r.summary[d * 4 + 1], p_waic: r.summary[d * 4 + 2], lppd: r.summary[d * 4 + 3], waic: -2 * r.summary[d * 4], high_variance: r.high[d] };
+      if (labels) o.n_groups = r.n_obs[d];
       if (want) o.pointwise = Array.from({ length: r.n_obs[d] }, (_, i) => [r.pointwise[(d * r.n_max + i) * 2], r.pointwise[(d * r.n_max + i) * 2 + 1]]);
       out.push(o);
     }
@@ -672,6 +695,7 @@ AmwgSampler.prototype.waic = function (opts) {
 function compare_waic(a, b) {
   if (!a || !b || !Array.isArray(a.pointwise) || !Array.isArray(b.pointwise)) throw 'compare_waic: both results need pointwise (ask for {pointwise: true})';
   const n = a.pointwise.length;
+  if (a.n_groups !== b.n_groups) throw 'compare_waic: the results hold ' + (a.n_groups === undefined ? 'observations' : a.n_groups + ' groups') + ' and ' + (b.n_groups === undefined ? 'observations' : b.n_groups + ' groups') + ': not the same units';
   if (n !== b.pointwise.length) throw 'compare_waic: the results hold ' + n + ' and ' + b.pointwise.length + ' observations: not the same data';
   const diff = new Float64Array(n);
   let elpd_diff = 0;
@@ -686,12 +710,15 @@ function compare_waic(a, b) {
  *  khat_i > 0.7: the estimate is unreliable there)[, pointwise: [[elpd_loo_i, lppd_i, khat_i] per observation]]}, ...].  The rule of include/amwg.h: per observation
  *  the smallest terms over the dataset's chains x kept draws selected, sorted and fitted by a generalised Pareto on the device, the importance weights smoothed;
  *  the totals in index order.  What to use where dataset_waic() reports high_variance.  Built-in families only.  A dataset lives wholly on one shard: no collective. */
+/** With opts.groups: over groups of observations, as dataset_waic (amwg_last_sample_dataset_loo_grouped). */
 AmwgSampler.prototype.dataset_loo = function (opts) {
   const N = native(), want = !!(opts && opts.pointwise), out = [];
-  for (const sh of this._shards) {
-    const r = N.datasetLoo(sh.handle, want);
+  const labels = opts && opts.groups ? this._groupLabels(opts.groups, 'dataset_loo') : null;
+  for (const [k, sh] of this._shards.entries()) {
+    const r = labels ? N.datasetLooGrouped(sh.handle, want, labels[k]) : N.datasetLoo(sh.handle, want);
     for (let d = 0; d < r.datasets; d++) {
       const o = { elpd_loo: r.summary[d * 4], se: r.summary[d * 4 + 1], p_loo: r.summary[d * 4 + 2], lppd: r.summary[d * 4 + 3], looic: -2 * r.summary[d * 4], high_k: r.high[d] };
+      if (labels) o.n_groups = r.n_obs[d];
       if (want) o.pointwise = Array.from({ length: r.n_obs[d] }, (_, i) => [0, 1, 2].map((k) => r.pointwise[(d * r.n_max + i) * 3 + k]));
       out.push(o);
     }
@@ -709,6 +736,7 @@ AmwgSampler.prototype.loo = function (opts) {
 function compare_loo(a, b) {
   if (!a || !b || !Array.isArray(a.pointwise) || !Array.isArray(b.pointwise)) throw 'compare_loo: both results need pointwise (ask for {pointwise: true})';
   const n = a.pointwise.length;
+  if (a.n_groups !== b.n_groups) throw 'compare_loo: the results hold ' + (a.n_groups === undefined ? 'observations' : a.n_groups + ' groups') + ' and ' + (b.n_groups === undefined ? 'observations' : b.n_groups + ' groups') + ': not the same units';
   if (n !== b.pointwise.length) throw 'compare_loo: the results hold ' + n + ' and ' + b.pointwise.length + ' observations: not the same data';
   const diff = new Float64Array(n);
   let elpd_diff = 0;

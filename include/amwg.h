@@ -329,6 +329,28 @@ int amwg_waic_info(const amwg_sampler *s, int32_t *armed, size_t *bytes);
  * A translated closure whose pointwise text is set is served as by amwg_last_sample_dataset_waic: the same observations, the same doubles, the same kStage rule. */
 int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary /* [D][4]: elpd_loo, se, p_loo, lppd */, int32_t *high /* [D] or NULL: observations with khat_i > 0.7 */,
                                  double *pointwise /* NULL or [D][n_max][3]: elpd_loo_i, lppd_i, khat_i; NaN beyond n_d */);
+/* WAIC and PSIS-LOO OVER GROUPS OF OBSERVATIONS -- leave-one-group-out: how well the model predicts a school, a patient or a segment it has not seen, where the two
+ * calls above ask about one more measurement of a group it knows.
+ * THE RULE.  Every observation i of dataset d carries an int32 label: labels holds the datasets' label arrays back to back, n_d each (amwg_dataset_n_obs; a closure:
+ *   kTermN each).  Labels need not be sorted, contiguous or dense.  The distinct labels of a dataset in ascending order are its groups g = 0 ... G_d - 1.
+ *   THE JOINT TERM  L_sg = (((l_s,i1 + l_s,i2) + l_s,i3) + ...) over the members i1 < i2 < i3 < ... of g in ASCENDING OBSERVATION INDEX: it starts from the first
+ *   member's term and takes fp64 additions in exactly that order; l_si is the pointwise term of the calls above, bit for bit.  The order depends on nothing else --
+ *   not on the launch geometry, not on how many draws a lane holds in registers, not on the other groups.
+ *   From L_sg on, the results are the rules of the two calls above with n := G_d and l := L: per group lppd_g and p_g (the 0.4 flag), elpd_loo_g, lppd_g and khat_g (the
+ *   0.7 flag); the totals and standard errors run over the groups in group order; the bounds hold with L for l.  A group with a non-finite L_sg for some draw gives
+ *   NaN for that group alone.  The split of the draws is waic_splits(S, G_d).  SINGLETON GROUPS (labels = 0 ... n_d - 1, in any order of the label values that leaves
+ *   one observation per group) reproduce the ungrouped call's pointwise bytes exactly, reordered by label.
+ *   summary [D][4] and high [D] (or NULL) as above; pointwise (NULL, or [D][G_max][2] for WAIC, [D][G_max][3] for LOO, NaN beyond G_d), G_max the largest G_d -- at
+ *   most n_max, so room for [D][n_max][..] always suffices; n_groups_out (NULL, or [D]) = G_d.
+ * Served: what the ungrouped calls serve, closures with a pointwise text included, but NOT the Bernoulli family (its two-valued evaluation says nothing about a sum
+ * over a group).  AMWG_EINVAL with a message that names the call, before any launch: a null s or summary, NULL labels, the Bernoulli family, no sample() yet or a
+ * summarising call (no draws are stored), fewer than 2 draws per dataset and the other shape limits of the ungrouped call, a closure without a pointwise text, a
+ * group_local sampler.  Scratch under the 256 MiB budget is the ungrouped call's with G_d for n_d; the groups themselves (4 (n_d + 2 G_d + 1) bytes per dataset, and 72
+ * bytes of description) are uploaded once per call, live across its batches and are NOT counted against that budget.
+ * OUT OF SCOPE: grouped WAIC folded by amwg_sample_summarize (amwg_set_waic folds per observation), amwg_group_* / amwg_comm_* twins, moment matching, tails beyond
+ * the LDS cap. */
+int amwg_last_sample_dataset_waic_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out);
+int amwg_last_sample_dataset_loo_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,

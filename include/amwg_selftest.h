@@ -94,6 +94,21 @@ int amwg_user_waic_check(int32_t device, const amwg_user_model *models, int32_t 
                          int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik);
 int amwg_user_loo_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
                         int64_t C, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails);
+/* The four over GROUPS of observations, the kernels of amwg_last_sample_dataset_waic_grouped / _loo_grouped through the route those calls take: labels are the
+ * datasets' label arrays back to back (n_d each), n_groups_out [D] (or NULL) the G_d; summary, high and pointwise as those calls return them, [D][G_max][2 | 3];
+ * loglik (NULL, or [D][S][G_max]) the joint terms L_sg themselves, under the group's number; tails [D][G_max][M + 1].  NULL labels and the Bernoulli family are
+ * refused by the words of the product's calls. */
+int amwg_waic_grouped_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const int32_t *labels,
+                            int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik, int32_t *n_groups_out);
+int amwg_loo_grouped_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const int32_t *labels,
+                           int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails, int32_t *n_groups_out);
+int amwg_user_waic_grouped_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                                 int64_t C, const int32_t *labels, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *loglik, int32_t *n_groups_out);
+int amwg_user_loo_grouped_check(int32_t device, const amwg_user_model *models, int32_t n_datasets, int32_t P, const char *terms_source, const double *draws, int64_t rows, int32_t PR,
+                                int64_t C, const int32_t *labels, int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *tails, int32_t *n_groups_out);
+/* the groups the host makes of one dataset's labels[n], with no device: start [G + 1] and member [n] (a stable sort of the observation indices by label), deal [G]
+ * (the groups by falling size, equal sizes by rising number: the order they are dealt to the tiles in); *n_groups = G.  Room for n + 1, n and n ints. */
+int amwg_group_csr_check(const int32_t *labels, int32_t n, int32_t *start, int32_t *member, int32_t *deal, int32_t *n_groups);
 /* what the last LOO call of this process did, for the measurement: *passes = the select passes over the terms; ms[4] = milliseconds of the lppd pass, the select,
  * the compaction, the sort and fit (-1 unless timing was on).  Then timing of later calls is switched on (1) or off (0).  Either pointer may be NULL. */
 int amwg_loo_stats(int32_t timing, int32_t *passes, double *ms);
