@@ -865,6 +865,62 @@ static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dat
 static napi_value DatasetWaicGrouped(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, NULL, amwg_last_sample_dataset_waic_grouped, 2); }
 static napi_value DatasetLooGrouped(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, NULL, amwg_last_sample_dataset_loo_grouped, 3); }
 
+/* datasetHeldout(handle, held[], Int32Array index | null, bool pointwise) -> {datasets, m_max, m: Int32Array [datasets], summary: Float64Array [datasets][2]
+ * (elpd_heldout, se)[, pointwise: Float64Array [datasets][m_max] (lppd_j; NaN beyond m_d)]}: held = one model description per dataset of the sampler, the
+ * observations it has not seen (amwg_last_sample_dataset_heldout) */
+static napi_value DatasetHeldout(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  if (!get_args(env, info, 4, a)) return NULL;
+  amwg_sampler *s = unwrap(env, a[0]);
+  if (!s) return NULL;
+  const size_t D = (size_t)amwg_num_datasets(s);
+  uint32_t n_held = 0;
+  if (napi_get_array_length(env, a[1], &n_held) != napi_ok || n_held != D) {
+    napi_throw_error(env, "AMWG_EINVAL", "amwg_napi.datasetHeldout: held must hold one model description per dataset of the sampler");
+    return NULL;
+  }
+  napi_typedarray_type type;
+  size_t n_index = 0;
+  void *index = NULL;
+  if (napi_get_typedarray_info(env, a[2], &type, &n_index, &index, NULL, NULL) != napi_ok || type != napi_int32_array) index = NULL;      /* (null: positions 0 ... m_d - 1) */
+  bool want = false;
+  napi_get_value_bool(env, a[3], &want);
+  int32_t *m = NULL;
+  double *summary = NULL, *pw = NULL;
+  napi_value vm = new_i32(env, D, &m), vs = new_f64(env, D * 2, &summary), vp = NULL;
+  if (!vm || !vs) return NULL;
+  amwg_model_desc *md = (amwg_model_desc *)calloc(D ? D : 1, sizeof *md);
+  size_t total = 0;
+  int32_t m_max = 0;
+  for (uint32_t d = 0; d < n_held; d++) {
+    napi_value e;
+    napi_get_element(env, a[1], d, &e);
+    read_model_desc(env, e, &md[d]);
+    m[d] = md[d].n_obs;
+    total += md[d].n_obs > 0 ? (size_t)md[d].n_obs : 0;
+    m_max = md[d].n_obs > m_max ? md[d].n_obs : m_max;
+  }
+  if (index && n_index != total) {
+    free(md);
+    napi_throw_error(env, "AMWG_EINVAL", "amwg_napi.datasetHeldout: index needs one position per held-out observation of every dataset");
+    return NULL;
+  }
+  if (want) { vp = new_f64(env, D * (size_t)m_max, &pw); if (!vp) { free(md); return NULL; } }
+  int rc = amwg_last_sample_dataset_heldout(s, md, (const int32_t *)index, summary, want ? pw : NULL);
+  free(md);
+  if (rc != AMWG_OK) return throw_amwg(env, rc);
+  napi_value o, t;
+  NAPI_OK(napi_create_object(env, &o));
+  napi_set_named_property(env, o, "summary", vs);
+  napi_set_named_property(env, o, "m", vm);
+  if (want) napi_set_named_property(env, o, "pointwise", vp);
+  napi_create_int32(env, (int32_t)D, &t);
+  napi_set_named_property(env, o, "datasets", t);
+  napi_create_int32(env, m_max, &t);
+  napi_set_named_property(env, o, "m_max", t);
+  return o;
+}
+
 /* setWaic(handle, bool on): amwg_set_waic -- arms (false: disarms) the WAIC fold for later summarising calls */
 static napi_value SetWaic(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -1310,7 +1366,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"datasetHeldout", DatasetHeldout},{"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setWaic", SetWaic}, {"waicInfo", WaicInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

@@ -11,6 +11,7 @@
 #include "amwg_histogram.h"
 #include "amwg_hpd.h"
 #include "amwg_loo.h"
+#include "amwg_heldout.h"
 #include "amwg_waic.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
@@ -464,6 +465,32 @@ extern "C" {
 int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                     int32_t *high, double *pointwise, double *loglik) {
   return pointwise_check("amwg_waic_check", false, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, loglik);
+}
+
+int64_t amwg_heldout_splits_check(int64_t S, int64_t m) { return heldout_splits(S, m); }
+
+// the refusals of amwg_last_sample_dataset_heldout that the arguments alone decide, the draws on the device, then its launcher
+int amwg_heldout_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
+                       const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise) {
+  static const char *call = "amwg_heldout_check";
+  if (!draws || !models || !held || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
+  TRYB(amwg_waic_shape(call, rows, PR, C, D));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
+  for (int d = 1; d < D; ++d)
+    if (models[d].model != models[0].model || models[d].K != models[0].K || models[d].G != models[0].G) return amwg_fail(AMWG_EINVAL, "%s: dataset %d is not of dataset 0's model, K and G", call, d);
+  TRYB(amwg_heldout_validate(call, models[0].model, models[0].G, models[0].K, D, held, index));
+  WaicModel base{};
+  base.model = models[0].model; base.G = models[0].G; base.exact_division = 0;
+  base.neg_half_log_2pi = -0.5 * log_v8(2 * kPi);
+  PointwiseLaunch K;
+  TRYB(amwg_pointwise_family(call, base, PR, D, K));
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  return amwg_heldout_launch(call, dd.as<double>(), rows, PR, C, D, base, held, index, summary, pointwise, (size_t)scratch_bytes, nullptr);
 }
 
 int amwg_waic_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t window_rows, double *summary,

@@ -225,6 +225,7 @@ function AmwgSampler(params, log_post, data, options) {
   // (asked only once it is settled that the family's own kernel runs: a recognised closure that is translated after all takes the flag)
   if (opt('pointwise', false) && recog) throw 'AmwgSampler (MI355X): options.pointwise is for translated closures (options.translate: true); a built-in family needs no flag: waic() and loo() know its pointwise terms';
   this.model = recog ? recog.family : 'translated';
+  this._recog = recog;      // (dataset_heldout describes held-out data objects as the constructor described the data)
   // (the translator folds data-dependent constants and storage types into the generated source: one source per dataset is not one sampler)
   // options.translate: true beside options.datasets asks for one source for all datasets (translate.js translate_datasets): opt-in, so that a call that threw keeps throwing
   const translatedDatasets = !!datasets && !recog && !!opt('translate', false);
@@ -747,6 +748,53 @@ function compare_loo(a, b) {
   return { elpd_diff, se_diff: Math.sqrt(n * ss / (n - 1)) };
 }
 
+/** Held-out predictive density per dataset -- the scoring step of K-fold cross-validation and of exact refits (amwg_last_sample_dataset_heldout; include/amwg.h).
+ *  data: one data object per dataset, shaped like the constructor's, holding the observations that dataset has NOT seen (an empty one scores 0).  opts.index (the
+ *  Poisson family): per dataset the positions of those observations in the original series; opts.pointwise: also lppd_j per observation.
+ *  -> [{elpd_heldout, se, n[, pointwise: [lppd_j ...]]}, ...].  Built-in families only.  A dataset lives wholly on one shard: no collective. */
+AmwgSampler.prototype.dataset_heldout = function (data, opts) {
+  if (!this._recog) throw 'AmwgSampler (MI355X): dataset_heldout: built-in families only: the data lengths of a translated closure are part of its compiled text';
+  const sets = this.options && this.options.datasets ? data : [data];
+  const nSets = this.options && this.options.datasets ? this.n_datasets : 1;
+  if (!Array.isArray(sets) || sets.length !== nSets) throw 'dataset_heldout: one held-out data object per dataset (' + nSets + ')';
+  const index = opts && opts.index ? (nSets === 1 && !Array.isArray(opts.index[0]) && !ArrayBuffer.isView(opts.index[0]) ? [opts.index] : opts.index) : null;
+  if (index && index.length !== nSets) throw 'dataset_heldout: options.index needs one array of positions per dataset (' + nSets + ')';
+  const N = native(), want = !!(opts && opts.pointwise), out = [];
+  const descs = sets.map((d) => buildModelDesc(this._recog, d, this.params));
+  let at = 0;
+  for (const sh of this._shards) {
+    const n = sh.datasets || 1, first = sh.datasets ? at : 0;      // (an ordinary sampler: every shard holds the one dataset; its chains are not pooled here)
+    const idx = index ? Int32Array.from([].concat(...index.slice(first, first + n).map((a) => Array.from(a)))) : null;
+    const r = N.datasetHeldout(sh.handle, descs.slice(first, first + n), idx, want);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = { elpd_heldout: r.summary[d * 2], se: r.summary[d * 2 + 1], n: r.m[d] };
+      if (want) o.pointwise = Array.from(r.pointwise.subarray(d * r.m_max, d * r.m_max + r.m[d]));
+      out.push(o);
+    }
+    at += n;
+  }
+  return out;
+};
+/** heldout(data, opts) of an ordinary sampler: dataset_heldout(data, opts)[0].  One device, as waic(). */
+AmwgSampler.prototype.heldout = function (data, opts) {
+  this._refusePooled('heldout');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): heldout() over several devices (options.devices) is out of scope; heldout() runs on one device';
+  return this.dataset_heldout(data, opts)[0];
+};
+/** The folds of a K-fold cross-validation put together: results = dataset_heldout(..., {pointwise: true}) (or several heldout() results), one entry per fold ->
+ *  {elpd_kfold, se, n} over the folds' pointwise lppd_j concatenated in fold order, by the finish rule of include/amwg.h: running sums from 0 in that order,
+ *  se = sqrt(n sum_j (lppd_j - elpd_kfold / n)^2 / (n - 1)), NaN for n = 1; n = 0 gives elpd_kfold 0 and se NaN.  Pure JavaScript. */
+function kfold_total(results) {
+  if (!Array.isArray(results) || !results.every((r) => r && Array.isArray(r.pointwise))) throw 'kfold_total: every result needs pointwise (ask for {pointwise: true})';
+  const all = [].concat(...results.map((r) => r.pointwise)), n = all.length;
+  let elpd_kfold = 0;
+  for (let j = 0; j < n; j++) elpd_kfold += all[j];
+  const centre = elpd_kfold / n;
+  let ss = 0;
+  for (let j = 0; j < n; j++) ss += (all[j] - centre) * (all[j] - centre);
+  return { elpd_kfold, se: n < 2 ? NaN : Math.sqrt(n * ss / (n - 1)), n };
+}
+
 // edges as the caller gives them -- {name: [e0, ..., e_bins]} per parameter or derived quantity (every element of a vector parameter under the same edges), or one
 // array for all recorded values; all of one length -- -> {flat: Float64Array [recorded][bins + 1], bins}
 AmwgSampler.prototype._histogramEdges = function (edges) {
@@ -1162,5 +1210,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, compare_waic, compare_loo, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, compare_waic, compare_loo, kfold_total, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

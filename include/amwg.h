@@ -324,7 +324,7 @@ int amwg_waic_info(const amwg_sampler *s, int32_t *armed, size_t *bytes);
  * only"; a group_local sampler; and, from the shape alone, M + 1 > 8192 (about 7.4e6 draws per dataset): one workgroup sorts and fits a tail in LDS, 8192 doubles (64 KB) of it at most.
  * Scratch -- per observation the tail (M + 1 padded to a power of two, at least 64 doubles), 512 bytes of counters, a double per run of draws -- is allocated per call
  * and freed before the call returns; the datasets go in batches under a budget of 256 MiB (a dataset beyond it runs alone).  A failed allocation is AMWG_EHIP.
- * OUT OF SCOPE: LOO after amwg_sample_summarize, moment matching or exact refits for observations of high khat, a relative-efficiency (r_eff) correction of the tail
+ * OUT OF SCOPE: LOO after amwg_sample_summarize, moment matching for observations of high khat (refits without them are scored by amwg_last_sample_dataset_heldout), a relative-efficiency (r_eff) correction of the tail
  * length, likelihood terms of a closure outside its final loop, a pooled LOO across devices, tails beyond the LDS cap.
  * A translated closure whose pointwise text is set is served as by amwg_last_sample_dataset_waic: the same observations, the same doubles, the same kStage rule. */
 int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary /* [D][4]: elpd_loo, se, p_loo, lppd */, int32_t *high /* [D] or NULL: observations with khat_i > 0.7 */,
@@ -351,6 +351,35 @@ int amwg_last_sample_dataset_loo(amwg_sampler *s, double *summary /* [D][4]: elp
  * the LDS cap. */
 int amwg_last_sample_dataset_waic_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out);
 int amwg_last_sample_dataset_loo_grouped(amwg_sampler *s, const int32_t *labels, double *summary, int32_t *high, double *pointwise, int32_t *n_groups_out);
+/* HELD-OUT PREDICTIVE DENSITY per dataset -- the scoring step of K-fold cross-validation and of exact refits, what to do where PSIS-LOO's high[d] is not zero: the K
+ * training folds (or the n - 1 refits) are fitted as the datasets of one sampler (amwg_create_datasets_ragged), and this call scores every dataset's stored draws on
+ * the observations that dataset has NOT seen, on the device.
+ *   held[d] describes them in the fields amwg_create reads: model, n_obs = m_d >= 0, x, y, g, G, K; hyper is ignored.  m_max is the largest m_d.
+ *   summary[D][2] = elpd_heldout, se;  pointwise (NULL, or [D][m_max] = lppd_j; NaN beyond m_d).
+ * THE RULE applies per dataset d and held-out observation j; S and the draw order are those of amwg_last_sample_dataset_waic.
+ *   l_sj is the family's own term for observation j under draw s: bit for bit the double amwg_last_sample_dataset_waic would form if that observation stood in the
+ *   sampler's data (the same device function; the Normal family's division by an invariant is the IEEE quotient wherever it is taken).
+ *   lppd_j = m_j + log(sum_s exp(l_sj - m_j)) - log S, with m_j = max_s l_sj.
+ *   THE ACCUMULATIONS ARE NOT FIXED TO THE BIT; with u = 2^-53 and E = 8 (S + 16) u:  |lppd_j - exact| <= E + 4 u |exact|  (WAIC's bound: it covers any merge tree).
+ *   NON-FINITE VALUES: a NaN or +-inf term makes that lppd_j, and the totals of that dataset, NaN and touches nothing else.
+ *   THE POISSON FAMILY's term depends on the observation's position in the series (+ beta[7] from i >= cp on): index gives every held-out observation's position in
+ *   the ORIGINAL series, the datasets' positions back to back, held[d].n_obs each, every one >= 0; index == NULL means positions 0 ... m_d - 1.  lfactorial of the
+ *   held-out counts is formed on the host as amwg_create forms it (+inf for a negative count: the term is -inf).  The other families ignore index.
+ *   THE HIERARCHICAL FAMILY: an ordinary sampler only; held.G must equal the sampler's G and the labels lie in [0, G).
+ *   THE BERNOULLI FAMILY: every held-out x_j is served directly (no two-valued shortcut at this size); an x that is neither 0 nor 1 gives the term -inf, hence NaN.
+ *   THE FINISH runs on the host inside the library, in index order, running sums from 0.0:
+ *     elpd_heldout = sum_j lppd_j;  se = sqrt(m_d * sum_j (lppd_j - elpd_heldout / m_d)^2 / (m_d - 1)), NaN for m_d = 1;  m_d = 0 gives elpd_heldout 0.0 and se NaN.
+ *   DETERMINISM: no floating-point atomics; a dataset's result bytes depend only on its own draws, its held-out data and (rows, C / D) -- not on D, the other
+ *   datasets or the scratch budget.  The draws are cut into heldout_splits(S, m_d) runs, merged by a fixed tree that depends on their number alone.
+ * AMWG_EINVAL with a message that names the call, before any device call: a null s, held or summary; a translated closure ("built-in families only": the closure's
+ * data lengths are part of its compiled text); no sample() yet; after a summarising call (the message names amwg_sample_summarize); fewer than 2 draws per
+ * dataset; a group_local sampler; a held[d].model, K or G that differs from the sampler's; a negative n_obs; a label or an index out of range.
+ * Scratch is 16 bytes per (run of draws, observation), in batches under the 256 MiB budget of the calls above; the held-out arrays are uploaded per call; both are
+ * freed before the call returns.  A failed allocation is AMWG_EHIP.
+ * OUT OF SCOPE: closures, held-out scoring folded by amwg_sample_summarize, amwg_group_* / amwg_comm_* twins, choosing the folds for the caller. */
+int amwg_last_sample_dataset_heldout(amwg_sampler *s, const amwg_model_desc *held /* [D] */,
+                                     const int32_t *index /* NULL or the datasets' positions back to back, held[d].n_obs each */,
+                                     double *summary /* [D][2]: elpd_heldout, se */, double *pointwise /* NULL or [D][m_max]: lppd_j; NaN beyond m_d */);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,

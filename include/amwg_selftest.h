@@ -76,6 +76,13 @@ int amwg_hpd_limits(int32_t device, int64_t scratch_bytes, int64_t *lds_keys, in
  * (0: the default of csrc/amwg_waic.h).  The arguments are checked before a device is opened. */
 int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                     int32_t *high, double *pointwise, double *loglik);
+/* the kernels of amwg_last_sample_dataset_heldout on a caller's draws[rows][PR][C] (host), through the launcher the sampler uses.  models[D] stand for the sampler:
+ * only model, G and K are read, and they must agree across the datasets; held[D] and index are that call's, refused by its rules; summary[D][2] and pointwise (NULL,
+ * or [D][m_max]) as that call returns them.  scratch_bytes: the scratch budget of this call (0: the default).  The arguments are checked before a device is opened. */
+int amwg_heldout_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
+                       const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise);
+/* the runs that call cuts the S draws of a dataset with m held-out observations into (csrc/amwg_heldout.h: heldout_splits); no device */
+int64_t amwg_heldout_splits_check(int64_t S, int64_t m);
 /* the WAIC fold of an armed summarising call (amwg_set_waic) on the same inputs: the array is cut into windows of window_rows rows (the last may be shorter, and
  * window_rows may exceed rows) and driven through the launcher the summarising call uses -- records allocated and zeroed, one fold per window, the finish.
  * state_bytes (may be NULL): the device bytes of the records. */
