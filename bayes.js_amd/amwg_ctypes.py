@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_heldout", "amwg_last_sample_dataset_waic_grouped", "amwg_last_sample_dataset_loo_grouped", "amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_heldout_check", "amwg_heldout_splits_check","amwg_waic_grouped_check", "amwg_loo_grouped_check", "amwg_user_waic_grouped_check", "amwg_user_loo_grouped_check", "amwg_group_csr_check", "amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_predictive", "amwg_last_sample_dataset_heldout", "amwg_last_sample_dataset_waic_grouped", "amwg_last_sample_dataset_loo_grouped", "amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_predictive_check", "amwg_predictive_totals_check", "amwg_heldout_check", "amwg_heldout_splits_check","amwg_waic_grouped_check", "amwg_loo_grouped_check", "amwg_user_waic_grouped_check", "amwg_user_loo_grouped_check", "amwg_group_csr_check", "amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -79,6 +79,7 @@ def lib():
         L.amwg_last_sample_dataset_waic_grouped.argtypes = [vp, pi32, pd, pi32, pd, pi32]
         L.amwg_last_sample_dataset_loo_grouped.argtypes = [vp, pi32, pd, pi32, pd, pi32]
         L.amwg_last_sample_dataset_heldout.argtypes = [vp, C.POINTER(ModelDesc), pi32, pd, pd]
+        L.amwg_last_sample_dataset_predictive.argtypes = [vp, C.POINTER(ModelDesc), pi32, pd, pd]
         L.amwg_set_waic.argtypes = [vp, i32]
         L.amwg_waic_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_burn.argtypes = [vp, i64]
@@ -203,6 +204,8 @@ def selftest_lib():
         L.amwg_user_loo_grouped_check.argtypes = L.amwg_user_waic_grouped_check.argtypes
         L.amwg_heldout_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), C.POINTER(ModelDesc), pi32, i64, pd, pd]
         L.amwg_heldout_splits_check.restype, L.amwg_heldout_splits_check.argtypes = i64, [i64, i64]
+        L.amwg_predictive_check.argtypes = L.amwg_heldout_check.argtypes
+        L.amwg_predictive_totals_check.argtypes = [pd, pd, i64, pd]
         L.amwg_group_csr_check.argtypes = [pi32, i32, pi32, pi32, pi32, pi32]
         L.amwg_loo_stats.argtypes = [i32, C.POINTER(i32), pd]
         L.amwg_fold_check.argtypes = [i32, pd, i64, i32, i64, i32, i64, pd, pd, pd, pd]
@@ -654,6 +657,13 @@ class Sampler:
         lppd_j, NaN beyond m_d]): the held-out predictive density by the rule of include/amwg.h, on the device (amwg_last_sample_dataset_heldout)"""
         return _heldout(lambda mds, ip, summary, pw: _check(lib().amwg_last_sample_dataset_heldout(self.h, mds, ip, summary, pw)), self.D, specs, index, pointwise)
 
+    def dataset_predictive(self, specs=None, index=None, pointwise=True):
+        """specs: None -- every dataset's OWN observations (in-sample: optimistic) -- or dataset_heldout's held-out descriptions, with its index -> dict(summary
+        [datasets][4] = cover50, cover90, rmse, mean_mid[, pointwise [datasets][m_max][4] = pit_hi, pit_lo, pred_mean, pred_sd, NaN beyond m_d]): posterior predictive
+        calibration by the rule of include/amwg.h, on the device (amwg_last_sample_dataset_predictive)"""
+        call = lambda mds, ip, summary, pw: _check(lib().amwg_last_sample_dataset_predictive(self.h, mds, ip, summary, pw))
+        return _heldout(call, self.D, specs, index, pointwise, width=4, own=self.dataset_n_obs)
+
     def dataset_loo(self, pointwise=False, groups=None):
         """-> dict(summary [datasets][4] = elpd_loo, se, p_loo, lppd; high [datasets] = observations with khat_i > 0.7; with pointwise=True also
         pointwise [datasets][n_max][3] = elpd_loo_i, lppd_i, khat_i, NaN beyond a dataset's n_obs): PSIS-LOO per dataset by the rule of include/amwg.h, the
@@ -981,21 +991,27 @@ def waic_check(draws, specs, pointwise=True, loglik=False, scratch_bytes=0, devi
     return out
 
 
-def _heldout(call, D, held, index, pointwise):
-    """the arrays of a held-out call: call(ModelDesc array, index pointer or None, summary, pointwise or None) -> the dict of Sampler.dataset_heldout"""
-    if len(held) != D:
-        raise AmwgError("amwg error -1: heldout: one description of held-out observations per dataset (%d datasets)" % D)
-    mds, keep = _model_descs(held)
+def _heldout(call, D, held, index, pointwise, width=0, own=None):
+    """the arrays of a held-out call: call(ModelDesc array, index pointer or None, summary, pointwise or None) -> the dict of Sampler.dataset_heldout.  width = 4:
+    of Sampler.dataset_predictive -- summary [D][4], pointwise [D][m_max][4], and held = None stands for the datasets' own observations, own() of them each"""
+    name = "predictive" if width else "heldout"
+    if held is None:
+        sizes, mds, keep = own(), None, []
+    else:
+        if len(held) != D:
+            raise AmwgError("amwg error -1: %s: one description of held-out observations per dataset (%d datasets)" % (name, D))
+        sizes = [int(q["n_obs"]) for q in held]
+        mds, keep = _model_descs(held)
     ip = None
     if index is not None:
-        if len(index) != D or [np.size(a) for a in index] != [int(q["n_obs"]) for q in held]:
-            raise AmwgError("amwg error -1: heldout: index: one position per held-out observation and dataset")
+        if len(index) != D or [np.size(a) for a in index] != sizes:
+            raise AmwgError("amwg error -1: %s: index: one position per held-out observation and dataset" % name)
         idx = np.ascontiguousarray(np.concatenate([np.asarray(a).ravel() for a in index] + [np.zeros(1)]), dtype=np.int32)
         keep.append(idx)
         ip = idx.ctypes.data_as(C.POINTER(C.c_int32))
-    m_max = max([int(q["n_obs"]) for q in held] + [1])
-    summary = np.empty((max(1, D), 2))
-    pw = np.empty((max(1, D), m_max)) if pointwise else None
+    m_max = max(sizes + [1])
+    summary = np.empty((max(1, D), width or 2))
+    pw = np.full((max(1, D), m_max) + ((width,) if width else ()), np.nan) if pointwise else None      # (all m_d = 0: the library writes nothing)
     call(mds, ip, _dp(summary), _dp(pw) if pointwise else None)
     out = {"summary": summary}
     if pointwise:
@@ -1018,6 +1034,30 @@ def heldout_check(draws, specs, held, index=None, pointwise=True, scratch_bytes=
         if L.amwg_heldout_check(device, _dp(dr), rows, PR, Cn, D, own, mds, ip, scratch_bytes, summary, pw) != 0:
             raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return _heldout(call, D, held, index, pointwise)
+
+
+def predictive_check(draws, specs, held=None, index=None, pointwise=True, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_predictive on any array draws [rows][PR][C].  specs stand for the sampler's datasets; held = None scores
+    their own observations, else held and index are dataset_heldout's -> dataset_predictive's dict (amwg_predictive_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: predictive_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    own, keep = _model_descs(specs)
+    L = selftest_lib()
+
+    def call(mds, ip, summary, pw):
+        if L.amwg_predictive_check(device, _dp(dr), rows, PR, Cn, len(specs), own, mds, ip, scratch_bytes, summary, pw) != 0:
+            raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return _heldout(call, len(specs), held, index, pointwise, width=4, own=lambda: [int(q["n_obs"]) for q in specs])
+
+
+def predictive_totals(pointwise, y):
+    """libamwg_selftest.so: THE FINISH of include/amwg.h over one dataset's pointwise [m][4] and observations y [m] -> summary [4] (amwg_predictive_totals_check)"""
+    pw, yy, out = np.ascontiguousarray(pointwise, dtype=np.float64).reshape(-1, 4), np.ascontiguousarray(y, dtype=np.float64), np.empty(4)
+    if selftest_lib().amwg_predictive_totals_check(_dp(pw), _dp(yy), len(yy), _dp(out)) != 0:
+        raise AmwgError("amwg error: %s" % selftest_lib().amwg_last_error().decode())
+    return out
 
 
 def waic_fold_check(draws, specs, window_rows, pointwise=True, device=0):

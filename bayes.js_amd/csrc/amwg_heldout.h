@@ -25,6 +25,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "amwg_host.h"
 #include "amwg_pointwise.h"
@@ -34,7 +35,22 @@
 // per dataset over the tiles of 64, a run at least one staged run long (amwg_pointwise.h)
 __host__ __device__ inline int64_t heldout_splits(int64_t S, int64_t m) { return amwg::waic_splits(S, m); }
 
+// held-out data on the device, packed as the sampler packs its own: what amwg_heldout_pack fills and a run reads (this call's kernels, and those of
+// amwg_predictive.hip).  The host vectors back the asynchronous uploads; everything is freed with the struct.
+struct HeldArrays {
+  WaicModel M{};                       // base with x, y, lfact, xb, invalid pointing into the arrays below
+  std::vector<WaicDataset> sets;       // [D], host: n_obs = m_d and the places of dataset d's arrays
+  int64_t m_max = 0;
+  const int32_t *index = nullptr;      // the Poisson family's positions on the device, at WaicDataset::off_xb; nullptr for the other families
+  std::vector<double> hx, hy, hlf;
+  std::vector<uint8_t> hxb, hbad;
+  std::vector<int32_t> hidx;
+  DevBuf dx, dy, dlf, dxb, dbad, didx;
+};
+
 #pragma GCC visibility push(hidden)
+// held [D] and index (validated) into `h`, the uploads enqueued on `stream`; h must outlive the stream's drain
+int amwg_heldout_pack(const WaicModel &base, int D, const amwg_model_desc *held, const int32_t *index, hipStream_t stream, HeldArrays &h);
 // AMWG_EINVAL "<call>: ..." unless held[0 .. D) can be scored by a sampler of (model, G, K): the same model, K and G, n_obs >= 0, the arrays the family reads, labels
 // in [0, G), the Poisson family's index >= 0 (the other families do not read it), the hierarchical family on one dataset.  Host only.
 int amwg_heldout_validate(const char *call, int model, int G, int K, int D, const amwg_model_desc *held, const int32_t *index);

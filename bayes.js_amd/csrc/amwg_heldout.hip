@@ -11,6 +11,7 @@
 #include "amwg_fold.h"
 #include "amwg_heldout.h"
 #include "amwg_host.h"
+#include "amwg_lanes.h"
 #include "amwg_terms.h"
 #include "amwg_waic.h"
 
@@ -26,25 +27,6 @@ __device__ __forceinline__ double rescaled(double sum, double m, double M) { ret
 __device__ __forceinline__ Lse lse_merge(const Lse &a, const Lse &b) {
   const double M = b.m > a.m ? b.m : a.m;
   return Lse{M, rescaled(a.sum, a.m, M) + rescaled(b.sum, b.m, M)};
-}
-
-// the value of lane ^ OFF, OFF = 1, 2, 4, 8, by DPP moves in the VALU: quad permutes; row_half_mirror then the quad reversed (xor 7, xor 3); row_mirror then
-// row_half_mirror (xor 15, xor 7)
-template <int OFF> __device__ __forceinline__ double dpp_xor(double v) {
-  int lo = (int)(uint32_t)f64_bits(v), hi = (int)(uint32_t)(f64_bits(v) >> 32);
-  if constexpr (OFF == 1) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  } else if constexpr (OFF == 2) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x4E, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0x4E, 0xF, 0xF, true);
-  } else if constexpr (OFF == 4) {
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x141, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0x141, 0xF, 0xF, true);
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x1B, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0x1B, 0xF, 0xF, true);
-  } else {
-    static_assert(OFF == 8, "DPP moves stay inside a row of 16 lanes");
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x140, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0x140, 0xF, 0xF, true);
-    lo = __builtin_amdgcn_mov_dpp(lo, 0x141, 0xF, 0xF, true); hi = __builtin_amdgcn_mov_dpp(hi, 0x141, 0xF, 0xF, true);
-  }
-  return bits_f64(((uint64_t)(uint32_t)hi << 32) | (uint64_t)(uint32_t)lo);
 }
 
 // one step of the butterfly: a merged with the Lse of lane ^ OFF, in every lane.  OFF = 16, 32: v_permlane16_swap / v_permlane32_swap with both operands the same
@@ -236,21 +218,20 @@ void amwg_heldout_totals(const double *lppd, int64_t m, double *summary) {
   summary[1] = m < 2 ? (double)NAN : std::sqrt((double)m * ss / (double)(m - 1));
 }
 
-int amwg_heldout_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &base, const amwg_model_desc *held, const int32_t *index,
-                        double *summary, double *pointwise, size_t scratch_bytes, hipStream_t stream) {
+int amwg_heldout_pack(const WaicModel &base, int D, const amwg_model_desc *held, const int32_t *index, hipStream_t stream, HeldArrays &h) {
   const int model = base.model;
-  int64_t cpd = C / D;      // (not const: the args[] list points at it)
-  const int64_t S = rows * cpd;
-  // ---- the held-out data as the family reads the sampler's own
-  WaicModel M = base;
+  WaicModel &M = h.M;
+  M = base;
   M.x = M.y = M.lfact = nullptr; M.xb = M.invalid = nullptr;
-  std::vector<WaicDataset> sets((size_t)D);
+  std::vector<WaicDataset> &sets = h.sets;
+  sets.assign((size_t)D, WaicDataset{});
   std::vector<int64_t> off;
-  std::vector<double> hx, hy, hlf;
-  std::vector<uint8_t> hxb, hbad;
-  std::vector<int32_t> hidx;
-  DevBuf dx, dy, dlf, dxb, dbad, didx;
-  int64_t m_max = 0;
+  std::vector<double> &hx = h.hx, &hy = h.hy, &hlf = h.hlf;
+  std::vector<uint8_t> &hxb = h.hxb, &hbad = h.hbad;
+  std::vector<int32_t> &hidx = h.hidx;
+  DevBuf &dx = h.dx, &dy = h.dy, &dlf = h.dlf, &dxb = h.dxb, &dbad = h.dbad, &didx = h.didx;
+  int64_t &m_max = h.m_max;
+  m_max = 0;
   for (int d = 0; d < D; ++d) { sets[(size_t)d] = WaicDataset{held[d].n_obs, 1, 0, 0, 0, 0}; m_max = held[d].n_obs > m_max ? held[d].n_obs : m_max; }
   if (model == AMWG_MODEL_NORMAL || model == AMWG_MODEL_HIER_NORMAL) {
     TRYB(pack<double>(D, held, 1, [&](int d, double *dst) { for (int i = 0; i < held[d].n_obs; ++i) dst[i] = held[d].x[i]; }, off, dx, stream, hx));
@@ -284,7 +265,22 @@ int amwg_heldout_launch(const char *call, const double *draws, int64_t rows, int
     for (int d = 0; d < D; ++d) sets[(size_t)d].off_xb = off[(size_t)d];
     M.x = dx.as<double>(); M.y = dy.as<double>(); M.lfact = dlf.as<double>();
   }
-  const int32_t *d_index = didx.as<int32_t>();
+  h.index = didx.as<int32_t>();
+  return AMWG_OK;
+}
+
+int amwg_heldout_launch(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const WaicModel &base, const amwg_model_desc *held, const int32_t *index,
+                        double *summary, double *pointwise, size_t scratch_bytes, hipStream_t stream) {
+  int64_t cpd = C / D;      // (not const: the args[] list points at it)
+  const int64_t S = rows * cpd;
+  // ---- the held-out data as the family reads the sampler's own
+  HeldArrays h;
+  TRYB(amwg_heldout_pack(base, D, held, index, stream, h));
+  const int model = base.model;
+  WaicModel M = h.M;
+  const std::vector<WaicDataset> &sets = h.sets;
+  const int64_t m_max = h.m_max;
+  const int32_t *d_index = h.index;
   // ---- the outputs, and the batches under the budget: 16 bytes per (split, observation)
   DevBuf d_sets, d_pw, d_off, d_parts;
   HIP_TRY(d_sets.alloc((size_t)D * sizeof(WaicDataset)));

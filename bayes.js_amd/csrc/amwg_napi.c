@@ -868,15 +868,28 @@ static napi_value DatasetLooGrouped(napi_env env, napi_callback_info info) { ret
 /* datasetHeldout(handle, held[], Int32Array index | null, bool pointwise) -> {datasets, m_max, m: Int32Array [datasets], summary: Float64Array [datasets][2]
  * (elpd_heldout, se)[, pointwise: Float64Array [datasets][m_max] (lppd_j; NaN beyond m_d)]}: held = one model description per dataset of the sampler, the
  * observations it has not seen (amwg_last_sample_dataset_heldout) */
-static napi_value DatasetHeldout(napi_env env, napi_callback_info info) {
+static napi_value dataset_scored(napi_env env, napi_callback_info info, int predictive);
+static napi_value DatasetHeldout(napi_env env, napi_callback_info info) { return dataset_scored(env, info, 0); }
+/* datasetPredictive(handle, held[] | null, Int32Array index | null, bool pointwise) -> the same object with summary [datasets][4] (cover50, cover90, rmse, mean_mid)
+ * and pointwise [datasets][m_max][4] (pit_hi, pit_lo, pred_mean, pred_sd); held null: every dataset's own observations (amwg_last_sample_dataset_predictive) */
+static napi_value DatasetPredictive(napi_env env, napi_callback_info info) { return dataset_scored(env, info, 1); }
+static napi_value dataset_scored(napi_env env, napi_callback_info info, int predictive) {
+  const size_t width = predictive ? 4 : 1;
+  const char *const bad_held = predictive ? "amwg_napi.datasetPredictive: held must be null or hold one model description per dataset of the sampler"
+                                          : "amwg_napi.datasetHeldout: held must hold one model description per dataset of the sampler";
+  const char *const bad_index = predictive ? "amwg_napi.datasetPredictive: index needs one position per scored observation of every dataset"
+                                           : "amwg_napi.datasetHeldout: index needs one position per held-out observation of every dataset";
   napi_value a[4];
   if (!get_args(env, info, 4, a)) return NULL;
   amwg_sampler *s = unwrap(env, a[0]);
   if (!s) return NULL;
   const size_t D = (size_t)amwg_num_datasets(s);
   uint32_t n_held = 0;
-  if (napi_get_array_length(env, a[1], &n_held) != napi_ok || n_held != D) {
-    napi_throw_error(env, "AMWG_EINVAL", "amwg_napi.datasetHeldout: held must hold one model description per dataset of the sampler");
+  napi_valuetype held_type = napi_undefined;
+  napi_typeof(env, a[1], &held_type);
+  const bool own = predictive && (held_type == napi_null || held_type == napi_undefined);      /* in-sample */
+  if (!own && (napi_get_array_length(env, a[1], &n_held) != napi_ok || n_held != D)) {
+    napi_throw_error(env, "AMWG_EINVAL", bad_held);
     return NULL;
   }
   napi_typedarray_type type;
@@ -887,7 +900,7 @@ static napi_value DatasetHeldout(napi_env env, napi_callback_info info) {
   napi_get_value_bool(env, a[3], &want);
   int32_t *m = NULL;
   double *summary = NULL, *pw = NULL;
-  napi_value vm = new_i32(env, D, &m), vs = new_f64(env, D * 2, &summary), vp = NULL;
+  napi_value vm = new_i32(env, D, &m), vs = new_f64(env, D * (predictive ? 4 : 2), &summary), vp = NULL;
   if (!vm || !vs) return NULL;
   amwg_model_desc *md = (amwg_model_desc *)calloc(D ? D : 1, sizeof *md);
   size_t total = 0;
@@ -900,13 +913,16 @@ static napi_value DatasetHeldout(napi_env env, napi_callback_info info) {
     total += md[d].n_obs > 0 ? (size_t)md[d].n_obs : 0;
     m_max = md[d].n_obs > m_max ? md[d].n_obs : m_max;
   }
+  if (own && amwg_dataset_n_obs(s, m) == AMWG_OK)
+    for (size_t d = 0; d < D; d++) { total += (size_t)m[d]; m_max = m[d] > m_max ? m[d] : m_max; }
   if (index && n_index != total) {
     free(md);
-    napi_throw_error(env, "AMWG_EINVAL", "amwg_napi.datasetHeldout: index needs one position per held-out observation of every dataset");
+    napi_throw_error(env, "AMWG_EINVAL", bad_index);
     return NULL;
   }
-  if (want) { vp = new_f64(env, D * (size_t)m_max, &pw); if (!vp) { free(md); return NULL; } }
-  int rc = amwg_last_sample_dataset_heldout(s, md, (const int32_t *)index, summary, want ? pw : NULL);
+  if (want) { vp = new_f64(env, D * (size_t)m_max * width, &pw); if (!vp) { free(md); return NULL; } }
+  int rc = predictive ? amwg_last_sample_dataset_predictive(s, own ? NULL : md, (const int32_t *)index, summary, want ? pw : NULL)
+                      : amwg_last_sample_dataset_heldout(s, md, (const int32_t *)index, summary, want ? pw : NULL);
   free(md);
   if (rc != AMWG_OK) return throw_amwg(env, rc);
   napi_value o, t;
@@ -1366,7 +1382,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"datasetHeldout", DatasetHeldout},{"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"datasetHeldout", DatasetHeldout}, {"datasetPredictive", DatasetPredictive},{"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setWaic", SetWaic}, {"waicInfo", WaicInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

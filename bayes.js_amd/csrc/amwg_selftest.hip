@@ -12,6 +12,7 @@
 #include "amwg_hpd.h"
 #include "amwg_loo.h"
 #include "amwg_heldout.h"
+#include "amwg_predictive.h"
 #include "amwg_waic.h"
 #include "amwg_eval.h"      // device evaluation of the arithmetic building blocks
 #include "amwg_host.h"
@@ -491,6 +492,39 @@ int amwg_heldout_check(int32_t device, const double *draws, int64_t rows, int32_
   HIP_TRY(dd.alloc(bytes));
   HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
   return amwg_heldout_launch(call, dd.as<double>(), rows, PR, C, D, base, held, index, summary, pointwise, (size_t)scratch_bytes, nullptr);
+}
+
+// the same for amwg_last_sample_dataset_predictive; held == NULL: the observations of `models` themselves, packed as held-out ones are
+int amwg_predictive_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
+                          const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise) {
+  static const char *call = "amwg_predictive_check";
+  if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
+  if (scratch_bytes < 0) return amwg_fail(AMWG_EINVAL, "%s: bad argument (scratch_bytes %lld)", call, (long long)scratch_bytes);
+  TRYB(amwg_waic_shape(call, rows, PR, C, D));
+  if (rows > INT64_MAX / 8 / PR / C) return amwg_fail(AMWG_EINVAL, "%s: array too large", call);
+  for (int d = 1; d < D; ++d)
+    if (models[d].model != models[0].model || models[d].K != models[0].K || models[d].G != models[0].G) return amwg_fail(AMWG_EINVAL, "%s: dataset %d is not of dataset 0's model, K and G", call, d);
+  if (!held) held = models;
+  TRYB(amwg_heldout_validate(call, models[0].model, models[0].G, models[0].K, D, held, index));
+  WaicModel base{};
+  base.model = models[0].model; base.G = models[0].G; base.exact_division = 0;
+  base.neg_half_log_2pi = -0.5 * log_v8(2 * kPi);
+  PointwiseLaunch K;
+  TRYB(amwg_pointwise_family(call, base, PR, D, K));
+  TRYB(use_device(device));
+  const size_t bytes = (size_t)rows * (size_t)PR * (size_t)C * 8;
+  DevBuf dd;
+  HIP_TRY(dd.alloc(bytes));
+  HIP_TRY(hipMemcpy(dd.p, draws, bytes, hipMemcpyHostToDevice));
+  HeldArrays h;
+  TRYB(amwg_heldout_pack(base, D, held, index, nullptr, h));
+  return amwg_predictive_run(dd.as<double>(), rows, PR, C, D, h.M, h.sets.data(), h.index, summary, pointwise, (size_t)scratch_bytes, nullptr);
+}
+
+int amwg_predictive_totals_check(const double *pw, const double *y, int64_t m, double *summary) {
+  if (!summary || (m > 0 && (!pw || !y)) || m < 0) return amwg_fail(AMWG_EINVAL, "amwg_predictive_totals_check: bad argument");
+  amwg_predictive_totals(pw, y, m, summary);
+  return AMWG_OK;
 }
 
 int amwg_waic_fold_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t window_rows, double *summary,

@@ -781,6 +781,60 @@ AmwgSampler.prototype.heldout = function (data, opts) {
   if (this._shards.length > 1) throw 'AmwgSampler (MI355X): heldout() over several devices (options.devices) is out of scope; heldout() runs on one device';
   return this.dataset_heldout(data, opts)[0];
 };
+/** Posterior predictive calibration per dataset (amwg_last_sample_dataset_predictive; include/amwg.h): opts.data -- one data object per dataset as dataset_heldout
+ *  takes them, with opts.index -- or none: every dataset's OWN observations (in-sample, which is optimistic: the honest check scores the held-out fold of each of K
+ *  training folds).  opts.pointwise (default true).
+ *  -> [{cover50, cover90, rmse, mean_mid, n[, pointwise: [{pit_hi, pit_lo, pred_mean, pred_sd} ...]]}, ...].  Built-in families only. */
+AmwgSampler.prototype.dataset_predictive = function (opts) {
+  if (!this._recog) throw 'AmwgSampler (MI355X): dataset_predictive: the predictive distribution of a closure is not known to the library; built-in families only';
+  const multi = !!(this.options && this.options.datasets), nSets = multi ? this.n_datasets : 1;
+  const data = opts && opts.data !== undefined && opts.data !== null ? opts.data : null;
+  const sets = data === null ? null : (multi ? data : [data]);
+  if (sets && (!Array.isArray(sets) || sets.length !== nSets)) throw 'dataset_predictive: one data object per dataset (' + nSets + ')';
+  const index = opts && opts.index ? (nSets === 1 && !Array.isArray(opts.index[0]) && !ArrayBuffer.isView(opts.index[0]) ? [opts.index] : opts.index) : null;
+  if (index && index.length !== nSets) throw 'dataset_predictive: options.index needs one array of positions per dataset (' + nSets + ')';
+  const N = native(), want = !(opts && opts.pointwise === false), out = [];
+  const descs = sets && sets.map((d) => buildModelDesc(this._recog, d, this.params));
+  let at = 0;
+  for (const sh of this._shards) {
+    const n = sh.datasets || 1, first = sh.datasets ? at : 0;      // (as dataset_heldout)
+    const idx = index ? Int32Array.from([].concat(...index.slice(first, first + n).map((a) => Array.from(a)))) : null;
+    const r = N.datasetPredictive(sh.handle, descs ? descs.slice(first, first + n) : null, idx, want);
+    for (let d = 0; d < r.datasets; d++) {
+      const o = { cover50: r.summary[d * 4], cover90: r.summary[d * 4 + 1], rmse: r.summary[d * 4 + 2], mean_mid: r.summary[d * 4 + 3], n: r.m[d] };
+      if (want) {
+        o.pointwise = [];
+        for (let j = 0; j < r.m[d]; j++) {
+          const q = (d * r.m_max + j) * 4;
+          o.pointwise.push({ pit_hi: r.pointwise[q], pit_lo: r.pointwise[q + 1], pred_mean: r.pointwise[q + 2], pred_sd: r.pointwise[q + 3] });
+        }
+      }
+      out.push(o);
+    }
+    at += n;
+  }
+  return out;
+};
+/** predictive(opts) of an ordinary sampler: dataset_predictive(opts)[0].  One device, as waic(). */
+AmwgSampler.prototype.predictive = function (opts) {
+  this._refusePooled('predictive');
+  if (this._shards.length > 1) throw 'AmwgSampler (MI355X): predictive() over several devices (options.devices) is out of scope; predictive() runs on one device';
+  return this.dataset_predictive(opts)[0];
+};
+/** The non-randomised PIT histogram of pointwise = [{pit_hi, pit_lo}, ...] (one result's, or several folds' concatenated) over `bins` equal bins of [0, 1]: an
+ *  observation spreads its unit mass uniformly over [pit_lo, pit_hi] -- a count's whole step of the distribution function -- and a continuous one (pit_lo ==
+ *  pit_hi) falls into one bin, 1 into the last.  -> [mass per bin]; a calibrated model gives n / bins each.  A NaN observation is left out.  Pure JavaScript. */
+function pit_histogram(pointwise, bins) {
+  if (!Array.isArray(pointwise) || !(bins >= 1) || bins !== Math.floor(bins)) throw 'pit_histogram: pointwise must be an array of {pit_hi, pit_lo} and bins a positive integer';
+  const h = new Array(bins).fill(0);
+  for (const p of pointwise) {
+    const lo = p.pit_lo, hi = p.pit_hi;
+    if (!(lo >= 0 && hi <= 1 && lo <= hi)) continue;
+    if (lo === hi) { h[Math.min(bins - 1, Math.floor(hi * bins))] += 1; continue; }
+    for (let b = Math.floor(lo * bins); b < bins && b / bins < hi; b++) h[b] += (Math.min(hi, (b + 1) / bins) - Math.max(lo, b / bins)) / (hi - lo);
+  }
+  return h;
+}
 /** The folds of a K-fold cross-validation put together: results = dataset_heldout(..., {pointwise: true}) (or several heldout() results), one entry per fold ->
  *  {elpd_kfold, se, n} over the folds' pointwise lppd_j concatenated in fold order, by the finish rule of include/amwg.h: running sums from 0 in that order,
  *  se = sqrt(n sum_j (lppd_j - elpd_kfold / n)^2 / (n - 1)), NaN for n = 1; n = 0 gives elpd_kfold 0 and se NaN.  Pure JavaScript. */
@@ -1210,5 +1264,5 @@ AmwgStepper.prototype.info = function () {     // keyed by the parameter each en
 /** {hits, misses, dir} of the on-disk cache of compiled closures in this process ($AMWG_CACHE_DIR | $XDG_CACHE_HOME/amwg | ~/.cache/amwg). */
 function code_cache_stats() { return native().codeCacheStats(); }
 
-module.exports = { interval_brackets, compare_waic, compare_loo, kfold_total, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
+module.exports = { interval_brackets, compare_waic, compare_loo, kfold_total, pit_histogram, correlation, autocorrelation_ess, code_cache_stats,runif, runif_discrete, rnorm, AmwgSampler, complete_params, param_init_fixed, componentOptions, shard_chain_offset, models, ld, native, translate: translator.translate,
   RealMetropolisStepper, IntMetropolisStepper, MultiRealComponentMetropolisStepper, MultiIntComponentMetropolisStepper, BinaryStepper, BinaryComponentStepper, AmwgStepper };

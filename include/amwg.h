@@ -380,6 +380,44 @@ int amwg_last_sample_dataset_loo_grouped(amwg_sampler *s, const int32_t *labels,
 int amwg_last_sample_dataset_heldout(amwg_sampler *s, const amwg_model_desc *held /* [D] */,
                                      const int32_t *index /* NULL or the datasets' positions back to back, held[d].n_obs each */,
                                      double *summary /* [D][2]: elpd_heldout, se */, double *pointwise /* NULL or [D][m_max]: lppd_j; NaN beyond m_d */);
+/* POSTERIOR PREDICTIVE CALIBRATION per dataset -- do the observations land where the predictive distribution says they should?  Per observation the probability
+ * integral transform (PIT), the predictive mean and the predictive sd over the stored draws, on the device; from these the PIT histogram, the 50 % / 90 % coverage
+ * and the predictive RMSE.
+ *   held == NULL scores every dataset's OWN observations (in-sample, m_d = n_d).  IN-SAMPLE PIT IS OPTIMISTIC: the draws have seen the observations.  The honest
+ *   check is the held-out form over K folds: the training folds as the datasets of one sampler, held[d] the fold dataset d has not seen.
+ *   Otherwise held[d] and index are read exactly as amwg_last_sample_dataset_heldout reads them: the fields, the Poisson family's index, the hierarchical family on
+ *   an ordinary sampler only, the Bernoulli family's x served directly.  m_max is the largest m_d.
+ *   summary[D][4] = cover50, cover90, rmse, mean_mid;  pointwise (NULL, or [D][m_max][4] = pit_hi, pit_lo, pred_mean, pred_sd; NaN beyond m_d).
+ * THE RULE applies per dataset d, observation j and draw s; S and the draw order are those of amwg_last_sample_dataset_waic.
+ *   family                 mean_sj                  var_sj           F_sj                                          Fm_sj
+ *   Normal, hierarchical   location (mu, theta[g_j]) sigma^2         0.5 erfc(-z sqrt(1/2)), z = (x_j - mean_sj) / sigma   = F_sj
+ *                                                                    (the subtraction and the division are IEEE operations)
+ *   Poisson (GLM)          lambda                   lambda           P(Y <= y_j | lambda)                          P(Y <= y_j - 1 | lambda), 0 for y_j = 0
+ *   Bernoulli              theta                    theta (1 - theta) 1 for x = 1, 1 - theta for x = 0              1 - theta for x = 1, 0 for x = 0
+ *   THE POISSON FAMILY: lambda = exp(eta), eta exactly the double its pointwise term forms (the position rule and index included).  A count that is negative or not
+ *   an integer gives NaN.  THE BERNOULLI FAMILY: any x other than 0 or 1 gives NaN.
+ *   pit_hi = mean_s F_sj;  pit_lo = mean_s Fm_sj;  pred_mean = mean_s mean_sj;  pred_sd = sqrt(mean_s var_sj + var_s mean_sj), the law of total variance, the second
+ *   term a population variance over the draws formed without cancellation (sums shifted by a lane's first draw, merged by Chan's formula).
+ *   THE ACCUMULATIONS ARE NOT FIXED TO THE BIT; with u = 2^-53 and E = 8 (S + 16) u, against THE RULE in exact arithmetic over the same draws:
+ *     |pit - exact| <= E + c,  c the bound of the distribution function per evaluation: erfc 2^-49 relative to the value, hence 2^-49 for F in [0, 1]; the Poisson
+ *     pair 2^-29 min(F, 1 - F) + u (csrc/amwg_cdf.h: the mass at y is formed in the exponent, and one rounding of y log(lambda) - lambda - log(y!) is its error);
+ *     the Bernoulli family none;  |pred_mean - exact| <= E max_s |mean_sj|;  |pred_sd^2 - exact| <= 4 E (max_s var_sj + max_s mean_sj^2).
+ *   NON-FINITE VALUES: a NaN or infinite F, mean or var makes the four values of that observation, and the summary of that dataset, NaN and touches nothing else.
+ *   THE FINISH runs on the host inside the library, in index order, running sums from 0.0, with mid_j = (pit_hi + pit_lo) / 2 and y_j the observation (x_j; the
+ *   Poisson family's count):  cover50 = the share of j with 0.25 <= mid_j <= 0.75;  cover90 = ... 0.05 <= mid_j <= 0.95;  rmse = sqrt(mean_j (y_j - pred_mean_j)^2);
+ *   mean_mid = mean_j mid_j.  m_d = 0 gives NaN, NaN, NaN, NaN.
+ *   DETERMINISM: no floating-point atomics; the draws are cut into runs whose number is a function of (S, m_d) alone and merged by a fixed tree; a dataset's bytes
+ *   depend only on its own draws, its data and (rows, C / D) -- not on D, the other datasets or the scratch budget; the in-sample bytes are those of the same call
+ *   given held = the sampler's own data.
+ * AMWG_EINVAL with a message that names the call, before any device call: the refusals of amwg_last_sample_dataset_heldout (held may be NULL here), and a
+ * translated closure: "the predictive distribution of a closure is not known to the library; built-in families only".
+ * Scratch is 48 bytes per (run of draws, observation), in batches under the 256 MiB budget of the calls above, freed before the call returns.  AMWG_EHIP as above.
+ * OUT OF SCOPE: closures, LOO-PIT (importance-weighted: it needs the PSIS weight of every draw), folding under amwg_sample_summarize, amwg_group_* / amwg_comm_*
+ * twins, predictive quantiles or intervals, simulated replicates. */
+int amwg_last_sample_dataset_predictive(amwg_sampler *s, const amwg_model_desc *held /* NULL, or [D] */,
+                                        const int32_t *index /* as amwg_last_sample_dataset_heldout */,
+                                        double *summary /* [D][4]: cover50, cover90, rmse, mean_mid */,
+                                        double *pointwise /* NULL or [D][m_max][4]: pit_hi, pit_lo, pred_mean, pred_sd; NaN beyond m_d */);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,

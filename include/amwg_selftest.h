@@ -81,6 +81,12 @@ int amwg_waic_check(int32_t device, const double *draws, int64_t rows, int32_t P
  * or [D][m_max]) as that call returns them.  scratch_bytes: the scratch budget of this call (0: the default).  The arguments are checked before a device is opened. */
 int amwg_heldout_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
                        const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise);
+/* the same for amwg_last_sample_dataset_predictive: summary[D][4], pointwise (NULL, or [D][m_max][4]).  held == NULL scores the observations of models[D] themselves,
+ * packed as held-out ones are (the sampler's in-sample route reads its own arrays where they lie; tests/test_gpu_predictive.py compares the two on a sampler). */
+int amwg_predictive_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
+                          const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise);
+/* THE FINISH of that call over one dataset on the host: pw[m][4], the observations y[m] -> summary[4]; no device */
+int amwg_predictive_totals_check(const double *pw, const double *y, int64_t m, double *summary);
 /* the runs that call cuts the S draws of a dataset with m held-out observations into (csrc/amwg_heldout.h: heldout_splits); no device */
 int64_t amwg_heldout_splits_check(int64_t S, int64_t m);
 /* the WAIC fold of an armed summarising call (amwg_set_waic) on the same inputs: the array is cut into windows of window_rows rows (the last may be shorter, and
