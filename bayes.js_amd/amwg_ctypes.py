@@ -48,8 +48,8 @@ class UserModel(C.Structure):
                 ("rows_n_obs", C.c_int32), ("rows_groups", C.c_int32), ("rows_sweep", C.c_int32)]
 
 
-EXPORTS = ["amwg_last_sample_dataset_predictive", "amwg_last_sample_dataset_heldout", "amwg_last_sample_dataset_waic_grouped", "amwg_last_sample_dataset_loo_grouped", "amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
-SELFTEST_EXPORTS = ["amwg_predictive_check", "amwg_predictive_totals_check", "amwg_heldout_check", "amwg_heldout_splits_check","amwg_waic_grouped_check", "amwg_loo_grouped_check", "amwg_user_waic_grouped_check", "amwg_user_loo_grouped_check", "amwg_group_csr_check", "amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
+EXPORTS = ["amwg_last_sample_dataset_loo_predictive", "amwg_last_sample_dataset_predictive", "amwg_last_sample_dataset_heldout", "amwg_last_sample_dataset_waic_grouped", "amwg_last_sample_dataset_loo_grouped", "amwg_set_waic", "amwg_waic_info", "amwg_set_pointwise", "amwg_pointwise_n_obs", "amwg_compile_pointwise", "amwg_last_sample_dataset_waic", "amwg_last_sample_dataset_loo", "amwg_last_sample_dataset_hpd", "amwg_last_sample_dataset_autocovariance", "amwg_set_autocovariance", "amwg_autocovariance_info", "amwg_last_sample_dataset_covariance", "amwg_set_covariance", "amwg_covariance_info", "amwg_last_sample_dataset_histogram", "amwg_set_histogram", "amwg_histogram_info", "amwg_sample_summarize","amwg_sample_summarize_async", "amwg_summary_info", "amwg_create_user_datasets", "amwg_compile_user_datasets", "amwg_create_datasets", "amwg_create_datasets_ragged", "amwg_num_datasets", "amwg_dataset_n_obs", "amwg_last_sample_dataset_moments", "amwg_last_sample_dataset_diagnostics", "amwg_last_sample_dataset_quantiles", "amwg_kernel_name", "amwg_summation_order", "amwg_group_gather_draws", "amwg_group_comm_info", "amwg_comm_unique_id", "amwg_comm_create", "amwg_comm_info", "amwg_comm_gather_draws", "amwg_comm_moments", "amwg_comm_destroy", "amwg_code_cache_stats", "amwg_tuning", "amwg_group_moments", "amwg_group_diagnostics", "amwg_group_quantiles", "amwg_last_sample_quantiles", "amwg_fp64_peak", "amwg_set_state", "amwg_last_sample_diagnostics", "amwg_create_user", "amwg_compile_user", "amwg_num_recorded", "amwg_create", "amwg_burn", "amwg_burn_async", "amwg_sample", "amwg_sample_async", "amwg_fetch_draws", "amwg_fetch_draws_slices", "amwg_sample_device", "amwg_set_adapting", "amwg_get_state", "amwg_info", "amwg_chain_diag", "amwg_last_sample_moments", "amwg_sync", "amwg_num_components", "amwg_num_chains", "amwg_launch_info", "amwg_destroy", "amwg_last_error", "amwg_version", "amwg_exp", "amwg_log", "amwg_uniform"]      # include/amwg.h: the product library
+SELFTEST_EXPORTS = ["amwg_loo_predictive_check", "amwg_predictive_check", "amwg_predictive_totals_check", "amwg_heldout_check", "amwg_heldout_splits_check","amwg_waic_grouped_check", "amwg_loo_grouped_check", "amwg_user_waic_grouped_check", "amwg_user_loo_grouped_check", "amwg_group_csr_check", "amwg_waic_fold_check", "amwg_user_waic_check", "amwg_user_loo_check", "amwg_waic_check", "amwg_loo_check", "amwg_loo_stats", "amwg_hpd_check", "amwg_hpd_limits", "amwg_autocovariance_check", "amwg_covariance_check", "amwg_histogram_check", "amwg_summaries_check","amwg_fold_check","amwg_dataset_quantiles_check", "amwg_prefault_selftest", "amwg_math1", "amwg_math2", "amwg_hypot3", "amwg_log1p", "amwg_expm1", "amwg_two_valued_sum_check", "amwg_two_valued_tables", "amwg_k_valued_sum_check", "amwg_pow", "amwg_ld_host", "amwg_ld_device", "amwg_device_eval", "amwg_stream_check"]      # include/amwg_selftest.h: libamwg_selftest.so only
 
 _lib = None
 
@@ -80,6 +80,7 @@ def lib():
         L.amwg_last_sample_dataset_loo_grouped.argtypes = [vp, pi32, pd, pi32, pd, pi32]
         L.amwg_last_sample_dataset_heldout.argtypes = [vp, C.POINTER(ModelDesc), pi32, pd, pd]
         L.amwg_last_sample_dataset_predictive.argtypes = [vp, C.POINTER(ModelDesc), pi32, pd, pd]
+        L.amwg_last_sample_dataset_loo_predictive.argtypes = [vp, pd, pi32, pd]
         L.amwg_set_waic.argtypes = [vp, i32]
         L.amwg_waic_info.argtypes = [vp, pi32, C.POINTER(C.c_size_t)]
         L.amwg_burn.argtypes = [vp, i64]
@@ -205,6 +206,7 @@ def selftest_lib():
         L.amwg_heldout_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), C.POINTER(ModelDesc), pi32, i64, pd, pd]
         L.amwg_heldout_splits_check.restype, L.amwg_heldout_splits_check.argtypes = i64, [i64, i64]
         L.amwg_predictive_check.argtypes = L.amwg_heldout_check.argtypes
+        L.amwg_loo_predictive_check.argtypes = [i32, pd, i64, i32, i64, i32, C.POINTER(ModelDesc), i64, pd, C.POINTER(i32), pd]
         L.amwg_predictive_totals_check.argtypes = [pd, pd, i64, pd]
         L.amwg_group_csr_check.argtypes = [pi32, i32, pi32, pi32, pi32, pi32]
         L.amwg_loo_stats.argtypes = [i32, C.POINTER(i32), pd]
@@ -657,10 +659,20 @@ class Sampler:
         lppd_j, NaN beyond m_d]): the held-out predictive density by the rule of include/amwg.h, on the device (amwg_last_sample_dataset_heldout)"""
         return _heldout(lambda mds, ip, summary, pw: _check(lib().amwg_last_sample_dataset_heldout(self.h, mds, ip, summary, pw)), self.D, specs, index, pointwise)
 
-    def dataset_predictive(self, specs=None, index=None, pointwise=True):
+    def dataset_predictive(self, specs=None, index=None, pointwise=True, loo=False):
         """specs: None -- every dataset's OWN observations (in-sample: optimistic) -- or dataset_heldout's held-out descriptions, with its index -> dict(summary
         [datasets][4] = cover50, cover90, rmse, mean_mid[, pointwise [datasets][m_max][4] = pit_hi, pit_lo, pred_mean, pred_sd, NaN beyond m_d]): posterior predictive
-        calibration by the rule of include/amwg.h, on the device (amwg_last_sample_dataset_predictive)"""
+        calibration by the rule of include/amwg.h, on the device (amwg_last_sample_dataset_predictive).  loo=True: the PSIS-LOO form over every dataset's own
+        observations, no refit (amwg_last_sample_dataset_loo_predictive) -> dict(summary, high [datasets] = observations with khat_i > 0.7[, pointwise
+        [datasets][n_max][5] = pit_hi, pit_lo, pred_mean, pred_sd, khat_i])"""
+        if loo:
+            if specs is not None or index is not None:
+                raise AmwgError("amwg error -1: amwg_last_sample_dataset_loo_predictive: held-out observations (specs, index) together with loo: PSIS-LOO scores "
+                                "every dataset's own observations")
+            summary, high = np.empty((self.D, 4)), np.zeros(self.D, dtype=np.int32)
+            pw = np.full((self.D, max(self._n_max(), 1), 5), np.nan) if pointwise else None
+            _check(lib().amwg_last_sample_dataset_loo_predictive(self.h, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None))
+            return dict({"summary": summary, "high": high}, **({"pointwise": pw} if pointwise else {}))
         call = lambda mds, ip, summary, pw: _check(lib().amwg_last_sample_dataset_predictive(self.h, mds, ip, summary, pw))
         return _heldout(call, self.D, specs, index, pointwise, width=4, own=self.dataset_n_obs)
 
@@ -1050,6 +1062,23 @@ def predictive_check(draws, specs, held=None, index=None, pointwise=True, scratc
         if L.amwg_predictive_check(device, _dp(dr), rows, PR, Cn, len(specs), own, mds, ip, scratch_bytes, summary, pw) != 0:
             raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
     return _heldout(call, len(specs), held, index, pointwise, width=4, own=lambda: [int(q["n_obs"]) for q in specs])
+
+
+def loo_predictive_check(draws, specs, pointwise=True, scratch_bytes=0, device=0):
+    """libamwg_selftest.so: the kernels of Sampler.dataset_predictive(loo=True) on any array draws [rows][PR][C] and the data of `specs` (as loo_check takes them)
+    -> its dict (amwg_loo_predictive_check)"""
+    dr = np.ascontiguousarray(draws, dtype=np.float64)
+    if dr.ndim != 3:
+        raise AmwgError("amwg error: loo_predictive_check: draws must be [rows][PR][C]")
+    rows, PR, Cn = dr.shape
+    mds, keep = _model_descs(specs)
+    D = len(specs)
+    summary, high = np.empty((max(1, D), 4)), np.zeros(max(1, D), dtype=np.int32)
+    pw = np.full((max(1, D), max([int(q["n_obs"]) for q in specs] + [1]), 5), np.nan) if pointwise else None
+    L = selftest_lib()
+    if L.amwg_loo_predictive_check(device, _dp(dr), rows, PR, Cn, D, mds, scratch_bytes, _dp(summary), high.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pw) if pointwise else None) != 0:
+        raise AmwgError("amwg error: %s" % L.amwg_last_error().decode())
+    return dict({"summary": summary, "high": high}, **({"pointwise": pw} if pointwise else {}))
 
 
 def predictive_totals(pointwise, y):

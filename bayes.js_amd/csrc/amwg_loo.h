@@ -48,7 +48,38 @@ inline int64_t loo_tail_len(int64_t S) {
 // milliseconds per phase summed over the batches
 struct LooStats { int32_t passes, timed; float ms_lppd, ms_select, ms_compact, ms_fit; };
 
+// events around a phase when timing is on
+struct Phase {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipStream_t stream;
+  Phase(hipStream_t s, bool timed) : stream(s) { if (timed) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, stream); } }
+  void end(float &into) {
+    if (!e0) return;
+    float ms = 0.f;
+    (void)hipEventRecord(e1, stream);
+    (void)hipEventSynchronize(e1);
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    into += ms;
+  }
+  ~Phase() { if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } }
+};
+
+constexpr uint32_t kFitSmall = 128;      // up to this many slots (S <= 1 800 or so) one wavefront sorts and fits: the network's compare loop has 64 pairs at most
+inline unsigned fit_threads(uint32_t cap) { return cap <= kFitSmall ? 64u : 256u; }
+inline uint32_t loo_cap(int64_t M) {
+  uint32_t c = 64;
+  while ((int64_t)c < M + 1) c <<= 1;
+  return c;
+}
+inline int loo_thetas(int64_t M) { return 30 + (int)(loo_isqrt_up(M + 1) - 1); }      // 30 + floor(sqrt(M)): the largest r with r * r <= M is isqrt_up(M + 1) - 1
+
+namespace amwg { struct LooState; }
+
 #pragma GCC visibility push(hidden)
+// Phase 1 of THE ROUTE for one batch of the plan: the states initialised, then select passes until no observation of the batch waits; *passes = how many.  obs_off:
+// the batch's slice of the plan's offsets on the device; d_state [b.obs], d_hist [b.obs][128], d_pending [1]: the call's scratch.  Synchronises `stream`.
+int amwg_loo_select(const PointwiseLaunch &K, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, const WaicDataset *d_sets, const PointwiseBatch &b,
+                    const int64_t *obs_off, amwg::LooState *d_state, uint32_t *d_hist, int *d_pending, uint32_t M, uint32_t cap, hipStream_t stream, int *passes);
 // AMWG_EINVAL "<call>: ..." unless the shape can be served: amwg_waic_shape's limits and loo_tail_len(S) + 1 <= kLooTailCap.  Host only.
 int amwg_loo_shape(const char *call, int64_t rows, int PR, int64_t C, int D);
 // The run over any PointwiseLaunch, as amwg_waic.h states it (PointwiseRunFn).  Host outputs: summary [D][4] (elpd_loo, se, p_loo, lppd), high [D] or nullptr,
@@ -64,5 +95,7 @@ void amwg_loo_totals(const double *pw, int64_t n, double *summary, int32_t *high
 // phase timing of later calls on or off (events around the phases); the record of the last call that ended (a call gathers its own and publishes it once, under a
 // lock: concurrent calls on several samplers do not share anything they write).  For the test library.
 void amwg_loo_set_timing(int on);
+int amwg_loo_timing();                                  // the switch as it stands
+void amwg_loo_publish_stats(const LooStats &stats);      // the record of a call that ended (amwg_loo_predictive_run publishes its own: ms_lppd = 0, it has no such pass)
 LooStats amwg_loo_last_stats();
 #pragma GCC visibility pop

@@ -11,6 +11,7 @@
 
 #include "amwg_host.h"
 #include "amwg_loo.h"
+#include "amwg_loo_fit.h"
 #include "amwg_select.h"
 #include "amwg_terms.h"
 
@@ -18,8 +19,6 @@ using namespace amwg;
 
 namespace {
 
-constexpr int kMaxTheta = 128;                                    // 30 + floor(sqrt(M)) <= 120 for M < kLooTailCap
-constexpr int kFitExtra = 2 * kMaxTheta + 16;                     // doubles of LDS of the fit beside the tail: L_j, w_j, the wavefronts' partial sums
 __global__ void __launch_bounds__(kThreads) loo_init_kernel(LooState *state, int64_t count) {
   const int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (k < count) state[k] = LooState{0, 0, kMaxKey, 0, 0, 0, 0, 0, 0};
@@ -77,22 +76,7 @@ __global__ void __launch_bounds__(kThreads) loo_compact_kernel(const double *__r
   loo_compact_body<Family<MODEL>>(draws, rows, PR, C, cpd, d0, M, sets, obs_off, part_off, state, tail, cap, parts);
 }
 
-// the sum of v over the workgroup's threads (one wavefront, or four), the same double in every thread: a butterfly over the lanes, then the wavefronts in the
-// order 0, 1, 2, 3
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return blockDim.x == 64 ? red[0] : ((red[0] + red[1]) + red[2]) + red[3];
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
+// (the workgroup's sums, the bitonic network, the excesses and the fit: amwg_loo_fit.h, shared with amwg_loo_predictive.hip)
 // One workgroup per observation -- 256 threads, or one wavefront for a tail of at most kFitSmall slots (fit_threads) --: the tail sorted in LDS, the fit, the smoothed sum.  out[(d * out_stride + i) * 2 + (0 | 1)] = elpd_loo_i | khat_i; the sorted
 // tail's first M + 1 go to tails_out[(d * out_stride + i) * (M + 1) + t] when asked for.  Dynamic LDS: (cap + kFitExtra) * 8 bytes.
 __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t cpd, int d0, const WaicDataset *__restrict__ sets, int bern, const int64_t *__restrict__ obs_off,
@@ -101,11 +85,9 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
                                                            double *__restrict__ tails_out) {
   extern __shared__ uint64_t lds[];
   uint64_t *keys = lds;
-  double *X = reinterpret_cast<double *>(lds);      // the excesses take the place of the keys: x_r at X[M - r]
   double *Lj = reinterpret_cast<double *>(lds + cap), *Wj = Lj + kMaxTheta, *red = Wj + kMaxTheta;
-  const int d = d0 + (int)blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int d = d0 + (int)blockIdx.y, tid = threadIdx.x;
   const uint32_t T = blockDim.x;
-  const int waves = (int)(T >> 6);
   const WaicDataset ds = sets[d];
   const int64_t n = bern ? (ds.n_obs > 0 ? 2 : 0) : ds.n_obs, S = rows * cpd, splits = waic_splits(S, n), i = blockIdx.x;
   if (i >= n) return;      // (uniform over the workgroup)
@@ -116,17 +98,7 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
   const uint32_t nv = st.inclusive ? taken : Mlen + 1;      // the slots that hold terms
   for (uint32_t t = tid; t < cap; t += T) keys[t] = t < taken ? select_key(my_tail[t]) : (!st.inclusive && t <= Mlen ? st.thr : kMaxKey);
   __syncthreads();
-  for (uint32_t kk = 2; kk <= cap; kk <<= 1) {
-    for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = tid; t < (cap >> 1); t += T) {
-        const uint32_t a = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = a | j;
-        const bool up = (a & kk) == 0;
-        const uint64_t x = keys[a], y = keys[l];
-        if ((x > y) == up) { keys[a] = y; keys[l] = x; }
-      }
-      __syncthreads();
-    }
-  }
+  loo_sort<false>(keys, nullptr, cap);
   double *res = out + (d * out_stride + i) * 2;
   if (st.bad) {      // a NaN or an infinity among the terms: NaN (the launcher filled the tails with NaN)
     if (tid == 0) { res[0] = __builtin_nan(""); res[1] = __builtin_nan(""); }
@@ -146,57 +118,26 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
   for (uint32_t t = Mlen + tid; t < nv; t += T) v += exp_v8(a0 - select_value(keys[t]));
   const double B = rest + block_sum(v, red);
   const double Sd = (double)S, Md = (double)Mlen;
-  bool raw = Mlen < 5;
-  double khat = kInf, elpd = 0.0;
+  const LooFit f = loo_gpd_fit(keys, Lj, Wj, red, Mlen, mm, a0, aM);      // (the excesses now stand where the keys stood)
+  const bool raw = f.raw;
+  const double khat = f.khat, sigma = f.sigma, ec = f.ec;
+  double elpd = 0.0;
   if (!raw) {
-    const double ec = exp_v8(a0 - aM);
-    __syncthreads();
-    for (uint32_t t = tid; t < Mlen; t += T) X[t] = exp_v8(a0 - select_value(keys[t])) - ec;      // (slot t is read and written by the same thread)
-    __syncthreads();
-    const double xM = X[0], xs = X[Mlen - (Mlen + 2) / 4];      // x_M; x* = x_{floor(M / 4 + 0.5)}
-    raw = !(xs > 0.0) || !(xM > 0.0);
-    if (!raw) {
-      const double mmd = (double)mm;
-      for (int j = wave + 1; j <= mm; j += waves) {
-        const double theta = 1.0 / xM + (1.0 - ::sqrt(mmd / ((double)j - 0.5))) / (3.0 * xs);
-        double s = 0.0;
-        for (uint32_t t = lane; t < Mlen; t += 64) s += log1p_v8(-theta * X[t]);
-        const double k = wave_sum(s) / Md;
-        if (lane == 0) Lj[j - 1] = Md * (log_v8(-theta / k) - k - 1.0);
-      }
-      __syncthreads();
-      if (tid < mm) {
-        double z = 0.0;
-        for (int q = 0; q < mm; ++q) z += exp_v8(Lj[q] - Lj[tid]);
-        Wj[tid] = 1.0 / z;
-      }
-      __syncthreads();
-      double th = 0.0;
-      for (int j = 1; j <= mm; ++j) th += (1.0 / xM + (1.0 - ::sqrt(mmd / ((double)j - 0.5))) / (3.0 * xs)) * Wj[j - 1];
-      double s = 0.0;
-      for (uint32_t t = tid; t < Mlen; t += T) s += log1p_v8(-th * X[t]);
-      const double kp = block_sum(s, red) / Md, sigma = -kp / th;
-      khat = (Md * kp + 5.0) / (Md + 10.0);
-      raw = !(__builtin_fabs(khat) < kInf);
-      if (!raw) {
-        double s1 = 0.0, s2 = 0.0;
-        for (uint32_t t = tid; t < Mlen; t += T) {
-          const double r = (double)(Mlen - t), lp = log1p_v8(-((r - 0.5) / Md));
-          const double q = khat == 0.0 ? -sigma * lp : sigma * expm1_v8(-khat * lp) / khat;
-          const double lq = log_v8(q + ec), lwt = lq > 0.0 ? 0.0 : lq;      // (a NaN stays a NaN)
-          s1 += exp_v8(lwt - (a0 - my_tail[t]));
-          s2 += exp_v8(lwt);
-        }
-        const double S1 = block_sum(s1, red), S2 = block_sum(s2, red);
-        elpd = a0 + (log_v8((Sd - Md) + S1) - log_v8(B + S2));      // (the difference of the logarithms first: identical draws give a_0 itself)
-      }
+    double s1 = 0.0, s2 = 0.0;
+    for (uint32_t t = tid; t < Mlen; t += T) {
+      const double r = (double)(Mlen - t), lp = log1p_v8(-((r - 0.5) / Md));
+      const double q = khat == 0.0 ? -sigma * lp : sigma * expm1_v8(-khat * lp) / khat;
+      const double lq = log_v8(q + ec), lwt = lq > 0.0 ? 0.0 : lq;      // (a NaN stays a NaN)
+      s1 += exp_v8(lwt - (a0 - my_tail[t]));
+      s2 += exp_v8(lwt);
     }
+    const double S1 = block_sum(s1, red), S2 = block_sum(s2, red);
+    elpd = a0 + (log_v8((Sd - Md) + S1) - log_v8(B + S2));      // (the difference of the logarithms first: identical draws give a_0 itself)
   }
   if (raw) {      // no fit: the plain importance-sampling estimate, log S - log sum_s exp(-l_s) taken at a_0
     double h = 0.0;
     for (uint32_t t = tid; t < Mlen; t += T) h += exp_v8(a0 - my_tail[t]);
     elpd = a0 + (log_v8(Sd) - log_v8(B + block_sum(h, red)));
-    khat = kInf;
   }
   if (tid == 0) { res[0] = elpd; res[1] = khat; }
 }
@@ -204,30 +145,6 @@ __global__ void __launch_bounds__(kThreads) loo_fit_kernel(int64_t rows, int64_t
 std::atomic<int> g_timing{0};      // the test library's switch
 std::mutex g_stats_lock;
 LooStats g_stats{};                // the last call's record, published once when it ends
-
-struct Phase {      // events around a phase when timing is on
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipStream_t stream;
-  Phase(hipStream_t s, bool timed) : stream(s) { if (timed) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, stream); } }
-  void end(float &into) {
-    if (!e0) return;
-    float ms = 0.f;
-    (void)hipEventRecord(e1, stream);
-    (void)hipEventSynchronize(e1);
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    into += ms;
-  }
-  ~Phase() { if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); } }
-};
-
-constexpr uint32_t kFitSmall = 128;      // up to this many slots (S <= 1 800 or so) one wavefront sorts and fits: the network's compare loop has 64 pairs at most
-inline unsigned fit_threads(uint32_t cap) { return cap <= kFitSmall ? 64u : (unsigned)kThreads; }
-inline uint32_t loo_cap(int64_t M) {
-  uint32_t c = 64;
-  while ((int64_t)c < M + 1) c <<= 1;
-  return c;
-}
-inline int loo_thetas(int64_t M) { return 30 + (int)(loo_isqrt_up(M + 1) - 1); }      // 30 + floor(sqrt(M)): the largest r with r * r <= M is isqrt_up(M + 1) - 1
 
 int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int64_t C, int D, const PointwiseLaunch &K, const WaicDataset *sets, const WaicDataset *d_sets,
                 int64_t n_max, double *d_pw, double *d_tails, LooStats &stats, size_t scratch_bytes, hipStream_t stream) {
@@ -270,30 +187,15 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
   const int32_t *csr = K.groups ? K.groups->d_csr.as<int32_t>() : nullptr;
   for (const PointwiseBatch &b : plan.batches) {
     if (b.tiles == 0) continue;
-    int d0 = b.d0, pass = 0;
-    const int64_t obs = b.obs, *obs_off = offs.as<int64_t>() + d0, *part_off = offs.as<int64_t>() + D + d0;
-    const dim3 walk((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), per_obs_grid((unsigned)((b.n_most + kThreads - 1) / kThreads), (unsigned)(b.d1 - d0));
-    void *hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &d_state, &d_hist, &pass};
+    int d0 = b.d0;
+    const int64_t *obs_off = offs.as<int64_t>() + d0, *part_off = offs.as<int64_t>() + D + d0;
+    const dim3 walk((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0));
     void *compact_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &part_off, &d_state, &d_tail, &cap, &d_parts};
-    void *grouped_hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &obs_off, &d_state, &d_hist, &pass};
     void *grouped_compact_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &obs_off, &part_off, &d_state, &d_tail, &cap, &d_parts};
-    hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((obs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_state, obs);
-    HIP_TRY(hipGetLastError());
     {
       Phase ph(stream, stats.timed != 0);
       int passes = 0;
-      for (pass = 0; pass < kPasses; ++pass) {      // (hist_args reads `pass`)
-        int waiting = 0;
-        HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)obs * kBins * 4, stream));
-        HIP_TRY(hipMemsetAsync(pending.p, 0, sizeof(int), stream));
-        HIP_TRY(amwg_pointwise_go(K, walk_fn + kPwLooHist, walk, stream, K.groups ? grouped_hist_args : hist_args));
-        hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern ? 1 : 0, obs_off, d_state, d_hist, pass, (uint32_t)M, cap, pending.as<int>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&waiting, pending.p, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        ++passes;
-        if (!waiting) break;
-      }
+      TRYB(amwg_loo_select(K, draws, rows, PR, C, cpd, d_sets, b, obs_off, d_state, d_hist, pending.as<int>(), (uint32_t)M, cap, stream, &passes));
       stats.passes = passes > stats.passes ? passes : stats.passes;
       ph.end(stats.ms_select);
     }
@@ -318,6 +220,39 @@ int run_kernels(const char *call, const double *draws, int64_t rows, int PR, int
   return AMWG_OK;
 }
 
+}  // namespace
+
+int amwg_loo_select(const PointwiseLaunch &K, const double *draws, int64_t rows, int PR, int64_t C, int64_t cpd, const WaicDataset *d_sets, const PointwiseBatch &b,
+                    const int64_t *obs_off, LooState *d_state, uint32_t *d_hist, int *d_pending, uint32_t M, uint32_t cap, hipStream_t stream, int *passes) {
+  const int bern = K.bern ? 1 : 0;
+  int d0 = b.d0, pass = 0;
+  const dim3 walk((unsigned)b.tiles, (unsigned)b.splits, (unsigned)(b.d1 - d0)), per_obs_grid((unsigned)((b.n_most + kThreads - 1) / kThreads), (unsigned)(b.d1 - d0));
+  const int walk_fn = K.groups ? kPwGrouped : 0;
+  const WaicDataset *obs_sets = K.groups ? K.groups->d_sets.as<WaicDataset>() : d_sets;
+  const GroupSet *gsets = K.groups ? K.groups->d_gsets.as<GroupSet>() : nullptr;
+  const int32_t *csr = K.groups ? K.groups->d_csr.as<int32_t>() : nullptr;
+  void *hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &d_sets, &obs_off, &d_state, &d_hist, &pass};
+  void *grouped_hist_args[] = {&draws, &rows, &PR, &C, &cpd, &d0, K.model_arg(), &obs_sets, &gsets, &csr, &obs_off, &d_state, &d_hist, &pass};
+  hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((b.obs + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, d_state, b.obs);
+  HIP_TRY(hipGetLastError());
+  *passes = 0;
+  for (pass = 0; pass < kPasses; ++pass) {      // (hist_args reads `pass`)
+    int waiting = 0;
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)b.obs * kBins * 4, stream));
+    HIP_TRY(hipMemsetAsync(d_pending, 0, sizeof(int), stream));
+    HIP_TRY(amwg_pointwise_go(K, walk_fn + kPwLooHist, walk, stream, K.groups ? grouped_hist_args : hist_args));
+    hipLaunchKernelGGL(loo_pick_kernel, per_obs_grid, dim3(kThreads), 0, stream, d0, d_sets, bern, obs_off, d_state, d_hist, pass, M, cap, d_pending);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&waiting, d_pending, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    ++*passes;
+    if (!waiting) break;
+  }
+  return AMWG_OK;
+}
+
+namespace {
+
 template <int... MODEL> const void *family_fn(PointwiseModels<MODEL...>, int model, int k) {
   const void *const fn[][2] = {{reinterpret_cast<const void *>(&loo_hist_kernel<MODEL>), reinterpret_cast<const void *>(&loo_compact_kernel<MODEL>)}...};
   return fn[model - AMWG_MODEL_NORMAL][k];
@@ -328,6 +263,11 @@ template <int... MODEL> const void *family_fn(PointwiseModels<MODEL...>, int mod
 const void *amwg_loo_family_fn(int model, int k) { return family_fn(BuiltinModels{}, model, k); }
 
 void amwg_loo_set_timing(int on) { g_timing.store(on); }
+int amwg_loo_timing() { return g_timing.load(); }
+void amwg_loo_publish_stats(const LooStats &stats) {
+  std::lock_guard<std::mutex> hold(g_stats_lock);
+  g_stats = stats;
+}
 LooStats amwg_loo_last_stats() {
   std::lock_guard<std::mutex> hold(g_stats_lock);
   return g_stats;
@@ -386,10 +326,7 @@ int amwg_loo_run(const char *call, const double *draws, int64_t rows, int PR, in
   PointwiseOut o;
   TRYB(amwg_pointwise_begin(call, sets, D, tails ? M + 1 : 0, stream, o));
   TRYB(run_kernels(call, draws, rows, PR, C, D, K, sets, o.sets.as<WaicDataset>(), n_max, o.pw.as<double>(), tails ? o.extra.as<double>() : nullptr, stats, scratch_bytes, stream));
-  {
-    std::lock_guard<std::mutex> hold(g_stats_lock);
-    g_stats = stats;
-  }
+  amwg_loo_publish_stats(stats);
   TRYB(amwg_pointwise_fetch(o, got.data(), tails));
   // the triples: (elpd_loo_i, WAIC's lppd_i, khat_i); all three NaN where either pass found the terms of (d, i) unfit
   std::vector<double> own;

@@ -860,6 +860,9 @@ static napi_value DatasetWaic(napi_env env, napi_callback_info info) { return da
 /* datasetLoo(handle, bool pointwise) -> the same object over amwg_last_sample_dataset_loo: summary [datasets][4] (elpd_loo, se, p_loo, lppd), high (observations with
  * khat_i > 0.7), pointwise [datasets][n_max][3] (elpd_loo_i, lppd_i, khat_i) */
 static napi_value DatasetLoo(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo, NULL, 3); }
+/* datasetLooPredictive(handle, bool pointwise) -> the same object over amwg_last_sample_dataset_loo_predictive: summary [datasets][4] (cover50, cover90, rmse, mean_mid),
+ * high (observations with khat_i > 0.7), pointwise [datasets][n_max][5] (pit_hi, pit_lo, pred_mean, pred_sd, khat_i) */
+static napi_value DatasetLooPredictive(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, amwg_last_sample_dataset_loo_predictive, NULL, 5); }
 /* datasetWaicGrouped(handle, bool pointwise, Int32Array labels), datasetLooGrouped(...): the same objects over groups of observations
  * (amwg_last_sample_dataset_waic_grouped, amwg_last_sample_dataset_loo_grouped) */
 static napi_value DatasetWaicGrouped(napi_env env, napi_callback_info info) { return dataset_pointwise(env, info, NULL, amwg_last_sample_dataset_waic_grouped, 2); }
@@ -1382,7 +1385,7 @@ static napi_value Uniform(napi_env env, napi_callback_info info) {
 
 static napi_value Init(napi_env env, napi_value exports) {
   static const struct { const char *name; napi_callback fn; } fns[] = {
-      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"datasetHeldout", DatasetHeldout}, {"datasetPredictive", DatasetPredictive},{"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
+      {"create", Create}, {"createDatasets", CreateDatasets}, {"createDatasetsRagged", CreateDatasetsRagged}, {"datasetMoments", DatasetMoments}, {"datasetConvergence", DatasetConvergence}, {"datasetQuantiles", DatasetQuantiles}, {"datasetHpd", DatasetHpd}, {"datasetWaic", DatasetWaic}, {"datasetLoo", DatasetLoo}, {"datasetLooPredictive", DatasetLooPredictive}, {"datasetWaicGrouped", DatasetWaicGrouped}, {"datasetLooGrouped", DatasetLooGrouped}, {"datasetHeldout", DatasetHeldout}, {"datasetPredictive", DatasetPredictive},{"setPointwise", SetPointwise}, {"createUser", CreateUser}, {"createUserDatasets", CreateUserDatasets}, {"compileUser", CompileUser}, {"destroy", Destroy}, {"burn", Burn}, {"burnAsync", BurnAsync}, {"sync", Sync},
       {"sample", Sample}, {"sampleAsync", SampleAsync}, {"sampleSummarizeAsync", SampleSummarizeAsync}, {"summaryInfo", SummaryInfo}, {"setWaic", SetWaic}, {"waicInfo", WaicInfo}, {"setHistogram", SetHistogram}, {"datasetHistogram", DatasetHistogram}, {"histogramInfo", HistogramInfo}, {"setCovariance", SetCovariance}, {"datasetCovariance", DatasetCovariance}, {"covarianceInfo", CovarianceInfo}, {"setAutocovariance", SetAutocovariance}, {"datasetAutocovariance", DatasetAutocovariance}, {"autocovarianceInfo", AutocovarianceInfo},{"fetchDraws", FetchDraws}, {"fetchDrawsSplit", FetchDrawsSplit}, {"setAdapting", SetAdapting},
       {"getState", GetState}, {"setState", SetState}, {"convergence", Convergence}, {"quantiles", Quantiles}, {"groupMoments", GroupMoments}, {"groupGatherDraws", GroupGatherDraws}, {"groupConvergence", GroupConvergence}, {"groupQuantiles", GroupQuantiles}, {"info", Info}, {"diag", Diag}, {"moments", Moments}, {"launchInfo", LaunchInfo}, {"codeCacheStats", CodeCacheStats},
       {"version", Version}, {"mathExp", MathExp}, {"mathLog", MathLog}, {"uniform", Uniform}};

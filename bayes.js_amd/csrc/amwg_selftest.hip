@@ -11,6 +11,7 @@
 #include "amwg_histogram.h"
 #include "amwg_hpd.h"
 #include "amwg_loo.h"
+#include "amwg_loo_predictive.h"
 #include "amwg_heldout.h"
 #include "amwg_predictive.h"
 #include "amwg_waic.h"
@@ -372,7 +373,7 @@ static int waic_pack(int D, Len len, Fill fill, std::vector<int64_t> &off, DevBu
 // (extra: WAIC's loglik, or LOO's tails)
 static int pointwise_check(const char *call, bool loo, int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models,
                            int64_t scratch_bytes, double *summary, int32_t *high, double *pointwise, double *extra, int64_t window_rows = 0, size_t *state_bytes = nullptr,
-                           bool grouped = false, const int32_t *labels = nullptr, int32_t *n_groups_out = nullptr) {
+                           bool grouped = false, const int32_t *labels = nullptr, int32_t *n_groups_out = nullptr, bool predictive = false) {
   double *loglik = loo ? nullptr : extra;
   if (!draws || !models || !summary) return amwg_fail(AMWG_EINVAL, "%s: null argument", call);
   if (grouped) TRYB(amwg_pointwise_labels(call, labels));
@@ -459,6 +460,7 @@ static int pointwise_check(const char *call, bool loo, int32_t device, const dou
     if (n_groups_out) for (int d = 0; d < D; ++d) n_groups_out[d] = groups.gsets[(size_t)d].G;
     return (loo ? amwg_loo_run : amwg_waic_run)(call, dd.as<double>(), rows, PR, C, D, K, groups.by_group.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
   }
+  if (predictive) return amwg_loo_predictive_launch(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, (size_t)scratch_bytes, nullptr);
   return (loo ? amwg_loo_launch : amwg_waic_launch)(call, dd.as<double>(), rows, PR, C, D, wm, sets.data(), summary, high, pointwise, extra, (size_t)scratch_bytes, nullptr);
 }
 extern "C" {
@@ -536,6 +538,12 @@ int amwg_waic_fold_check(int32_t device, const double *draws, int64_t rows, int3
 int amwg_loo_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes, double *summary,
                    int32_t *high, double *pointwise, double *tails) {
   return pointwise_check("amwg_loo_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, tails);
+}
+
+// amwg_last_sample_dataset_loo_predictive on a caller's draws and data: pointwise [D][n_max][5]
+int amwg_loo_predictive_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes,
+                              double *summary, int32_t *high, double *pointwise) {
+  return pointwise_check("amwg_loo_predictive_check", true, device, draws, rows, PR, C, D, models, scratch_bytes, summary, high, pointwise, nullptr, 0, nullptr, false, nullptr, nullptr, true);
 }
 
 int amwg_waic_grouped_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const int32_t *labels,

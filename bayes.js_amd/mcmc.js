@@ -784,11 +784,26 @@ AmwgSampler.prototype.heldout = function (data, opts) {
 /** Posterior predictive calibration per dataset (amwg_last_sample_dataset_predictive; include/amwg.h): opts.data -- one data object per dataset as dataset_heldout
  *  takes them, with opts.index -- or none: every dataset's OWN observations (in-sample, which is optimistic: the honest check scores the held-out fold of each of K
  *  training folds).  opts.pointwise (default true).
- *  -> [{cover50, cover90, rmse, mean_mid, n[, pointwise: [{pit_hi, pit_lo, pred_mean, pred_sd} ...]]}, ...].  Built-in families only. */
+ *  -> [{cover50, cover90, rmse, mean_mid, n[, pointwise: [{pit_hi, pit_lo, pred_mean, pred_sd} ...]]}, ...].  Built-in families only.
+ *  opts.loo: the PSIS-LOO form (amwg_last_sample_dataset_loo_predictive) -- the leave-one-out PIT, mean and sd of every dataset's own observations from the stored
+ *  draws of this one fit, no refit: the same objects with high_k (observations with khat_i > 0.7) and khat per observation; opts.data / opts.index are refused. */
 AmwgSampler.prototype.dataset_predictive = function (opts) {
   if (!this._recog) throw 'AmwgSampler (MI355X): dataset_predictive: the predictive distribution of a closure is not known to the library; built-in families only';
   const multi = !!(this.options && this.options.datasets), nSets = multi ? this.n_datasets : 1;
   const data = opts && opts.data !== undefined && opts.data !== null ? opts.data : null;
+  if (opts && opts.loo) {
+    if (data !== null || opts.index) throw 'AmwgSampler (MI355X): dataset_predictive (amwg_last_sample_dataset_loo_predictive): held-out observations (options.data, options.index) together with options.loo: PSIS-LOO scores every dataset\'s own observations';
+    const want = opts.pointwise !== false, out = [];
+    for (const sh of this._shards) {
+      const r = native().datasetLooPredictive(sh.handle, want);
+      for (let d = 0; d < r.datasets; d++) {
+        const o = { cover50: r.summary[d * 4], cover90: r.summary[d * 4 + 1], rmse: r.summary[d * 4 + 2], mean_mid: r.summary[d * 4 + 3], n: r.n_obs[d], high_k: r.high[d] };
+        if (want) o.pointwise = Array.from({ length: r.n_obs[d] }, (_, j) => { const q = (d * r.n_max + j) * 5; return { pit_hi: r.pointwise[q], pit_lo: r.pointwise[q + 1], pred_mean: r.pointwise[q + 2], pred_sd: r.pointwise[q + 3], khat: r.pointwise[q + 4] }; });
+        out.push(o);
+      }
+    }
+    return out;
+  }
   const sets = data === null ? null : (multi ? data : [data]);
   if (sets && (!Array.isArray(sets) || sets.length !== nSets)) throw 'dataset_predictive: one data object per dataset (' + nSets + ')';
   const index = opts && opts.index ? (nSets === 1 && !Array.isArray(opts.index[0]) && !ArrayBuffer.isView(opts.index[0]) ? [opts.index] : opts.index) : null;

@@ -412,12 +412,46 @@ int amwg_last_sample_dataset_heldout(amwg_sampler *s, const amwg_model_desc *hel
  * AMWG_EINVAL with a message that names the call, before any device call: the refusals of amwg_last_sample_dataset_heldout (held may be NULL here), and a
  * translated closure: "the predictive distribution of a closure is not known to the library; built-in families only".
  * Scratch is 48 bytes per (run of draws, observation), in batches under the 256 MiB budget of the calls above, freed before the call returns.  AMWG_EHIP as above.
- * OUT OF SCOPE: closures, LOO-PIT (importance-weighted: it needs the PSIS weight of every draw), folding under amwg_sample_summarize, amwg_group_* / amwg_comm_*
+ * OUT OF SCOPE: closures, folding under amwg_sample_summarize, amwg_group_* / amwg_comm_*
  * twins, predictive quantiles or intervals, simulated replicates. */
 int amwg_last_sample_dataset_predictive(amwg_sampler *s, const amwg_model_desc *held /* NULL, or [D] */,
                                         const int32_t *index /* as amwg_last_sample_dataset_heldout */,
                                         double *summary /* [D][4]: cover50, cover90, rmse, mean_mid */,
                                         double *pointwise /* NULL or [D][m_max][4]: pit_hi, pit_lo, pred_mean, pred_sd; NaN beyond m_d */);
+/* PSIS-LOO PREDICTIVE CALIBRATION per dataset -- the honest form of the call above without a refit: the Pareto-smoothed importance weights that
+ * amwg_last_sample_dataset_loo forms and reduces to elpd_loo_i turn the stored draws of ONE fit into leave-one-out expectations.  Per observation the LOO-PIT, the
+ * leave-one-out predictive mean and sd (the loo package's E_loo) and khat_i; from them the coverage, the RMSE and the PIT histogram.  Every dataset's OWN observations.
+ *   summary[D][4] = cover50, cover90, rmse, mean_mid: THE FINISH of amwg_last_sample_dataset_predictive over the values below, the same host code;
+ *   high[D] (or NULL) = the number of observations with khat_i > 0.7, where the weights are unreliable;
+ *   pointwise (NULL, or [D][n_max][5] = pit_hi, pit_lo, pred_mean, pred_sd, khat_i; NaN beyond n_d).
+ * THE RULE applies per dataset d and observation i.  S, the draw order, the terms l_s, their ascending key order a_0 <= ... <= a_{S-1}, M, the excesses, the fit,
+ *   khat_i and the smoothed lw~_r are those of amwg_last_sample_dataset_loo; khat_i is returned as the same bytes.  F_s, Fm_s, mean_s and var_s are those of
+ *   amwg_last_sample_dataset_predictive, from the same device functions.
+ *   THE WEIGHT OF A DRAW depends on the key of its term alone -- no draw index, no tie-break:
+ *     RAW ROUTE (M < 5, or LOO's degenerate-tail conditions): w_s = exp_v8(a_0 - l_s) for every draw.
+ *     SMOOTHED ROUTE: sorted position t < M has rank r = M - t and the smoothed weight exp_v8(lw~_r).  A CLASS c is the set of draws whose terms have one key; let it
+ *     occupy m_c positions t < M and have o_c further members at positions >= M (o_c > 0 is possible only for the key of a_M).  Every member of a class with
+ *     m_c > 0 has  w = (sum_{its positions t < M} exp_v8(lw~_{M-t}) + o_c exp_v8(a_0 - c)) / (m_c + o_c),  the sum in ascending t; every other draw has
+ *     w = exp_v8(a_0 - l_s).  In exact arithmetic sum_s w_s is the denominator of LOO's elpd_loo_i.
+ *     TIES ARE THE NORMAL CASE: a Metropolis chain repeats a draw whenever it rejects.  Repeated draws share F, mean and var as well as l, so any tie rule would give
+ *     them the same result; the average makes the result independent of order for DISTINCT draws with equal terms too.
+ *   pit_hi = sum_s w_s F_s / sum_s w_s;  pit_lo the same with Fm;  pred_mean = sum_s w_s mean_s / sum_s w_s;
+ *   pred_sd = sqrt(sum_s w_s (var_s + (mean_s - c)^2) / sum_s w_s - (pred_mean - c)^2), with the shift c = mean of draw s = 0: the variance over the draws is formed
+ *   without cancellation.
+ *   THE ACCUMULATIONS ARE NOT FIXED TO THE BIT.  With E, c (the distribution function's bound) and E_k as the two calls above state them:
+ *     |pit - exact| <= E + c + 4 ln(2 M) E_k;  |pred_mean - exact| <= E max_s |mean_s| + 4 ln(2 M) E_k;  |pred_sd^2 - exact| <= 4 E (max_s var_s + max_s mean_s^2) + 4 ln(2 M) E_k
+ *   (the form of the two parents; measured, not proven: tests/README.loo_predictive.md has the measurement and the largest ratios observed).
+ *   NON-FINITE VALUES: a non-finite term, F, mean or var makes the five values of that observation NaN, and the summary of that dataset NaN; nothing else is touched.
+ *   The Bernoulli family is served by LOO's two-value expansion.
+ *   DETERMINISM is LOO's: no floating-point atomics, a split of the draws that is a function of (S, n_d) alone, a fixed merge order; a dataset's bytes do not depend
+ *   on D, its neighbours or the scratch budget.
+ * AMWG_EINVAL with a message that names the call, before any device call: the refusals of amwg_last_sample_dataset_loo (the cap of M + 1 <= 8192 included: key and
+ * draw index of a tail are 12 bytes a slot, 96 KB of the 160 KB of LDS), and a translated closure, with or without a pointwise text: "the predictive distribution of a
+ * closure is not known to the library; built-in families only".  Held-out observations are not taken (the bindings refuse `held` together with `loo`).
+ * Scratch is LOO's plus 4 bytes per tail slot and 96 bytes per (run of draws, observation), allocated per call under the 256 MiB budget and freed before return.
+ * OUT OF SCOPE: grouped and held-out forms, folding under amwg_sample_summarize, moment matching, r_eff, amwg_group_* / amwg_comm_* twins, tails beyond the LDS cap. */
+int amwg_last_sample_dataset_loo_predictive(amwg_sampler *s, double *summary /* [D][4]: cover50, cover90, rmse, mean_mid */, int32_t *high /* [D] or NULL */,
+                                            double *pointwise /* NULL or [D][n_max][5]: pit_hi, pit_lo, pred_mean, pred_sd, khat_i; NaN beyond n_d */);
 
 /* A user-written `log_post(state, data)` closure (mcmc.js:958-960) translated to HIP by
  * bayes.js_amd/translate.js.  `source` defines `struct amwg::UserModel` (interface: csrc/amwg_kernel.h,

@@ -85,6 +85,10 @@ int amwg_heldout_check(int32_t device, const double *draws, int64_t rows, int32_
  * packed as held-out ones are (the sampler's in-sample route reads its own arrays where they lie; tests/test_gpu_predictive.py compares the two on a sampler). */
 int amwg_predictive_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, const amwg_model_desc *held,
                           const int32_t *index, int64_t scratch_bytes, double *summary, double *pointwise);
+/* amwg_last_sample_dataset_loo_predictive on a caller's draws and data, as amwg_loo_check takes them, through the launcher the sampler uses: summary[D][4], high[D] or
+ * NULL, pointwise (NULL, or [D][n_max][5]) */
+int amwg_loo_predictive_check(int32_t device, const double *draws, int64_t rows, int32_t PR, int64_t C, int32_t D, const amwg_model_desc *models, int64_t scratch_bytes,
+                              double *summary, int32_t *high, double *pointwise);
 /* THE FINISH of that call over one dataset on the host: pw[m][4], the observations y[m] -> summary[4]; no device */
 int amwg_predictive_totals_check(const double *pw, const double *y, int64_t m, double *summary);
 /* the runs that call cuts the S draws of a dataset with m held-out observations into (csrc/amwg_heldout.h: heldout_splits); no device */
